@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- latent trajectories/s of the GP-ODE hot path on MI355X (driver contract).
 
-    python bench.py --gpus N --steps K --warmup W [--workload cfg2|cfg4|cfg3|cfg1]
+    python bench.py --gpus N --steps K --warmup W [--workload cfg2|cfg4|cfg3|cfg1] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic input already resident in HBM.
   --mode elbo (default): the full training step of main.py:199-211 -- encoder, GP draw (cache build), RK4
@@ -11,9 +11,12 @@ One process per GPU; for N>1 the minibatch axis is sharded (every rank owns `bat
 integrate under the SAME GP draw) and, in elbo mode, the gradient bucket is all-reduced over RCCL before the
 optimizer step -> weak scaling.
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel, timed live with HIP events on the
-launch stream; `cpu_baseline` times the CPU oracle (kind "port": the reference itself never travels to the
-GPU box) on a bounded sample of the same workload.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`).
+--full adds what takes runs of its own: `roofline` for the dominant kernel, timed live with HIP events on the
+launch stream; `cpu_baseline`, the CPU oracle (kind "port": a torch-CPU restatement of the reference's arithmetic) on a
+bounded sample of the same workload; in elbo mode on one GPU, `extra.configs` (the other BASELINE configurations).
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last step computed to DIR/<name>.npy.  The inputs are seeded:
+the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -173,6 +176,21 @@ def cpu_baseline_elbo(w, model, X, budget_s=15.0):
                 sample='%d full training steps (fwd + bwd + Adam, batch %d) of the torch-CPU oracle in %.1f s' % (n, N, el))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: one d/<name>.npy per tensor (float32, or float64 where the tensor is), after the timed steps."""
+    arrays = {k: v.detach().to('cpu', v.dtype if v.dtype in (torch.float32, torch.float64) else torch.float32).numpy()
+              for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit('bench.py: --dump-outputs would write %d bytes (limit %d)' % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + '.npy'), v)
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -256,14 +274,19 @@ def main():
     ap.add_argument('--seed', type=int, default=121)
     ap.add_argument('--L', type=int, default=1, help='Monte-Carlo draws per step (main.py:200 trains at L = 1, then L = 5); a trajectory '
                     'is one (sample, draw) pair, so a step integrates batch x L of them')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extra', action='store_true', help='skip extra.configs (configs[0], configs[2], integrator-only figures)')
+    ap.add_argument('--full', action='store_true', help='after the headline: roofline, CPU baselines and extra.configs (each takes runs of '
+                    'its own); without it the run does only what the headline needs')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy (float32 / float64)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU oracle legs')
+    ap.add_argument('--no-extra', action='store_true', help='--full: skip extra.configs (configs[0], configs[2], integrator-only figures)')
     ap.add_argument('--no-overlap', action='store_true', help='keep the GP cache build / cache backward on the main stream')
     ap.add_argument('--no-sync-bn', action='store_true', help='N > 1: BatchNorm with per-rank statistics instead of the global minibatch')
     ap.add_argument('--dp-graph', default='whole', choices=['whole', 'fwdbwd', 'off'],
                     help='N > 1 over RCCL: what one HIP graph holds (whole step incl. collectives / forward+backward / nothing)')
     ap.add_argument('--no-graph', action='store_true', help='launch every kernel of the step eagerly instead of replaying a captured HIP graph')
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
 
     # --gpus N without a launcher (the driver's `python bench.py --gpus N`): this process only starts the N ranks.  Nothing
     # above or inside spawn_ranks touches the GPU.
@@ -470,7 +493,12 @@ def run_elbo(a, w, dev, rank, n_gpus, dist, barrier):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = t.item()
     value = w['batch'] * a.L * n_gpus * a.steps / el          # trajectories = (sample, Monte-Carlo draw) pairs
-    roof = dominant_kernel_roofline(w, dev, a.L)
+    if a.dump_outputs and rank == 0:
+        # what a caller of the training step gets back: the loss, the state after the Adam update, the gradients of the step
+        arrays = {'loss': last['loss']}
+        arrays.update(('state.' + k, v) for k, v in model.state_dict().items() if v.is_floating_point())
+        arrays.update(('grad.' + k, p.grad) for k, p in model.named_parameters() if p.grad is not None)
+        dump_outputs(a.dump_outputs, arrays)
     out = {
         'metric': 'latent_trajectories_per_sec', 'value': value, 'unit': 'trajectories/s',
         'n_gpus': n_gpus, 'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': el / a.steps * 1e3,
@@ -480,15 +508,18 @@ def run_elbo(a, w, dev, rank, n_gpus, dist, barrier):
                    'hip_graph': graphed, 'graph_scope': mode, 'gp_side_stream': not a.no_overlap,
                    'batchnorm': 'global-minibatch statistics (all-gather per layer)' if bn_sync is not None else 'per-process statistics'},
         'elbo_step_ms': el / a.steps * 1e3,
-        'roofline': roof,
     }
     if coll is not None:
         out['collectives_per_step'] = coll
+    if rank == 0:
+        print('[bench] gpu leg done: %.1f traj/s, %.3f ms/step' % (value, el / a.steps * 1e3), file=sys.stderr, flush=True)
+    if not a.full:
+        return out
+    roof = out['roofline'] = dominant_kernel_roofline(w, dev, a.L)
     # whole-step roofline: SURVEY 8(d)'s algorithmic flops per trajectory (forward + backward) x trajectories/s over the fp32 peak
     roof['step_frac'] = w['elbo_mflop'] * 1e6 * (value / n_gpus) / 1e12 / PEAK_FP32_TFLOPS
     roof['step_note'] = '%.0f MFLOP per trajectory (SURVEY 8d, full ELBO step) x per-GPU trajectories/s / %.1f TFLOP/s' % (w['elbo_mflop'], PEAK_FP32_TFLOPS)
     if rank == 0:
-        print('[bench] gpu leg done: %.1f traj/s, %.3f ms/step' % (value, el / a.steps * 1e3), file=sys.stderr, flush=True)
         if n_gpus == 1 and not a.no_extra:
             extra = other_configs(a, dev, a.workload)      # (same launch form as the headline leg: graph replay, side-stream overlap)
             main = extra.pop(a.workload)
@@ -748,14 +779,15 @@ def run_integrator(a, w, dev, rank, n_gpus, dist, barrier):
             ev[1].record()
         return zt
 
-    gp.set_noise(nzd)  # the public API path once (untimed) must agree with the bracketed form
-    if not torch.equal(flow(z0d, tsd), step()):
-        raise SystemExit('Flow.forward and the bracketed step disagree')
+    if a.full:
+        gp.set_noise(nzd)  # the public API path once (untimed) must agree with the bracketed form
+        if not torch.equal(flow(z0d, tsd), step()):
+            raise SystemExit('Flow.forward and the bracketed step disagree')
 
-    # rollout launch duration: a few eager steps bracketed by events on the launch stream
+    # --full: rollout launch duration from a few eager steps bracketed by events on the launch stream
     for _ in range(max(a.warmup, 1)):
         step()
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(a.steps, 20))]
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(a.steps, 20) if a.full else 0)]
     for ev in evs:
         zt = step(ev)
     torch.cuda.synchronize()
@@ -783,12 +815,10 @@ def run_integrator(a, w, dev, rank, n_gpus, dist, barrier):
         t = torch.tensor([el], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = t.item()
-    # kernels are launched on torch's current stream (ops._stream), so these events bracket the rollout kernel
-    roll_ms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in evs]))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {'zt': zt})             # Flow.forward's result: (batch, T, D) latent trajectories
     total_traj = w['batch'] * n_gpus * a.steps
     value = total_traj / el
-    flops_per_launch = w['mflop'] * 1e6 * w['batch']
-    achieved = flops_per_launch / (roll_ms * 1e-3) / 1e12
     out = {
         'metric': 'latent_trajectories_per_sec', 'value': value, 'unit': 'trajectories/s',
         'n_gpus': n_gpus, 'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': el / a.steps * 1e3,
@@ -796,14 +826,22 @@ def run_integrator(a, w, dev, rank, n_gpus, dist, barrier):
         'config': {'workload': w['desc'] + '; step = GP draw (K_uu, Cholesky, nu) + rk4 rollout, L=1 [integrator fwd]',
                    'global_batch': w['batch'] * n_gpus, 'solver': 'rk4 (3/8 rule)', 'parallelism': 'dp%d' % n_gpus,
                    'hip_graph': graphed},
-        'roofline': {'bound': 'mfma', 'kernel': 'rollout_kernel', 'achieved': achieved, 'peak': PEAK_FP32_TFLOPS,
-                     'unit': 'TFLOP/s', 'frac': achieved / PEAK_FP32_TFLOPS, 'traffic': None,
-                     'ms_per_launch': roll_ms,
-                     'note': 'fp32 VALU+transcendental kernel priced against the fp32 peak (vector = MFMA = 157.3 TF); '
-                             'algorithmic flops = %.3f MFLOP/traj x %d traj (SURVEY 8d)' % (w['mflop'], w['batch'])},
     }
     if rank == 0:
-        print('[bench] gpu leg done: %.1f traj/s, rollout %.3f ms/launch' % (value, roll_ms), file=sys.stderr, flush=True)
+        print('[bench] gpu leg done: %.1f traj/s, %.3f ms/step' % (value, el / a.steps * 1e3), file=sys.stderr, flush=True)
+    if not a.full:
+        return out
+    # kernels are launched on torch's current stream (ops._stream), so these events bracket the rollout kernel
+    roll_ms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in evs]))
+    flops_per_launch = w['mflop'] * 1e6 * w['batch']
+    achieved = flops_per_launch / (roll_ms * 1e-3) / 1e12
+    out['roofline'] = {'bound': 'mfma', 'kernel': 'rollout_kernel', 'achieved': achieved, 'peak': PEAK_FP32_TFLOPS,
+                       'unit': 'TFLOP/s', 'frac': achieved / PEAK_FP32_TFLOPS, 'traffic': None,
+                       'ms_per_launch': roll_ms,
+                       'note': 'fp32 VALU+transcendental kernel priced against the fp32 peak (vector = MFMA = 157.3 TF); '
+                               'algorithmic flops = %.3f MFLOP/traj x %d traj (SURVEY 8d)' % (w['mflop'], w['batch'])}
+    if rank == 0:
+        print('[bench] rollout %.3f ms/launch' % roll_ms, file=sys.stderr, flush=True)
         if not a.no_cpu_baseline and n_gpus == 1:
             out['cpu_baseline'] = cpu_baseline(w, p, nz, z0, ts)
             out['gpu_over_cpu'] = value / out['cpu_baseline']['value']

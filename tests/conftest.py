@@ -16,8 +16,16 @@ def pytest_configure(config):
 
 
 def load_golden(name):
-    z = np.load(os.path.join(GOLDEN, name + '.npz'))
-    return {k: torch.from_numpy(z[k]) for k in z.files}
+    """A fixture is name.npz, followed by name.1.npz, name.2.npz, ... when it is split to keep every file under 1 MiB
+    (tests/golden/make_golden.py:save_fixture): the blocks of a key are concatenated along axis 0 in file order."""
+    blocks, i, fn = {}, 0, os.path.join(GOLDEN, name + '.npz')
+    while os.path.exists(fn) or i == 0:
+        z = np.load(fn)
+        for k in z.files:
+            blocks.setdefault(k, []).append(z[k])
+        i += 1
+        fn = os.path.join(GOLDEN, '%s.%d.npz' % (name, i))
+    return {k: torch.from_numpy(v[0] if len(v) == 1 else np.concatenate(v)) for k, v in blocks.items()}
 
 
 def sub(d, prefix):

@@ -158,6 +158,26 @@ def npy(t):
     return t.detach().cpu().numpy()
 
 
+def save_fixture(name, out, budget=900_000):
+    """np.savez_compressed, split so that no file exceeds the repository's 1 MiB limit: a fixture larger than `budget` raw bytes
+    goes to name.npz, name.1.npz, name.2.npz, ..., an array larger than `budget` is cut into row blocks, and no file holds two
+    blocks of one array.  tests/conftest.py:load_golden concatenates the blocks of each key along axis 0 in file order."""
+    pieces = []
+    for k, v in out.items():
+        v = np.asarray(v)
+        rows = max(1, budget // max(1, v[:1].nbytes)) if v.ndim and v.nbytes > budget else None
+        pieces += [(k, v[i:i + rows]) for i in range(0, len(v), rows)] if rows else [(k, v)]
+    parts, size = [{}], 0
+    for k, v in pieces:
+        if parts[-1] and (k in parts[-1] or size + v.nbytes > budget):
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += v.nbytes
+    for i, part in enumerate(parts):
+        np.savez_compressed(os.path.join(OUT, name + ('.%d' % i if i else '') + '.npz'), **part)
+
+
 def gp_case(name, kernel, order, N, M, S, q, T, seed, uniform_hyper=False, spread=0.25, q_diag=False, dimwise=True):
     """GP layer + flow goldens (no images)."""
     out = {}
@@ -203,7 +223,7 @@ def gp_case(name, kernel, order, N, M, S, q, T, seed, uniform_hyper=False, sprea
         out['grad_' + solver + '.z0'] = npy(z0.grad)
         for kk, p in model.flow.named_parameters():
             out['grad_' + solver + '.' + kk] = npy(p.grad)
-    np.savez_compressed(os.path.join(OUT, name + '.npz'), **out)
+    save_fixture(name, out)
     print(name, {k: v.shape for k, v in out.items() if k.startswith(('zt', 'nu', 'Ku'))})
 
 
@@ -241,7 +261,7 @@ def model_case(name, kernel, order, N, M, S, q, T, L, solver, seed):
     for kk in sd1:
         if 'running' in kk or 'num_batches' in kk:
             out['sd_after.' + kk] = npy(sd1[kk])
-    np.savez_compressed(os.path.join(OUT, name + '.npz'), **out)
+    save_fixture(name, out)
     print(name, 'loss', float(loss), 'nlhood', float(nlhood), 'kl_reg', float(kl_reg), 'kl_u', float(kl_u))
 
 
@@ -265,7 +285,7 @@ def model_case_intermediates(name, kernel, order, N, M, S, q, T, L, solver, seed
     out = dict(Xrec=npy(Xrec), s_mu=npy(s_mu), s_logv=npy(s_logv), z0=npy(captured['z0']), ztL=npy(captured['ztL']))
     if order == 2:
         out.update(v_mu=npy(v_mu), v_logv=npy(v_logv))
-    np.savez_compressed(os.path.join(OUT, name + '_fwd.npz'), **out)
+    save_fixture(name + '_fwd', out)
 
 
 def cond_case(name, order, q, M, N, seed, q_diag=False, dimwise=True):
@@ -283,7 +303,7 @@ def cond_case(name, order, q, M, N, seed, q_diag=False, dimwise=True):
         mean_f, cov = gp.build_conditional(x, full_cov=True)
     out = {'sd.' + k: npy(v) for k, v in model.state_dict().items() if k.startswith('flow.odefunc.diffeq')}
     out.update(x=npy(x), mean=npy(mean), var=npy(var), mean_full=npy(mean_f), cov=npy(cov))
-    np.savez_compressed(os.path.join(OUT, name + '.npz'), **out)
+    save_fixture(name, out)
 
 
 def data_case(name, seed):

@@ -6,7 +6,7 @@ R=$PWD
 T=${1:-rXX}
 O=$R/gpurun_out/$T
 mkdir -p $O
-timeout -k 10 300 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 300 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 tail -c 400 $O/bench_default.json; echo
 cd /tmp && export TMPDIR=/tmp
 for W in cfg2 cfg1; do
