@@ -128,10 +128,10 @@ template <class L, int NCS_> struct BwdDataPolicy {
 template <class PL> constexpr bool igemm_tf_in_pad() { return PL::PS % 4 == 0 && (PL::HP * PL::HP + 3) / 4 * 4 + 4 <= PL::PS; }
 
 // All k-steps (tap x 4*KB source channels) of NG pixel tiles x NCJ channel tiles of one wavefront.
-template <class CG, int NG, int TG, int NCJ, int KC, int WROW, int PS, int KBMAX = 8>
+template <class CG, int NG, int TG, int NCJ, int KC, int WROW, int PS>
 __device__ __forceinline__ void igemm_tile_mma(const float* __restrict__ s_img, const float* __restrict__ sw, const int (&abase)[TG],
                                                int lk, int lr, f32x4 (&acc)[TG][NCJ]) {
-  constexpr int KB = (KC / 4) < KBMAX ? (KC / 4) : KBMAX;   // MFMA k-steps per fetch batch
+  constexpr int KB = (KC / 4) < 8 ? (KC / 4) : 8;   // MFMA k-steps per fetch batch
   constexpr int NB = KC / (4 * KB);                 // batches per tap
   constexpr int nsteps = CG::ntaps * NB;
   float bfA[KB][NCJ], afA[KB][NG], bfB[KB][NCJ], afB[KB][NG];
@@ -158,27 +158,13 @@ __device__ __forceinline__ void igemm_tile_mma(const float* __restrict__ s_img, 
   };
   fetch(0, bfA, afA);
   int s = 0;
-  if constexpr (KBMAX < 8) {
-    // three wavefronts per SIMD (168 registers): keep the k loop a loop -- unrolled over all taps the scheduler hoists the operand
-    // fetches of every step to the top and spills
-#pragma nounroll
-    while (true) {
-      if (s + 1 < nsteps) fetch(s + 1, bfB, afB);
-      mma(bfA, afA);
-      if (++s >= nsteps) break;
-      if (s + 1 < nsteps) fetch(s + 1, bfA, afA);
-      mma(bfB, afB);
-      if (++s >= nsteps) break;
-    }
-  } else {
-    while (true) {
-      if (s + 1 < nsteps) fetch(s + 1, bfB, afB);
-      mma(bfA, afA);
-      if (++s >= nsteps) break;
-      if (s + 1 < nsteps) fetch(s + 1, bfA, afA);
-      mma(bfB, afB);
-      if (++s >= nsteps) break;
-    }
+  while (true) {
+    if (s + 1 < nsteps) fetch(s + 1, bfB, afB);
+    mma(bfA, afA);
+    if (++s >= nsteps) break;
+    if (s + 1 < nsteps) fetch(s + 1, bfA, afA);
+    mma(bfB, afB);
+    if (++s >= nsteps) break;
   }
 }
 
@@ -188,22 +174,19 @@ extern __shared__ __attribute__((aligned(16))) float igemm_smem[];
 // NCJ: channel tiles per job.  PAIR: process the px = 0 / px = 1 classes of a row parity together and store float2
 // (stride-2 layers with an even output width: without it every 64-byte line of y is written twice, half each time --
 // measured 401 MB of HBM writes for a 205 MB output).
-// PC (producer / consumer; NTHR = 768, double-buffered planes): wavefronts 0..7 only multiply and store -- wavefronts 8..11 (one per
-// SIMD, raised priority) fetch the next group from HBM and scatter it into the other plane buffer meanwhile; ONE barrier per group.
-// In the other forms all wavefronts walk through fetch, scatter, multiply and store in lockstep, and the matrix pipe idles in every
-// phase but one (tools/convt_probe.hip: the MFMA phase is 62 % of a decnn.7 forward wavefront's life and pipe-bound inside).
+// All wavefronts walk through fetch, scatter, multiply and store in lockstep, and the matrix pipe idles in every phase but one
+// (tools/convt_probe.hip: the MFMA phase is 62 % of a decnn.7 forward wavefront's life and pipe-bound inside); the producer /
+// consumer form of the decnn.7 input gradient is conv_bwd_v2.hpp.
 // STATS: the BatchNorm statistics of the OUTPUT are summed while it is stored and finalised by the last workgroup (bn_sink.hpp).
-template <class PL, int IPB, int TG, int NCJ, bool PAIR, int NTHR, bool DB = false, bool PC = false, bool STATS = false>
+template <class PL, int IPB, int TG, int NCJ, bool PAIR, int NTHR, bool DB = false, bool STATS = false>
 __global__ __launch_bounds__(NTHR, NTHR == 256 ? 2 : 1) void k_conv_igemm(const float* __restrict__ x, const float* __restrict__ w,
                                                       const float* __restrict__ bias, float* __restrict__ y, int B,
                                                       const float* __restrict__ in_bn, BnSink sink) {
   constexpr int KC = PL::KC, NC = PL::NC, NCS = PL::NCS, NCLS = PL::NCLS, SH = PL::SH, OH = PL::OH, HP = PL::HP, PS = PL::PS;
   constexpr int PADL = PL::PADL, WROW = PL::WROW, NWE = PL::NWE;
   static_assert(NCS % 16 == 0 && NC % NCS == 0 && KC % 4 == 0 && NTHR % 256 == 0, "MFMA tiling");
-  static_assert(!PC || (NTHR == 768 && DB), "producer / consumer form: 8 + 4 wavefronts on double-buffered planes");
-  constexpr int NW = PC ? 8 : NTHR / 64;             // wavefronts that run the jobs
-  constexpr int PT = PC ? 256 : NTHR;                // threads that fetch and scatter the source images
-  constexpr int KBM = PC ? 4 : 8;                    // k-steps per operand fetch batch (PC: three wavefronts per SIMD, 168 registers)
+  constexpr int NW = NTHR / 64;                      // wavefronts that run the jobs
+  constexpr int PT = NTHR;                           // threads that fetch and scatter the source images
   constexpr int NCO = NCS / 16;                      // channel tiles per pass
   static_assert(NCO % NCJ == 0, "channel tiles per job");
   constexpr int NJ = NCO / NCJ;                      // job columns per pixel tile
@@ -230,7 +213,7 @@ __global__ __launch_bounds__(NTHR, NTHR == 256 ? 2 : 1) void k_conv_igemm(const 
   auto tf_slot = [&](int ch) -> float4* { return TF_PAD ? reinterpret_cast<float4*>(s_img + ch * PS + TFO) : s_tf_tail + ch; };
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lr = lane & 15, lk = lane >> 4;
-  const int ptid = PC ? tid - 512 : tid;             // index among the fetching threads (PC: negative in the consumers, unused there)
+  const int ptid = tid;                              // index among the fetching threads
   const int ngroups = (B + IPB - 1) / IPB;
   const float4* x4 = reinterpret_cast<const float4*>(x);
   // wavefront w runs on SIMD w & 3: order the wavefronts SIMD-major so that each SIMD owns a contiguous cost range
@@ -287,8 +270,7 @@ __global__ __launch_bounds__(NTHR, NTHR == 256 ? 2 : 1) void k_conv_igemm(const 
 #pragma unroll
       for (int i = 0; i < NLD; ++i) {
         const int f = ptid + PT * i;
-        if (PC) pre[i] = src[min(f, nf4 - 1)];       // unconditional (clamped): no branch and no vmcnt(0) per load
-        else if (f < nf4) pre[i] = src[f];
+        if (f < nf4) pre[i] = src[f];
       }
     };
     // the prefetched source group -> zero-padded planes (BatchNorm + ReLU on the way when in_bn)
@@ -375,10 +357,10 @@ __global__ __launch_bounds__(NTHR, NTHR == 256 ? 2 : 1) void k_conv_igemm(const 
           auto run = [&](auto gtag, const float* sw, const int (&ab)[TG], f32x4 (&ac)[TG][NCJ]) {
             using GG = typename decltype(gtag)::type;
             switch (ng) {                            // wave-uniform
-              case 1: igemm_tile_mma<GG, 1, TG, NCJ, KC, WROW, PS, KBM>(img, sw, ab, lk, lr, ac); break;
-              case 2: if constexpr (TG >= 2) igemm_tile_mma<GG, 2, TG, NCJ, KC, WROW, PS, KBM>(img, sw, ab, lk, lr, ac); break;
-              case 3: if constexpr (TG >= 3) igemm_tile_mma<GG, 3, TG, NCJ, KC, WROW, PS, KBM>(img, sw, ab, lk, lr, ac); break;
-              default: if constexpr (TG >= 4) igemm_tile_mma<GG, 4, TG, NCJ, KC, WROW, PS, KBM>(img, sw, ab, lk, lr, ac); break;
+              case 1: igemm_tile_mma<GG, 1, TG, NCJ, KC, WROW, PS>(img, sw, ab, lk, lr, ac); break;
+              case 2: if constexpr (TG >= 2) igemm_tile_mma<GG, 2, TG, NCJ, KC, WROW, PS>(img, sw, ab, lk, lr, ac); break;
+              case 3: if constexpr (TG >= 3) igemm_tile_mma<GG, 3, TG, NCJ, KC, WROW, PS>(img, sw, ab, lk, lr, ac); break;
+              default: if constexpr (TG >= 4) igemm_tile_mma<GG, 4, TG, NCJ, KC, WROW, PS>(img, sw, ab, lk, lr, ac); break;
             }
           };
           run(std::common_type<G>{}, swc + jc * NCJ * 16, abase, acc);
@@ -415,33 +397,7 @@ __global__ __launch_bounds__(NTHR, NTHR == 256 ? 2 : 1) void k_conv_igemm(const 
       });
       if (pf_grp >= 0) prefetch(pf_grp);             // a wavefront without a job in this group
     };
-    if constexpr (PC) {
-      const bool producer = wave >= 8;
-      int cur = 0;
-      if (producer) {
-        __builtin_amdgcn_s_setprio(3);               // the youngest wavefront of its SIMD: let it issue whenever it can
-        if (gfirst < ngroups) prefetch(gfirst);
-      }
-      __syncthreads();                               // zero fill, slabs, table
-      if (producer) {
-        if (gfirst < ngroups) scatter(s_img, min(IPB, B - gfirst * IPB));
-        if (gfirst + gstride < ngroups) prefetch(gfirst + gstride);
-      }
-      __syncthreads();
-      for (int grp = gfirst; grp < ngroups; grp += gstride) {
-        const int b0 = grp * IPB, nxt = grp + gstride;
-        if (producer) {
-          if (nxt < ngroups) {
-            scatter(s_img + (cur ^ 1) * (IPB * IMG), min(IPB, B - nxt * IPB));
-            if (nxt + gstride < ngroups) prefetch(nxt + gstride);
-          }
-        } else {
-          jobs(s_img + cur * (IPB * IMG), b0, min(IPB, B - b0));
-        }
-        __syncthreads();                             // next buffer complete; this one free for the group after next
-        cur ^= 1;
-      }
-    } else if constexpr (!DB) {
+    if constexpr (!DB) {
       if (gfirst < ngroups) prefetch(gfirst);
       for (int grp = gfirst; grp < ngroups; grp += gstride) {
         const int b0 = grp * IPB;

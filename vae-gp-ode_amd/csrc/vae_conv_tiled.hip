@@ -375,23 +375,18 @@ static bool use_mfma() {
 // workgroups a BnSink's partial sums must have room for (every statistics-producing launch below stays within it)
 constexpr int kSinkMaxWg = 512;
 
-template <class PL, int IPB, int TG, int NCJ, bool PAIR = false, int NTHR = 512, bool DB = false, bool PC = false, bool STATS = false>
+template <class PL, int IPB, int TG, int NCJ, bool PAIR = false, int NTHR = 512, bool DB = false, bool STATS = false>
 static int launch_igemm(const float* x, const float* w, const float* bias, float* y, int B, hipStream_t st, const char* what,
                         const float* in_bn = nullptr, const BnSink* sink = nullptr) {
   constexpr size_t lds = igemm_lds_bytes<PL, IPB, DB, STATS>();
   static_assert(lds <= (NTHR >= 512 ? 160 : 80) * 1024, "LDS budget");
-  auto km = k_conv_igemm<PL, IPB, TG, NCJ, PAIR, NTHR, DB, PC, STATS>;
+  auto km = k_conv_igemm<PL, IPB, TG, NCJ, PAIR, NTHR, DB, STATS>;
   if (set_max_lds((const void*)km, lds)) return 1;
   const int ngroups = (B + IPB - 1) / IPB;
   const int cap = num_cus() * (NTHR >= 512 ? 1 : 2);
   if (STATS && cap > kSinkMaxWg) return set_error("%s: more workgroups than the statistics scratch holds", what);
   hipLaunchKernelGGL(km, ngroups < cap ? ngroups : cap, NTHR, lds, st, x, w, bias, y, B, in_bn, STATS ? *sink : BnSink{});
   return check_launch(what);
-}
-
-static bool conv_pc_enabled() {     // A/B only (GPODE_CONV_PC=1): see launch_T1
-  static const bool on = [] { const char* e = getenv("GPODE_CONV_PC"); return e && e[0] == '1'; }();
-  return on;
 }
 
 // IPB: images per workgroup of the VALU kernel; IPBM / COS: images per group and output channels per pass of the MFMA kernel
@@ -411,15 +406,8 @@ static int launch_T1(const float* x, const float* w, const float* bias, float* y
       // the kernel to begin with -- the idle matrix-pipe cycles are not in the phases the second buffer overlaps.
       static const bool db = [] { const char* e = getenv("GPODE_DEC7_FWD_DB"); return e && e[0] == '1'; }();
       if (db) return launch_igemm<FwdPolicy<L, COS>, 1, TG, COS / 16, PAIR, 512, true>(x, w, bias, y, B, st, "convT_fwd_mfma", in_bn);
-      // GPODE_CONV_PC=1 (A/B only): producer / consumer wavefronts (conv_mfma.hpp, PC) -- one image per buffer, 8 multiplying + 4
-      // fetching wavefronts, one barrier per image.  Measured SLOWER as a port of this engine's job loop (4096 images: 0.274 vs
-      // 0.241 ms): three wavefronts per SIMD leave 168 registers, which the tile-group loop (16 copies of the k loop after the
-      // compiler's unswitching) only fits with one pixel tile per job -- two LDS operand reads per MFMA and conditional prefetches.
-      // The weight-gradient engine (conv_wgrad_v2.hpp) got its gain from a loop written FOR that budget; this one would need the same.
-      if (conv_pc_enabled() && B > 2 * num_cus() && !sink)
-        return launch_igemm<FwdPolicy<L, COS>, 1, 2, COS / 16, PAIR, 768, true, true>(x, w, bias, y, B, st, "convT_fwd_mfma_pc", in_bn);
     }
-    if (sink) return launch_igemm<FwdPolicy<L, COS>, IPBM, TG, COS / 16, PAIR, 512, false, false, true>(x, w, bias, y, B, st, "convT_fwd_mfma_stats", in_bn, sink);
+    if (sink) return launch_igemm<FwdPolicy<L, COS>, IPBM, TG, COS / 16, PAIR, 512, false, true>(x, w, bias, y, B, st, "convT_fwd_mfma_stats", in_bn, sink);
     return launch_igemm<FwdPolicy<L, COS>, IPBM, TG, COS / 16, PAIR>(x, w, bias, y, B, st, "convT_fwd_mfma", in_bn);
   }
   if (sink) return set_error("convT forward with output statistics needs the matrix-core path (16-byte aligned input, GPODE_CONV_VALU unset)");
@@ -570,6 +558,14 @@ int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx
   return -1;
 }
 
+// second convolution engine (conv_bwd_v2.hpp, its own translation unit vae_conv_v2.hip): decnn.7 d/d input on producer / consumer
+// wavefronts with the weights in registers.  GPODE_CONV_V1=1: the first engine (A/B)
+int conv_v2_dec7_bwd_data(const float* gy, const float* w, float* gx, int B, hipStream_t st);
+static bool conv_v2_enabled() {
+  static const bool off = [] { const char* e = getenv("GPODE_CONV_V1"); return e && e[0] == '1'; }();
+  return !off && use_mfma();
+}
+
 // ConvTranspose2d d/d input (conv geometry: x := grad_output (B,Ci,H,W) -> y (B,Co,Ho,Wo)), no bias
 int tiled_fwd(const float* x, const float* w, const float* bias, float* y, int B, int Ci, int H, int W, int Co, int K, int S, int P,
               int Ho, int Wo, hipStream_t st) {
@@ -579,7 +575,10 @@ int tiled_fwd(const float* x, const float* w, const float* bias, float* y, int B
     if (matches<Enc6>(Ci, Co, H, Ho, K, S, P)) return launch_igemm<BwdDataPolicy<Enc6, 32>, 8, 1, 2>(x, w, bias, y, B, st, "enc_conv6_fwd_mfma");
   }
   if (bias) return -1;
-  if (matches<Dec7>(Ci, Co, H, Ho, K, S, P)) return launch_T2<Dec7, 2, 8, 1, 16, 2, 1, 256>(x, w, y, B, st);
+  if (matches<Dec7>(Ci, Co, H, Ho, K, S, P)) {
+    if (conv_v2_enabled() && (reinterpret_cast<uintptr_t>(x) & 15) == 0) return conv_v2_dec7_bwd_data(x, w, y, B, st);
+    return launch_T2<Dec7, 2, 8, 1, 16, 2, 1, 256>(x, w, y, B, st);
+  }
   // decnn.4 d/d input: 36 output pixels per image; two images and two 16-channel halves per pass make 10 equal jobs for 8
   // wavefronts (tools/convt_probe.hip: 28 % of wavefront 0's cycles in the group barrier).  Three images per group with 16
   // channels per pass (7 jobs, one idle wavefront) was measured and is NOT faster (0.455 vs 0.444 ms for d/d input + d/d weight at
