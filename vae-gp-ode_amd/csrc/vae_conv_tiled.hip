@@ -558,9 +558,10 @@ int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx
   return -1;
 }
 
-// second convolution engine (conv_bwd_v2.hpp, its own translation unit vae_conv_v2.hip): decnn.7 d/d input on producer / consumer
-// wavefronts with the weights in registers.  GPODE_CONV_V1=1: the first engine (A/B)
+// second convolution engine (conv_bwd_v2.hpp, its own translation unit vae_conv_v2.hip): decnn.7 and decnn.4 d/d input on producer /
+// consumer wavefronts with the weights in registers.  GPODE_CONV_V1=1: the first engine (A/B)
 int conv_v2_dec7_bwd_data(const float* gy, const float* w, float* gx, int B, hipStream_t st);
+int conv_v2_dec4_bwd_data(const float* gy, const float* w, float* gx, int B, hipStream_t st);
 static bool conv_v2_enabled() {
   static const bool off = [] { const char* e = getenv("GPODE_CONV_V1"); return e && e[0] == '1'; }();
   return !off && use_mfma();
@@ -579,11 +580,12 @@ int tiled_fwd(const float* x, const float* w, const float* bias, float* y, int B
     if (conv_v2_enabled() && (reinterpret_cast<uintptr_t>(x) & 15) == 0) return conv_v2_dec7_bwd_data(x, w, y, B, st);
     return launch_T2<Dec7, 2, 8, 1, 16, 2, 1, 256>(x, w, y, B, st);
   }
-  // decnn.4 d/d input: 36 output pixels per image; two images and two 16-channel halves per pass make 10 equal jobs for 8
+  // decnn.4 d/d input, first engine: 36 output pixels per image; two images and two 16-channel halves per pass make 10 equal jobs for 8
   // wavefronts (tools/convt_probe.hip: 28 % of wavefront 0's cycles in the group barrier).  Three images per group with 16
   // channels per pass (7 jobs, one idle wavefront) was measured and is NOT faster (0.455 vs 0.444 ms for d/d input + d/d weight at
-  // 4096 images: twice the passes over the source images eat the gain); GPODE_DEC4_BWD_3IMG=1 selects it for A/B.
+  // 4096 images: twice the passes over the source images eat the gain); GPODE_DEC4_BWD_3IMG=1 selects it for A/B (with GPODE_CONV_V1=1).
   if (matches<Dec4>(Ci, Co, H, Ho, K, S, P)) {
+    if (conv_v2_enabled() && (reinterpret_cast<uintptr_t>(x) & 15) == 0) return conv_v2_dec4_bwd_data(x, w, y, B, st);
     static const bool alt = [] { const char* e = getenv("GPODE_DEC4_BWD_3IMG"); return e && e[0] == '1'; }();
     if (alt) return launch_T2<Dec4, 3, 8, 3, 16, 1, 1>(x, w, y, B, st);
     return launch_T2<Dec4, 3, 8, 2, 32, 1, 1>(x, w, y, B, st);
