@@ -324,6 +324,24 @@ int gpode_dec10_bn_bwd_apply(const float* c, const float* gy, const float* w, co
  * gy == NULL: out = y = relu?(affine(x)); gy != NULL: out = d/dx (frozen layer: no affine gradients). */
 int gpode_bn_eval(const float* x, const float* gy, const float* gamma, const float* beta, const float* running_mean,
                   const float* running_var, float eps, float* out, int B, int C, int HW, int relu, void* stream);
+/* Evaluation-mode BatchNorm as a table: table[C][4] = {running_mean, rsqrtf(running_var + eps), gamma, beta}, the layout
+ * gpode_bn_stats writes, so gpode_conv2d_bwd_data_bn runs a frozen decoder (the notebooks' `odegpvae.eval()`,
+ * plots_dynamics.ipynb cell 13; create_plots.py:19-23) without materialising the normalised activations.  The inverse standard
+ * deviation is formed as gpode_bn_eval forms it.  Reads the module's buffers and writes none of them. */
+int gpode_bn_eval_table(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps, float* table,
+                        int C, void* stream);
+/* The decoder's last stage on a frozen decoder fused with the posterior-predictive statistics (plots_dynamics.ipynb cell 13,
+ * compute_mse_std: `Xrec = sigmoid(decnn.10(...))`, `se = (Xrec - X) ** 2`, `torch.mean(se)`, `torch.std(se)`; and the mean / variance
+ * of Xrec over the draws).  c: raw decnn.7 output of Lc x F images of 16 x 28 x 28 floats laid out (draw, frame), F = N * Th frames;
+ * table: decnn.8's {mean, invstd, gamma, beta}; w, bias: decnn.10; X: targets (N, T_obs, 1, 28, 28), frame n * Th + t has one iff
+ * t < T_obs (T_obs <= Th).  State, updated in place, neither logits nor reconstructions are written:
+ *   pred_mean, pred_m2 [F][784]  Welford mean / M2 of sigmoid(logit) over the draws (both may be NULL)
+ *   se_state [F][3]              {count, mean, M2} of the squared error over draws and pixels of the frame
+ *   done                         draws already folded into the state (0: the state is initialised, not read)
+ * Deterministic: the draws of a frame are folded in order by one workgroup, so any split of the draws over launches gives the same
+ * bits as one launch.  The F frame states are combined on the host in double precision (evaluate.merge_states). */
+int gpode_dec10_predict(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th,
+                        int T_obs, int done, float* pred_mean, float* pred_m2, float* se_state, void* stream);
 /* out[c] = sum_{b,hw} v[b,c,hw] (bias gradients); scratch: gpode_bn_scratch(B,C) floats. */
 int gpode_chan_sum(const float* v, float* out, int B, int C, int HW, float* scratch, void* stream);
 /* mode 0: ReLU, 1: sigmoid (vae.py:60,121).  Backward takes the forward OUTPUT y. */

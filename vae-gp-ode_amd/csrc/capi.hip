@@ -377,6 +377,16 @@ int gpode_bn_eval(const float* x, const float* gy, const float* gamma, const flo
   if (!x || !gamma || !beta || !running_mean || !running_var || !out) return gp::set_error("gpode_bn_eval: null pointer");
   return gp::bn_eval(x, gy, gamma, beta, running_mean, running_var, eps, out, B, C, HW, relu, GP_ST);
 }
+int gpode_bn_eval_table(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps, float* table,
+                        int C, void* stream) {
+  if (!gamma || !beta || !running_mean || !running_var || !table) return gp::set_error("gpode_bn_eval_table: null pointer");
+  return gp::bn_eval_table(gamma, beta, running_mean, running_var, eps, table, C, GP_ST);
+}
+int gpode_dec10_predict(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th,
+                        int T_obs, int done, float* pred_mean, float* pred_m2, float* se_state, void* stream) {
+  if (!c || !table || !w || !X || !se_state) return gp::set_error("gpode_dec10_predict: null pointer");
+  return gp::dec10_predict(c, table, w, bias, X, Lc, F, Th, T_obs, done, pred_mean, pred_m2, se_state, GP_ST);
+}
 int gpode_chan_sum(const float* v, float* out, int B, int C, int HW, float* scratch, void* stream) {
   if (!v || !out || !scratch) return gp::set_error("gpode_chan_sum: null pointer");
   return gp::chan_sum(v, out, B, C, HW, scratch, GP_ST);

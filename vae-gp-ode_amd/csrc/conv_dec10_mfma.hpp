@@ -107,6 +107,164 @@ __global__ __launch_bounds__(512) void k_fwd(const float* __restrict__ x, const 
 }
 
 // ---------------------------------------------------------------------------------------------
+// posterior-predictive last stage (evaluation: the notebooks' compute_mse_std and the predictive moments over the draws).
+// x holds the raw decnn.7 output of Lc x F images laid out (draw, frame), F = N Th frames; frame f = n Th + t has a target
+// X[n][t] iff t < T_obs.  A workgroup owns a FRAME and walks its Lc draws with the tile loop of k_fwd; in the shift-and-add epilogue
+// a thread owns the same one or two pixels for every image, so it carries in registers
+//   per pixel   mean / M2 of z = sigmoid(logit) over the draws (Welford; draw number = done + l + 1),
+// and the workgroup carries
+//   per frame   {count, mean, M2} of e = (z - X)^2 over draws and pixels: every wavefront reduces its 64 .. 128 pixels to {mean, M2 about
+//               that mean}, the 8 wavefronts are merged in a fixed order (Chan et al.) into the image's triple, and that is merged
+//               into the frame's state -- once per draw, so the recurrence does not depend on how the draws are split over
+//               launches, and nothing depends on workgroup arrival order.  Two barriers per image, as k_fwd.
+// Neither logits nor reconstructions are stored.  State in global memory between launches: pred_mean / pred_m2 [F][784] (both NULL:
+// error statistics only), se_state [F][3]; `done` = draws already folded in (0: the state is initialised here, not read).
+// grid <= min(F, CUs), block 512, LDS = 25 * PST + 16 floats.
+// ---------------------------------------------------------------------------------------------
+// pixels owned by the 64 threads of wavefront wv in the epilogue: 64 (o = tid) plus those of o = tid + 512 below 784
+__host__ __device__ constexpr int wave_pixels(int wv) { return 64 + (NP - 512 - 64 * wv > 64 ? 64 : (NP - 512 - 64 * wv > 0 ? NP - 512 - 64 * wv : 0)); }
+
+__global__ __launch_bounds__(512) void k_fwd_predict(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                     const float* __restrict__ in_bn, const float* __restrict__ X, int Lc, int F, int Th,
+                                                     int T_obs, int done, float* __restrict__ pred_mean, float* __restrict__ pred_m2,
+                                                     float* __restrict__ se_state) {
+  float* s_T = igemm_smem;                           // [25][PST], zero borders
+  float* s_r = s_T + KK * PST;                       // [8][2] the wavefronts' {mean, M2} of the current image
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lr = lane & 15, lk = lane >> 4;
+  constexpr int MAXT = (NTILE + 7) / 8;
+  for (int e = tid; e < KK * PST; e += 512) s_T[e] = 0.f;
+  float wa[4][2];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int tap = 16 * c + lr;
+      wa[ks][c] = tap < KK ? w[(size_t)(4 * ks + lk) * KK + tap] : 0.f;
+    }
+  const float bv = bias ? bias[0] : 0.f;
+  float4 tf[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) tf[ks] = reinterpret_cast<const float4*>(in_bn)[4 * ks + lk];
+  float xb[MAXT][4];
+  auto prefetch = [&](int f, int l) {                // image (draw l, frame f)
+    const float* xp = x + ((size_t)l * F + f) * (CI * NP) + lr;
+#pragma unroll
+    for (int j = 0; j < MAXT; ++j) {
+      const int t = wave + 8 * j;
+      if (t < NTILE) {
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) xb[j][ks] = xp[(size_t)(4 * ks + lk) * NP + 16 * t];
+      }
+    }
+  };
+  if ((int)blockIdx.x < F) prefetch(blockIdx.x, 0);
+  __syncthreads();
+  const int o1 = tid + 512;                          // this thread's pixels: tid and (tid < 272) tid + 512
+  const bool two = o1 < NP;
+  const float inv_nw = 1.f / (float)wave_pixels(wave);
+  for (int f = blockIdx.x; f < F; f += gridDim.x) {
+    const int n = f / Th, t = f % Th;
+    const bool has_t = t < T_obs;                    // workgroup-uniform
+    float xt[2] = {0.f, 0.f}, pm[2] = {0.f, 0.f}, pq[2] = {0.f, 0.f};
+    if (has_t) {
+      const float* Xp = X + ((size_t)n * T_obs + t) * NP;
+      xt[0] = Xp[tid];
+      if (two) xt[1] = Xp[o1];
+    }
+    if (pred_mean && done > 0) {
+      pm[0] = pred_mean[(size_t)f * NP + tid]; pq[0] = pred_m2[(size_t)f * NP + tid];
+      if (two) { pm[1] = pred_mean[(size_t)f * NP + o1]; pq[1] = pred_m2[(size_t)f * NP + o1]; }
+    }
+    float sn = 0.f, sm = 0.f, sq = 0.f;              // the frame's {count, mean, M2} of e, identical in every thread
+    if (has_t && done > 0) { sn = se_state[(size_t)f * 3]; sm = se_state[(size_t)f * 3 + 1]; sq = se_state[(size_t)f * 3 + 2]; }
+    for (int l = 0; l < Lc; ++l) {
+#pragma unroll
+      for (int j = 0; j < MAXT; ++j) {
+        const int tl = wave + 8 * j;
+        if (tl < NTILE) {                            // wave-uniform
+          f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+          for (int ks = 0; ks < 4; ++ks) {
+            const float xv = bn_relu(xb[j][ks], tf[ks]);
+#pragma unroll
+            for (int c = 0; c < 2; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[ks][c], xv, acc[c], 0, 0, 0);
+          }
+          const int p = 16 * tl + lr, pa = (p / H + 2) * WP + p % H + 2;
+#pragma unroll
+          for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int tap = 16 * c + 4 * lk + r;
+              if (tap < KK) s_T[tap * PST + pa] = acc[c][r];
+            }
+        }
+      }
+      if (l + 1 < Lc) prefetch(f, l + 1);
+      else if (f + (int)gridDim.x < F) prefetch(f + gridDim.x, 0);
+      __syncthreads();
+      const float kinv = 1.f / (float)(done + l + 1);
+      float ev[2] = {0.f, 0.f};
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int o = tid + 512 * q;
+        if (o < NP) {
+          const int oy = o / H, ox = o % H;
+          const float* tp = s_T + (oy + 4) * WP + ox + 4;
+          float s0 = bv, s1 = 0.f;
+#pragma unroll
+          for (int ky = 0; ky < 5; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 5; ++kx) {
+              const float v = tp[(ky * 5 + kx) * PST - ky * WP - kx];
+              if ((ky * 5 + kx) & 1) s1 += v; else s0 += v;
+            }
+          const float z = 1.f / (1.f + expf(-(s0 + s1)));            // k_act's sigmoid
+          const float d = z - pm[q];
+          pm[q] = __fmaf_rn(d, kinv, pm[q]);
+          pq[q] = __fmaf_rn(d, z - pm[q], pq[q]);
+          const float df = z - xt[q];
+          ev[q] = df * df;
+        }
+      }
+      if (has_t) {
+        // this wavefront's pixels: its mean, then M2 about that mean -- two wavefront reductions, no barrier in between
+        const float in1[1] = {ev[0] + ev[1]};
+        float out1[1];
+        wave_sum_multi<1>(in1, out1);
+        const float mw = out1[0] * inv_nw;
+        const float d0 = ev[0] - mw, d1 = two ? ev[1] - mw : 0.f;
+        const float in2[1] = {__fmaf_rn(d0, d0, d1 * d1)};
+        wave_sum_multi<1>(in2, out1);
+        if (lane == 0) { s_r[2 * wave] = mw; s_r[2 * wave + 1] = out1[0]; }
+      }
+      __syncthreads();                               // s_T is free again; the wavefronts' {mean, M2} are visible
+      if (has_t) {
+        // the 8 wavefronts in a fixed order (Chan et al.; their pixel counts are constants), then the image into the frame
+        float an = 0.f, am = 0.f, aq = 0.f;
+#pragma unroll
+        for (int wv = 0; wv < 8; ++wv) {
+          const float nb = (float)wave_pixels(wv), nn = an + nb, rb = nb / nn;
+          const float dl = s_r[2 * wv] - am;
+          aq = aq + s_r[2 * wv + 1] + dl * dl * (an * rb);
+          am = __fmaf_rn(dl, rb, am);
+          an = nn;
+        }
+        const float nn = sn + (float)NP, dl = am - sm, rb = (float)NP / nn;
+        sq = sq + aq + dl * dl * (sn * rb);
+        sm = __fmaf_rn(dl, rb, sm);
+        sn = nn;
+      }
+    }
+    if (pred_mean) {
+      pred_mean[(size_t)f * NP + tid] = pm[0]; pred_m2[(size_t)f * NP + tid] = pq[0];
+      if (two) { pred_mean[(size_t)f * NP + o1] = pm[1]; pred_m2[(size_t)f * NP + o1] = pq[1]; }
+    }
+    if (tid == 0) { se_state[(size_t)f * 3] = sn; se_state[(size_t)f * 3 + 1] = sm; se_state[(size_t)f * 3 + 2] = sq; }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // d/d input.  grid <= 256, block 512, LDS = IPB planes.
 // ---------------------------------------------------------------------------------------------
 template <int IPB>

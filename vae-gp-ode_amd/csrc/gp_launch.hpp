@@ -160,6 +160,11 @@ int bn_bwd_apply(const float* x, const float* gy, const float* gamma, const floa
                  float* scratch, hipStream_t st);
 int bn_eval(const float* x, const float* gy, const float* gamma, const float* beta, const float* running_mean, const float* running_var,
             float eps, float* out, int B, int C, int HW, int relu, hipStream_t st);
+int bn_eval_table(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps, float* table, int C,
+                  hipStream_t st);
+// decnn.10 of a frozen decoder fused with the predictive statistics over the draws (vae_conv_tiled.hip)
+int dec10_predict(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th, int T_obs,
+                  int done, float* pred_mean, float* pred_m2, float* se_state, hipStream_t st);
 int chan_sum(const float* v, float* out, int B, int C, int HW, float* scratch, hipStream_t st);
 int act_fwd(const float* x, float* y, size_t n, int mode, hipStream_t st);
 int act_bwd(const float* y, const float* gy, float* gx, size_t n, int mode, hipStream_t st);

@@ -614,6 +614,22 @@ int tiled_fwd(const float* x, const float* w, const float* bias, float* y, int B
   return -1;
 }
 
+// decnn.10 on a frozen decoder fused with the predictive statistics over the draws (conv_dec10_mfma.hpp, k_fwd_predict): one workgroup
+// per frame, at most one per CU; the frame's draws are folded in order, so the grid size does not enter the result.
+int dec10_predict(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th, int T_obs,
+                  int done, float* pred_mean, float* pred_m2, float* se_state, hipStream_t st) {
+  if (!use_mfma()) return set_error("gpode_dec10_predict: matrix-core kernel only (GPODE_CONV_VALU is set)");
+  if (Lc < 1 || F < 1 || Th < 1 || T_obs < 1 || T_obs > Th || F % Th != 0 || done < 0)
+    return set_error("gpode_dec10_predict: need Lc, F >= 1, 1 <= T_obs <= Th, F a multiple of Th, done >= 0");
+  if ((pred_mean == nullptr) != (pred_m2 == nullptr)) return set_error("gpode_dec10_predict: pred_mean and pred_m2 go together");
+  if ((reinterpret_cast<uintptr_t>(table) & 15) != 0) return set_error("gpode_dec10_predict: the table must be 16-byte aligned");
+  const size_t lds = sizeof(float) * (dec10::KK * dec10::PST + 16);
+  if (set_max_lds((const void*)dec10::k_fwd_predict, lds)) return 1;
+  hipLaunchKernelGGL(dec10::k_fwd_predict, F < num_cus() ? F : num_cus(), 512, lds, st, c, w, bias, table, X, Lc, F, Th, T_obs, done, pred_mean,
+                     pred_m2, se_state);
+  return check_launch("dec10_predict");
+}
+
 // decnn.10's input gradient fused with the backward of the BatchNorm + ReLU in front of it (conv_dec10_mfma.hpp, k_bwd_data_bn).
 // scratch: part[nwg][16][2] | part_gx[nwg][16][2], nwg <= kDec10BnMaxWg.  The grid is a function of B alone, so the two
 // passes (and the partials they exchange through scratch) agree.

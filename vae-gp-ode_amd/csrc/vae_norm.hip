@@ -597,6 +597,23 @@ int bn_bwd_apply(const float* x, const float* gy, const float* gamma, const floa
   return check_launch("bn_bwd_apply");
 }
 
+// evaluation mode as a TABLE: table[c] = {running_mean, rsqrtf(running_var + eps), gamma, beta}, the layout bn_stats writes, with the
+// inverse standard deviation formed exactly as k_bn_eval forms it -- a convolution that applies bn_relu from this table builds the
+// operand k_bn_eval would have stored.  Reads the module's buffers, writes none.
+__global__ __launch_bounds__(64) void k_bn_eval_table(const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ rmean,
+                                                      const float* __restrict__ rvar, float eps, float* __restrict__ table, int C) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c < C) reinterpret_cast<float4*>(table)[c] = float4{rmean[c], rsqrtf(rvar[c] + eps), gamma[c], beta[c]};
+}
+
+int bn_eval_table(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps, float* table, int C,
+                  hipStream_t st) {
+  if (C < 1) return set_error("gpode_bn_eval_table: C >= 1");
+  if (!aligned16(table)) return set_error("gpode_bn_eval_table: the table must be 16-byte aligned");
+  hipLaunchKernelGGL(k_bn_eval_table, (C + 63) / 64, 64, 0, st, gamma, beta, running_mean, running_var, eps, table, C);
+  return check_launch("bn_eval_table");
+}
+
 // gy == nullptr: forward (out = y); otherwise out = gx
 int bn_eval(const float* x, const float* gy, const float* gamma, const float* beta, const float* running_mean, const float* running_var,
             float eps, float* out, int B, int C, int HW, int relu, hipStream_t st) {

@@ -1,0 +1,213 @@
+"""Posterior-predictive evaluation of a trained model: what the reference's evaluation notebooks compute from a checkpoint
+(experiments/plots_dynamics.ipynb cell 13, ``compute_mse_std``: model in ``eval()``, encode, L function draws, integrate, decode,
+``torch.mean`` / ``torch.std`` of the squared error over every draw, sequence, frame and pixel) and the long roll-out of
+create_plots.py:19-23 (``odegpvae(test_batch, T_custom=Troll*T)``), plus the predictive mean and variance over the draws.
+
+The decoder runs frozen (``Decoder.decode_frozen_raw``: running statistics as tables, BatchNorm + ReLU folded into the transposed
+convolutions) and its last stage is ``gpode_dec10_predict``: the sigmoid, the squared error and every reduction over draws and
+pixels happen in the registers of the convolution's epilogue, so neither the (L,N,T,1,28,28) stack of reconstructions nor any
+element-wise temporary exists.  The kernel leaves one {count, mean, M2} triple per frame; they are combined here, on the host, in
+double precision and in a fixed order (``merge_states``) after one copy of 3 F floats.
+
+Command line (``python -m vae_gp_ode_amd.evaluate``, the flags of ``vae_gp_ode_amd.main`` so a training command line can be
+reused): loads ``--model_path``, evaluates the test split with L = ``--eval_sample_size`` draws, rolls ``--Troll`` * T frames out for
+the first three test sequences, prints one JSON line and writes ``eval.json``, ``rollout_mean.npy``, ``rollout_var.npy`` under
+``--save``.  The draws come from the host generators as in the reference (two of them unseeded there, SURVEY F6, so two runs differ
+by Monte-Carlo noise); ``--device_noise True`` draws on the device, reproducibly from ``--seed``.  Single process: data-parallel
+evaluation is not built.  No plots.
+"""
+import json
+import math
+import os
+import sys
+import time
+import warnings
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+Prediction = namedtuple('Prediction', 'mean var mse std count mse_t state passes')
+Prediction.__doc__ = """mean, var (N,Th,1,28,28): predictive mean and unbiased variance of the decoded images over the L draws (None
+without ``variance``; var is nan for L = 1, as torch.var);  mse, std: mean and unbiased standard deviation of the squared error over
+all ``count`` = L N T_obs 784 elements;  mse_t (T_obs,): error per time step;  state: the (n, mean, M2) triple behind mse / std, for
+merging over batches;  passes: draws per decoder pass."""
+
+
+def merge_states(states):
+    """Combine (n, mean, M2) triples of disjoint samples into one (Chan, Golub & LeVeque), sequentially in the order given, in double
+    precision.  Empty triples (n = 0) are skipped; no triple at all gives (0, 0, 0)."""
+    n, mean, m2 = 0.0, 0.0, 0.0
+    for nb, mb, qb in states:
+        nb, mb, qb = float(nb), float(mb), float(qb)
+        if nb == 0.0:
+            continue
+        if n == 0.0:
+            n, mean, m2 = nb, mb, qb
+            continue
+        tot = n + nb
+        delta = mb - mean
+        mean = mean + delta * (nb / tot)
+        m2 = m2 + qb + delta * delta * (n * nb / tot)
+        n = tot
+    return n, mean, m2
+
+
+def mean_std(state):
+    """(mean, sqrt(M2 / (n - 1))): torch.mean and torch.std (unbiased, its default) of the sample behind the triple; a single element
+    has no standard deviation (nan, as torch gives)."""
+    n, mean, m2 = state
+    if n < 1:
+        return float('nan'), float('nan')
+    return mean, (math.sqrt(max(m2, 0.0) / (n - 1)) if n > 1 else float('nan'))
+
+
+def plan_passes(L, images_per_draw, images_per_pass):
+    """Split L draws of ``images_per_draw`` decoded images each into passes of whole draws of at most ``images_per_pass`` images:
+    a list of (first draw, end draw).  A budget smaller than one draw cannot be met -- a draw is the unit the kernel folds -- so it
+    falls back to one draw per pass and warns."""
+    if L < 1 or images_per_draw < 1 or images_per_pass < 1:
+        raise ValueError('plan_passes: L, images_per_draw and images_per_pass must be positive')
+    per = images_per_pass // images_per_draw
+    if per < 1:
+        warnings.warn('images_per_pass=%d is smaller than one draw (%d images): decoding one draw per pass' % (images_per_pass, images_per_draw))
+        per = 1
+    return [(l0, min(L, l0 + per)) for l0 in range(0, L, per)]
+
+
+class _EvalMode:
+    """model.eval() for the duration of a call; every submodule's own ``training`` flag is put back afterwards."""
+
+    def __init__(self, model):
+        self.model = model
+
+    def __enter__(self):
+        self.flags = [(m, m.training) for m in self.model.modules()]
+        self.model.eval()
+
+    def __exit__(self, *exc):
+        for m, flag in self.flags:
+            m.training = flag
+        return False
+
+
+def predict(model, X, L=1, T_custom=None, images_per_pass=8192, variance=True):
+    """Posterior-predictive statistics of ``model`` (ODEGPVAE) for the sequences X (N,T,1,28,28): encode once, one z0 sample per
+    sequence, L function draws shared by the batch, integrate ``T_custom or T`` steps, decode (positions only for order 2) --
+    the order of operations of the notebook routine -- and reduce inside the decoder's last kernel.  Frames beyond T have no
+    target: they enter the predictive mean / variance and not the error.  The draws go through the decoder in passes of at most
+    ``images_per_pass`` images (8192: the largest image count the decoder's parity tests cover, not a tuned value).
+    ``variance=False``: the error statistics only; the roll-out then stops at T, since the first T frames of a longer one are
+    the same trajectory.  Runs without autograd and in eval mode; leaves every module buffer and ``training`` flag as it found them."""
+    from . import vae_ops as V
+    if X.dim() != 5 or tuple(X.shape[2:]) != (1, 28, 28):
+        raise ValueError('predict: X must be (N,T,1,28,28)')
+    N, T = X.shape[0], X.shape[1]
+    Th = int(T_custom) if T_custom else T
+    if Th < T:
+        raise ValueError('predict: T_custom (%d) must be at least the observed length (%d)' % (Th, T))
+    if not variance:
+        Th = T              # forecast frames have no target: without the moments over the draws nothing would come of them
+    L = int(L)
+    F = N * Th
+    passes = plan_passes(L, F, int(images_per_pass))
+    dec = model.vae.decoder
+    with torch.no_grad(), _EvalMode(model):
+        X = X.contiguous().float()
+        z0, _, _ = model.encode_initial_state(X)
+        ztL = model.sample_trajectories(z0, Th, L)                     # (L,N,Th,order*q)
+        lat = ztL if model.order == 1 else ztL[..., :ztL.shape[-1] // 2]
+        tables = dec._frozen_tables()
+        state = V.PredictState(F, X.device, variance)
+        for l0, l1 in passes:
+            c, t8 = dec.decode_frozen_raw(lat[l0:l1], tables)
+            V.dec10_predict(c, t8, dec.decnn[10].weight, dec.decnn[10].bias, X, Th, state)
+            del c
+        se = state.se.double().cpu().view(N, Th, 3)[:, :T]            # one copy of 3 F floats; frames t >= T hold zeros
+        mean = var = None
+        if variance:
+            mean = state.mean.view(N, Th, 1, 28, 28)
+            var = (state.m2 / (L - 1) if L > 1 else torch.full_like(state.m2, float('nan'))).view(N, Th, 1, 28, 28)
+    total = merge_states(se.reshape(-1, 3).tolist())
+    mse, std = mean_std(total)
+    mse_t = se[:, :, 1].mean(0)                                        # every frame holds the same count L * 784
+    return Prediction(mean, var, mse, std, int(total[0]), mse_t, total, [b - a for a, b in passes])
+
+
+def compute_mse_std(model, loader, L=1, images_per_pass=8192):
+    """(mse, std) of the squared reconstruction error over a whole loader with L draws per batch -- ``compute_mse_std`` of the
+    evaluation notebook: the batches' (n, mean, M2) triples are merged, so the result is the mean / std over all elements."""
+    from .main import _frames
+    dev = next(model.parameters()).device
+    states = [predict(model, _frames(batch).to(dev), L, images_per_pass=images_per_pass, variance=False).state for batch in loader]
+    return mean_std(merge_states(states))
+
+
+def build_from_checkpoint(args):
+    """(model, test loader, checkpoint file) for a parsed command line, the way ``vae_gp_ode_amd.main`` sets a run up: seed, data,
+    model, kernel initialisation, then the checkpoint ``--model_path`` (the .pth file, or the results directory that holds
+    odegpvae_mnist.pth).  As in ``main``, ``--device`` is a place holder: ``args.device`` becomes the current HIP device."""
+    from .main import load_data
+    from .model.core.initialization import initialize_and_fix_kernel_parameters
+    from .model.create_model import build_model
+    from .model.misc.torch_utils import seed_everything
+    seed_everything(args.seed)
+    args.device = torch.device('cuda')
+    fname = args.model_path
+    if os.path.isdir(fname) or not fname.endswith('.pth'):
+        fname = os.path.join(fname, 'odegpvae_mnist.pth')
+    if not os.path.exists(fname):
+        raise SystemExit('--model_path: no checkpoint at %s' % fname)
+    _, testset = load_data(args)
+    model = build_model(args).to(args.device)
+    model = initialize_and_fix_kernel_parameters(model, lengthscale_value=args.lengthscale, variance_value=args.variance, fix=False)
+    model.load_state_dict(torch.load(fname, map_location=args.device))
+    if args.device_noise or args.hip_graph:          # as main.py: draws from the device generator, reproducible from --seed
+        from .model.core.noise import install_device_noise
+        install_device_noise(model, args.seed + 1)
+    return model, testset, fname
+
+
+def main(argv=None):
+    from .main import _frames, make_parser
+    args = make_parser().parse_args(argv)
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        raise SystemExit('vae_gp_ode_amd.evaluate is a single-process tool: data-parallel evaluation is not built '
+                         '(start it without torchrun, or with one rank)')
+    if not torch.cuda.is_available():
+        raise SystemExit('this build runs on an MI355X (no CPU fallback)')
+    model, testset, fname = build_from_checkpoint(args)
+    L = args.eval_sample_size
+
+    torch.cuda.synchronize()
+    t0 = time.time()
+    states, per_step, nseq, first = [], None, 0, None
+    for batch in testset:
+        Xb = _frames(batch).to(args.device)
+        first = Xb if first is None else first
+        p = predict(model, Xb, L, variance=False)
+        states.append(p.state)
+        per_step = p.mse_t * Xb.shape[0] if per_step is None else per_step + p.mse_t * Xb.shape[0]
+        nseq += Xb.shape[0]
+    total = merge_states(states)
+    mse, std = mean_std(total)
+    T = first.shape[1]
+    roll = predict(model, first[:3].contiguous(), L, T_custom=args.Troll * T)
+    torch.cuda.synchronize()
+    ms = (time.time() - t0) * 1e3
+
+    os.makedirs(args.save, exist_ok=True)
+    out = dict(mse=mse, std=std, mse_t=(per_step / nseq).tolist(), L=L, sequences=nseq, T=T, count=int(total[0]),
+               rollout_sequences=int(roll.mean.shape[0]), rollout_T=int(roll.mean.shape[1]), rollout_mse=roll.mse, ms=ms,
+               checkpoint=os.path.abspath(fname), ranks=1)
+    np.save(os.path.join(args.save, 'rollout_mean.npy'), roll.mean.cpu().numpy())
+    np.save(os.path.join(args.save, 'rollout_var.npy'), roll.var.cpu().numpy())
+    with open(os.path.join(args.save, 'eval.json'), 'w') as f:
+        json.dump(out, f)
+    print(json.dumps(out))
+    sys.stdout.flush()
+    return out
+
+
+if __name__ == '__main__':
+    main()

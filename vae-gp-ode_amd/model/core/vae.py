@@ -6,7 +6,9 @@ so checkpoints interchange.  The arithmetic -- convolutions, transposed convolut
 BatchNorm, ReLU/sigmoid, the linear layers and the Bernoulli log-likelihood, forward and backward -- runs in
 the hand-written HIP kernels of csrc/vae_conv.hip through ``vae_ops``; nothing is dispatched to torch.nn.
 BatchNorm runs on batch statistics exactly as the reference's training loop does (it never calls
-``.eval()``); eval-mode BatchNorm (only reached via ``--pretrained`` / ``VAE.test``) is not built.
+``.eval()``).  Evaluation mode (``--pretrained`` / ``VAE.test`` / the evaluation notebooks) runs on the running
+statistics: layer by layer through ``gpode_bn_eval`` in ``forward``, or with each BatchNorm + ReLU folded into the transposed
+convolution behind it in ``Decoder.decode_frozen`` (the route ``evaluate.predict`` takes).
 """
 import numpy as np
 import torch
@@ -128,6 +130,36 @@ class Decoder(nn.Module):
         h = _bn(V.conv_transpose2d(h, d[4].weight, d[4].bias, 2, 1), d[5], relu=True)     # 6 -> 13
         h = _bn(V.conv_transpose2d(h, d[7].weight, d[7].bias, 2, 1, 1), d[8], relu=True)  # 13 -> 28
         return out(V.conv_transpose2d(h, d[10].weight, d[10].bias, 1, 2))
+
+    def _frozen_tables(self):
+        d = self.decnn
+        if any(d[i].training for i in (2, 5, 8)):
+            raise RuntimeError('Decoder.decode_frozen needs the three BatchNorm modules in evaluation mode (module.eval())')
+        return [V.bn_eval_table(d[i]) for i in (2, 5, 8)]
+
+    def decode_frozen_raw(self, x, tables=None):
+        """The frozen decoder up to the RAW output of decnn.7 (B, 16, 28, 28) and the table of decnn.8: what the last stage
+        (decnn.10, or vae_ops.dec10_predict) consumes.  No graph is recorded."""
+        d = self.decnn
+        t2, t5, t8 = tables if tables is not None else self._frozen_tables()
+        with torch.no_grad():
+            flat = x.contiguous().view([int(np.prod(list(x.shape[:-1]))), x.shape[-1]])
+            h = V.linear(flat, self.fc.weight, self.fc.bias)
+            h = h.view(h.size(0), h[0].numel() // 16, 4, 4)                                   # UnFlatten(4)
+            c = V.conv_transpose2d(h, d[1].weight, d[1].bias, 1, 0)                           # 4 -> 6
+            c = V.table_conv_transpose2d(c, t2, d[4].weight, d[4].bias, 2, 1)                 # 6 -> 13
+            c = V.table_conv_transpose2d(c, t5, d[7].weight, d[7].bias, 2, 1, 1)              # 13 -> 28
+        return c, t8
+
+    def decode_frozen(self, x, logits=False):
+        """``forward`` of a decoder whose BatchNorm modules are in evaluation mode, forward only: the running statistics enter as
+        per-channel tables and every BatchNorm + ReLU is applied by the transposed convolution behind it while it stages its input --
+        the same kernels the training path uses, so the normalised activations never go through memory.  Reads the running
+        statistics, updates nothing."""
+        c, t8 = self.decode_frozen_raw(x)
+        with torch.no_grad():
+            y = V.table_conv_transpose2d(c, t8, self.decnn[10].weight, self.decnn[10].bias, 1, 2)
+            return y if logits else V.sigmoid(y)
 
     @property
     def device(self):

@@ -951,3 +951,59 @@ def bernoulli_loglik(X, z):
 
 def bernoulli_loglik_rowsum(X, z, rows):
     return _LogLikRowSum.apply(X, z, rows)
+
+
+# ---- frozen decoder / posterior-predictive evaluation (forward only; evaluate.py) ------------------------------------------------
+def bn_eval_table(bn):
+    """{running_mean, rsqrt(running_var + eps), gamma, beta} per channel of an nn.BatchNorm2d in evaluation mode, (C, 4): the table
+    gpode_conv2d_bwd_data_bn / gpode_dec10_predict apply to the raw output of the layer in front.  Writes no module buffer."""
+    if bn.training:
+        raise _lib.GpodeError('bn_eval_table: the BatchNorm module is in training mode (its batch statistics are not a table of constants)')
+    g = _chk(bn.weight.detach(), 'gamma')
+    table = _new((g.shape[0], 4), g)
+    _lib.call('gpode_bn_eval_table', _ptr(g), _ptr(_chk(bn.bias.detach(), 'beta')), _ptr(_chk(bn.running_mean, 'running_mean')),
+              _ptr(_chk(bn.running_var, 'running_var')), ctypes.c_float(bn.eps), _ptr(table), g.shape[0], _stream())
+    return table
+
+
+def table_conv_transpose2d(c, table, w, b, stride, pad, out_pad=0):
+    """conv_transpose2d(relu(bn(c)), w, b) with the BatchNorm given as a (C, 4) table; no graph is recorded."""
+    c, w, table = _chk(c.detach(), 'c'), _chk(w.detach(), 'weight'), _chk(table, 'table')
+    B, Cin, Hi, Wi = c.shape
+    _, Cout, K, _ = w.shape
+    if tuple(table.shape) != (Cin, 4):
+        raise _lib.GpodeError('table_conv_transpose2d: table must be (%d, 4)' % Cin)
+    Ht, Wt = (Hi - 1) * stride - 2 * pad + K + out_pad, (Wi - 1) * stride - 2 * pad + K + out_pad
+    y = _new((B, Cout, Ht, Wt), c)
+    _lib.call('gpode_conv2d_bwd_data_bn', _ptr(c), _ptr(table), _ptr(w), _ptr(None if b is None else _chk(b.detach(), 'bias')), _ptr(y),
+              B, Cout, Ht, Wt, Cin, K, stride, pad, Hi, Wi, _stream())
+    return y
+
+
+class PredictState:
+    """State of gpode_dec10_predict for F = N * Th frames: Welford mean / M2 of the decoded images over the draws (``variance``),
+    {count, mean, M2} of the squared error per frame, and the number of draws folded in so far."""
+
+    def __init__(self, F, device, variance=True):
+        self.F, self.done = int(F), 0
+        self.mean = torch.zeros(F, 784, dtype=torch.float32, device=device) if variance else None
+        self.m2 = torch.zeros(F, 784, dtype=torch.float32, device=device) if variance else None
+        self.se = torch.zeros(F, 3, dtype=torch.float32, device=device)
+
+
+def dec10_predict(c, table, w, b, X, Th, state):
+    """Fold the draws held in ``c`` -- raw decnn.7 output (Lc * F, 16, 28, 28) laid out (draw, frame) -- into ``state``:
+    sigmoid(decnn.10(relu(bn(c)))) is formed in registers and only its statistics against the targets X (N, T_obs, 1, 28, 28) leave
+    the kernel (frames t >= T_obs of a sequence have no target and add nothing to the error)."""
+    c, w, table, X = _chk(c.detach(), 'c'), _chk(w.detach(), 'weight'), _chk(table, 'table'), _chk(X, 'X')
+    F = state.F
+    N, T_obs = X.shape[0], X.shape[1]
+    if tuple(c.shape[1:]) != (16, 28, 28) or tuple(w.shape) != (16, 1, 5, 5) or tuple(table.shape) != (16, 4):
+        raise _lib.GpodeError('dec10_predict: c (B,16,28,28), weight (16,1,5,5), table (16,4)')
+    if tuple(X.shape[2:]) != (1, 28, 28) or F != N * Th or c.shape[0] % F != 0 or c.shape[0] == 0:
+        raise _lib.GpodeError('dec10_predict: X (N,T_obs,1,28,28), F = N * Th frames, c a whole number of draws of F frames')
+    Lc = c.shape[0] // F
+    _lib.call('gpode_dec10_predict', _ptr(c), _ptr(table), _ptr(w), _ptr(None if b is None else _chk(b.detach(), 'bias')), _ptr(X),
+              Lc, F, int(Th), T_obs, state.done, _ptr(state.mean), _ptr(state.m2), _ptr(state.se), _stream())
+    state.done += Lc
+    return state
