@@ -4,4 +4,3 @@ EXTRA="" run eagerred GPODE_EAGER_REDUCTIONS=1
 EXTRA="" run bn1 GPODE_BN_ONE_LAUNCH=0
 EXTRA="--no-sync-bn" run nosyncbn A=1
 EXTRA="--dp-graph fwdbwd" run fwdbwd A=1
-EXTRA="" run nomarker GPODE_NO_MARKER=1

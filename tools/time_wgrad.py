@@ -1,5 +1,5 @@
 """d/d weight of decnn.7 / decnn.4 alone (gpode_conv2d_bwd_weight[_bn], kernel + reduction of the partials) with HIP events.
-GPODE_WGRAD_V1=1 selects the first engine.  usage: python tools/time_wgrad.py [images]"""
+usage: python tools/time_wgrad.py [images]"""
 import ctypes
 import os
 import sys
@@ -35,6 +35,5 @@ for name, Cin, Cout, Hi, Ht, K, S, P, macs in LAYERS:
         e1.record()
         torch.cuda.synchronize()
         ms = e0.elapsed_time(e1) / 20
-        print('%s d/d weight%s  %d images  %.1f us  %.1f TFLOP/s  frac %.2f   (%s engine)' % (
-            name, ' + BN/ReLU input' if bn else '', B, ms * 1e3, 2 * macs * B / ms / 1e9, 2 * macs * B / ms / 1e9 / 157.3,
-            'first' if os.environ.get('GPODE_WGRAD_V1') == '1' else 'second'))
+        print('%s d/d weight%s  %d images  %.1f us  %.1f TFLOP/s  frac %.2f' % (
+            name, ' + BN/ReLU input' if bn else '', B, ms * 1e3, 2 * macs * B / ms / 1e9, 2 * macs * B / ms / 1e9 / 157.3))

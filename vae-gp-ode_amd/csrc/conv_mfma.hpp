@@ -178,7 +178,7 @@ extern __shared__ __attribute__((aligned(16))) float igemm_smem[];
 // (tools/convt_probe.hip: the MFMA phase is 62 % of a decnn.7 forward wavefront's life and pipe-bound inside); the producer /
 // consumer form of the decnn.7 input gradient is conv_bwd_v2.hpp.
 // STATS: the BatchNorm statistics of the OUTPUT are summed while it is stored and finalised by the last workgroup (bn_sink.hpp).
-template <class PL, int IPB, int TG, int NCJ, bool PAIR, int NTHR, bool DB = false, bool STATS = false>
+template <class PL, int IPB, int TG, int NCJ, bool PAIR, int NTHR, bool STATS = false>
 __global__ __launch_bounds__(NTHR, NTHR == 256 ? 2 : 1) void k_conv_igemm(const float* __restrict__ x, const float* __restrict__ w,
                                                       const float* __restrict__ bias, float* __restrict__ y, int B,
                                                       const float* __restrict__ in_bn, BnSink sink) {
@@ -197,9 +197,8 @@ __global__ __launch_bounds__(NTHR, NTHR == 256 ? 2 : 1) void k_conv_igemm(const 
   constexpr int SRC = KC * SH * SH;                  // floats per source image
   static_assert(SRC % 4 == 0, "float4 source fetch");
   constexpr int NLD = (IPB * SRC / 4 + PT - 1) / PT;       // float4 fetches per (fetching) thread per group
-  constexpr int NBUF = DB ? 2 : 1;
-  float* s_img = igemm_smem;                         // [NBUF][IPB][KC][PS] zero padded planes
-  float* s_w = igemm_smem + NBUF * IPB * IMG;        // [cls][tap][KC][WROW]
+  float* s_img = igemm_smem;                         // [IPB][KC][PS] zero padded planes
+  float* s_w = igemm_smem + IPB * IMG;               // [cls][tap][KC][WROW]
   // in_bn ([KC][4] = mean, invstd, gamma, beta per source channel): the source is the raw output of the previous
   // convolution and the BatchNorm + ReLU that follows it is applied while the images are scattered to LDS, so the
   // normalised activation never goes through HBM (the zero padding is written once and stays zero)
@@ -220,7 +219,7 @@ __global__ __launch_bounds__(NTHR, NTHR == 256 ? 2 : 1) void k_conv_igemm(const 
   const int jw = (wave & 3) * (NW / 4) + (wave >> 2);
 
   PROBE_T(pt_all);
-  for (int e = tid; e < NBUF * IPB * IMG / 4; e += NTHR) reinterpret_cast<float4*>(s_img)[e] = float4{0.f, 0.f, 0.f, 0.f};
+  for (int e = tid; e < IPB * IMG / 4; e += NTHR) reinterpret_cast<float4*>(s_img)[e] = float4{0.f, 0.f, 0.f, 0.f};
   if (in_bn) {
     if (TF_PAD) __syncthreads();                     // the zero fill above covers the slots
     for (int e = tid; e < KC; e += NTHR) *tf_slot(e) = reinterpret_cast<const float4*>(in_bn)[e];
@@ -296,7 +295,7 @@ __global__ __launch_bounds__(NTHR, NTHR == 256 ? 2 : 1) void k_conv_igemm(const 
     // all (class, pixel tile, channel-tile column) jobs of this wavefront for the group staged in `img`
     // pf_grp >= 0: the fetch of that group is issued after this wavefront's first job (right behind the barrier it would queue
     // behind the previous group's output stores: tools/convt_probe.hip, 4.3k cycles per group)
-    auto jobs = [&](const float* __restrict__ img, int b0, int nimg, int pf_grp = -1) {
+    auto jobs = [&](const float* __restrict__ img, int b0, int nimg, int pf_grp) {
       PROBE_T(pt_rng);
       // cost (k-steps) of all jobs of the group, and this wavefront's share [lo, hi) of it
       int wtot = 0;
@@ -397,51 +396,20 @@ __global__ __launch_bounds__(NTHR, NTHR == 256 ? 2 : 1) void k_conv_igemm(const 
       });
       if (pf_grp >= 0) prefetch(pf_grp);             // a wavefront without a job in this group
     };
-    if constexpr (!DB) {
-      if (gfirst < ngroups) prefetch(gfirst);
-      for (int grp = gfirst; grp < ngroups; grp += gstride) {
-        const int b0 = grp * IPB;
-        const int nimg = min(IPB, B - b0);
-        PROBE_T(pt_b1);
-        __syncthreads();                             // previous group's MFMAs have read s_img; zero fill / slabs staged
-        PROBE_ADD(1, pt_b1);
-        PROBE_T(pt_sc);
-        scatter(s_img, nimg);
-        __syncthreads();
-        PROBE_ADD(2, pt_sc);
-        PROBE_T(pt_pf);
-        PROBE_ADD(7, pt_pf);
-        jobs(s_img, b0, nimg, grp + gstride < ngroups ? grp + gstride : -1);
-      }
-    } else {
-      // Double-buffered planes, ONE barrier per group: while a group is multiplied out of one buffer the next one is
-      // scattered into the other.  The two wavefronts of a SIMD (w and w + NW/2) take the scatter at opposite ends of
-      // the group -- one before its jobs, one after -- so that on every SIMD one wavefront's scatter / global stores run
-      // under the other's MFMAs instead of all eight scattering, multiplying and storing in lockstep.
-      const bool early = wave < NW / 2;
-      int cur = 0;
-      if (gfirst < ngroups) prefetch(gfirst);
-      __syncthreads();                               // zero fill, slabs, table
-      if (gfirst < ngroups) scatter(s_img, min(IPB, B - gfirst * IPB));
-      if (gfirst + gstride < ngroups) prefetch(gfirst + gstride);
+    if (gfirst < ngroups) prefetch(gfirst);
+    for (int grp = gfirst; grp < ngroups; grp += gstride) {
+      const int b0 = grp * IPB;
+      const int nimg = min(IPB, B - b0);
+      PROBE_T(pt_b1);
+      __syncthreads();                               // previous group's MFMAs have read s_img; zero fill / slabs staged
+      PROBE_ADD(1, pt_b1);
+      PROBE_T(pt_sc);
+      scatter(s_img, nimg);
       __syncthreads();
-      for (int grp = gfirst; grp < ngroups; grp += gstride) {
-        const int b0 = grp * IPB, nxt = grp + gstride;
-        const int nimg = min(IPB, B - b0);
-        float* bc = s_img + cur * (IPB * IMG);
-        float* bn = s_img + (cur ^ 1) * (IPB * IMG);
-        if (early && nxt < ngroups) {
-          scatter(bn, min(IPB, B - nxt * IPB));
-          if (nxt + gstride < ngroups) prefetch(nxt + gstride);
-        }
-        jobs(bc, b0, nimg);
-        if (!early && nxt < ngroups) {
-          scatter(bn, min(IPB, B - nxt * IPB));
-          if (nxt + gstride < ngroups) prefetch(nxt + gstride);
-        }
-        __syncthreads();                             // next buffer complete; this one free for the group after next
-        cur ^= 1;
-      }
+      PROBE_ADD(2, pt_sc);
+      PROBE_T(pt_pf);
+      PROBE_ADD(7, pt_pf);
+      jobs(s_img, b0, nimg, grp + gstride < ngroups ? grp + gstride : -1);
     }
     if constexpr (STATS) {
       // the pass's sums: over the 16 lanes of a row (one pixel each), then over the wavefronts through the (now idle) slab region
@@ -707,8 +675,8 @@ static __global__ __launch_bounds__(1024) void k_sum_splits4(const float* __rest
   }
 }
 
-template <class PL, int IPB, bool DB = false, bool STATS = false> constexpr size_t igemm_lds_bytes() {   // planes + weight slabs (+ the input-transform table when it does not fit the plane tails) (+ the output-statistics sums)
-  return sizeof(float) * ((size_t)(DB ? 2 : 1) * IPB * PL::KC * PL::PS + (size_t)PL::WSLAB + (igemm_tf_in_pad<PL>() ? 0 : (size_t)4 * PL::KC) +
+template <class PL, int IPB, bool STATS = false> constexpr size_t igemm_lds_bytes() {   // planes + weight slabs (+ the input-transform table when it does not fit the plane tails) (+ the output-statistics sums)
+  return sizeof(float) * ((size_t)IPB * PL::KC * PL::PS + (size_t)PL::WSLAB + (igemm_tf_in_pad<PL>() ? 0 : (size_t)4 * PL::KC) +
                           (STATS ? (size_t)2 * PL::NC : 0));
 }
 

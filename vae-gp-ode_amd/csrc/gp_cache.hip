@@ -293,33 +293,14 @@ __device__ __forceinline__ float chol_rsqrt(float piv) {
   return inv * (1.5f - 0.5f * piv * inv * inv);
 }
 
-// Pivot J.  Its scalar chain (broadcast of the diagonal, v_rsq, Newton step: ~8 dependent instructions, 60-80 cycles for a
-// lone wavefront) was computed by pivot J-1 right after J-1's update of column J -- i.e. under J-1's remaining column updates,
-// which do not depend on it -- and arrives as (piv, inv).  Same operations on the same values in the same order per element as
-// the straight loop: results are bit-identical.
-template <int J> __device__ __forceinline__ void chol_pivots(float (&row)[NB], int lane, bool& bad, float piv, float inv) {
-  if constexpr (J < NB) {
-    const float sc = row[J] * inv;
-    row[J] = (lane == J) ? piv * inv : sc;
-    const float nsc = -row[J];
-    float piv_n = 1.f, inv_n = 1.f;
-    if constexpr (J + 1 < NB) {
-      chol_cols_group<J, J + 1>(row, nsc);           // columns J+1 .. J+4: column J+1 is final for pivot J+1
-      piv_n = GP_BCAST(row[J + 1], J + 1);
-      bad |= !(piv_n > 0.f);
-      inv_n = chol_rsqrt(piv_n);
-      chol_cols<J, J + 5>(row, nsc);                 // the other columns, independent of the chain above
-    }
-    chol_pivots<J + 1>(row, lane, bad, piv_n, inv_n);
-  }
-}
-
-// The same elimination with the division in front (LDL^T order): the multiplier column of pivot J is w = a_J / p_J, the update
+// The elimination with the division in front (LDL^T order): the multiplier column of pivot J is w = a_J / p_J, the update
 // a_C -= w * a_J[C] broadcasts the UNSCALED column (every broadcast of a pivot can issue as soon as the pivot starts), and the
 // scaling of the finished column by rsqrt(p_J) -- its final Cholesky values, sqrt(p_J) on the diagonal since a_J[J] = p_J --
 // leaves the dependent chain: per pivot it is  w = a_J * (1/p) -> update of column J+1 -> broadcast of p_(J+1) -> v_rcp + one
-// Newton step  (6 instructions; the classic order above has 12: v_rsq, Newton, scale, select, negate in line).  The 32 pivots
-// are a serial chain (tools/draw_probe.py: ~300 cycles per pivot, chain-bound from pivot ~12 on), so its length is the time.
+// Newton step  (6 instructions; scaling each column by rsqrt(p_J) before its update puts 12 on the chain: v_rsq, Newton, scale,
+// select, negate).  The scalar chain of pivot J+1 is computed by pivot J right after its update of column J+1, i.e. under J's
+// remaining column updates, which do not depend on it, and arrives as (piv, rinv).  The 32 pivots are a serial chain
+// (tools/draw_probe.py: ~300 cycles per pivot, chain-bound from pivot ~12 on), so its length is the time.
 __device__ __forceinline__ float chol_rcp(float p) {
   const float r = __builtin_amdgcn_rcpf(p);
   return r * fmaf(-p, r, 2.f);
@@ -341,14 +322,10 @@ template <int J> __device__ __forceinline__ void ldl_pivots(float (&row)[NB], bo
 }
 
 // returns true when a pivot was not positive (matrix not positive definite)
-__device__ __forceinline__ bool chol32_panel_wave(float (&row)[NB], int lane) {
+__device__ __forceinline__ bool chol32_panel_wave(float (&row)[NB]) {
   const float piv = GP_BCAST(row[0], 0);
   bool bad = !(piv > 0.f);
-#ifdef GPODE_CHOL_CLASSIC
-  chol_pivots<0>(row, lane, bad, piv, chol_rsqrt(piv));
-#else
   ldl_pivots<0>(row, bad, piv, chol_rcp(piv));
-#endif
   return bad;
 }
 
@@ -395,7 +372,7 @@ __global__ __launch_bounds__(256) void k_chol_rl(float* __restrict__ Aall, float
     float row[NB];
 #pragma unroll
     for (int c = 0; c < NB; ++c) row[c] = panel ? (wv == 0 ? sI[r][c] : sJ[r][c]) : sD[r][c];
-    const bool bad = chol32_panel_wave(row, lane);
+    const bool bad = chol32_panel_wave(row);
     if (bad && wv == 0 && t == 0 && lane == 0) atomicOr(info, 1);  // not positive definite (reference raises)
     // branch-free write-back: panel halves go to lI / lJ, D halves to lD (both waves hold the same L_kk;
     // the duplicate store writes identical values)
@@ -469,7 +446,7 @@ __device__ __forceinline__ bool tile_factor(const float (&Dt)[NB][NB + 1], const
   float row[NB];
 #pragma unroll
   for (int c = 0; c < NB; ++c) row[c] = panel ? Pt[r][c] : Dt[r][c];
-  const bool bad = chol32_panel_wave(row, lane);
+  const bool bad = chol32_panel_wave(row);
   if (panel) {
 #pragma unroll
     for (int c = 0; c < NB; ++c) Lp[r][c] = row[c];
@@ -1029,7 +1006,7 @@ __global__ __launch_bounds__(512) void k_draw_lds(int Di, int Do, int M, int n, 
       }
       __syncthreads();                               // every wavefront holds its copy of D_k before anyone overwrites it
       if (active) {
-        const bool bad = chol32_panel_wave(row, lane);
+        const bool bad = chol32_panel_wave(row);
         if (bad && wave == 0 && t0 == 0 && lane == 0) atomicOr(info, 1);
         if (!panel) {
           if (wave == 0 && t0 == 0) {
@@ -1165,7 +1142,7 @@ static inline size_t draw_lds_bytes(int np, int M, int Di, int nd) {   // sA, sv
   return sizeof(float) * ((size_t)np * (np + 2) + (size_t)nd * np + NB + (size_t)Di * (M | 1) + (size_t)Di * Di + Di);
 }
 static inline bool draw_in_lds(int np, int M, int Di, int nd) {
-  static const bool off = [] { const char* e = getenv("GPODE_DRAW_CHAIN"); return e && e[0] == '1'; }();
+  static const bool off = env_flag("GPODE_DRAW_CHAIN");
   return !off && np <= 192 && draw_lds_bytes(np, M, Di, nd) <= 160 * 1024;
 }
 
@@ -1316,14 +1293,12 @@ static void cholesky_blocked(float* A, float* Lmat, float* Dfac, int np, int nbl
         hipLaunchKernelGGL(k_syrk_mfma, dim3(Tt * (Tt + 1) / 2, w.batch), 256, 0, st, A, Lmat, w.np, bstride, jlim * NB, K * ST);
     }
   } else {
-    static const bool single = [] { const char* e = getenv("GPODE_CHOL_SINGLE_STEP"); return e && e[0] == '1'; }();
     int k = 0;
-    if (!single)
-      for (; k + 1 < w.nblk; k += 2) {                 // two block columns per launch (k_chol_rl2)
-        const int T = w.nblk - k;
-        hipLaunchKernelGGL(k_chol_rl2, dim3(T * (T + 1) / 2, w.batch), 256, 0, st, A, Lmat, w.np, bstride, Dfac, dstride, k, info, w.nblk, nreal);
-      }
-    for (; k < w.nblk; ++k) {
+    for (; k + 1 < w.nblk; k += 2) {                   // two block columns per launch (k_chol_rl2)
+      const int T = w.nblk - k;
+      hipLaunchKernelGGL(k_chol_rl2, dim3(T * (T + 1) / 2, w.batch), 256, 0, st, A, Lmat, w.np, bstride, Dfac, dstride, k, info, w.nblk, nreal);
+    }
+    for (; k < w.nblk; ++k) {                          // an odd column count ends on a single-column launch
       const int T = w.nblk - k;
       hipLaunchKernelGGL(k_chol_rl, dim3(T * (T + 1) / 2, w.batch), 256, 0, st, A, Lmat, w.np, bstride, Dfac, dstride, k, info, w.nblk, w.nblk, nreal);
     }

@@ -1,5 +1,6 @@
 // gp_launch.hpp -- host-side helpers shared by the launchers (error slot, launch checks).
 #pragma once
+#include <cstdint>
 #include <cstdlib>
 #include <hip/hip_runtime.h>
 #include <cstdarg>
@@ -23,6 +24,17 @@ inline int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error("%s: launch failed: %s", what, hipGetErrorString(e));
   return 0;
+}
+
+// A GPODE_* switch that is on when set to "1".  Call sites keep the answer in a function-local static: read once per process.
+inline bool env_flag(const char* name) {
+  const char* e = getenv(name);
+  return e && e[0] == '1';
+}
+
+// the float4 / b128 paths need 16-byte aligned operands; absent operands (nullptr) count as aligned
+inline bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
 }
 
 // Raise a kernel's dynamic-LDS limit above the 64 KB default.  The attribute is set once per (kernel, size) and
@@ -209,7 +221,7 @@ int adam_multi(float* const* params, const float* const* grads, float* const* m1
 // big factors (np a multiple of 128, >= 1024) take the panelled / matrix-core kernels; GPODE_SMALL_FACTOR_KERNELS=1 keeps the
 // 32-tile kernels for every size (an A/B switch for tests and profiling, same results up to summation order)
 inline bool big_factor(int np) {
-  static const bool off = [] { const char* e = getenv("GPODE_SMALL_FACTOR_KERNELS"); return e && e[0] == '1'; }();
+  static const bool off = env_flag("GPODE_SMALL_FACTOR_KERNELS");
   return !off && np % 128 == 0 && np >= 1024;
 }
 

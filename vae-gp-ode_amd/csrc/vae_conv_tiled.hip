@@ -1,11 +1,16 @@
 // vae_conv_tiled.hip -- layer-specialised kernels and dispatch for the VAE's convolutions (vae.py:52-59, 64-84).
 //
-// The production path is on the fp32 matrix cores: the implicit-GEMM engine of conv_mfma.hpp (decnn.1/4/7 forward, d/d input,
-// d/d weight; the encoder's cnn.3 / cnn.6 where the channel counts fill MFMA tiles) and conv_dec10_mfma.hpp (decnn.10 with
-// the 25 taps as the GEMM dimension).  This file holds the layer geometry (CTLayer), the dispatch by geometry
-// (tiled_fwd / tiled_bwd_data / tiled_bwd_weight; -1 = no specialisation, the caller falls back to the generic direct
-// kernels of vae_conv.hip) and the earlier LDS-resident VALU kernels, kept selectable with GPODE_CONV_VALU=1 as the
-// A/B baseline the MFMA numbers in DESIGN.md are quoted against:
+// tiled_fwd / tiled_bwd_data / tiled_bwd_weight dispatch by layer geometry (CTLayer, conv_layers.hpp); -1 = no specialisation,
+// the caller falls back to the generic direct kernels of vae_conv.hip.  What runs, per layer:
+//   decnn.1   conv_dec1_mfma.hpp (taps folded into the GEMM's columns); with a fused BatchNorm input the first engine
+//   decnn.4   forward: conv_dec4_mfma.hpp (taps as columns) up to 4 images per CU, the first engine above;
+//             d/d input, d/d weight: the producer / consumer engines (conv_bwd_v2.hpp, conv_wgrad_v2.hpp)
+//   decnn.7   forward: the first engine; d/d input, d/d weight: the producer / consumer engines
+//   decnn.10  conv_dec10_mfma.hpp (the 25 taps as the GEMM dimension)
+//   cnn.3 / cnn.6 (encoder)  the first engine where the channel counts fill MFMA tiles; T1 for cnn.3's d/d input from 96 images
+// "The first engine" is the implicit-GEMM plane-scatter engine of conv_mfma.hpp on the fp32 matrix cores.  All of these need
+// 16-byte aligned operands.  Unaligned operands, and every layer under GPODE_CONV_VALU=1, take the LDS-resident VALU kernels of
+// this file, which are also the baseline the MFMA numbers in DESIGN.md are quoted against:
 //
 //   a workgroup stages a few whole images (zero-padded, so taps never branch) and a slab of weights in LDS; a thread
 //   owns ONE pixel x 16 channels of output in registers.  Per (input channel, tap) it reads one input value
@@ -18,9 +23,7 @@
 //                  images streamed through LDS; batch split over workgroups, slabs summed in fixed order
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-#include <cstdint>
 #include "gp_launch.hpp"
-#include <type_traits>
 #include "conv_layers.hpp"
 #include "conv_mfma.hpp"
 #include "conv_dec10_mfma.hpp"
@@ -28,8 +31,6 @@
 #include "conv_dec4_mfma.hpp"
 
 namespace gp {
-
-
 
 extern __shared__ __attribute__((aligned(16))) float tsm[];
 
@@ -356,7 +357,8 @@ __global__ void k_sum_splits_t(const float* __restrict__ part, int nsplit, size_
 
 // ---------------------------------------------------------------------------------------------
 // host: dispatch by geometry; return -1 when no tiled specialisation applies (caller falls back to the
-// generic direct kernels of vae_conv.hip)
+// generic direct kernels of vae_conv.hip).  Every arm reads: the layer's matrix-core kernel when use_mfma() and the
+// operands are 16-byte aligned, else the VALU kernel above.
 // ---------------------------------------------------------------------------------------------
 template <class L> static bool matches(int Ci_conv, int Co_conv, int H, int Ho, int K, int S, int P) {
   // conv geometry of the adjoint: "input" (B, Ci_conv = L::CO, H = L::HO), "output" (B, Co_conv = L::CI, Ho = L::HI)
@@ -364,23 +366,22 @@ template <class L> static bool matches(int Ci_conv, int Co_conv, int H, int Ho, 
 }
 
 static bool use_mfma() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("GPODE_CONV_VALU"); v = (e && e[0] == '1') ? 0 : 1; }
-  return v == 1;
+  static const bool valu = env_flag("GPODE_CONV_VALU");
+  return !valu;
 }
 
-// matrix-core path (conv_mfma.hpp): persistent grid of one 512-thread workgroup per CU
-// NTHR = 256 with a footprint <= 80 KB: TWO independent 4-wavefront workgroups per CU, whose scatter / store phases interleave
-// with each other's MFMA phases instead of idling the matrix pipe in lockstep
 // workgroups a BnSink's partial sums must have room for (every statistics-producing launch below stays within it)
 constexpr int kSinkMaxWg = 512;
 
-template <class PL, int IPB, int TG, int NCJ, bool PAIR = false, int NTHR = 512, bool DB = false, bool STATS = false>
+// first matrix-core engine (conv_mfma.hpp, k_conv_igemm): persistent grid of one 512-thread workgroup per CU, or with NTHR = 256
+// and a footprint <= 80 KB TWO independent 4-wavefront workgroups per CU, whose scatter / store phases interleave with each
+// other's MFMA phases instead of idling the matrix pipe in lockstep
+template <class PL, int IPB, int TG, int NCJ, bool PAIR = false, int NTHR = 512, bool STATS = false>
 static int launch_igemm(const float* x, const float* w, const float* bias, float* y, int B, hipStream_t st, const char* what,
                         const float* in_bn = nullptr, const BnSink* sink = nullptr) {
-  constexpr size_t lds = igemm_lds_bytes<PL, IPB, DB, STATS>();
+  constexpr size_t lds = igemm_lds_bytes<PL, IPB, STATS>();
   static_assert(lds <= (NTHR >= 512 ? 160 : 80) * 1024, "LDS budget");
-  auto km = k_conv_igemm<PL, IPB, TG, NCJ, PAIR, NTHR, DB, STATS>;
+  auto km = k_conv_igemm<PL, IPB, TG, NCJ, PAIR, NTHR, STATS>;
   if (set_max_lds((const void*)km, lds)) return 1;
   const int ngroups = (B + IPB - 1) / IPB;
   const int cap = num_cus() * (NTHR >= 512 ? 1 : 2);
@@ -389,42 +390,31 @@ static int launch_igemm(const float* x, const float* w, const float* bias, float
   return check_launch(what);
 }
 
-// IPB: images per workgroup of the VALU kernel; IPBM / COS: images per group and output channels per pass of the MFMA kernel
+// ConvTranspose2d forward on the first engine, else T1.  IPB: images per workgroup of the VALU kernel; IPBM / COS: images per
+// group and output channels per pass of the MFMA kernel
 template <class L, int IPB, int IPBM, int COS>
 static int launch_T1(const float* x, const float* w, const float* bias, float* y, int B, hipStream_t st, const float* in_bn,
                      const BnSink* sink = nullptr) {
-  constexpr int MAXTAPS = ((L::K + L::S - 1) / L::S) * ((L::K + L::S - 1) / L::S);
-  const size_t lds = sizeof(float) * ((size_t)IPB * L::CI * L::HP * L::HP + (size_t)MAXTAPS * L::CI * L::CO);
-  if (use_mfma() && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
+  if (use_mfma() && aligned16(x)) {
     constexpr int TG = COS >= 64 ? 1 : (COS >= 32 ? 2 : 4);
     // column-parity classes pair up when both cover the same pixel grid: stride 2, (HO + P) even
     constexpr bool PAIR = L::S == 2 && (L::HO % 2 == 0) && (L::P % 2 == 1);
-    if constexpr (std::is_same<L, Dec7>::value) {
-      // GPODE_DEC7_FWD_DB=1 (A/B only): ONE image per group in double-buffered planes (2 x 38 KB + 50 KB of slabs), one barrier
-      // per group, the two wavefronts of a SIMD scattering at opposite ends of it.  Measured SLOWER than the default below
-      // (4096 images: 0.244 vs 0.229 ms): a single image per group quantises to 13 tiles for 12.25 and the scatter was 2 % of
-      // the kernel to begin with -- the idle matrix-pipe cycles are not in the phases the second buffer overlaps.
-      static const bool db = [] { const char* e = getenv("GPODE_DEC7_FWD_DB"); return e && e[0] == '1'; }();
-      if (db) return launch_igemm<FwdPolicy<L, COS>, 1, TG, COS / 16, PAIR, 512, true>(x, w, bias, y, B, st, "convT_fwd_mfma", in_bn);
-    }
-    if (sink) return launch_igemm<FwdPolicy<L, COS>, IPBM, TG, COS / 16, PAIR, 512, false, true>(x, w, bias, y, B, st, "convT_fwd_mfma_stats", in_bn, sink);
+    if (sink) return launch_igemm<FwdPolicy<L, COS>, IPBM, TG, COS / 16, PAIR, 512, true>(x, w, bias, y, B, st, "convT_fwd_mfma_stats", in_bn, sink);
     return launch_igemm<FwdPolicy<L, COS>, IPBM, TG, COS / 16, PAIR>(x, w, bias, y, B, st, "convT_fwd_mfma", in_bn);
   }
   if (sink) return set_error("convT forward with output statistics needs the matrix-core path (16-byte aligned input, GPODE_CONV_VALU unset)");
   if (in_bn) return set_error("convT forward with a fused BatchNorm input needs the matrix-core path (16-byte aligned input, GPODE_CONV_VALU unset)");
+  constexpr int MAXTAPS = ((L::K + L::S - 1) / L::S) * ((L::K + L::S - 1) / L::S);
+  const size_t lds = sizeof(float) * ((size_t)IPB * L::CI * L::HP * L::HP + (size_t)MAXTAPS * L::CI * L::CO);
   auto kern = k_convT_fwd<L, IPB>;
   if (set_max_lds((const void*)kern, lds)) return 1;
   hipLaunchKernelGGL(kern, (B + IPB - 1) / IPB, 256, lds, st, x, w, bias, y, B);
   return check_launch("convT_fwd_tiled");
 }
 
-// IPBM / CIS / TG / NCJ: images per group, input channels per pass, pixel tiles and channel tiles per job of the MFMA kernel
-template <class L, int IPB, int COC, int IPBM, int CIS, int TG, int NCJ, int NTHR = 512>
+// T2 (VALU): IPB images per workgroup, weights staged COC output channels at a time
+template <class L, int IPB, int COC>
 static int launch_T2(const float* gy, const float* w, float* gx, int B, hipStream_t st) {
-  if constexpr (IPBM > 0) {
-    if (use_mfma() && (reinterpret_cast<uintptr_t>(gy) & 15) == 0)
-      return launch_igemm<BwdDataPolicy<L, CIS>, IPBM, TG, NCJ, false, NTHR>(gy, w, nullptr, gx, B, st, "convT_bwd_data_mfma");
-  }
   const size_t lds = sizeof(float) * ((size_t)IPB * L::CO * L::GP_ * L::GP_ + (size_t)COC * L::K * L::K * L::CI);
   auto kern = k_convT_bwd_data<L, IPB, COC>;
   if (set_max_lds((const void*)kern, lds)) return 1;
@@ -432,17 +422,18 @@ static int launch_T2(const float* gy, const float* w, float* gx, int B, hipStrea
   return check_launch("convT_bwd_data_tiled");
 }
 
-template <class L, int IPBM, int WM, int WN, int WT, bool PIPE>
+// d/d weight on the first engine (conv_mfma.hpp, k_convT_wgrad_mfma): 8 images per group, 8 wavefronts split WM x WN x WT over
+// (ci tiles, co tiles, taps), one workgroup per CU
+template <class L, int WM, int WN, int WT>
 static int launch_wgrad_mfma(const float* x, const float* gy, float* gw, float* scratch, int B, hipStream_t st, const float* in_bn) {
-  constexpr int NTHR = WM * WN * WT * 64;            // 512: one workgroup per CU; 256: two (footprint <= 80 KB)
+  constexpr int IPBM = 8, NTHR = WM * WN * WT * 64;
   constexpr size_t ldsm = wgrad_lds_bytes<L, IPBM>();
-  static_assert(ldsm <= (NTHR == 512 ? 160 : 80) * 1024, "LDS budget");
-  auto km = k_convT_wgrad_mfma<L, IPBM, WM, WN, WT, PIPE, false, NTHR>;
-  auto kb = k_convT_wgrad_mfma<L, IPBM, WM, WN, WT, PIPE, true, NTHR>;
+  static_assert(NTHR == 512 && ldsm <= 160 * 1024, "one workgroup per CU");
+  auto km = k_convT_wgrad_mfma<L, IPBM, WM, WN, WT, true, false, NTHR>;
+  auto kb = k_convT_wgrad_mfma<L, IPBM, WM, WN, WT, true, true, NTHR>;
   if (set_max_lds((const void*)km, ldsm) || set_max_lds((const void*)kb, ldsm)) return 1;
   const int ngroups = (B + IPBM - 1) / IPBM;
-  const int cap = num_cus() * (512 / NTHR);
-  const int nwg = ngroups < cap ? ngroups : cap;
+  const int nwg = ngroups < num_cus() ? ngroups : num_cus();
   if (in_bn) hipLaunchKernelGGL(kb, nwg, NTHR, ldsm, st, x, gy, scratch, B, in_bn);
   else hipLaunchKernelGGL(km, nwg, NTHR, ldsm, st, x, gy, scratch, B, in_bn);
   const size_t n = (size_t)L::CI * L::CO * L::K * L::K;
@@ -450,20 +441,9 @@ static int launch_wgrad_mfma(const float* x, const float* gy, float* gw, float* 
   return check_launch("convT_wgrad_mfma");
 }
 
-// second engine (conv_wgrad_v2.hpp, its own translation unit vae_wgrad_v2.hip): 8 consumer + 4 producer wavefronts, one image per plane
-// buffer.  GPODE_WGRAD_V1=1: the first engine (A/B)
-int wgrad_v2_dec7(const float* x, const float* gy, float* gw, float* scratch, int B, hipStream_t st, const float* in_bn);
-int wgrad_v2_dec4(const float* x, const float* gy, float* gw, float* scratch, int B, hipStream_t st, const float* in_bn);
-static bool wgrad_v2_enabled() {
-  static const bool off = [] { const char* e = getenv("GPODE_WGRAD_V1"); return e && e[0] == '1'; }();
-  return !off && use_mfma();
-}
-
-// IPBM / WM x WN x WT: images per group and wavefront split (ci tiles, co tiles, taps) of the MFMA kernel
-template <class L, int COW, int IPBM, int WM, int WN, int WT, bool PIPE>
+// T3 (VALU): a workgroup owns COW output channels and a slice of the batch
+template <class L, int COW>
 static int launch_T3(const float* x, const float* gy, float* gw, float* scratch, int B, hipStream_t st, const float* in_bn) {
-  if (use_mfma() && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gy)) & 15) == 0)
-    return launch_wgrad_mfma<L, IPBM, WM, WN, WT, PIPE>(x, gy, gw, scratch, B, st, in_bn);
   if (in_bn) return set_error("convT weight gradient with a fused BatchNorm input needs the matrix-core path");
   constexpr int NT = L::CI * (COW / 4), PSPLIT = 256 / NT, KK = L::K * L::K;
   size_t fl = (size_t)L::HI * L::HI * L::CI + (size_t)L::GP_ * L::GP_ * COW;
@@ -509,8 +489,7 @@ int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx
     return launch_T1<Dec4, 3, 2, 16>(gy, w, bias, gx, B, st, in_bn, sink);
   }
   if (matches<Dec1>(Ci, Co, H, Ho, K, S, P)) {
-    static const bool old = [] { const char* e = getenv("GPODE_DEC1_ENGINE"); return e && e[0] == '1'; }();
-    if (!in_bn && use_mfma() && (!old || sink)) {    // taps folded into the GEMM's columns, weights resident in registers
+    if (!in_bn && use_mfma()) {    // conv_dec1_mfma.hpp: taps folded into the GEMM's columns, weights resident in registers
       const size_t lds = sizeof(float) * 2 * dec1::NPI * dec1::TLD;
       if (set_max_lds((const void*)dec1::k_fwd<false>, lds) || set_max_lds((const void*)dec1::k_fwd<true>, lds)) return 1;
       const int cap = 2 * num_cus();                 // 74 KB of LDS per workgroup
@@ -518,7 +497,7 @@ int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx
       else hipLaunchKernelGGL(dec1::k_fwd<false>, B < cap ? B : cap, 256, lds, st, gy, w, bias, gx, B, BnSink{});
       return check_launch("dec1_fwd_mfma");
     }
-    return launch_T1<Dec1, 8, 8, 64>(gy, w, bias, gx, B, st, in_bn);
+    return launch_T1<Dec1, 8, 8, 64>(gy, w, bias, gx, B, st, in_bn);   // dec1::k_fwd takes no in_bn: the first engine does
   }
   if (matches<Enc3>(Ci, Co, H, Ho, K, S, P) && !in_bn && B >= 96) {
     // d/d input of the encoder's cnn.3 (16 -> 8 channels: no matrix-core tile shape) from 96 images on: the LDS-tiled vector kernel, two
@@ -532,12 +511,10 @@ int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx
     hipLaunchKernelGGL(kern, (B + IPB - 1) / IPB, 256, lds, st, gy, w, bias, gx, B);
     return check_launch("enc_conv3_bwd_data_tiled");
   }
-  if (matches<Enc6>(Ci, Co, H, Ho, K, S, P) && use_mfma() && (reinterpret_cast<uintptr_t>(gy) & 15) == 0)   // d/d input of the encoder's cnn.6
-  {
+  if (matches<Enc6>(Ci, Co, H, Ho, K, S, P) && use_mfma() && aligned16(gy)) {   // d/d input of the encoder's cnn.6
     // 8 images per group fill the chip from 2048 images on; a minibatch of 256 made 32 workgroups (73 us on an eighth of the CUs):
-    // 2 images per group below half a wave of groups (GPODE_ENC6_IPB8=1: the former launch, A/B)
-    static const bool ipb8 = [] { const char* e = getenv("GPODE_ENC6_IPB8"); return e && e[0] == '1'; }();
-    if (!ipb8 && B < 4 * num_cus()) return launch_igemm<FwdPolicy<Enc6, 16>, 2, 4, 1>(gy, w, bias, gx, B, st, "enc_conv6_bwd_data_mfma", in_bn);
+    // 2 images per group below half a wave of groups
+    if (B < 4 * num_cus()) return launch_igemm<FwdPolicy<Enc6, 16>, 2, 4, 1>(gy, w, bias, gx, B, st, "enc_conv6_bwd_data_mfma", in_bn);
     return launch_igemm<FwdPolicy<Enc6, 16>, 8, 4, 1>(gy, w, bias, gx, B, st, "enc_conv6_bwd_data_mfma", in_bn);
   }
   if (matches<Dec10>(Ci, Co, H, Ho, K, S, P)) {
@@ -559,57 +536,56 @@ int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx
 }
 
 // second convolution engine (conv_bwd_v2.hpp, its own translation unit vae_conv_v2.hip): decnn.7 and decnn.4 d/d input on producer /
-// consumer wavefronts with the weights in registers.  GPODE_CONV_V1=1: the first engine (A/B)
+// consumer wavefronts with the weights in registers.  GPODE_CONV_V1=1 runs the first engine instead: the reference the tests of the
+// second engine compare against.
 int conv_v2_dec7_bwd_data(const float* gy, const float* w, float* gx, int B, hipStream_t st);
 int conv_v2_dec4_bwd_data(const float* gy, const float* w, float* gx, int B, hipStream_t st);
-static bool conv_v2_enabled() {
-  static const bool off = [] { const char* e = getenv("GPODE_CONV_V1"); return e && e[0] == '1'; }();
-  return !off && use_mfma();
+static bool conv_v1() {
+  static const bool on = env_flag("GPODE_CONV_V1");
+  return on;
 }
 
 // ConvTranspose2d d/d input (conv geometry: x := grad_output (B,Ci,H,W) -> y (B,Co,Ho,Wo)), no bias
 int tiled_fwd(const float* x, const float* w, const float* bias, float* y, int B, int Ci, int H, int W, int Co, int K, int S, int P,
               int Ho, int Wo, hipStream_t st) {
   if (H != W || Ho != Wo) return -1;
-  if (use_mfma() && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {   // encoder Conv2d layers (with their bias)
+  const bool mfma = use_mfma() && aligned16(x);
+  if (mfma) {   // encoder Conv2d layers (with their bias)
     if (matches<Enc3>(Ci, Co, H, Ho, K, S, P)) return launch_igemm<BwdDataPolicy<Enc3, 16>, 4, 4, 1>(x, w, bias, y, B, st, "enc_conv3_fwd_mfma");
     if (matches<Enc6>(Ci, Co, H, Ho, K, S, P)) return launch_igemm<BwdDataPolicy<Enc6, 32>, 8, 1, 2>(x, w, bias, y, B, st, "enc_conv6_fwd_mfma");
   }
   if (bias) return -1;
   if (matches<Dec7>(Ci, Co, H, Ho, K, S, P)) {
-    if (conv_v2_enabled() && (reinterpret_cast<uintptr_t>(x) & 15) == 0) return conv_v2_dec7_bwd_data(x, w, y, B, st);
-    return launch_T2<Dec7, 2, 8, 1, 16, 2, 1, 256>(x, w, y, B, st);
+    if (mfma && !conv_v1()) return conv_v2_dec7_bwd_data(x, w, y, B, st);
+    // first engine: one image and 16 input channels per pass, two pixel tiles per job, two 256-thread workgroups per CU
+    if (mfma) return launch_igemm<BwdDataPolicy<Dec7, 16>, 1, 2, 1, false, 256>(x, w, nullptr, y, B, st, "convT_bwd_data_mfma");
+    return launch_T2<Dec7, 2, 8>(x, w, y, B, st);
   }
-  // decnn.4 d/d input, first engine: 36 output pixels per image; two images and two 16-channel halves per pass make 10 equal jobs for 8
-  // wavefronts (tools/convt_probe.hip: 28 % of wavefront 0's cycles in the group barrier).  Three images per group with 16
-  // channels per pass (7 jobs, one idle wavefront) was measured and is NOT faster (0.455 vs 0.444 ms for d/d input + d/d weight at
-  // 4096 images: twice the passes over the source images eat the gain); GPODE_DEC4_BWD_3IMG=1 selects it for A/B (with GPODE_CONV_V1=1).
   if (matches<Dec4>(Ci, Co, H, Ho, K, S, P)) {
-    if (conv_v2_enabled() && (reinterpret_cast<uintptr_t>(x) & 15) == 0) return conv_v2_dec4_bwd_data(x, w, y, B, st);
-    static const bool alt = [] { const char* e = getenv("GPODE_DEC4_BWD_3IMG"); return e && e[0] == '1'; }();
-    if (alt) return launch_T2<Dec4, 3, 8, 3, 16, 1, 1>(x, w, y, B, st);
-    return launch_T2<Dec4, 3, 8, 2, 32, 1, 1>(x, w, y, B, st);
+    if (mfma && !conv_v1()) return conv_v2_dec4_bwd_data(x, w, y, B, st);
+    // first engine: 36 output pixels per image; two images and two 16-channel halves per pass make 10 equal jobs for 8 wavefronts
+    // (tools/convt_probe.hip: 28 % of wavefront 0's cycles in the group barrier)
+    if (mfma) return launch_igemm<BwdDataPolicy<Dec4, 32>, 2, 1, 1>(x, w, nullptr, y, B, st, "convT_bwd_data_mfma");
+    return launch_T2<Dec4, 3, 8>(x, w, y, B, st);
   }
   if (matches<Dec1>(Ci, Co, H, Ho, K, S, P)) {
-    static const bool old = [] { const char* e = getenv("GPODE_DEC1_ENGINE"); return e && e[0] == '1'; }();
-    if (use_mfma() && !old && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
+    if (mfma) {
       const size_t lds = sizeof(float) * (2 * dec1::GYF + 4 * dec1::NPI * 33);
       const int cap = 2 * num_cus();
       hipLaunchKernelGGL(dec1::k_bwd_data, B < cap ? B : cap, 256, lds, st, x, w, y, B);
       return check_launch("dec1_bwd_data_mfma");
     }
-    return launch_T2<Dec1, 8, 32, 6, 32, 1, 1>(x, w, y, B, st);
+    return launch_T2<Dec1, 8, 32>(x, w, y, B, st);
   }
-
   if (matches<Dec10>(Ci, Co, H, Ho, K, S, P)) {
-    if (use_mfma() && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
+    if (mfma) {
       constexpr int IPB = 8;
       const size_t ldsm = sizeof(float) * IPB * dec10::PLANE;
       const int ngroups = (B + IPB - 1) / IPB;
       hipLaunchKernelGGL(dec10::k_bwd_data<IPB>, ngroups < num_cus() ? ngroups : num_cus(), 512, ldsm, st, x, w, y, B);
       return check_launch("dec10_bwd_data_mfma");
     }
-    return launch_T2<Dec10, 1, 1, 0, 16, 1, 1>(x, w, y, B, st);
+    return launch_T2<Dec10, 1, 1>(x, w, y, B, st);
   }
   return -1;
 }
@@ -622,7 +598,7 @@ int dec10_predict(const float* c, const float* table, const float* w, const floa
   if (Lc < 1 || F < 1 || Th < 1 || T_obs < 1 || T_obs > Th || F % Th != 0 || done < 0)
     return set_error("gpode_dec10_predict: need Lc, F >= 1, 1 <= T_obs <= Th, F a multiple of Th, done >= 0");
   if ((pred_mean == nullptr) != (pred_m2 == nullptr)) return set_error("gpode_dec10_predict: pred_mean and pred_m2 go together");
-  if ((reinterpret_cast<uintptr_t>(table) & 15) != 0) return set_error("gpode_dec10_predict: the table must be 16-byte aligned");
+  if (!aligned16(table)) return set_error("gpode_dec10_predict: the table must be 16-byte aligned");
   const size_t lds = sizeof(float) * (dec10::KK * dec10::PST + 16);
   if (set_max_lds((const void*)dec10::k_fwd_predict, lds)) return 1;
   hipLaunchKernelGGL(dec10::k_fwd_predict, F < num_cus() ? F : num_cus(), 512, lds, st, c, w, bias, table, X, Lc, F, Th, T_obs, done, pred_mean,
@@ -664,7 +640,7 @@ static int dec10_bn_nwg(int B, int& ipb) {
 int dec10_bn_wgrad_scratch_floats() { return kDec10BnMaxWg * dec10::CI * dec10::KK + kDec10BnMaxWg; }
 int dec10_bn_bwd_sums(const float* c, const float* gy, const float* w, const float* gamma, const float* beta, const float* mean,
                       const float* invstd, float* sums, int B, float* scratch, hipStream_t st, float* gw, float* wscratch, float* gbias) {
-  if (((reinterpret_cast<uintptr_t>(gy) | reinterpret_cast<uintptr_t>(c)) & 15) != 0) return set_error("gpode_dec10_bn_bwd_sums: c / gy must be 16-byte aligned");
+  if (!aligned16(gy, c)) return set_error("gpode_dec10_bn_bwd_sums: c / gy must be 16-byte aligned");
   if (gw && !wscratch) return set_error("gpode_dec10_bn_bwd_sums_wgrad: scratch for the weight-gradient partials missing");
   int ipb;
   const int nwg = dec10_bn_nwg(B, ipb);
@@ -689,7 +665,7 @@ int dec10_bn_bwd_sums(const float* c, const float* gy, const float* w, const flo
 int dec10_bn_bwd_apply(const float* c, const float* gy, const float* w, const float* gamma, const float* beta, const float* mean,
                        const float* invstd, const float* gathered, const float* wts, int W, float count_all, float* gc, float* ggamma,
                        float* gbeta, float* gc_chansum, int B, float* scratch, hipStream_t st) {
-  if (((reinterpret_cast<uintptr_t>(gy) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(gc)) & 15) != 0)
+  if (!aligned16(gy, c, gc))
     return set_error("gpode_dec10_bn_bwd_apply: c / gy / gc must be 16-byte aligned");
   if (gathered && (W < 1 || !wts)) return set_error("gpode_dec10_bn_bwd_apply: gathered sums need their weights");
   int ipb;
@@ -704,36 +680,40 @@ int dec10_bn_bwd_apply(const float* c, const float* gy, const float* w, const fl
   return check_launch("dec10_bn_bwd_apply");
 }
 
+// second d/d weight engine (conv_wgrad_v2.hpp, its own translation unit vae_wgrad_v2.hip): 8 consumer + 4 producer wavefronts, one
+// image per plane buffer
+int wgrad_v2_dec7(const float* x, const float* gy, float* gw, float* scratch, int B, hipStream_t st, const float* in_bn);
+int wgrad_v2_dec4(const float* x, const float* gy, float* gw, float* scratch, int B, hipStream_t st, const float* in_bn);
+
 // ConvTranspose2d d/d weight (conv geometry: x := grad_output, gy := the layer's input)
 int tiled_bwd_weight(const float* x, const float* gy, float* gw, float* scratch, int B, int Ci, int H, int W, int Co, int K, int S,
                      int P, int Ho, int Wo, const float* in_bn, hipStream_t st) {
   if (H != W || Ho != Wo) return -1;
-  const bool aligned = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gy)) & 15) == 0;
+  const bool mfma = use_mfma() && aligned16(x, gy);
   if (matches<Dec7>(Ci, Co, H, Ho, K, S, P)) {
-    if (wgrad_v2_enabled() && aligned) return wgrad_v2_dec7(gy, x, gw, scratch, B, st, in_bn);
-    return launch_T3<Dec7, 16, 2, 1, 1, 8, true>(gy, x, gw, scratch, B, st, in_bn);
+    if (mfma) return wgrad_v2_dec7(gy, x, gw, scratch, B, st, in_bn);
+    return launch_T3<Dec7, 16>(gy, x, gw, scratch, B, st, in_bn);
   }
   if (matches<Dec4>(Ci, Co, H, Ho, K, S, P)) {
-    if (wgrad_v2_enabled() && aligned) return wgrad_v2_dec4(gy, x, gw, scratch, B, st, in_bn);
-    return launch_T3<Dec4, 16, 2, 4, 2, 1, false>(gy, x, gw, scratch, B, st, in_bn);
+    if (mfma) return wgrad_v2_dec4(gy, x, gw, scratch, B, st, in_bn);
+    return launch_T3<Dec4, 16>(gy, x, gw, scratch, B, st, in_bn);
   }
   if (matches<Dec1>(Ci, Co, H, Ho, K, S, P)) {
-    static const bool old = [] { const char* e = getenv("GPODE_DEC1_ENGINE"); return e && e[0] == '1'; }();
-    if (!in_bn && use_mfma() && !old && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {   // gy: the layer's input, x: grad_output
+    if (!in_bn && use_mfma() && aligned16(x)) {   // conv_dec1_mfma.hpp
       const size_t lds = sizeof(float) * 2 * dec1::GYF;
-      static const int wcap = [] { const char* e = getenv("GPODE_DEC1_WGRAD_WGS"); return e ? atoi(e) : 256; }();   // 256: 33.8 + 7.8 us (kernel + reduction of the partials) at 4096 images; 512: 33.1 + 10.8; 128: 56 + 6
-      const int cap = 2 * num_cus() < wcap ? 2 * num_cus() : wcap;
+      // partial slabs: 256 costs 33.8 + 7.8 us (kernel + reduction of the partials) at 4096 images; 512: 33.1 + 10.8; 128: 56 + 6
+      const int cap = 2 * num_cus() < 256 ? 2 * num_cus() : 256;
       const int nwg = B < cap ? B : cap;
       hipLaunchKernelGGL(dec1::k_wgrad, nwg, 256, lds, st, gy, x, scratch, B);
       if (reduce_job(RedJob{scratch, gw, nwg, dec1::CI * dec1::NN, 0, 0, 0, 0}, st)) return 1;
       return check_launch("dec1_wgrad_mfma");
     }
-    return launch_T3<Dec1, 32, 8, 2, 4, 1, true>(gy, x, gw, scratch, B, st, in_bn);
+    if (mfma) return launch_wgrad_mfma<Dec1, 2, 4, 1>(gy, x, gw, scratch, B, st, in_bn);   // dec1::k_wgrad takes no in_bn: the first engine does
+    return launch_T3<Dec1, 32>(gy, x, gw, scratch, B, st, in_bn);
   }
-  if (matches<Enc6>(Ci, Co, H, Ho, K, S, P) && use_mfma() && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gy)) & 15) == 0)
-    return launch_wgrad_mfma<Enc6, 8, 2, 1, 4, true>(gy, x, gw, scratch, B, st, in_bn);   // d/d weight of the encoder's cnn.6
-  if (matches<Dec10>(Ci, Co, H, Ho, K, S, P) && use_mfma() &&
-      ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gy)) & 15) == 0) {
+  if (matches<Enc6>(Ci, Co, H, Ho, K, S, P) && mfma)
+    return launch_wgrad_mfma<Enc6, 2, 1, 4>(gy, x, gw, scratch, B, st, in_bn);   // d/d weight of the encoder's cnn.6
+  if (matches<Dec10>(Ci, Co, H, Ho, K, S, P) && mfma) {
     constexpr int IPB = 1;
     const size_t fl = (size_t)IPB * dec10::PLANE > 8 * 16 * 32 ? (size_t)IPB * dec10::PLANE : 8 * 16 * 32;
     const int ngroups = (B + IPB - 1) / IPB;

@@ -479,7 +479,6 @@ inline Split pick(int B) {
   s.used = (B + s.bps - 1) / s.bps;
   return s;
 }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // elements per channel up to which ONE workgroup per channel does the whole layer in one launch (GPODE_BN_ONE_LAUNCH=0: never)
 // (configs[0], us, one launch vs two: forward 18k elements per channel 6.0 vs 9.9, 6k 5.6 vs 9.1, 1.5k 5.3 vs 8.2, but 86k 41.8 vs 10;
 //  backward 1.5k 5.1 vs 9.9, 6k 12.7 vs 10.3, 18k 11.5 vs 11 -- a lone workgroup streams at a few GB/s)

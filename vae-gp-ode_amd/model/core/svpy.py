@@ -157,7 +157,6 @@ class SVGP_Layer(torch.nn.Module):
         # waits for it) and stays referenced by the cache until the step's join
         nz, params = self._cache_inputs(draws=draws)
         side = ops.fork_side_stream()
-        ops.start_marker()
         with ops.launch_on(side):
             self._prebuilt = cache = self._launch_cache_build(nz, params)
         # the flow waits for THIS point of the side stream only; the gradient-independent half of the cache backward (L^-1 from the
@@ -166,7 +165,7 @@ class SVGP_Layer(torch.nn.Module):
         self._prebuilt_ready = torch.cuda.Event()
         self._prebuilt_ready.record(side)
         cache.prepared = None
-        if ops.PREPARE_WITH_PREBUILD and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             with ops.launch_on(side):
                 cache.prepared = ops.cache_bwd_prepare(cache)
 

@@ -99,21 +99,10 @@ def _main_marker():
     backward replays 0.07-0.15 ms slower (configs[1] 3.19 -> 3.12 ms, configs[0] 1.07 -> 0.93 ms; the first three nodes of
     the following replay then start ~55 us apart -- profiles/r02b_notes.txt).  Measured, not understood: a property of how the
     graph executor lays branches onto hardware queues."""
-    if _NO_MARKER:
-        return
     d = _overlap.get('marker')
     if d is None or d.device != torch.device('cuda', torch.cuda.current_device()):
         d = _overlap['marker'] = torch.zeros(1, dtype=torch.float32, device='cuda')
     d.zero_()
-
-
-_START_MARKER = os.environ.get('GPODE_START_MARKER', '0') == '1'
-
-
-def start_marker():
-    """EXPERIMENT (GPODE_START_MARKER=1): the main branch's node created first at the fork that opens the step as well."""
-    if _START_MARKER and _overlap['on']:
-        _main_marker()
 
 
 def defer_kl_grads(params, grads):
@@ -124,28 +113,6 @@ def defer_kl_grads(params, grads):
         return False
     _overlap['kl'] = (tuple(params), tuple(grads))
     return True
-
-
-_NO_MARKER = os.environ.get('GPODE_NO_MARKER', '0') == '1'
-PREPARE_WITH_PREBUILD = os.environ.get('GPODE_PREPARE_FORK', '0') != '1'
-_HEARTBEAT = os.environ.get('GPODE_SIDE_HEARTBEAT', '0') == '1'
-
-
-def side_heartbeat():
-    """EXPERIMENT (GPODE_SIDE_HEARTBEAT=1): a trivial kernel on the side stream that waits for the current point of the main
-    stream.  The side branch of the backward pass starts 60-115 us after the kernel it depends on has finished, and the longer
-    the side queue has sat blocked the longer that takes; heartbeats keep its waits short."""
-    if not (_HEARTBEAT and _overlap['on']):
-        return
-    side = side_stream()
-    side.wait_stream(torch.cuda.current_stream())
-    _main_marker()                                   # the main branch's node is created first: it keeps the parent's queue
-    d = _overlap.get('hb')
-    if d is None:
-        d = _overlap['hb'] = torch.zeros(1, dtype=torch.float32, device='cuda')
-    with torch.cuda.stream(side):
-        d.zero_()
-    _overlap['forked'] = True
 
 
 def join_side_stream():

@@ -189,9 +189,6 @@ def batch_norm_train_pair(x1, bn1, x2, bn2, relu):
 _dec10_fused = os.environ.get('GPODE_DEC10_BN_UNFUSED', '0') != '1'
 
 
-_DEC10_WGRAD_FUSED = os.environ.get('GPODE_DEC10_WGRAD_PASS', '0') != '1'
-
-
 def _dec10_bn_bwd(sync, c, gy, w, gamma, beta, mean, invstd, gw=None, gbias=None):
     """decnn.10's input gradient + the BatchNorm/ReLU backward in front of it in two passes over c (include/gpode.h,
     gpode_dec10_bn_bwd_*): (gc, ggamma, gbeta, channel sums of gc).  ``gw`` (a tensor to fill): the layer's weight gradient rides
@@ -406,11 +403,10 @@ class _BnReluConvT(torch.autograd.Function):
     def backward(ctx, gy):
         c, gamma, beta, mean, invstd, table, w = ctx.saved_tensors
         B, Cout, Ht, Wt, Cin, K, S, P, Hi, Wi, has_b = ctx.geom
-        ops.side_heartbeat()
         gy = gy.contiguous()
         gw = gb = None
         last_stage = _dec10_fused and (Cout, Cin, K, S, P, Hi, Wi, Ht, Wt) == (1, 16, 5, 1, 2, 28, 28, 28, 28)
-        gw_rides = last_stage and _DEC10_WGRAD_FUSED and ctx.needs_input_grad[8] and c.data_ptr() % 16 == 0
+        gw_rides = last_stage and ctx.needs_input_grad[8] and c.data_ptr() % 16 == 0
         if ctx.needs_input_grad[8]:
             gw = _new(w.shape, c)
             if not gw_rides:                         # (the last stage's weight gradient rides in its BatchNorm sums pass below)
@@ -763,16 +759,13 @@ class _SigmoidLogLikParts(torch.autograd.Function):
         return None, ga, None
 
 
-_ELBO_LL_FUSED = os.environ.get('GPODE_ELBO_LL_SEPARATE', '0') != '1'
-
-
 class _ElboAll(torch.autograd.Function):
     """(loss, -mean lhood, mean KL(z0), KL(u)) of create_model.py:61-73 from the likelihood partial sums, the encoder's packed
     (mu | logvar) rows and the inducing posterior, one launch forward and one backward (gpode_elbo_all_fwd / _bwd)."""
 
     @staticmethod
     def forward(ctx, lpart, hs, hv, Um, Us, rows, M, nobs, ll=None):
-        ctx.ll = ll if (_ELBO_LL_FUSED and ll is not None and ll[1].numel() % ll[0].numel() == 0) else None
+        ctx.ll = ll if (ll is not None and ll[1].numel() % ll[0].numel() == 0) else None
         lpart, hs, Um, Us = _chk(lpart, 'lpart'), _chk(hs, 'hs'), _chk(Um, 'Um'), _chk(Us, 'Us_sqrt.optvar')
         hv = _chk(hv, 'hv') if hv is not None else None
         N, q = hs.shape[0], hs.shape[1] // 2
@@ -863,7 +856,7 @@ def elbo_all(lpart, mu_s, logvar_s, mu_v, logvar_v, Um, Us_packed, M, nobs):
     if mu_v is not None:
         hv0 = _packed_halves(mu_v, logvar_v)
         klv = getattr(hv0, '_gpode_klpart', None) if hv0 is not None else None
-    if (_ELBO_LL_FUSED and ll is not None and ll[1].numel() % ll[0].numel() == 0 and kls is not None and (mu_v is None or klv is not None)):
+    if (ll is not None and ll[1].numel() % ll[0].numel() == 0 and kls is not None and (mu_v is None or klv is not None)):
         return _ElboAllKL.apply(lpart, kls, klv, Um, Us_packed, lpart.shape[0], mu_s.shape[0], M, float(nobs), ll)
     hv = _pack(mu_v, logvar_v) if mu_v is not None else None
     return _ElboAll.apply(lpart, _pack(mu_s, logvar_s), hv, Um, Us_packed, lpart.shape[0], M, float(nobs), getattr(lpart, '_gpode_ll', None))
@@ -874,12 +867,9 @@ def _pack(mu, logvar):
     return h if h is not None else torch.cat((mu, logvar), dim=1)
 
 
-_REPARAM_KL = os.environ.get('GPODE_REPARAM_KL_SEPARATE', '0') != '1'
-
-
 def reparam(mu, logvar, eps):
     h = _packed_halves(mu, logvar)
-    if h is not None and _REPARAM_KL and h.requires_grad:
+    if h is not None and h.requires_grad:
         # (mu | logvar) are the halves of the encoder's fc output: the KL term's partial sums ride along for elbo_all()
         z, klpart = _ReparamKL.apply(h, eps)
         h._gpode_klpart = klpart
