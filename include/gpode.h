@@ -33,6 +33,9 @@ extern "C" {
 /* Library / build identification. */
 const char* gpode_version(void);
 const char* gpode_last_error(void);
+/* Tag of the launcher that ran last on the calling thread ("" before the first): which kernel a dispatching entry point chose,
+ * e.g. "conv_v2_dec7_fwd_bn_stats" (second convolution engine) or "convT_fwd_mfma_stats" (first).  For tests and diagnosis. */
+const char* gpode_last_launch(void);
 /* 1 if (kernel,Di,Do) has a compiled specialisation. */
 int gpode_supported(int kernel, int Di, int Do);
 

@@ -38,7 +38,7 @@ with tempfile.TemporaryDirectory() as td:
         starts = [i for i, ln in enumerate(text) if re.match(r'^_Z\S+:', ln) and flt in ln]
         for i in starts:
             kname = text[i].split(':')[0]
-            end = next(j for j in range(i, len(text)) if 's_endpgm' in text[j])
+            end = next(j for j in range(i, len(text)) if text[j].startswith('.Lfunc_end'))   # past early-exit s_endpgm's
             print(kname)
             tot = [0, 0]
             for bname, ins in blocks(text[i + 1:end]):

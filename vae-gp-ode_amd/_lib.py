@@ -18,6 +18,7 @@ _sz_p = ctypes.POINTER(ctypes.c_size_t)
 SIGNATURES = {
     'gpode_version': (ctypes.c_char_p, []),
     'gpode_last_error': (ctypes.c_char_p, []),
+    'gpode_last_launch': (ctypes.c_char_p, []),
     'gpode_supported': (_i, [_i, _i, _i]),
     'gpode_cache_sizes': (_i, [_i, _i, _i, _i, _i, _sz_p, _sz_p]),
     'gpode_cache_build_fwd': (_i, [_i] * 5 + [_c_float_p] * 20),

@@ -7,12 +7,17 @@ char* error_slot() {
   static thread_local char buf[512] = {0};
   return buf;
 }
+const char** last_launch_slot() {
+  static thread_local const char* tag = "";
+  return &tag;
+}
 }  // namespace gp
 
 extern "C" {
 
 const char* gpode_version(void) { return "gpode-hip 0.1 (gfx950)"; }
 const char* gpode_last_error(void) { return gp::error_slot(); }
+const char* gpode_last_launch(void) { return *gp::last_launch_slot(); }
 int gpode_supported(int kernel, int Di, int Do) { return gp::dims_supported(kernel, Di, Do); }
 
 int gpode_cache_sizes(int kernel, int Di, int Do, int M, int S, size_t* pack_floats, size_t* ws_floats) {

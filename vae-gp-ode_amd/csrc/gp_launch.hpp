@@ -11,6 +11,7 @@
 namespace gp {
 
 char* error_slot();  // thread-local 512-byte buffer (capi.hip)
+const char** last_launch_slot();  // thread-local: the tag of the launcher that ran last (capi.hip, gpode_last_launch)
 
 inline int set_error(const char* fmt, ...) {
   va_list ap;
@@ -21,6 +22,7 @@ inline int set_error(const char* fmt, ...) {
 }
 
 inline int check_launch(const char* what) {
+  *last_launch_slot() = what;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error("%s: launch failed: %s", what, hipGetErrorString(e));
   return 0;

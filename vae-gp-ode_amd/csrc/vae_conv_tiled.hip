@@ -5,7 +5,7 @@
 //   decnn.1   conv_dec1_mfma.hpp (taps folded into the GEMM's columns); with a fused BatchNorm input the first engine
 //   decnn.4   forward: conv_dec4_mfma.hpp (taps as columns) up to 4 images per CU, the first engine above;
 //             d/d input, d/d weight: the producer / consumer engines (conv_bwd_v2.hpp, conv_wgrad_v2.hpp)
-//   decnn.7   forward: the first engine; d/d input, d/d weight: the producer / consumer engines
+//   decnn.7   forward, d/d input, d/d weight: the producer / consumer engines (conv_fwd_v2.hpp, conv_bwd_v2.hpp, conv_wgrad_v2.hpp)
 //   decnn.10  conv_dec10_mfma.hpp (the 25 taps as the GEMM dimension)
 //   cnn.3 / cnn.6 (encoder)  the first engine where the channel counts fill MFMA tiles; T1 for cnn.3's d/d input from 96 images
 // "The first engine" is the implicit-GEMM plane-scatter engine of conv_mfma.hpp on the fp32 matrix cores.  All of these need
@@ -462,6 +462,18 @@ static int launch_T3(const float* x, const float* gy, float* gw, float* scratch,
 }
 
 
+// second convolution engine (conv_bwd_v2.hpp, conv_fwd_v2.hpp, its own translation unit vae_conv_v2.hip): decnn.7 forward, decnn.7 and
+// decnn.4 d/d input on producer / consumer wavefronts with the weights in registers.  GPODE_CONV_V1=1 runs the first engine instead:
+// the reference the tests of the second engine compare against.
+int conv_v2_dec7_bwd_data(const float* gy, const float* w, float* gx, int B, hipStream_t st);
+int conv_v2_dec4_bwd_data(const float* gy, const float* w, float* gx, int B, hipStream_t st);
+int conv_v2_dec7_fwd(const float* x, const float* w, const float* bias, float* y, int B, const float* in_bn, const BnSink* sink,
+                     hipStream_t st);
+static bool conv_v1() {
+  static const bool on = env_flag("GPODE_CONV_V1");
+  return on;
+}
+
 // ConvTranspose2d forward (called with the conv geometry of its adjoint, as conv2d_bwd_data is)
 int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx, int B, int Ci, int H, int W, int Co, int K, int S,
                    int P, int Ho, int Wo, const float* in_bn, hipStream_t st, const BnSink* sink) {
@@ -469,7 +481,12 @@ int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx
   if (sink && !(use_mfma() && (matches<Dec7>(Ci, Co, H, Ho, K, S, P) || matches<Dec4>(Ci, Co, H, Ho, K, S, P) ||
                                (matches<Dec1>(Ci, Co, H, Ho, K, S, P) && !in_bn))))
     return set_error("gpode_convT_fwd_stats: no specialisation for this geometry");
-  if (matches<Dec7>(Ci, Co, H, Ho, K, S, P)) return launch_T1<Dec7, 3, 2, 16>(gy, w, bias, gx, B, st, in_bn, sink);
+  if (matches<Dec7>(Ci, Co, H, Ho, K, S, P)) {
+    // second engine at every batch size: with in_bn + sink 46.0 vs 48.4 us on the first engine at 512 images (configs[0], two images per
+    // CU), 42.5 vs 46.3 us at 256, 242 vs 254 us at 4096; with in_bn alone 36.5 vs 43.7, 22.0 vs 40.9, 199 vs 241 us -- no batch threshold
+    if (use_mfma() && aligned16(gy, in_bn) && !conv_v1()) return conv_v2_dec7_fwd(gy, w, bias, gx, B, in_bn, sink, st);
+    return launch_T1<Dec7, 3, 2, 16>(gy, w, bias, gx, B, st, in_bn, sink);
+  }
   if (matches<Dec4>(Ci, Co, H, Ho, K, S, P)) {
     // taps-as-columns form (conv_dec4_mfma.hpp): 48.5 vs 59.7 us for the stage at 512 images (no weight slabs to stage before the first
     // image), 276 vs 267 us at 4096 -- so it takes the small batches (configs[0]: 512 images); GPODE_DEC4_TAPCOLS=0 / 1 forces one
@@ -533,16 +550,6 @@ int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx
     return check_launch("dec10_fwd");
   }
   return -1;
-}
-
-// second convolution engine (conv_bwd_v2.hpp, its own translation unit vae_conv_v2.hip): decnn.7 and decnn.4 d/d input on producer /
-// consumer wavefronts with the weights in registers.  GPODE_CONV_V1=1 runs the first engine instead: the reference the tests of the
-// second engine compare against.
-int conv_v2_dec7_bwd_data(const float* gy, const float* w, float* gx, int B, hipStream_t st);
-int conv_v2_dec4_bwd_data(const float* gy, const float* w, float* gx, int B, hipStream_t st);
-static bool conv_v1() {
-  static const bool on = env_flag("GPODE_CONV_V1");
-  return on;
 }
 
 // ConvTranspose2d d/d input (conv geometry: x := grad_output (B,Ci,H,W) -> y (B,Co,Ho,Wo)), no bias
