@@ -222,7 +222,10 @@ int gpode_conv2d_bwd_data(const float* gy, const float* w, const float* bias, fl
 /* The same with the BatchNorm + ReLU that precedes the ConvTranspose2d folded into its input staging: gy is the RAW output of the
  * previous layer, gy_bn its per-channel table {mean, invstd, gamma, beta} from gpode_bn_stats; the normalised activation is
  * never written to memory (vae.py:113-120: ConvTranspose2d -> BatchNorm2d -> ReLU -> ConvTranspose2d).  Matrix-core
- * specialisations only (decnn.4/7/10); other geometries return an error. */
+ * specialisations only (decnn.1/4/7/10, cnn.6): other geometries return an error, and so does every call -- this one,
+ * gpode_conv2d_bwd_weight_bn and gpode_convT_fwd_stats alike -- under GPODE_CONV_VALU=1 or with an operand (gy, gy_bn, w, gx) that
+ * is not 16-byte aligned; nothing is written then.  Without a table and without statistics, such a call runs on the VALU / generic
+ * kernels. */
 int gpode_conv2d_bwd_data_bn(const float* gy, const float* gy_bn, const float* w, const float* bias, float* gx, int B, int Ci, int H,
                              int W, int Co, int K, int S, int P, int Ho, int Wo, void* stream);
 /* gpode_conv2d_fwd / gpode_conv2d_bwd_weight on a BATCH-STRIDED input: image b starts x_batch_stride floats after image b - 1 and is

@@ -35,8 +35,8 @@ inline bool env_flag(const char* name) {
 }
 
 // the float4 / b128 paths need 16-byte aligned operands; absent operands (nullptr) count as aligned
-inline bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
-  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
+template <class... T> inline bool aligned16(const T*... p) {
+  return ((uintptr_t{0} | ... | reinterpret_cast<uintptr_t>(p)) & 15) == 0;
 }
 
 // Raise a kernel's dynamic-LDS limit above the 64 KB default.  The attribute is set once per (kernel, size) and

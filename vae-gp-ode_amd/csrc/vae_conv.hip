@@ -424,6 +424,8 @@ int conv2d_bwd_weight(const float* x, const float* gy, float* gw, float* gbias, 
                       int K, int S, int P, int Ho, int Wo, const float* gy_bn, hipStream_t st, size_t xbs) {
   if (xbs == (size_t)Ci * H * W) xbs = 0;
   if (xbs && Ci % 4 == 0) return set_error("gpode_conv2d_bwd_weight_bs: batch-strided input is for the generic kernels");
+  // chan_sum's own argument check, made before the weight gradient is launched: a refused call writes nothing
+  if (gbias && ((Ho * Wo) & 3) == 0 && !aligned16(gy)) return set_error("gpode_conv2d_bwd_weight: the bias gradient needs a 16-byte aligned gy");
   if (!xbs) {
     const int r = tiled_bwd_weight(x, gy, gw, scratch, B, Ci, H, W, Co, K, S, P, Ho, Wo, gy_bn, st);
     if (r > 0) return r;

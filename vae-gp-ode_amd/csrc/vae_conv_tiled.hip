@@ -357,8 +357,11 @@ __global__ void k_sum_splits_t(const float* __restrict__ part, int nsplit, size_
 
 // ---------------------------------------------------------------------------------------------
 // host: dispatch by geometry; return -1 when no tiled specialisation applies (caller falls back to the
-// generic direct kernels of vae_conv.hip).  Every arm reads: the layer's matrix-core kernel when use_mfma() and the
-// operands are 16-byte aligned, else the VALU kernel above.
+// generic direct kernels of vae_conv.hip).  Every arm reads: the layer's matrix-core kernel when use_mfma() and ALL of the
+// arm's operands (inputs, weights, output, BatchNorm table) are 16-byte aligned -- the matrix-core kernels fetch their sources and
+// the table as float4 and some store float2 / float4 -- else the VALU kernel above, which touches global memory by scalars only.
+// A request the VALU kernels cannot serve (a fused BatchNorm input, output statistics) is refused with an error, never served
+// without the table.
 // ---------------------------------------------------------------------------------------------
 template <class L> static bool matches(int Ci_conv, int Co_conv, int H, int Ho, int K, int S, int P) {
   // conv geometry of the adjoint: "input" (B, Ci_conv = L::CO, H = L::HO), "output" (B, Co_conv = L::CI, Ho = L::HI)
@@ -395,15 +398,15 @@ static int launch_igemm(const float* x, const float* w, const float* bias, float
 template <class L, int IPB, int IPBM, int COS>
 static int launch_T1(const float* x, const float* w, const float* bias, float* y, int B, hipStream_t st, const float* in_bn,
                      const BnSink* sink = nullptr) {
-  if (use_mfma() && aligned16(x)) {
+  if (use_mfma() && aligned16(x, w, y, in_bn)) {
     constexpr int TG = COS >= 64 ? 1 : (COS >= 32 ? 2 : 4);
     // column-parity classes pair up when both cover the same pixel grid: stride 2, (HO + P) even
     constexpr bool PAIR = L::S == 2 && (L::HO % 2 == 0) && (L::P % 2 == 1);
     if (sink) return launch_igemm<FwdPolicy<L, COS>, IPBM, TG, COS / 16, PAIR, 512, true>(x, w, bias, y, B, st, "convT_fwd_mfma_stats", in_bn, sink);
     return launch_igemm<FwdPolicy<L, COS>, IPBM, TG, COS / 16, PAIR>(x, w, bias, y, B, st, "convT_fwd_mfma", in_bn);
   }
-  if (sink) return set_error("convT forward with output statistics needs the matrix-core path (16-byte aligned input, GPODE_CONV_VALU unset)");
-  if (in_bn) return set_error("convT forward with a fused BatchNorm input needs the matrix-core path (16-byte aligned input, GPODE_CONV_VALU unset)");
+  if (sink) return set_error("convT forward with output statistics needs the matrix-core path (16-byte aligned operands, GPODE_CONV_VALU unset)");
+  if (in_bn) return set_error("convT forward with a fused BatchNorm input needs the matrix-core path (16-byte aligned operands, GPODE_CONV_VALU unset)");
   constexpr int MAXTAPS = ((L::K + L::S - 1) / L::S) * ((L::K + L::S - 1) / L::S);
   const size_t lds = sizeof(float) * ((size_t)IPB * L::CI * L::HP * L::HP + (size_t)MAXTAPS * L::CI * L::CO);
   auto kern = k_convT_fwd<L, IPB>;
@@ -444,7 +447,7 @@ static int launch_wgrad_mfma(const float* x, const float* gy, float* gw, float* 
 // T3 (VALU): a workgroup owns COW output channels and a slice of the batch
 template <class L, int COW>
 static int launch_T3(const float* x, const float* gy, float* gw, float* scratch, int B, hipStream_t st, const float* in_bn) {
-  if (in_bn) return set_error("convT weight gradient with a fused BatchNorm input needs the matrix-core path");
+  if (in_bn) return set_error("convT weight gradient with a fused BatchNorm input needs the matrix-core path (16-byte aligned operands, GPODE_CONV_VALU unset)");
   constexpr int NT = L::CI * (COW / 4), PSPLIT = 256 / NT, KK = L::K * L::K;
   size_t fl = (size_t)L::HI * L::HI * L::CI + (size_t)L::GP_ * L::GP_ * COW;
   const size_t red = PSPLIT > 1 ? (size_t)PSPLIT * NT * KK * 4 : 0;
@@ -478,20 +481,22 @@ static bool conv_v1() {
 int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx, int B, int Ci, int H, int W, int Co, int K, int S,
                    int P, int Ho, int Wo, const float* in_bn, hipStream_t st, const BnSink* sink) {
   if (H != W || Ho != Wo) return -1;
-  if (sink && !(use_mfma() && (matches<Dec7>(Ci, Co, H, Ho, K, S, P) || matches<Dec4>(Ci, Co, H, Ho, K, S, P) ||
-                               (matches<Dec1>(Ci, Co, H, Ho, K, S, P) && !in_bn))))
+  // (whether the matrix-core path is open is each arm's test below: its refusal names that reason)
+  if (sink && !(matches<Dec7>(Ci, Co, H, Ho, K, S, P) || matches<Dec4>(Ci, Co, H, Ho, K, S, P) ||
+                (matches<Dec1>(Ci, Co, H, Ho, K, S, P) && !in_bn)))
     return set_error("gpode_convT_fwd_stats: no specialisation for this geometry");
+  const bool mfma = use_mfma() && aligned16(gy, w, gx, in_bn);
   if (matches<Dec7>(Ci, Co, H, Ho, K, S, P)) {
     // second engine at every batch size: with in_bn + sink 46.0 vs 48.4 us on the first engine at 512 images (configs[0], two images per
     // CU), 42.5 vs 46.3 us at 256, 242 vs 254 us at 4096; with in_bn alone 36.5 vs 43.7, 22.0 vs 40.9, 199 vs 241 us -- no batch threshold
-    if (use_mfma() && aligned16(gy, in_bn) && !conv_v1()) return conv_v2_dec7_fwd(gy, w, bias, gx, B, in_bn, sink, st);
+    if (mfma && !conv_v1()) return conv_v2_dec7_fwd(gy, w, bias, gx, B, in_bn, sink, st);
     return launch_T1<Dec7, 3, 2, 16>(gy, w, bias, gx, B, st, in_bn, sink);
   }
   if (matches<Dec4>(Ci, Co, H, Ho, K, S, P)) {
     // taps-as-columns form (conv_dec4_mfma.hpp): 48.5 vs 59.7 us for the stage at 512 images (no weight slabs to stage before the first
     // image), 276 vs 267 us at 4096 -- so it takes the small batches (configs[0]: 512 images); GPODE_DEC4_TAPCOLS=0 / 1 forces one
     static const int tapcols = [] { const char* e = getenv("GPODE_DEC4_TAPCOLS"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
-    if ((tapcols == 1 || (tapcols < 0 && B <= 4 * num_cus())) && use_mfma()) {
+    if ((tapcols == 1 || (tapcols < 0 && B <= 4 * num_cus())) && mfma) {
       const size_t lds = sizeof(float) * (dec4::NPI * dec4::TLD + 4 * dec4::CI + (sink ? 2 * dec4::CO * dec4::NPO : 0));
       if (set_max_lds((const void*)dec4::k_fwd<true>, lds) || set_max_lds((const void*)dec4::k_fwd<false>, lds) ||
           set_max_lds((const void*)dec4::k_fwd<true, true>, lds) || set_max_lds((const void*)dec4::k_fwd<false, true>, lds)) return 1;
@@ -506,7 +511,7 @@ int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx
     return launch_T1<Dec4, 3, 2, 16>(gy, w, bias, gx, B, st, in_bn, sink);
   }
   if (matches<Dec1>(Ci, Co, H, Ho, K, S, P)) {
-    if (!in_bn && use_mfma()) {    // conv_dec1_mfma.hpp: taps folded into the GEMM's columns, weights resident in registers
+    if (!in_bn && mfma) {    // conv_dec1_mfma.hpp: taps folded into the GEMM's columns, weights resident in registers
       const size_t lds = sizeof(float) * 2 * dec1::NPI * dec1::TLD;
       if (set_max_lds((const void*)dec1::k_fwd<false>, lds) || set_max_lds((const void*)dec1::k_fwd<true>, lds)) return 1;
       const int cap = 2 * num_cus();                 // 74 KB of LDS per workgroup
@@ -514,6 +519,7 @@ int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx
       else hipLaunchKernelGGL(dec1::k_fwd<false>, B < cap ? B : cap, 256, lds, st, gy, w, bias, gx, B, BnSink{});
       return check_launch("dec1_fwd_mfma");
     }
+    if (sink) return set_error("convT forward with output statistics needs the matrix-core path (16-byte aligned operands, GPODE_CONV_VALU unset)");
     return launch_T1<Dec1, 8, 8, 64>(gy, w, bias, gx, B, st, in_bn);   // dec1::k_fwd takes no in_bn: the first engine does
   }
   if (matches<Enc3>(Ci, Co, H, Ho, K, S, P) && !in_bn && B >= 96) {
@@ -528,20 +534,22 @@ int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx
     hipLaunchKernelGGL(kern, (B + IPB - 1) / IPB, 256, lds, st, gy, w, bias, gx, B);
     return check_launch("enc_conv3_bwd_data_tiled");
   }
-  if (matches<Enc6>(Ci, Co, H, Ho, K, S, P) && use_mfma() && aligned16(gy)) {   // d/d input of the encoder's cnn.6
+  if (matches<Enc6>(Ci, Co, H, Ho, K, S, P) && mfma) {   // d/d input of the encoder's cnn.6
     // 8 images per group fill the chip from 2048 images on; a minibatch of 256 made 32 workgroups (73 us on an eighth of the CUs):
     // 2 images per group below half a wave of groups
     if (B < 4 * num_cus()) return launch_igemm<FwdPolicy<Enc6, 16>, 2, 4, 1>(gy, w, bias, gx, B, st, "enc_conv6_bwd_data_mfma", in_bn);
     return launch_igemm<FwdPolicy<Enc6, 16>, 8, 4, 1>(gy, w, bias, gx, B, st, "enc_conv6_bwd_data_mfma", in_bn);
   }
   if (matches<Dec10>(Ci, Co, H, Ho, K, S, P)) {
-    if (use_mfma()) {
+    if (mfma) {
       const size_t ldsm = sizeof(float) * dec10::KK * dec10::PST;
       if (set_max_lds((const void*)dec10::k_fwd<true>, ldsm) || set_max_lds((const void*)dec10::k_fwd<false>, ldsm)) return 1;
       if (in_bn) hipLaunchKernelGGL(dec10::k_fwd<true>, B < num_cus() ? B : num_cus(), 512, ldsm, st, gy, w, bias, gx, B, in_bn);
       else hipLaunchKernelGGL(dec10::k_fwd<false>, B < num_cus() ? B : num_cus(), 512, ldsm, st, gy, w, bias, gx, B, in_bn);
       return check_launch("dec10_fwd_mfma");
     }
+    if (in_bn) return set_error("convT forward with a fused BatchNorm input needs the matrix-core path (16-byte aligned operands, GPODE_CONV_VALU unset)");
+    if (!aligned16(gx)) return -1;     // k_dec10_fwd stores four pixels of a row as one float4: the generic kernel takes over
     constexpr int IPB = 2;
     const size_t lds = sizeof(float) * ((size_t)IPB * 16 * 32 * 32 + 16 * 5 * 8);
     auto kern = k_dec10_fwd<IPB>;
@@ -556,7 +564,7 @@ int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx
 int tiled_fwd(const float* x, const float* w, const float* bias, float* y, int B, int Ci, int H, int W, int Co, int K, int S, int P,
               int Ho, int Wo, hipStream_t st) {
   if (H != W || Ho != Wo) return -1;
-  const bool mfma = use_mfma() && aligned16(x);
+  const bool mfma = use_mfma() && aligned16(x, w, y);
   if (mfma) {   // encoder Conv2d layers (with their bias)
     if (matches<Enc3>(Ci, Co, H, Ho, K, S, P)) return launch_igemm<BwdDataPolicy<Enc3, 16>, 4, 4, 1>(x, w, bias, y, B, st, "enc_conv3_fwd_mfma");
     if (matches<Enc6>(Ci, Co, H, Ho, K, S, P)) return launch_igemm<BwdDataPolicy<Enc6, 32>, 8, 1, 2>(x, w, bias, y, B, st, "enc_conv6_fwd_mfma");
@@ -696,7 +704,7 @@ int wgrad_v2_dec4(const float* x, const float* gy, float* gw, float* scratch, in
 int tiled_bwd_weight(const float* x, const float* gy, float* gw, float* scratch, int B, int Ci, int H, int W, int Co, int K, int S,
                      int P, int Ho, int Wo, const float* in_bn, hipStream_t st) {
   if (H != W || Ho != Wo) return -1;
-  const bool mfma = use_mfma() && aligned16(x, gy);
+  const bool mfma = use_mfma() && aligned16(x, gy, in_bn);
   if (matches<Dec7>(Ci, Co, H, Ho, K, S, P)) {
     if (mfma) return wgrad_v2_dec7(gy, x, gw, scratch, B, st, in_bn);
     return launch_T3<Dec7, 16>(gy, x, gw, scratch, B, st, in_bn);
@@ -706,7 +714,7 @@ int tiled_bwd_weight(const float* x, const float* gy, float* gw, float* scratch,
     return launch_T3<Dec4, 16>(gy, x, gw, scratch, B, st, in_bn);
   }
   if (matches<Dec1>(Ci, Co, H, Ho, K, S, P)) {
-    if (!in_bn && use_mfma() && aligned16(x)) {   // conv_dec1_mfma.hpp
+    if (!in_bn && mfma) {   // conv_dec1_mfma.hpp
       const size_t lds = sizeof(float) * 2 * dec1::GYF;
       // partial slabs: 256 costs 33.8 + 7.8 us (kernel + reduction of the partials) at 4096 images; 512: 33.1 + 10.8; 128: 56 + 6
       const int cap = 2 * num_cus() < 256 ? 2 * num_cus() : 256;
@@ -730,6 +738,7 @@ int tiled_bwd_weight(const float* x, const float* gy, float* gw, float* scratch,
     return check_launch("dec10_wgrad_mfma");
   }
   if (matches<Dec10>(Ci, Co, H, Ho, K, S, P)) {
+    if (in_bn) return set_error("convT weight gradient with a fused BatchNorm input needs the matrix-core path (16-byte aligned operands, GPODE_CONV_VALU unset)");
     int nsplit = B < 256 ? B : 256;
     const int bps = (B + nsplit - 1) / nsplit;
     nsplit = (B + bps - 1) / bps;

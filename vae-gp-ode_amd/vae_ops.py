@@ -903,9 +903,25 @@ def batch_norm_train(x, bn, relu):
                                  bn.num_batches_tracked if bn.training else None)
 
 
+def _matrix_core_path(*tensors):
+    """False under GPODE_CONV_VALU=1 (the library reads it once per process) or when an operand is not a 16-byte aligned dense tensor as
+    it stands: the convolutions then run their VALU / generic kernels, which take no BatchNorm table."""
+    return os.environ.get('GPODE_CONV_VALU', '0') != '1' and all(not t.is_contiguous() or t.data_ptr() % 16 == 0 for t in tensors)
+
+
 def bn_relu_conv_transpose2d(c, bn, w, b, stride, pad, out_pad=0, stats_for=None):
     """conv_transpose2d(relu(bn(c)), w, b) for a BatchNorm2d module in training mode, fused (see _BnReluConvT).  ``stats_for``: the
     BatchNorm2d that follows THIS convolution (see conv_transpose2d)."""
+    if not _matrix_core_path(c, w):
+        # the fused form exists on the matrix-core kernels only: the separate ops, same result
+        pre = getattr(c, '_gpode_bnstats', None)
+        if c.data_ptr() % 16:                        # (the BatchNorm kernels read float4 where the image size allows)
+            c = c.clone(memory_format=torch.contiguous_format)
+        if pre is not None and pre[0] is bn:         # the producer of c has updated bn's running statistics already
+            a = _BatchNormTrain.apply(c, bn.weight, bn.bias, None, None, bn.momentum, bn.eps, True, None)
+        else:
+            a = batch_norm_train(c, bn, True)
+        return conv_transpose2d(a, w, b, stride, pad, out_pad, stats_for)
     return _BnReluConvT.apply(c, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps,
                               w, b, stride, pad, out_pad, bn, stats_for)
 
