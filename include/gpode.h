@@ -16,7 +16,8 @@
  *
  *  kernel: 0 = RBF dimwise  (kernels.py:29-195),  1 = divergence-free (kernels.py:201-393, Di==Do)
  *  order : 1 | 2            (flow.py:27-45)
- *  method: 0 = euler, 1 = rk4 (torchdiffeq fixed-grid 3/8 rule; flow.py:76-85), 2 = midpoint (y1 = y + dt f(y + dt/2 f(y)))
+ *  method: 0 = euler, 1 = rk4 (torchdiffeq fixed-grid 3/8 rule; flow.py:76-85), 2 = midpoint (y1 = y + dt f(y + dt/2 f(y))),
+ *          3 = dopri5 (adaptive Dormand-Prince 5(4)) -- the gpode_rollout_adaptive_* entry points only; the fixed-grid ones refuse it
  */
 #ifndef GPODE_H
 #define GPODE_H
@@ -29,6 +30,8 @@ extern "C" {
 #define GPODE_KERNEL_DF 1
 #define GPODE_METHOD_EULER 0
 #define GPODE_METHOD_RK4 1
+#define GPODE_METHOD_MIDPOINT 2
+#define GPODE_METHOD_DOPRI5 3
 
 /* Library / build identification. */
 const char* gpode_version(void);
@@ -133,6 +136,26 @@ int gpode_rollout_fwd_n(int kernel, int order, int method, int Di, int Do, int M
 int gpode_rollout_bwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                         const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
                         float* gz0, float* astage, void* stream);
+/* Adaptive rollout (method = GPODE_METHOD_DOPRI5): Dormand-Prince 5(4) with one step-size controller per trajectory, steps landing
+ * on the output times ts (strictly increasing), tolerances rtol / atol on the RMS norm over the state.  K = accepted steps a
+ * trajectory may take (the capacity of its record).
+ *   zt     (L,N,T,D)      the states at ts; NaN from the first output a failed trajectory did not reach
+ *   counts (L,N,4) int32  accepted steps, rejected steps, status (0 ok, 1 budget K exhausted, 2 step size underflow,
+ *                         3 ts not increasing), evaluations of f (= 1 + 6 (accepted + rejected))
+ * and, when gradients are needed (xstage != NULL; with xstage == NULL nothing but zt and counts is written):
+ *   xstage (L,N,K,6,D)    the six stage inputs of every accepted step, consecutively     } zero past a trajectory's
+ *   hstep  (L,N,K)        the accepted step sizes                                        } count of accepted steps
+ *   iend   (L,N,T-1) int32  accepted steps taken when output t+1 was reached (non-decreasing)
+ * gpode_rollout_adaptive_bwd_n walks the record backwards (step sizes constant; rejected steps and the error estimate carry no
+ * gradient): gzt (L,N,T,D) -> gz0 (L,N,D), astage (L,N,K,6,Do) = dL/df at every recorded evaluation, zero past the count -- so
+ * gpode_param_grad_n runs over all K * 6 rows of (xstage, astage) unchanged.  No fused parameter-gradient form
+ * (gpode_rollout_bwd_pgrad_chunks returns 0 for this method). */
+int gpode_rollout_adaptive_fwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                                 const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
+                                 float* zt, float* xstage, float* hstep, int* iend, int* counts, void* stream);
+int gpode_rollout_adaptive_bwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                                 const float* pack, const float* xstage, const float* hstep, const int* iend, const float* gzt,
+                                 int N, int T, int K, float* gz0, float* astage, void* stream);
 /* gpode_rollout_bwd_n and gpode_param_grad_n in ONE pass: the reverse sweep visits every (stage input, adjoint) row anyway, so the
  * rows' parameter-gradient terms are accumulated on the way and come out as gpack (ndraws, pack_floats) -- what the two calls
  * produce together, with one launch and one pass over the rows less.  slab: ndraws * nchunk * pack_floats floats of scratch with

@@ -1,0 +1,432 @@
+// gp_adaptive.hip -- adaptive Dormand-Prince 5(4) rollout (forward) and its reverse sweep.
+//
+// Replaces torchdiffeq's `dopri5` behind Flow.forward (flow.py:49,68-86).  As in the fixed-grid rollout one wavefront (wave
+// mapping) or one workgroup of four (team mapping) carries a trajectory from z0 to z_{T-1} in ONE launch; only the trip count
+// is data-dependent.  Differences to torchdiffeq, by design:
+//   * one controller PER TRAJECTORY (torchdiffeq couples the batch through one RMS norm): every trajectory meets its own tolerance;
+//   * steps LAND on the output times (a step that would pass ts[t+1] is shortened to end on it; no dense output), so zt[:, t] is a
+//     step end point and the reverse sweep needs no interpolant.  Results agree to the tolerances, not step by step.
+//
+// Controller (Hairer, Noersett, Wanner, Solving ODEs I, II.4-5)
+//   err_i  = h sum_j e_j k_j,i                      (5th-order minus embedded 4th-order solution)
+//   ratio  = sqrt(mean_i (err_i / (atol + rtol max(|y_i|, |ynew_i|)))^2),   accept iff ratio <= 1
+//   h_new  = h clamp(0.9 ratio^(-1/5), 0.2, 10);  no growth on the step after a rejection
+//   first step: h = min(100 h0, (0.01 / d1)^(1/5), ts[1] - ts[0]),  h0 = 0.01 d0 / d1,  d0 = |y0|, d1 = |f0| in the scaled RMS norm:
+//               Hairer's estimate without its second-derivative probe, so that it costs no evaluation beyond f0 (= k1 of step one)
+//   landing: inside an interval with `rem` left, a proposal with 1.01 h >= rem is replaced by rem (the 1 % stretch of Hairer's
+//            DOPRI5 code: no sliver of a step is left over); after such a cut step the larger of the uncut proposal and the
+//            controller's is carried into the next interval
+//   failure: budget (K accepted steps recorded and more needed) -> status 1; step <= 16 eps max(|t|, |h|) -> status 2;
+//            ts not increasing -> status 3.  The trajectory stops, its remaining outputs are NaN; others are unaffected.
+//
+// The seven slopes k_j are wave-uniform values.  They are kept in a wavefront-private row block of LDS (7 x 16 floats), not in
+// registers: the stage loop then indexes them dynamically (ONE inlined evaluation of f instead of seven) and the kernel needs
+// no more registers than the fixed-grid rk4 one, whose four slopes in registers are at the edge already at D = 16.
+//
+// Record (for the reverse sweep; all zero past the count): xstage (N,K,6,D) the six stage inputs of every ACCEPTED step (b7 = 0,
+// so the seventh does not enter the step), hstep (N,K), iend (N,T-1) = accepted steps taken when output t+1 was reached.
+#include "gp_rollout.hpp"
+
+namespace gp {
+
+// Dormand-Prince 5(4).  Row s: the weights of k_0 .. k_{s-1} in the input of stage s; row 6 is the 5th-order solution itself
+// (FSAL: its slope is k_0 of the next step).  dp_e = 5th-order minus 4th-order weights.
+__constant__ float dp_a[7][6] = {
+    {0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
+    {(float)(1.0 / 5.0), 0.f, 0.f, 0.f, 0.f, 0.f},
+    {(float)(3.0 / 40.0), (float)(9.0 / 40.0), 0.f, 0.f, 0.f, 0.f},
+    {(float)(44.0 / 45.0), (float)(-56.0 / 15.0), (float)(32.0 / 9.0), 0.f, 0.f, 0.f},
+    {(float)(19372.0 / 6561.0), (float)(-25360.0 / 2187.0), (float)(64448.0 / 6561.0), (float)(-212.0 / 729.0), 0.f, 0.f},
+    {(float)(9017.0 / 3168.0), (float)(-355.0 / 33.0), (float)(46732.0 / 5247.0), (float)(49.0 / 176.0), (float)(-5103.0 / 18656.0), 0.f},
+    {(float)(35.0 / 384.0), 0.f, (float)(500.0 / 1113.0), (float)(125.0 / 192.0), (float)(-2187.0 / 6784.0), (float)(11.0 / 84.0)}};
+__constant__ float dp_e[7] = {(float)(71.0 / 57600.0), 0.f, (float)(-71.0 / 16695.0), (float)(71.0 / 1920.0),
+                              (float)(-17253.0 / 339200.0), (float)(22.0 / 525.0), (float)(-1.0 / 40.0)};
+
+constexpr int KP = 16;                  // floats per slope row in LDS (D <= 16 for every compiled width)
+constexpr int NREC = 6;                 // recorded stage inputs per accepted step
+
+struct AdaptFwd {
+  const float* pack; size_t pack_stride; int M, S;
+  const float* z0; const float* ts; int N, T, K;
+  float rtol, atol;
+  float* zt; float* xstage; float* hstep; int* iend; int* counts;
+};
+struct AdaptBwd {
+  const float* pack; size_t pack_stride; int M, S;
+  const float* xstage; const float* hstep; const int* iend; const float* gzt; int N, T, K;
+  float* gz0; float* astage;
+};
+
+// a value every lane holds identically -> a scalar: the controller's branches are then scalar branches, the same in every
+// wavefront of a team (whose evaluations carry a workgroup barrier) because the slopes they derive from are bit-identical there
+__device__ __forceinline__ float uni(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+
+template <int DI> __device__ __forceinline__ void put_row(float* __restrict__ row, const float (&v)[DI]) {
+#pragma unroll
+  for (int d = 0; d < DI; ++d) row[d] = v[d];      // every lane writes the same value to the same address; it reads back its own
+}
+
+template <int DI> __device__ __forceinline__ float scaled_rms(const float (&v)[DI], const float (&a)[DI], const float (&b)[DI], float rtol, float atol) {
+  float sq = 0.f;
+#pragma unroll
+  for (int d = 0; d < DI; ++d) {
+    const float r = v[d] / (atol + rtol * fmaxf(fabsf(a[d]), fabsf(b[d])));
+    sq = fmaf(r, r, sq);
+  }
+  return sqrtf(sq * (1.f / DI));
+}
+
+// One trajectory, start to end.  kst: this wavefront's 7 x KP floats of LDS.  wr: this wavefront writes the outputs (in a team all
+// four compute the same values).  Pointers are the draw's.
+template <class EV, int DI, int DO, int ORDER>
+__device__ __forceinline__ void dopri5_trajectory(EV& ev, const AdaptFwd& a, const float* __restrict__ z0, float* __restrict__ zt,
+                                                  float* __restrict__ xstage, float* __restrict__ hstep, int* __restrict__ iend,
+                                                  int* __restrict__ counts, int n, float* __restrict__ kst, bool wr, int lane) {
+  const int T = a.T, K = a.K;
+  const float rtol = a.rtol, atol = a.atol;
+  const bool rec = xstage != nullptr && wr;
+  float y[DI], xs[DI], kv[DI];
+#pragma unroll
+  for (int i = 0; i < DI; ++i) y[i] = z0[(size_t)n * DI + i];
+  float* out = zt + (size_t)n * T * DI;
+  float* xrec = rec ? xstage + (size_t)n * K * NREC * DI : nullptr;
+  float* hrec = rec ? hstep + (size_t)n * K : nullptr;
+  int* irec = rec ? iend + (size_t)n * (T - 1) : nullptr;
+  if (wr) store_state<DI>(out, y, lane);
+  ode_rhs_mut<EV, DI, DO, ORDER>(ev, y, kv);
+  put_row<DI>(kst, kv);
+  int nacc = 0, nrej = 0, status = 0, nfe = 1, t = 0;
+  float h = 0.f;
+  bool after_reject = false;
+  if (T > 1) {
+    const float d0 = scaled_rms<DI>(y, y, y, rtol, atol), d1 = scaled_rms<DI>(kv, y, y, rtol, atol);
+    const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
+    const float h1 = d1 <= 1e-15f ? fmaxf(1e-6f, h0 * 1e-3f) : powf(0.01f / d1, 0.2f);
+    h = uni(fminf(fminf(100.f * h0, h1), a.ts[1] - a.ts[0]));
+  }
+  for (; t + 1 < T; ++t) {
+    const float t0 = a.ts[t], t1 = a.ts[t + 1];
+    const float dt = t1 - t0, tabs = fmaxf(fabsf(t0), fabsf(t1));
+    if (!(dt > 0.f)) { status = 3; break; }
+    float rem = dt;
+    while (true) {
+      if (nacc >= K) { status = 1; break; }
+      const bool cut = 1.01f * h >= rem;
+      const float hs = cut ? rem : h;
+      if (!(hs > 16.f * 1.1920929e-7f * fmaxf(tabs, fabsf(hs)))) { status = 2; break; }   // also a NaN step
+      if (rec) store_state<DI>(xrec + (size_t)(nacc * NREC) * DI, y, lane);
+      for (int s = 1; s < 7; ++s) {
+        float acc[DI];
+#pragma unroll
+        for (int d = 0; d < DI; ++d) acc[d] = 0.f;
+        for (int j = 0; j < s; ++j) {
+          const float c = dp_a[s][j];
+#pragma unroll
+          for (int d = 0; d < DI; ++d) acc[d] = fmaf(c, kst[j * KP + d], acc[d]);
+        }
+#pragma unroll
+        for (int d = 0; d < DI; ++d) xs[d] = fmaf(hs, acc[d], y[d]);
+        if (rec && s < NREC) store_state<DI>(xrec + (size_t)(nacc * NREC + s) * DI, xs, lane);
+        ode_rhs_mut<EV, DI, DO, ORDER>(ev, xs, kv);
+        put_row<DI>(kst + s * KP, kv);
+      }
+      nfe += 6;
+      // xs = the 5th-order solution, kv = its slope
+      float err[DI];
+#pragma unroll
+      for (int d = 0; d < DI; ++d) err[d] = 0.f;
+      for (int j = 0; j < 7; ++j) {
+        const float c = dp_e[j];
+#pragma unroll
+        for (int d = 0; d < DI; ++d) err[d] = fmaf(c, kst[j * KP + d], err[d]);
+      }
+#pragma unroll
+      for (int d = 0; d < DI; ++d) err[d] *= hs;
+      const float ratio = uni(scaled_rms<DI>(err, y, xs, rtol, atol));
+      float fac = uni(fminf(fmaxf(0.9f * powf(ratio, -0.2f), 0.2f), 10.f));   // ratio 0 -> 10; NaN -> 0.2
+      if (ratio <= 1.f) {
+        if (after_reject) fac = fminf(fac, 1.f);
+        after_reject = false;
+#pragma unroll
+        for (int d = 0; d < DI; ++d) y[d] = xs[d];
+        put_row<DI>(kst, kv);
+        if (rec && lane == 0) hrec[nacc] = hs;
+        ++nacc;
+        h = cut ? fmaxf(h, hs * fac) : hs * fac;
+        if (cut) break;
+        rem -= hs;
+      } else {
+        ++nrej;
+        after_reject = true;
+        h = hs * fac;
+      }
+    }
+    if (status) break;
+    if (wr) store_state<DI>(out + (size_t)(t + 1) * DI, y, lane);
+    if (rec && lane == 0) irec[t] = nacc;
+  }
+  if (status && wr) {                                // a failed trajectory: NaN from the output it did not reach
+    const float qnan = __int_as_float(0x7fc00000);
+    for (int i = (t + 1) * DI + lane; i < T * DI; i += 64) out[i] = qnan;
+    if (rec) for (int i = t + lane; i < T - 1; i += 64) irec[i] = nacc;
+  }
+  if (rec) {                                         // rows past the count (and what a rejected attempt left there) are zero
+    for (size_t i = (size_t)nacc * NREC * DI + lane; i < (size_t)K * NREC * DI; i += 64) xrec[i] = 0.f;
+    for (int i = nacc + lane; i < K; i += 64) hrec[i] = 0.f;
+  }
+  if (wr && lane == 0) {
+    int* c = counts + (size_t)n * 4;
+    c[0] = nacc; c[1] = nrej; c[2] = status; c[3] = nfe;
+  }
+}
+
+// blockIdx.y = Monte-Carlo draw: its own pack, the shared initial states, its own trajectories and record
+#define GP_ADAPT_DRAW_POINTERS                                                                                   \
+  const size_t dr = blockIdx.y, NT = (size_t)a.N;                                                                \
+  const float* pack = a.pack + dr * a.pack_stride;                                                               \
+  float* zt = a.zt + dr * NT * a.T * DI;                                                                         \
+  float* xstage = a.xstage ? a.xstage + dr * NT * a.K * NREC * DI : nullptr;                                     \
+  float* hstep = a.xstage ? a.hstep + dr * NT * a.K : nullptr;                                                   \
+  int* iend = a.xstage ? a.iend + dr * NT * (a.T - 1) : nullptr;                                                 \
+  int* counts = a.counts + dr * NT * 4;
+
+// One wavefront per trajectory.  The (up to four) wavefronts of a workgroup take different numbers of steps: after the pack is
+// staged there is no workgroup barrier.
+template <class EV, int DI, int DO, int ORDER, bool USE_LDS>
+__global__ __launch_bounds__(256) void rollout_adaptive_kernel(AdaptFwd a, size_t lds_f4) {
+  static_assert(DI == ORDER * DO && DI <= KP, "state dim = order * D_out");
+  __shared__ float kst[4][7 * KP];
+  GP_ADAPT_DRAW_POINTERS
+  if (USE_LDS) stage_pack_lds(pack, lds_f4);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
+  EV ev;
+  ev.init(pack, a.M, a.S, lane);
+  for (int n = blockIdx.x * wpb + wave; n < a.N; n += gridDim.x * wpb)
+    dopri5_trajectory<EV, DI, DO, ORDER>(ev, a, a.z0, zt, xstage, hstep, iend, counts, n, kst[wave], true, lane);
+}
+
+// One workgroup per trajectory.  Every evaluation carries the team's barrier, so the four wavefronts must take the same steps:
+// they do, the controller's inputs are the combined slopes, which every wavefront sums from the same LDS slots in the same order.
+template <class EV, int DI, int DO, int ORDER>
+__global__ __launch_bounds__(64 * EV::kTeam) void rollout_adaptive_team_kernel(AdaptFwd a) {
+  static_assert(DI == ORDER * DO && DI <= KP, "state dim = order * D_out");
+  __shared__ float slots[2 * EV::kTeam * TeamCombine::DP];
+  __shared__ float kst[EV::kTeam][7 * KP];
+  GP_ADAPT_DRAW_POINTERS
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  EV ev;
+  ev.init(pack, a.M, a.S, slots, wave, lane);
+  for (int n = blockIdx.x; n < a.N; n += gridDim.x)
+    dopri5_trajectory<EV, DI, DO, ORDER>(ev, a, a.z0, zt, xstage, hstep, iend, counts, n, kst[wave], wave == 0, lane);
+}
+
+// Reverse sweep: the adjoint of an explicit Runge-Kutta step, over the recorded accepted steps, step sizes constant.
+//   y1 = y + h sum_j b_j k_j,  k_j = F(x_j),  x_j = y + h sum_{l<j} a_jl k_l      (j = 0..5; b_6 = 0)
+//   ak_j = h b_j lam;  for j = 5..0: g = J_F(x_j)^T ak_j, lam' += g, ak_l += h a_jl g (l < j);  lam <- lam + sum g
+// gzt[:, t] enters before the step that ended on ts[t] is undone (iend[t-1] = its number).  The slope adjoints live in LDS like
+// the slopes of the forward pass.  Sequential per trajectory, no atomics: deterministic.
+template <class EV, int DI, int DO, int ORDER>
+__global__ __launch_bounds__(64 * EV::kTeam) void rollout_adaptive_bwd_kernel(AdaptBwd a) {
+  static_assert(DI == ORDER * DO && DI <= KP, "state dim = order * D_out");
+  __shared__ float slots[2 * EV::kTeam * TeamCombine::DP];
+  __shared__ float akst[EV::kTeam][NREC * KP];
+  const size_t dr = blockIdx.y, NT = (size_t)a.N;
+  const int T = a.T, K = a.K;
+  const float* pack = a.pack + dr * a.pack_stride;
+  const float* xstage = a.xstage + dr * NT * K * NREC * DI;
+  const float* hstep = a.hstep + dr * NT * K;
+  const int* iend = a.iend + dr * NT * (T - 1);
+  const float* gzt = a.gzt + dr * NT * T * DI;
+  float* gz0 = a.gz0 + dr * NT * DI;
+  float* astage = a.astage + dr * NT * K * NREC * DO;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float* ak = akst[wave];
+  EV ev;
+  ev.init(pack, a.M, a.S, slots, wave, lane);
+  for (int n = blockIdx.x; n < a.N; n += gridDim.x) {
+    const float* gz = gzt + (size_t)n * T * DI;
+    const int* ie = iend + (size_t)n * (T - 1);
+    int nacc = T > 1 ? __builtin_amdgcn_readfirstlane(ie[T - 2]) : 0;
+    nacc = nacc < 0 ? 0 : (nacc > K ? K : nacc);
+    float lam[DI];
+#pragma unroll
+    for (int d = 0; d < DI; ++d) lam[d] = 0.f;
+    int tq = T - 2;                                  // outputs tq + 1 and below still wait for their gradient
+    for (int i = nacc;; --i) {
+      while (tq >= 0 && __builtin_amdgcn_readfirstlane(ie[tq]) >= i) {
+#pragma unroll
+        for (int d = 0; d < DI; ++d) lam[d] += gz[(size_t)(tq + 1) * DI + d];
+        --tq;
+      }
+      if (i == 0) break;
+      const size_t row = (size_t)n * K + (i - 1);
+      const float hs = uni(hstep[row]);
+      const float* xr = xstage + row * NREC * DI;
+      float* ar = astage + row * NREC * DO;
+      for (int j = 0; j < NREC; ++j) {
+        const float c = hs * dp_a[6][j];
+#pragma unroll
+        for (int d = 0; d < DI; ++d) ak[j * KP + d] = c * lam[d];
+      }
+      for (int j = NREC - 1; j >= 0; --j) {
+        float x[DI], aj[DI], g[DI], af[DO];
+#pragma unroll
+        for (int d = 0; d < DI; ++d) { x[d] = xr[j * DI + d]; aj[d] = ak[j * KP + d]; }
+        ode_vjp<EV, DI, DO, ORDER>(ev, x, aj, g, af);
+        if (wave == 0) store_state<DO>(ar + j * DO, af, lane);
+#pragma unroll
+        for (int d = 0; d < DI; ++d) lam[d] += g[d];
+        for (int l = 0; l < j; ++l) {
+          const float c = hs * dp_a[j][l];
+#pragma unroll
+          for (int d = 0; d < DI; ++d) ak[l * KP + d] = fmaf(c, g[d], ak[l * KP + d]);
+        }
+      }
+    }
+#pragma unroll
+    for (int d = 0; d < DI; ++d) lam[d] += gz[d];
+    if (wave == 0) {
+      store_state<DI>(gz0 + (size_t)n * DI, lam, lane);
+      float* az = astage + (size_t)n * K * NREC * DO;
+      for (size_t i = (size_t)nacc * NREC * DO + lane; i < (size_t)K * NREC * DO; i += 64) az[i] = 0.f;
+    }
+  }
+}
+
+// ----------------------------------------------------------------------------------------------
+// host launchers: the dispatch of the fixed-grid rollout (gp_forward.hip, gp_backward.hip)
+// ----------------------------------------------------------------------------------------------
+template <int DI, int DO, int ORDER>
+static int launch_adaptive_rbf(const AdaptFwd& a, int nd, hipStream_t st) {
+  const int N = a.N, M = a.M, S = a.S;
+  int grid, block;
+  grid_for(N, grid, block);
+  if (N <= kTeamMaxRows && DO <= 16) {
+    if (RbfTeamEval<DI, DO, 1>::fits(M, S)) {
+      hipLaunchKernelGGL((rollout_adaptive_team_kernel<RbfTeamEval<DI, DO, 1>, DI, DO, ORDER>), dim3(team_grid(N), nd), 256, 0, st, a);
+      return check_launch("rollout_adaptive_rbf_team");
+    }
+  }
+  if (N <= kTeamMaxRows) {
+    hipLaunchKernelGGL((rollout_adaptive_team_kernel<RbfStreamTeam<DI, DO>, DI, DO, ORDER>), dim3(team_grid(N), nd), 256, 0, st, a);
+    return check_launch("rollout_adaptive_rbf_team_stream");
+  }
+  const int SJ = cdiv(S, 64), MJ = cdiv(M, 64);
+  if constexpr (rbf_reg_fits<DI, DO, 4, 2>()) {
+    if (SJ == 4 && MJ == 2) {
+      hipLaunchKernelGGL((rollout_adaptive_kernel<RbfRegEval<DI, DO, 4, 2>, DI, DO, ORDER, false>), dim3(grid, nd), block, 0, st, a, (size_t)0);
+      return check_launch("rollout_adaptive_rbf");
+    }
+  }
+  if constexpr (rbf_reg_fits<DI, DO, 1, 1>()) {
+    if (SJ == 1 && MJ == 1) {
+      hipLaunchKernelGGL((rollout_adaptive_kernel<RbfRegEval<DI, DO, 1, 1>, DI, DO, ORDER, false>), dim3(grid, nd), block, 0, st, a, (size_t)0);
+      return check_launch("rollout_adaptive_rbf");
+    }
+  }
+  hipLaunchKernelGGL((rollout_adaptive_kernel<RbfStreamEval<DI, DO>, DI, DO, ORDER, false>), dim3(grid, nd), block, 0, st, a, (size_t)0);
+  return check_launch("rollout_adaptive_rbf");
+}
+
+template <int D>
+static int launch_adaptive_df(const AdaptFwd& a, int nd, hipStream_t st) {
+  using L = DfLayout<D>;
+  const int N = a.N, M = a.M, S = a.S;
+  const size_t f4 = L::rff_f4(S) + L::ind_f4(M);
+  int grid, block;
+  grid_for(N, grid, block);
+  if constexpr (D <= 8) {
+    if (N <= kTeamMaxRows && DfTeamEval<D, 1>::fits(M, S)) {
+      hipLaunchKernelGGL((rollout_adaptive_team_kernel<DfTeamEval<D, 1>, D, D, 1>), dim3(team_grid(N), nd), 256, 0, st, a);
+      return check_launch("rollout_adaptive_df_team");
+    }
+  }
+  if (N <= kTeamMaxRows) {
+    hipLaunchKernelGGL((rollout_adaptive_team_kernel<DfStreamTeam<D>, D, D, 1>), dim3(team_grid(N), nd), 256, 0, st, a);
+    return check_launch("rollout_adaptive_df_team_stream");
+  }
+  if (f4 * 16 <= kLdsLimitBytes) {
+    if (N <= 1024) { block = 64; grid = N < 256 ? N : 256; }
+    else { block = 256; grid = 256; }
+    auto kern = rollout_adaptive_kernel<DfEval<D, true>, D, D, 1, true>;
+    if (set_max_lds((const void*)kern, f4 * 16)) return 1;
+    hipLaunchKernelGGL(kern, dim3(grid, nd), block, f4 * 16, st, a, f4);
+  } else {
+    hipLaunchKernelGGL((rollout_adaptive_kernel<DfEval<D, false>, D, D, 1, false>), dim3(grid, nd), block, 0, st, a, (size_t)0);
+  }
+  return check_launch("rollout_adaptive_df");
+}
+
+template <int DI, int DO>
+static int adaptive_rbf_dispatch(int order, const AdaptFwd& a, int nd, hipStream_t st) {
+  if constexpr (DI == DO) { if (order == 1) return launch_adaptive_rbf<DI, DO, 1>(a, nd, st); }
+  if constexpr (DI == 2 * DO) { if (order == 2) return launch_adaptive_rbf<DI, DO, 2>(a, nd, st); }
+  return set_error("gpode_rollout_adaptive_fwd: order=%d needs Di == order*Do (Di=%d Do=%d)", order, DI, DO);
+}
+
+int rollout_adaptive_fwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
+                         const float* z0, const float* ts, int N, int T, float rtol, float atol, int K, float* zt, float* xstage,
+                         float* hstep, int* iend, int* counts, hipStream_t st) {
+  const AdaptFwd a{pack, pack_stride, M, S, z0, ts, N, T, K, rtol, atol, zt, xstage, hstep, iend, counts};
+  if (kernel == 0) {
+#define X(p, q) if (Di == p && Do == q) return adaptive_rbf_dispatch<p, q>(order, a, nd, st);
+    GP_RBF_DIMS(X)
+#undef X
+  } else {
+    if (order != 1) return set_error("gpode_rollout_adaptive_fwd: DF kernel is first-order only (kernels.py:259-262)");
+#define X(p) if (Di == p && Do == p) return launch_adaptive_df<p>(a, nd, st);
+    GP_DF_DIMS(X)
+#undef X
+  }
+  return set_error("gpode_rollout_adaptive_fwd: no specialisation for kernel=%d Di=%d Do=%d", kernel, Di, Do);
+}
+
+template <int DI, int DO, int ORDER>
+static int launch_adaptive_bwd_rbf(const AdaptBwd& a, int nd, hipStream_t st) {
+  if constexpr (DO <= 8) {
+    if (rbf_team_ok<DI, DO>(a.M, a.S)) {
+      hipLaunchKernelGGL((rollout_adaptive_bwd_kernel<RbfTeamEval<DI, DO, 1>, DI, DO, ORDER>), dim3(team_grid(a.N), nd), 256, 0, st, a);
+      return check_launch("rollout_adaptive_bwd_rbf");
+    }
+  }
+  hipLaunchKernelGGL((rollout_adaptive_bwd_kernel<RbfStreamTeam<DI, DO>, DI, DO, ORDER>), dim3(team_grid(a.N), nd), 256, 0, st, a);
+  return check_launch("rollout_adaptive_bwd_rbf_stream");
+}
+
+template <int D>
+static int launch_adaptive_bwd_df(const AdaptBwd& a, int nd, hipStream_t st) {
+  if constexpr (D <= 8) {
+    if (df_team_ok<D>(a.M, a.S)) {
+      hipLaunchKernelGGL((rollout_adaptive_bwd_kernel<DfTeamEval<D, 1>, D, D, 1>), dim3(team_grid(a.N), nd), 256, 0, st, a);
+      return check_launch("rollout_adaptive_bwd_df");
+    }
+  }
+  hipLaunchKernelGGL((rollout_adaptive_bwd_kernel<DfStreamTeam<D>, D, D, 1>), dim3(team_grid(a.N), nd), 256, 0, st, a);
+  return check_launch("rollout_adaptive_bwd_df_stream");
+}
+
+template <int DI, int DO>
+static int adaptive_bwd_rbf_dispatch(int order, const AdaptBwd& a, int nd, hipStream_t st) {
+  if constexpr (DI == DO) { if (order == 1) return launch_adaptive_bwd_rbf<DI, DO, 1>(a, nd, st); }
+  if constexpr (DI == 2 * DO) { if (order == 2) return launch_adaptive_bwd_rbf<DI, DO, 2>(a, nd, st); }
+  return set_error("gpode_rollout_adaptive_bwd: order=%d needs Di == order*Do (Di=%d Do=%d)", order, DI, DO);
+}
+
+int rollout_adaptive_bwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
+                         const float* xstage, const float* hstep, const int* iend, const float* gzt, int N, int T, int K,
+                         float* gz0, float* astage, hipStream_t st) {
+  const AdaptBwd a{pack, pack_stride, M, S, xstage, hstep, iend, gzt, N, T, K, gz0, astage};
+  if (kernel == 0) {
+#define X(p, q) if (Di == p && Do == q) return adaptive_bwd_rbf_dispatch<p, q>(order, a, nd, st);
+    GP_RBF_DIMS(X)
+#undef X
+  } else {
+    if (order != 1) return set_error("gpode_rollout_adaptive_bwd: DF kernel is first-order only");
+#define X(p) if (Di == p && Do == p) return launch_adaptive_bwd_df<p>(a, nd, st);
+    GP_DF_DIMS(X)
+#undef X
+  }
+  return set_error("gpode_rollout_adaptive_bwd: no specialisation for kernel=%d Di=%d Do=%d", kernel, Di, Do);
+}
+
+}  // namespace gp

@@ -14,9 +14,7 @@
 //     results go to a slab that a second kernel sums in fixed order (deterministic, no float atomics).
 //     Gradients come out in PACK LAYOUT (d/d om, d/d aw, d/d z, d/d cc ... + the uniform tail), which
 //     gp_cache_bwd.hip chains back to the raw parameters.
-#include "gp_eval.hpp"
-#include "gp_team.hpp"
-#include "gp_launch.hpp"
+#include "gp_rollout.hpp"
 
 namespace gp {
 
@@ -29,8 +27,6 @@ template <int DI> __device__ __forceinline__ void store_vec(float* __restrict__ 
   }
 }
 
-// ODE-level VJP (flow.py:27-45): order 1: dy = f(y); order 2: dy = [y[q:], f(y)].
-// a (DI) = adjoint of dy  ->  gx (DI) = (d dy / d y)^T a ;  af (DO) = the part that multiplies J_f.
 template <int DI, int DO, int NJ>
 __device__ __forceinline__ void store_grads_rbf(const typename RbfTeamEval<DI, DO, NJ>::Grads& G, float* __restrict__ out, int M, int S,
                                                 int wave, int lane, float (*sInd)[64][4 * RbfLayout<DI, DO>::RQ2],
@@ -39,18 +35,6 @@ template <int D, int NJ, int PART = 0>
 __device__ __forceinline__ void store_grads_df(const typename DfTeamEval<D, NJ>::Grads& G, float* __restrict__ out, int M, int S, int wave,
                                                int lane, float (*sInd)[64][4 * DfLayout<D>::RQ2],
                                                float (*sUni)[2 * D * ((D + 1) / 2) + (D + 1) / 2]);
-struct NoGrads {};
-template <class EV, int DI, int DO, int ORDER, class GR = NoGrads>
-__device__ __forceinline__ void ode_vjp(EV& ev, const float (&x)[DI], const float (&a)[DI], float (&gx)[DI], float (&af)[DO], GR* G = nullptr) {
-#pragma unroll
-  for (int i = 0; i < DO; ++i) af[i] = ORDER == 1 ? a[i] : a[DO + i];
-  if constexpr (std::is_same<GR, NoGrads>::value) ev.vjp(x, af, gx);
-  else ev.vjp_grad(x, af, gx, *G);                  // the row's parameter-gradient terms ride along (PGRAD form of the reverse sweep)
-  if (ORDER != 1) {
-#pragma unroll
-    for (int i = 0; i < DO; ++i) gx[DO + i] += a[i];
-  }
-}
 
 template <class EV, bool PG> struct GradsOf { using type = NoGrads; };
 template <class EV> struct GradsOf<EV, true> { using type = typename EV::Grads; };
@@ -658,15 +642,6 @@ __global__ __launch_bounds__(1024) void reduce_slab_kernel(const float* __restri
 // ---------------------------------------------------------------------------------------------
 static inline int team_grid_b(int N) { return N < 2048 ? N : 2048; }
 
-// register-resident team when the quarter pack fits (S <= 256, M <= 128, D <= 8), streamed team otherwise
-template <int DI, int DO> static bool rbf_team_ok(int M, int S) {
-  if constexpr (DO <= 8) return RbfTeamEval<DI, DO, 1>::fits(M, S);
-  return false;
-}
-template <int D> static bool df_team_ok(int M, int S) {
-  if constexpr (D <= 8) return DfTeamEval<D, 1>::fits(M, S);
-  return false;
-}
 
 template <int DI, int DO, int ORDER, int METHOD>
 static int launch_bwd_rbf(const float* pack, int M, int S, const float* xstage, const float* gzt, const float* ts, int N, int T,
@@ -719,7 +694,7 @@ static int bwd_rbf_dispatch(int order, int method, const float* pack, int M, int
 
 int rollout_bwd(int kernel, int order, int method, int Di, int Do, int M, int S, const float* pack, const float* xstage,
                 const float* gzt, const float* ts, int N, int T, float* gz0, float* astage, hipStream_t st, Draws dw) {
-  if (method < 0 || method > 2) return set_error("gpode_rollout_bwd: method %d", method);
+  if (method < 0 || method > 2) return set_error("gpode_rollout_bwd: method %d (0 euler, 1 rk4, 2 midpoint; 3 dopri5: gpode_rollout_adaptive_bwd_n)", method);
   if (kernel == 0) {
 #define X(a, b) if (Di == a && Do == b) return bwd_rbf_dispatch<a, b>(order, method, pack, M, S, xstage, gzt, ts, N, T, gz0, astage, st, dw);
     GP_BWD_RBF_DIMS(X)

@@ -90,6 +90,13 @@ int rollout_bwd_pgrad_chunks(int kernel, int order, int method, int Di, int Do, 
 int rollout_bwd_pgrad(int kernel, int order, int method, int Di, int Do, int M, int S, const float* pack, const float* xstage,
                       const float* gzt, const float* ts, int N, int T, float* gz0, float* astage, float* slab, int nchunk,
                       float* gpack, hipStream_t st, Draws dw = Draws{});
+// adaptive Dormand-Prince rollout and its reverse sweep (gp_adaptive.hip); every per-draw operand is dense, `pack_stride` apart
+int rollout_adaptive_fwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
+                         const float* z0, const float* ts, int N, int T, float rtol, float atol, int K, float* zt, float* xstage,
+                         float* hstep, int* iend, int* counts, hipStream_t st);
+int rollout_adaptive_bwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
+                         const float* xstage, const float* hstep, const int* iend, const float* gzt, int N, int T, int K,
+                         float* gz0, float* astage, hipStream_t st);
 int rhs_vjp(int kernel, int Di, int Do, int M, int S, const float* pack, const float* x, const float* a, int R, float* gx,
             int prior_only, hipStream_t st, Draws dw = Draws{});
 int param_grad(int kernel, int Di, int Do, int M, int S, const float* pack, const float* xr, const float* ar, int R,

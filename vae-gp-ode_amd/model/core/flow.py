@@ -1,9 +1,12 @@
-"""ODE right-hand side wrapper and fixed-grid flow -- operator API of experiments/model/core/flow.py.
+"""ODE right-hand side wrapper and flow -- operator API of experiments/model/core/flow.py.
 
 The reference hands ``ODEfunc`` to torchdiffeq, which calls it 1 (euler) or 4 (rk4) times per step
-from Python.  Here ``Flow.forward`` is ONE persistent HIP kernel per MC draw (csrc/gp_forward.hip):
-each wavefront integrates one trajectory over the whole grid.  Fixed-grid methods only ('euler',
-'rk4' = torchdiffeq's 3/8 rule, 'midpoint'); adaptive solvers are out of scope.
+from Python.  Here ``Flow.forward`` is ONE persistent HIP kernel for all MC draws: each wavefront (or
+team of four) integrates one trajectory over the whole grid.  Solvers: the fixed-grid 'euler', 'rk4'
+(= torchdiffeq's 3/8 rule) and 'midpoint' (csrc/gp_forward.hip), and the adaptive 'dopri5'
+(csrc/gp_adaptive.hip: Dormand-Prince 5(4), one step-size controller per trajectory, steps landing
+on ``ts`` -- it agrees with torchdiffeq's to the tolerances, not step by step).  The rest of the
+reference's --solver list (bdf, adams, explicit_adams, fixed_adams) is refused: ops.REFUSED_SOLVERS.
 """
 import torch
 import torch.nn as nn
@@ -20,9 +23,10 @@ class ODEfunc(nn.Module):
         self.order = order
         self.register_buffer('_num_evals', torch.tensor(0.))
         self._host_evals = None                      # count of the last fused solve, not yet written to the buffer
+        self._counts = None                          # adaptive solve: its per-trajectory counts, still on the device
 
     def before_odeint(self, rebuild_cache):
-        self._host_evals = None
+        self._host_evals = self._counts = None
         self._num_evals.fill_(0)
         if rebuild_cache:
             self.diffeq.build_cache()
@@ -30,15 +34,32 @@ class ODEfunc(nn.Module):
     def _set_evals(self, n):
         """The fused rollout knows its evaluation count on the host: the ``_num_evals`` buffer (a state_dict entry of the
         reference, flow.py:14) is brought up to date when somebody looks -- not by a fill and an add on the device in every step."""
-        self._host_evals = float(n)
+        self._host_evals, self._counts = float(n), None
+
+    def _set_counts(self, counts):
+        """An adaptive solve: the count is data, ([L,] N, 4) int32 on the device.  Kept as it is -- no synchronisation, nothing a
+        graph capture could not record -- and reduced to the largest evaluation count when somebody looks."""
+        self._host_evals, self._counts = None, counts
+
+    def _resolve_counts(self):
+        if self._counts is not None:
+            c, self._counts = self._counts, None
+            self._host_evals = float(c[..., 3].max().item()) if c.numel() else 0.0
 
     def _flush_evals(self):
+        self._resolve_counts()
         if self._host_evals is not None:
             self._num_evals.fill_(self._host_evals)
             self._host_evals = None
 
     def num_evals(self):
+        self._resolve_counts()
         return self._host_evals if self._host_evals is not None else self._num_evals.item()
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        # the loaded buffer is the count now: a pending one of an earlier solve must not overwrite it at the next look
+        self._host_evals = self._counts = None
+        super()._load_from_state_dict(*args, **kwargs)
 
     def _save_to_state_dict(self, destination, prefix, keep_vars):
         self._flush_evals()
@@ -59,25 +80,47 @@ class ODEfunc(nn.Module):
 
 
 class Flow(nn.Module):
-    def __init__(self, diffeq, order=2, solver='dopri5', atol=1e-6, rtol=1e-6, use_adjoint=False):
+    def __init__(self, diffeq, order=2, solver='dopri5', atol=1e-6, rtol=1e-6, use_adjoint=False, max_steps=None):
         super().__init__()
         self.odefunc = ODEfunc(diffeq, order)
         self.solver = solver
-        self.atol, self.rtol = atol, rtol  # ignored by fixed-grid methods (as in torchdiffeq)
+        # read by 'dopri5' only (as in torchdiffeq).  The reference's defaults of 1e-6 are at the fp32 floor: the controller then
+        # works against rounding as much as against truncation error -- Flow(..., atol=, rtol=) is the knob
+        self.atol, self.rtol = atol, rtol
+        self.max_steps = max_steps         # dopri5: accepted steps a trajectory may take; None = 4 (T - 1)
         self.use_adjoint = use_adjoint     # same forward; gradients are discretise-then-optimise either way
+        self._last_counts = None
 
     def forward(self, z0, ts, draws=None):
         """z0 (N,D), ts (T,) -> zt (N,T,D) for a fresh function draw (flow.py:68-86).  ``draws`` = L: L fresh draws integrated in
         one pass -> (L,N,T,D), the stack ODEGPVAE.sample_trajectories builds from L calls (odegpvae.py:41-44); ``_num_evals`` ends
-        at the count of ONE solve, as it does after the reference's last call."""
-        if self.solver not in EVALS_PER_STEP:
-            raise ValueError("solver '%s': this build integrates on the fixed grid with 'euler', 'midpoint' or 'rk4' only" % self.solver)
+        at the count of ONE solve, as it does after the reference's last call.
+        'dopri5': a trajectory that exhausts ``max_steps`` or whose step underflows is NaN from the output it missed (status in
+        ``last_counts``); the others are unaffected."""
+        try:
+            ops.check_solver(self.solver)
+        except ops._lib.GpodeError as e:
+            raise ValueError(str(e)) from None
         gp = self.odefunc.diffeq
+        self._last_counts = None
+        if self.solver == 'dopri5':
+            return ops.flow(gp, z0, ts, self.odefunc.order, self.solver, draws, (self.rtol, self.atol, self.max_steps, self._take_counts))
         zt = ops.flow(gp, z0, ts, self.odefunc.order, self.solver, draws)
         self.odefunc._set_evals(EVALS_PER_STEP[self.solver] * (ts.shape[0] - 1))
         return zt
 
+    def _take_counts(self, counts):
+        self._last_counts = counts
+        self.odefunc._set_counts(counts)
+
+    @property
+    def last_counts(self):
+        """'dopri5': ([L,] N, 4) int32 of the last solve, on the device -- accepted steps, rejected steps, status (0 ok, 1 step
+        budget exhausted, 2 step size underflow, 3 ts not increasing), evaluations of f.  None after a fixed-grid solve."""
+        return self._last_counts
+
     def num_evals(self):
+        """Evaluations of f in the last solve; 'dopri5': the largest count over the trajectories (read from the device here)."""
         return self.odefunc.num_evals()
 
     def kl(self):

@@ -11,7 +11,23 @@ import torch
 from . import _lib
 
 KERNEL_ID = {'RBF': 0, 'DF': 1}
-METHOD_ID = {'euler': 0, 'rk4': 1, 'midpoint': 2}
+METHOD_ID = {'euler': 0, 'rk4': 1, 'midpoint': 2, 'dopri5': 3}
+# the rest of the reference's --solver list (main.py SOLVERS): names that stay refused, and why
+REFUSED_SOLVERS = {
+    'bdf': "implicit multistep: a Newton solve on the Jacobian of f per step, which the rollout kernels do not have (torchdiffeq itself no longer ships it)",
+    'adams': "adaptive-order Adams-Bashforth-Moulton: its order-1..15 coefficient tables exist only in torchdiffeq's source, so the result cannot be pinned here",
+    'explicit_adams': "fixed-grid Adams-Bashforth of torchdiffeq, same unpinned coefficient tables",
+    'fixed_adams': "fixed-grid Adams-Bashforth-Moulton of torchdiffeq, same unpinned coefficient tables (implicit corrector)",
+}
+
+
+def check_solver(method):
+    """Raise for a solver name this build does not integrate with, naming the reason."""
+    if method in METHOD_ID:
+        return
+    why = REFUSED_SOLVERS.get(method)
+    raise _lib.GpodeError("solver '%s' is not built%s; this build integrates with %s"
+                          % (method, ' (%s)' % why if why else '', ', '.join(sorted(METHOD_ID))))
 
 
 def _ptr(t):
@@ -288,15 +304,80 @@ def rhs(cache, x, mode=0):
     return f
 
 
-NSTAGE = {'euler': 1, 'rk4': 4, 'midpoint': 2}
+NSTAGE = {'euler': 1, 'rk4': 4, 'midpoint': 2, 'dopri5': 6}   # recorded stage inputs per step
 
 
-def rollout(cache, z0, ts, order, method, save_stages=False):
+_ts_checked = [None]
+
+
+def _check_increasing(ts):
+    """Refuse output times that are not strictly increasing.  Reads the device, so it is skipped while the stream is being
+    captured into a graph and remembered per tensor (the kernel itself gives such a trajectory status 3 and NaN)."""
+    key = (ts.data_ptr(), ts._version, ts.shape[0])
+    if ts.shape[0] < 2 or _ts_checked[0] == key or torch.cuda.is_current_stream_capturing():
+        return
+    if not bool((ts[1:] > ts[:-1]).all()):
+        raise _lib.GpodeError('dopri5: ts must be strictly increasing')
+    _ts_checked[0] = key
+
+
+def rollout_adaptive(cache, z0, ts, order, rtol=1e-6, atol=1e-6, max_steps=None, save_stages=False):
+    """Adaptive Dormand-Prince 5(4) rollout (gpode_rollout_adaptive_fwd_n): one step-size controller per trajectory, steps landing
+    on ts.  ``max_steps`` = accepted steps a trajectory may take (default 4 (T-1)).  -> zt ([L,] N,T,D), counts ([L,] N,4) int32
+    = (accepted, rejected, status, evaluations of f); with save_stages also the record of the accepted steps: xstage
+    ([L,] N,K,6,D), hstep ([L,] N,K), iend ([L,] N,T-1) int32.  A trajectory with status != 0 is NaN from the output it missed."""
+    z0 = _chk(z0, 'z0'); ts = _chk(ts, 'ts')
+    N, D = z0.shape
+    if D != cache.Di or D != order * cache.Do:
+        raise _lib.GpodeError('state dim %d must equal D_in=%d = order*D_out=%d' % (D, cache.Di, order * cache.Do))
+    T = ts.shape[0]
+    K = 4 * max(T - 1, 0) if max_steps is None else int(max_steps)
+    if K < 0:
+        raise _lib.GpodeError('max_steps must be >= 0, got %d' % K)
+    _check_increasing(ts)
+    lead, dev = cache.lead, z0.device
+    zt = torch.empty(lead + (N, T, D), dtype=torch.float32, device=dev)
+    counts = torch.empty(lead + (N, 4), dtype=torch.int32, device=dev)
+    xs = hs = ie = None
+    if save_stages:
+        xs = torch.empty(lead + (N, K, NSTAGE['dopri5'], D), dtype=torch.float32, device=dev)
+        hs = torch.empty(lead + (N, K), dtype=torch.float32, device=dev)
+        ie = torch.empty(lead + (N, max(T - 1, 0)), dtype=torch.int32, device=dev)
+    _lib.call('gpode_rollout_adaptive_fwd_n', KERNEL_ID[cache.kernel], order, METHOD_ID['dopri5'], cache.Di, cache.Do, cache.M,
+              cache.S, cache.nd, _ptr(cache.pack), _ptr(z0), _ptr(ts), N, T, float(rtol), float(atol), K, _ptr(zt), _ptr(xs), _ptr(hs),
+              _ptr(ie), _ptr(counts), _stream())
+    return (zt, counts, xs, hs, ie) if save_stages else (zt, counts)
+
+
+def rollout_adaptive_bwd(cache, xstage, hstep, iend, gzt, order):
+    """Reverse sweep over the recorded accepted steps: gzt ([L,] N,T,D) -> gz0 ([L,] N,D), astage ([L,] N,K,6,Do), zero past the count."""
+    gzt = _chk(gzt, 'gzt')
+    lead = cache.lead
+    if gzt.dim() != 3 + len(lead) or tuple(gzt.shape[:len(lead)]) != lead:
+        raise _lib.GpodeError('gzt: expected %s + (N,T,D), got %s' % (lead, tuple(gzt.shape)))
+    N, T, D = gzt.shape[-3:]
+    K = hstep.shape[-1]
+    xstage = _chk(xstage, 'xstage', lead + (N, K, NSTAGE['dopri5'], D)); hstep = _chk(hstep, 'hstep', lead + (N, K))
+    if iend.dtype != torch.int32 or tuple(iend.shape) != lead + (N, max(T - 1, 0)) or not iend.is_contiguous():
+        raise _lib.GpodeError('iend: expected contiguous int32 %s, got %s %s' % (lead + (N, T - 1), iend.dtype, tuple(iend.shape)))
+    gz0 = torch.empty(lead + (N, D), dtype=torch.float32, device=gzt.device)
+    ast = torch.empty(lead + (N, K, NSTAGE['dopri5'], cache.Do), dtype=torch.float32, device=gzt.device)
+    _lib.call('gpode_rollout_adaptive_bwd_n', KERNEL_ID[cache.kernel], order, METHOD_ID['dopri5'], cache.Di, cache.Do, cache.M,
+              cache.S, cache.nd, _ptr(cache.pack), _ptr(xstage), _ptr(hstep), _ptr(iend), _ptr(gzt), N, T, K, _ptr(gz0), _ptr(ast),
+              _stream())
+    return gz0, ast
+
+
+def rollout(cache, z0, ts, order, method, save_stages=False, rtol=1e-6, atol=1e-6, max_steps=None):
     """Flow.forward (flow.py:68-86) for a built cache: z0 (N,D), ts (T,) -> zt (N,T,D); a cache of L draws integrates all L * N
     trajectories in ONE launch -> zt (L,N,T,D) (the stack of odegpvae.py:41-44).
-    save_stages=True also returns the inputs of all RHS evaluations ([L,] N,T-1,NS,D) for the reverse sweep."""
-    if method not in METHOD_ID:
-        raise _lib.GpodeError("solver '%s' is not a fixed-grid method of this build (euler, rk4, midpoint)" % method)
+    save_stages=True also returns the inputs of all RHS evaluations ([L,] N,T-1,NS,D) for the reverse sweep.
+    method 'dopri5' (the only one that reads rtol / atol / max_steps) is rollout_adaptive(): with save_stages the second value is its
+    record (xstage, hstep, iend, counts), which rollout_bwd takes in place of xstage."""
+    check_solver(method)
+    if method == 'dopri5':
+        out = rollout_adaptive(cache, z0, ts, order, rtol, atol, max_steps, save_stages)
+        return (out[0], (out[2], out[3], out[4], out[1])) if save_stages else out[0]
     z0 = _chk(z0, 'z0'); ts = _chk(ts, 'ts')
     N, D = z0.shape
     if D != cache.Di or D != order * cache.Do:
@@ -311,7 +392,10 @@ def rollout(cache, z0, ts, order, method, save_stages=False):
 
 
 def rollout_bwd(cache, xstage, gzt, ts, order, method):
-    """Reverse sweep: gzt ([L,] N,T,D) -> gz0 ([L,] N,D), astage ([L,] N,T-1,NS,Do)."""
+    """Reverse sweep: gzt ([L,] N,T,D) -> gz0 ([L,] N,D), astage ([L,] N,T-1,NS,Do) (dopri5: xstage is rollout's record, astage
+    ([L,] N,K,6,Do))."""
+    if method == 'dopri5':
+        return rollout_adaptive_bwd(cache, xstage[0], xstage[1], xstage[2], gzt, order)
     gzt = _chk(gzt, 'gzt'); xstage = _chk(xstage, 'xstage'); ts = _chk(ts, 'ts')
     lead = cache.lead
     if gzt.dim() != 3 + len(lead) or tuple(gzt.shape[:len(lead)]) != lead:
@@ -547,10 +631,13 @@ class _Flow(torch.autograd.Function):
     pass -- ONE cache build that factors K_uu once, ONE rollout launch over L * N trajectories, zt (L,N,T,D); the backward is one
     reverse sweep, one parameter-sum launch and one cache backward on the gradients summed over the draws.
     Forward: gpode_cache_build_fwd_n + gpode_rollout_fwd_n.  Backward: gpode_rollout_bwd_n (reverse sweep), gpode_param_grad_n
-    (pack-layout parameter gradients), gpode_cache_build_bwd_n."""
+    (pack-layout parameter gradients), gpode_cache_build_bwd_n.
+    method 'dopri5': the adaptive entry points; ``adaptive`` = (rtol, atol, max_steps, sink) -- sink(counts) is handed the counts
+    tensor of the solve.  The record (xstage, hstep, iend) takes the place of xs; its rows past a trajectory's count are zero
+    in both xstage and astage, so the parameter sums run over all K * 6 rows."""
 
     @staticmethod
-    def forward(ctx, z0, ts, raw_ell, raw_var, Z, Um, Us, gp, order, method, draws=None):
+    def forward(ctx, z0, ts, raw_ell, raw_var, Z, Um, Us, gp, order, method, draws=None, adaptive=None):
         cache = gp.take_prebuilt_cache() if hasattr(gp, 'take_prebuilt_cache') else None
         if cache is None:
             cache = gp.build_cache() if draws is None else gp.build_cache(draws=draws)
@@ -565,17 +652,23 @@ class _Flow(torch.autograd.Function):
             side = fork_side_stream()
             with launch_on(side):
                 ctx.prepared = cache_bwd_prepare(cache)
-        if need:
+        hs = ie = None
+        if method == 'dopri5':
+            rtol, atol, max_steps, sink = adaptive if adaptive is not None else (1e-6, 1e-6, None, None)
+            zt, counts, xs, hs, ie = (rollout_adaptive(cache, z0, ts, order, rtol, atol, max_steps, save_stages=need) + (None,) * 3)[:5]
+            if sink is not None:
+                sink(counts)
+        elif need:
             zt, xs = rollout(cache, z0, ts, order, method, save_stages=True)
         else:
             zt, xs = rollout(cache, z0, ts, order, method), None
         ctx.cache, ctx.order, ctx.method = cache, order, method
-        ctx.save_for_backward(ts, xs, raw_ell.detach(), raw_var.detach(), Z.detach())
+        ctx.save_for_backward(ts, xs, raw_ell.detach(), raw_var.detach(), Z.detach(), hs, ie)
         return zt
 
     @staticmethod
     def backward(ctx, gzt):
-        ts, xs, raw_ell, raw_var, Z = ctx.saved_tensors
+        ts, xs, raw_ell, raw_var, Z, hs, ie = ctx.saved_tensors
         c = ctx.cache
         lead = c.lead
         want_p = any(ctx.needs_input_grad[2:7])
@@ -585,12 +678,14 @@ class _Flow(torch.autograd.Function):
         gpack_f = None
         if nch:
             gz0, ast, gpack_f = rollout_bwd_pgrad(c, xs, gzt.contiguous(), ts, ctx.order, ctx.method, nch)
+        elif ctx.method == 'dopri5':
+            gz0, ast = rollout_adaptive_bwd(c, xs, hs, ie, gzt.contiguous(), ctx.order)
         else:
             gz0, ast = rollout_bwd(c, xs, gzt.contiguous(), ts, ctx.order, ctx.method)
         if c.stacked:
             gz0 = gz0.sum(0)                         # every draw starts from the same z0 (odegpvae.py:42)
         if not want_p:
-            return (gz0,) + (None,) * 10
+            return (gz0,) + (None,) * 11
         leaves = all(p.is_leaf and p.requires_grad for p in ctx.params) and all(ctx.needs_input_grad[2:7])
         if _overlap['on'] and leaves:
             # parameter gradients on the side stream, next to the encoder's backward; join_side_stream() adds them
@@ -608,26 +703,33 @@ class _Flow(torch.autograd.Function):
             # every buffer a side-stream kernel touches stays referenced until join_side_stream(): the allocator would
             # otherwise hand the block to the encoder-backward kernels the main stream launches meanwhile
             _overlap['pending'].append((ctx.params, [gg.view_as(p) for gg, p in zip(grads, ctx.params)],
-                                        (g, gpack, xs, ast, c, scratch, raw_ell, raw_var, Z, ctx.prepared)))
-            return (gz0,) + (None,) * 10
+                                        (g, gpack, xs, ast, c, scratch, raw_ell, raw_var, Z, ctx.prepared, hs, ie)))
+            return (gz0,) + (None,) * 11
         if ctx.prepared is not None:
             torch.cuda.current_stream().wait_stream(side_stream())
         gpack = gpack_f if gpack_f is not None else param_grad(c, xs.reshape(lead + (-1, c.Di)), ast.reshape(lead + (-1, c.Do)))
         g = cache_build_bwd(c, raw_ell, raw_var, Z, gpack, prepared=ctx.prepared)
-        return (gz0, None, g['raw_ell'], g['raw_var'], g['Z'], g['Um'], g['Us'], None, None, None, None)
+        return (gz0, None, g['raw_ell'], g['raw_var'], g['Z'], g['Um'], g['Us'], None, None, None, None, None)
 
 
-def flow(gp, z0, ts, order, method, draws=None):
-    """One function draw -> zt (N,T,D); ``draws`` = L -> the L draws of odegpvae.py:41-44 in one pass, zt (L,N,T,D)."""
+def flow(gp, z0, ts, order, method, draws=None, adaptive=None):
+    """One function draw -> zt (N,T,D); ``draws`` = L -> the L draws of odegpvae.py:41-44 in one pass, zt (L,N,T,D).
+    ``adaptive`` = (rtol, atol, max_steps, sink) for method 'dopri5' (see _Flow)."""
+    check_solver(method)
     k = gp.kern
     raw_ell, raw_var = k.raw_dimwise() if hasattr(k, 'raw_dimwise') else (k.unconstrained_lengthscales, k.unconstrained_variance)
     params = (raw_ell, raw_var, gp.inducing_loc.optvar, gp.Um.optvar, gp.us_packed() if hasattr(gp, 'us_packed') else gp.Us_sqrt.optvar)
     pad = getattr(gp, 'width_pad', None)
     if pad is None:
-        return _Flow.apply(z0, ts, *params, gp, order, method, draws)
+        return _Flow.apply(z0, ts, *params, gp, order, method, draws, adaptive)
     # a width outside the compiled list: the compiled kernels on zero-padded operands (see WidthPad); autograd carries the
     # gradients back through the scatter / slice
-    zt = _Flow.apply(pad.state(z0), ts, *pad.params(*params), gp, order, method, draws)
+    if adaptive is not None:
+        # the controller's RMS norm runs over the padded state, whose extra components (and their errors) are exactly 0:
+        # tolerances scaled by sqrt(D / D_padded) give the ratio over the D real components
+        w = (len(pad.in_index) / float(pad.Dip)) ** 0.5
+        adaptive = (adaptive[0] * w, adaptive[1] * w) + tuple(adaptive[2:])
+    zt = _Flow.apply(pad.state(z0), ts, *pad.params(*params), gp, order, method, draws, adaptive)
     return pad.unstate(zt)
 
 
