@@ -156,6 +156,25 @@ int gpode_rollout_adaptive_fwd_n(int kernel, int order, int method, int Di, int 
 int gpode_rollout_adaptive_bwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                                  const float* pack, const float* xstage, const float* hstep, const int* iend, const float* gzt,
                                  int N, int T, int K, float* gz0, float* astage, void* stream);
+/* The adaptive rollout with DENSE OUTPUT (flow.py:76-86 with torchdiffeq's free-stepping dopri5): the controller of
+ * gpode_rollout_adaptive_fwd_n, but a step is cut only at the last output time ts[T-1] and the first step is capped by
+ * ts[T-1] - ts[0]; the interior outputs are read off the 4th-order continuous extension of the pair (Shampine; Hairer, Noersett,
+ * Wanner II.6), z(theta) = y_n + h sum_{j=1..7} w_j(theta) k_j, which costs no evaluation (counts as above).  The last output is the
+ * end state of the last step.  Record, written when xstage != NULL, zero past a trajectory's count:
+ *   xstage (L,N,K,7,D)      the six stage inputs of every accepted step and its end state (the input of the seventh slope)
+ *   hstep  (L,N,K)          the accepted step sizes
+ *   istep  (L,N,T-1) int32  1-based number of the accepted step that holds output t+1 (non-decreasing; several outputs may share
+ *                           a step, a step may hold none); the count of accepted steps for outputs a failed trajectory did not reach
+ *   theta  (L,N,T-1)        (ts[t+1] - t_n) / h inside that step, in (0, 1]; exactly 1 for the last output
+ * gpode_rollout_dense_bwd_n (flow.py:76-86, the gradient of the above): gzt (L,N,T,D) -> gz0 (L,N,D), astage (L,N,K,7,Do) = dL/df at
+ * every recorded evaluation; row 6 of a step is zero unless the step holds an output with theta < 1 (w_7(1) = 0), rows past the count
+ * are zero -- gpode_param_grad_n runs over all K * 7 rows of (xstage, astage).  Deterministic, no atomics. */
+int gpode_rollout_dense_fwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                              const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
+                              float* zt, float* xstage, float* hstep, int* istep, float* theta, int* counts, void* stream);
+int gpode_rollout_dense_bwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                              const float* pack, const float* xstage, const float* hstep, const int* istep, const float* theta,
+                              const float* gzt, int N, int T, int K, float* gz0, float* astage, void* stream);
 /* gpode_rollout_bwd_n and gpode_param_grad_n in ONE pass: the reverse sweep visits every (stage input, adjoint) row anyway, so the
  * rows' parameter-gradient terms are accumulated on the way and come out as gpack (ndraws, pack_floats) -- what the two calls
  * produce together, with one launch and one pass over the rows less.  slab: ndraws * nchunk * pack_floats floats of scratch with

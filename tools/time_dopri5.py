@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Time the adaptive 'dopri5' rollout against the fixed-grid 'rk4' one at a BASELINE workload's shapes (default configs[0]):
 forward without and with the record, and the reverse sweep, each bracketed by events on the current stream; prints the step
-statistics of the adaptive solve next to the times.
+statistics of the adaptive solve next to the times.  With --dense the dense-output mode (steps free of the output grid, outputs
+interpolated) is timed in the same run.
 
-    python tools/time_dopri5.py [--workload cfg1] [--reps 20] [--tol 1e-3 1e-5]
+Everything that is compared is timed in the SAME run in alternating windows: one window = ``--window`` back-to-back calls of one
+variant between two events; the variants take turns, ``--reps`` windows each, and the figure is the median over the windows of
+the time per call.
+
+    python tools/time_dopri5.py [--workload cfg1] [--reps 20] [--window 10] [--tol 1e-3 1e-5] [--dense] [--out FILE.json]
 """
 import argparse
 import json
@@ -16,13 +21,41 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def timed_together(fns, reps, window):
+    """{name: callable} -> {name: median ms per call}; the callables take turns, window by window."""
+    for f in fns.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, f in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(window):
+                f()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / window)
+    return {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+
+
+def stats(cnt, budget):
+    cnt = cnt.cpu().long()
+    return dict(accepted_mean=cnt[:, 0].float().mean().item(), accepted_max=int(cnt[:, 0].max()), rejected_mean=cnt[:, 1].float().mean().item(),
+                evals_mean=cnt[:, 3].float().mean().item(), evals_max=int(cnt[:, 3].max()), failed=int((cnt[:, 2] != 0).sum()), budget=int(budget))
+
+
 def main():
     import bench
     from vae_gp_ode_amd import ops
     ap = argparse.ArgumentParser()
     ap.add_argument('--workload', default='cfg1')
     ap.add_argument('--reps', type=int, default=20)
+    ap.add_argument('--window', type=int, default=10)
     ap.add_argument('--tol', type=float, nargs='+', default=[1e-3, 1e-5])
+    ap.add_argument('--dense', action='store_true', help='time the dense-output mode next to the landing mode and rk4')
+    ap.add_argument('--out', default=None, help='also write the JSON result to this file')
     a = ap.parse_args()
     w = bench.WORKLOADS[a.workload]
     dev = torch.device('cuda:0')
@@ -35,34 +68,41 @@ def main():
     c.check_factorisation()
     gw = torch.randn(z0.shape[0], ts.shape[0], z0.shape[1], device=dev)
 
-    def timed(fn):
-        ms = []
-        for _ in range(a.reps + 3):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            out = fn()
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-        ms = sorted(ms[3:])
-        return out, ms[len(ms) // 2]
-
-    res = {'workload': w['desc'], 'reps': a.reps}
-    _, res['rk4_fwd_ms'] = timed(lambda: ops.rollout(c, z0, ts, order, 'rk4'))
-    (_, xs), res['rk4_fwd_record_ms'] = timed(lambda: ops.rollout(c, z0, ts, order, 'rk4', save_stages=True))
-    _, res['rk4_bwd_ms'] = timed(lambda: ops.rollout_bwd(c, xs, gw, ts, order, 'rk4'))
-    res['rk4_evals'] = 4 * (ts.shape[0] - 1)
+    res = {'workload': w['desc'], 'reps': a.reps, 'window': a.window, 'N': int(z0.shape[0]), 'T': int(ts.shape[0]),
+           'rk4_evals': 4 * (ts.shape[0] - 1)}
+    _, xs4 = ops.rollout(c, z0, ts, order, 'rk4', save_stages=True)
+    rk4 = {'rk4_fwd_ms': lambda: ops.rollout(c, z0, ts, order, 'rk4'),
+           'rk4_fwd_record_ms': lambda: ops.rollout(c, z0, ts, order, 'rk4', save_stages=True),
+           'rk4_bwd_ms': lambda: ops.rollout_bwd(c, xs4, gw, ts, order, 'rk4')}
     for tol in a.tol:
-        r = {}
-        _, r['fwd_ms'] = timed(lambda: ops.rollout_adaptive(c, z0, ts, order, tol, tol))
-        (zt, cnt, xs, hs, ie), r['fwd_record_ms'] = timed(lambda: ops.rollout_adaptive(c, z0, ts, order, tol, tol, save_stages=True))
-        _, r['bwd_ms'] = timed(lambda: ops.rollout_adaptive_bwd(c, xs, hs, ie, gw, order))
-        cnt = cnt.cpu().long()
-        r.update(accepted_mean=cnt[:, 0].float().mean().item(), accepted_max=int(cnt[:, 0].max()), rejected_mean=cnt[:, 1].float().mean().item(),
-                 evals_mean=cnt[:, 3].float().mean().item(), evals_max=int(cnt[:, 3].max()), failed=int((cnt[:, 2] != 0).sum()),
-                 budget=int(hs.shape[-1]))
+        modes = {'landing': False}
+        if a.dense:
+            modes['dense'] = True
+        fns, rec = dict(rk4), {}
+        for name, dense in modes.items():
+            out = ops.rollout_adaptive(c, z0, ts, order, tol, tol, save_stages=True, dense=dense)
+            rec[name] = out
+            fns[name + '.fwd_ms'] = lambda dense=dense: ops.rollout_adaptive(c, z0, ts, order, tol, tol, dense=dense)
+            fns[name + '.fwd_record_ms'] = lambda dense=dense: ops.rollout_adaptive(c, z0, ts, order, tol, tol, save_stages=True, dense=dense)
+            fns[name + '.bwd_ms'] = lambda out=out: ops.rollout_adaptive_bwd(c, out[2], out[3], out[4], gw, order, theta=out[5] if len(out) > 5 else None)
+        t = timed_together(fns, a.reps, a.window)
+        r = {k: v for k, v in t.items() if k.startswith('rk4')}               # rk4 in this tolerance's run: the yardstick of its windows
+        for name in modes:
+            sub = {k.split('.', 1)[1]: v for k, v in t.items() if k.startswith(name + '.')}
+            sub.update(stats(rec[name][1], rec[name][3].shape[-1]))
+            if name == 'landing':
+                r.update(sub)
+            else:
+                sub['max_abs_diff_to_landing'] = (rec['dense'][0] - rec['landing'][0]).abs().max().item()
+                r[name] = sub
         res['dopri5_tol_%g' % tol] = r
-    print(json.dumps(res))
+        for k in ('rk4_fwd_ms', 'rk4_fwd_record_ms', 'rk4_bwd_ms'):
+            res.setdefault(k, r[k])
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, 'w') as f:
+            f.write(json.dumps(res, indent=1) + '\n')
 
 
 if __name__ == '__main__':

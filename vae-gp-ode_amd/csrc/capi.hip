@@ -168,6 +168,38 @@ int gpode_rollout_adaptive_bwd_n(int kernel, int order, int method, int Di, int 
                                   (hipStream_t)stream);
 }
 
+int gpode_rollout_dense_fwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                              const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
+                              float* zt, float* xstage, float* hstep, int* istep, float* theta, int* counts, void* stream) {
+  if (method != GPODE_METHOD_DOPRI5) return gp::set_error("gpode_rollout_dense_fwd: method %d (3 dopri5)", method);
+  if (N < 0 || T < 1 || K < 0 || ndraws < 1 || ndraws > 65535)
+    return gp::set_error("gpode_rollout_dense_fwd: N=%d T=%d K=%d draws=%d", N, T, K, ndraws);
+  if (!(rtol >= 0.f) || !(atol >= 0.f) || !(rtol + atol > 0.f) || !(rtol + atol < 1e30f))
+    return gp::set_error("gpode_rollout_dense_fwd: rtol=%g atol=%g (both >= 0, not both 0)", rtol, atol);
+  if (N == 0) return 0;
+  if (!pack || !z0 || !ts || !zt || !counts) return gp::set_error("gpode_rollout_dense_fwd: null pointer");
+  if (xstage && T > 1 && (!istep || !theta || (K > 0 && !hstep)))
+    return gp::set_error("gpode_rollout_dense_fwd: xstage without hstep / istep / theta");
+  size_t pf = 0;
+  if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
+  return gp::rollout_dense_fwd(kernel, order, Di, Do, M, S, ndraws, pack, pf, z0, ts, N, T, rtol, atol, K, zt, xstage, hstep, istep, theta,
+                               counts, (hipStream_t)stream);
+}
+int gpode_rollout_dense_bwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                              const float* pack, const float* xstage, const float* hstep, const int* istep, const float* theta,
+                              const float* gzt, int N, int T, int K, float* gz0, float* astage, void* stream) {
+  if (method != GPODE_METHOD_DOPRI5) return gp::set_error("gpode_rollout_dense_bwd: method %d (3 dopri5)", method);
+  if (N < 0 || T < 1 || K < 0 || ndraws < 1 || ndraws > 65535)
+    return gp::set_error("gpode_rollout_dense_bwd: N=%d T=%d K=%d draws=%d", N, T, K, ndraws);
+  if (N == 0) return 0;
+  if (!pack || !gzt || !gz0 || (T > 1 && (!istep || !theta)) || (T > 1 && K > 0 && (!xstage || !hstep || !astage)))
+    return gp::set_error("gpode_rollout_dense_bwd: null pointer");
+  size_t pf = 0;
+  if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
+  return gp::rollout_dense_bwd(kernel, order, Di, Do, M, S, ndraws, pack, pf, xstage, hstep, istep, theta, gzt, N, T, K, gz0, astage,
+                               (hipStream_t)stream);
+}
+
 int gpode_rhs_vjp(int kernel, int Di, int Do, int M, int S, const float* pack,
                   const float* x, const float* a, int R, float* gx, void* stream) {
   if (!pack || !x || !a || !gx) return gp::set_error("gpode_rhs_vjp: null pointer");

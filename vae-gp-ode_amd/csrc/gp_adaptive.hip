@@ -4,8 +4,9 @@
 // mapping) or one workgroup of four (team mapping) carries a trajectory from z0 to z_{T-1} in ONE launch; only the trip count
 // is data-dependent.  Differences to torchdiffeq, by design:
 //   * one controller PER TRAJECTORY (torchdiffeq couples the batch through one RMS norm): every trajectory meets its own tolerance;
-//   * steps LAND on the output times (a step that would pass ts[t+1] is shortened to end on it; no dense output), so zt[:, t] is a
-//     step end point and the reverse sweep needs no interpolant.  Results agree to the tolerances, not step by step.
+//   * by default steps LAND on the output times (a step that would pass ts[t+1] is shortened to end on it; no dense output), so
+//     zt[:, t] is a step end point and the reverse sweep needs no interpolant.  Results agree to the tolerances, not step by step.
+//     The opt-in dense-output mode further down steps freely and interpolates, as torchdiffeq does.
 //
 // Controller (Hairer, Noersett, Wanner, Solving ODEs I, II.4-5)
 //   err_i  = h sum_j e_j k_j,i                      (5th-order minus embedded 4th-order solution)
@@ -25,6 +26,17 @@
 //
 // Record (for the reverse sweep; all zero past the count): xstage (N,K,6,D) the six stage inputs of every ACCEPTED step (b7 = 0,
 // so the seventh does not enter the step), hstep (N,K), iend (N,T-1) = accepted steps taken when output t+1 was reached.
+//
+// Dense-output mode (template parameter DENSE; gpode_rollout_dense_*): the controller above with `rem` the distance to the LAST
+// output time -- the cut happens once, at ts[T-1], and the first step is capped by ts[T-1] - ts[0].  The interior outputs are read
+// off the 4th-order continuous extension of the pair (Shampine; Hairer, Noersett, Wanner II.6, CONTD5), which costs no evaluation:
+//   z(theta) = y_n + h sum_j w_j(theta) k_j,   theta = (t - t_n) / h in (0, 1],   j = 1..7 (k_7 = the FSAL slope at y_{n+1})
+//   w_j(theta) = theta [b_j + (1 - theta) ((d_j1 - b_j) + theta ((2 b_j - d_j1 - d_j7) + (1 - theta) dp_d[j]))]
+// Every output not yet written with ts[j] <= t_n + h belongs to the accepted step, and is formed before the step's seventh slope
+// replaces row 0 of the slope block; the last output is the end state of the last step (theta = 1 exactly).  Time is an fp32 offset
+// tn from ts[0] (the running sum of the accepted steps); theta and every loop condition derive from scalars.
+// Record: xstage (N,K,7,D) (row 6 = y_{n+1}, where k_7 is evaluated), hstep (N,K), istep (N,T-1) = 1-based number of the accepted
+// step that holds output t+1 (non-decreasing; a step may hold several outputs or none), theta (N,T-1).
 #include "gp_rollout.hpp"
 
 namespace gp {
@@ -43,7 +55,13 @@ __constant__ float dp_e[7] = {(float)(71.0 / 57600.0), 0.f, (float)(-71.0 / 1669
                               (float)(-17253.0 / 339200.0), (float)(22.0 / 525.0), (float)(-1.0 / 40.0)};
 
 constexpr int KP = 16;                  // floats per slope row in LDS (D <= 16 for every compiled width)
-constexpr int NREC = 6;                 // recorded stage inputs per accepted step
+// the quartic's free coefficient per slope (dense output)
+__constant__ float dp_d[7] = {(float)(-12715105075.0 / 11282082432.0), 0.f, (float)(87487479700.0 / 32700410799.0),
+                              (float)(-10690763975.0 / 1880347072.0), (float)(701980252875.0 / 199316789632.0),
+                              (float)(-1453857185.0 / 822651844.0), (float)(69997945.0 / 29380423.0)};
+
+constexpr int NREC = 6;                 // recorded stage inputs per accepted step (landing mode)
+constexpr int NDEN = 7;                 // ... in dense mode: the end state, where the seventh slope is evaluated, is one of them
 
 struct AdaptFwd {
   const float* pack; size_t pack_stride; int M, S;
@@ -56,6 +74,11 @@ struct AdaptBwd {
   const float* xstage; const float* hstep; const int* iend; const float* gzt; int N, T, K;
   float* gz0; float* astage;
 };
+// the dense mode's kernels take one pointer more; the landing kernels keep their argument block (and with it their machine code)
+struct AdaptFwdDense : AdaptFwd { float* theta; };
+struct AdaptBwdDense : AdaptBwd { const float* theta; };
+template <bool DENSE> using AdaptFwdArg = std::conditional_t<DENSE, AdaptFwdDense, AdaptFwd>;
+template <bool DENSE> using AdaptBwdArg = std::conditional_t<DENSE, AdaptBwdDense, AdaptBwd>;
 
 // a value every lane holds identically -> a scalar: the controller's branches are then scalar branches, the same in every
 // wavefront of a team (whose evaluations carry a workgroup barrier) because the slopes they derive from are bit-identical there
@@ -76,12 +99,21 @@ template <int DI> __device__ __forceinline__ float scaled_rms(const float (&v)[D
   return sqrtf(sq * (1.f / DI));
 }
 
+// weight of slope j (0-based) in the continuous extension at theta
+__device__ __forceinline__ float dense_w(int j, float th) {
+  const float b = j < 6 ? dp_a[6][j] : 0.f, d1 = j == 0 ? 1.f : 0.f, d7 = j == 6 ? 1.f : 0.f, om = 1.f - th;
+  return th * (b + om * ((d1 - b) + th * ((2.f * b - d1 - d7) + om * dp_d[j])));
+}
+
 // One trajectory, start to end.  kst: this wavefront's 7 x KP floats of LDS.  wr: this wavefront writes the outputs (in a team all
 // four compute the same values).  Pointers are the draw's.
-template <class EV, int DI, int DO, int ORDER>
+// DENSE: one "interval" from ts[0] to ts[T-1]; the outputs inside it are interpolated when the step that holds them is accepted.
+template <class EV, int DI, int DO, int ORDER, bool DENSE>
 __device__ __forceinline__ void dopri5_trajectory(EV& ev, const AdaptFwd& a, const float* __restrict__ z0, float* __restrict__ zt,
                                                   float* __restrict__ xstage, float* __restrict__ hstep, int* __restrict__ iend,
-                                                  int* __restrict__ counts, int n, float* __restrict__ kst, bool wr, int lane) {
+                                                  float* __restrict__ theta, int* __restrict__ counts, int n, float* __restrict__ kst,
+                                                  bool wr, int lane) {
+  constexpr int NR = DENSE ? NDEN : NREC;
   const int T = a.T, K = a.K;
   const float rtol = a.rtol, atol = a.atol;
   const bool rec = xstage != nullptr && wr;
@@ -89,23 +121,30 @@ __device__ __forceinline__ void dopri5_trajectory(EV& ev, const AdaptFwd& a, con
 #pragma unroll
   for (int i = 0; i < DI; ++i) y[i] = z0[(size_t)n * DI + i];
   float* out = zt + (size_t)n * T * DI;
-  float* xrec = rec ? xstage + (size_t)n * K * NREC * DI : nullptr;
+  float* xrec = rec ? xstage + (size_t)n * K * NR * DI : nullptr;
   float* hrec = rec ? hstep + (size_t)n * K : nullptr;
   int* irec = rec ? iend + (size_t)n * (T - 1) : nullptr;
+  float* trec = DENSE && rec ? theta + (size_t)n * (T - 1) : nullptr;
   if (wr) store_state<DI>(out, y, lane);
   ode_rhs_mut<EV, DI, DO, ORDER>(ev, y, kv);
   put_row<DI>(kst, kv);
   int nacc = 0, nrej = 0, status = 0, nfe = 1, t = 0;
-  float h = 0.f;
+  float h = 0.f, tn = 0.f;                           // tn (dense): time reached, as an offset from ts[0]
+  int jout = 1;                                      // dense: the first output not yet written
   bool after_reject = false;
   if (T > 1) {
     const float d0 = scaled_rms<DI>(y, y, y, rtol, atol), d1 = scaled_rms<DI>(kv, y, y, rtol, atol);
     const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
     const float h1 = d1 <= 1e-15f ? fmaxf(1e-6f, h0 * 1e-3f) : powf(0.01f / d1, 0.2f);
-    h = uni(fminf(fminf(100.f * h0, h1), a.ts[1] - a.ts[0]));
+    h = uni(fminf(fminf(100.f * h0, h1), a.ts[DENSE ? T - 1 : 1] - a.ts[0]));
+  }
+  if constexpr (DENSE) {
+    for (int i = 0; i + 1 < T; ++i)
+      if (!(a.ts[i + 1] - a.ts[i] > 0.f)) status = 3;
+    if (status) t = T;                               // nothing is integrated
   }
   for (; t + 1 < T; ++t) {
-    const float t0 = a.ts[t], t1 = a.ts[t + 1];
+    const float t0 = a.ts[t], t1 = a.ts[DENSE ? T - 1 : t + 1];
     const float dt = t1 - t0, tabs = fmaxf(fabsf(t0), fabsf(t1));
     if (!(dt > 0.f)) { status = 3; break; }
     float rem = dt;
@@ -114,7 +153,7 @@ __device__ __forceinline__ void dopri5_trajectory(EV& ev, const AdaptFwd& a, con
       const bool cut = 1.01f * h >= rem;
       const float hs = cut ? rem : h;
       if (!(hs > 16.f * 1.1920929e-7f * fmaxf(tabs, fabsf(hs)))) { status = 2; break; }   // also a NaN step
-      if (rec) store_state<DI>(xrec + (size_t)(nacc * NREC) * DI, y, lane);
+      if (rec) store_state<DI>(xrec + (size_t)(nacc * NR) * DI, y, lane);
       for (int s = 1; s < 7; ++s) {
         float acc[DI];
 #pragma unroll
@@ -126,7 +165,7 @@ __device__ __forceinline__ void dopri5_trajectory(EV& ev, const AdaptFwd& a, con
         }
 #pragma unroll
         for (int d = 0; d < DI; ++d) xs[d] = fmaf(hs, acc[d], y[d]);
-        if (rec && s < NREC) store_state<DI>(xrec + (size_t)(nacc * NREC + s) * DI, xs, lane);
+        if (rec && s < NR) store_state<DI>(xrec + (size_t)(nacc * NR + s) * DI, xs, lane);
         ode_rhs_mut<EV, DI, DO, ORDER>(ev, xs, kv);
         put_row<DI>(kst + s * KP, kv);
       }
@@ -147,6 +186,37 @@ __device__ __forceinline__ void dopri5_trajectory(EV& ev, const AdaptFwd& a, con
       if (ratio <= 1.f) {
         if (after_reject) fac = fminf(fac, 1.f);
         after_reject = false;
+        if constexpr (DENSE) {
+          // the outputs this step holds: every one up to its end point, all that are left when it is the cut step; rows 0..6 of
+          // the slope block are k_1..k_7 of this step, y its start
+          const float tnew = tn + hs;
+          while (jout < T) {
+            const float to = uni(a.ts[jout] - t0);
+            if (!(cut || to <= tnew)) break;
+            const bool last = jout == T - 1;
+            const float th = last ? 1.f : uni(fminf(fmaxf((to - tn) / hs, 1.1920929e-7f), 1.f));
+            if (wr) {
+              if (last) {
+                store_state<DI>(out + (size_t)jout * DI, xs, lane);
+              } else {
+                float acc[DI], z[DI];
+#pragma unroll
+                for (int d = 0; d < DI; ++d) acc[d] = 0.f;
+                for (int j = 0; j < 7; ++j) {
+                  const float c = dense_w(j, th);
+#pragma unroll
+                  for (int d = 0; d < DI; ++d) acc[d] = fmaf(c, kst[j * KP + d], acc[d]);
+                }
+#pragma unroll
+                for (int d = 0; d < DI; ++d) z[d] = fmaf(hs, acc[d], y[d]);
+                store_state<DI>(out + (size_t)jout * DI, z, lane);
+              }
+              if (rec && lane == 0) { irec[jout - 1] = nacc + 1; trec[jout - 1] = th; }
+            }
+            ++jout;
+          }
+          tn = tnew;
+        }
 #pragma unroll
         for (int d = 0; d < DI; ++d) y[d] = xs[d];
         put_row<DI>(kst, kv);
@@ -154,7 +224,8 @@ __device__ __forceinline__ void dopri5_trajectory(EV& ev, const AdaptFwd& a, con
         ++nacc;
         h = cut ? fmaxf(h, hs * fac) : hs * fac;
         if (cut) break;
-        rem -= hs;
+        if constexpr (DENSE) rem = dt - tn;
+        else rem -= hs;
       } else {
         ++nrej;
         after_reject = true;
@@ -162,16 +233,21 @@ __device__ __forceinline__ void dopri5_trajectory(EV& ev, const AdaptFwd& a, con
       }
     }
     if (status) break;
+    if constexpr (DENSE) break;                      // the one interval is done, its outputs are written
     if (wr) store_state<DI>(out + (size_t)(t + 1) * DI, y, lane);
     if (rec && lane == 0) irec[t] = nacc;
   }
   if (status && wr) {                                // a failed trajectory: NaN from the output it did not reach
     const float qnan = __int_as_float(0x7fc00000);
-    for (int i = (t + 1) * DI + lane; i < T * DI; i += 64) out[i] = qnan;
-    if (rec) for (int i = t + lane; i < T - 1; i += 64) irec[i] = nacc;
+    const int first = DENSE ? jout : t + 1;
+    for (int i = first * DI + lane; i < T * DI; i += 64) out[i] = qnan;
+    if (rec) for (int i = first - 1 + lane; i < T - 1; i += 64) {
+      irec[i] = nacc;
+      if constexpr (DENSE) trec[i] = 1.f;
+    }
   }
   if (rec) {                                         // rows past the count (and what a rejected attempt left there) are zero
-    for (size_t i = (size_t)nacc * NREC * DI + lane; i < (size_t)K * NREC * DI; i += 64) xrec[i] = 0.f;
+    for (size_t i = (size_t)nacc * NR * DI + lane; i < (size_t)K * NR * DI; i += 64) xrec[i] = 0.f;
     for (int i = nacc + lane; i < K; i += 64) hrec[i] = 0.f;
   }
   if (wr && lane == 0) {
@@ -185,15 +261,17 @@ __device__ __forceinline__ void dopri5_trajectory(EV& ev, const AdaptFwd& a, con
   const size_t dr = blockIdx.y, NT = (size_t)a.N;                                                                \
   const float* pack = a.pack + dr * a.pack_stride;                                                               \
   float* zt = a.zt + dr * NT * a.T * DI;                                                                         \
-  float* xstage = a.xstage ? a.xstage + dr * NT * a.K * NREC * DI : nullptr;                                     \
+  float* xstage = a.xstage ? a.xstage + dr * NT * a.K * (DENSE ? NDEN : NREC) * DI : nullptr;                    \
   float* hstep = a.xstage ? a.hstep + dr * NT * a.K : nullptr;                                                   \
   int* iend = a.xstage ? a.iend + dr * NT * (a.T - 1) : nullptr;                                                 \
+  float* theta = nullptr;                                                                                        \
+  if constexpr (DENSE) theta = a.xstage ? a.theta + dr * NT * (a.T - 1) : nullptr;                               \
   int* counts = a.counts + dr * NT * 4;
 
 // One wavefront per trajectory.  The (up to four) wavefronts of a workgroup take different numbers of steps: after the pack is
 // staged there is no workgroup barrier.
-template <class EV, int DI, int DO, int ORDER, bool USE_LDS>
-__global__ __launch_bounds__(256) void rollout_adaptive_kernel(AdaptFwd a, size_t lds_f4) {
+template <class EV, int DI, int DO, int ORDER, bool USE_LDS, bool DENSE>
+__global__ __launch_bounds__(256) void rollout_adaptive_kernel(AdaptFwdArg<DENSE> a, size_t lds_f4) {
   static_assert(DI == ORDER * DO && DI <= KP, "state dim = order * D_out");
   __shared__ float kst[4][7 * KP];
   GP_ADAPT_DRAW_POINTERS
@@ -202,13 +280,13 @@ __global__ __launch_bounds__(256) void rollout_adaptive_kernel(AdaptFwd a, size_
   EV ev;
   ev.init(pack, a.M, a.S, lane);
   for (int n = blockIdx.x * wpb + wave; n < a.N; n += gridDim.x * wpb)
-    dopri5_trajectory<EV, DI, DO, ORDER>(ev, a, a.z0, zt, xstage, hstep, iend, counts, n, kst[wave], true, lane);
+    dopri5_trajectory<EV, DI, DO, ORDER, DENSE>(ev, a, a.z0, zt, xstage, hstep, iend, theta, counts, n, kst[wave], true, lane);
 }
 
 // One workgroup per trajectory.  Every evaluation carries the team's barrier, so the four wavefronts must take the same steps:
 // they do, the controller's inputs are the combined slopes, which every wavefront sums from the same LDS slots in the same order.
-template <class EV, int DI, int DO, int ORDER>
-__global__ __launch_bounds__(64 * EV::kTeam) void rollout_adaptive_team_kernel(AdaptFwd a) {
+template <class EV, int DI, int DO, int ORDER, bool DENSE>
+__global__ __launch_bounds__(64 * EV::kTeam) void rollout_adaptive_team_kernel(AdaptFwdArg<DENSE> a) {
   static_assert(DI == ORDER * DO && DI <= KP, "state dim = order * D_out");
   __shared__ float slots[2 * EV::kTeam * TeamCombine::DP];
   __shared__ float kst[EV::kTeam][7 * KP];
@@ -217,7 +295,7 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rollout_adaptive_team_kernel(A
   EV ev;
   ev.init(pack, a.M, a.S, slots, wave, lane);
   for (int n = blockIdx.x; n < a.N; n += gridDim.x)
-    dopri5_trajectory<EV, DI, DO, ORDER>(ev, a, a.z0, zt, xstage, hstep, iend, counts, n, kst[wave], wave == 0, lane);
+    dopri5_trajectory<EV, DI, DO, ORDER, DENSE>(ev, a, a.z0, zt, xstage, hstep, iend, theta, counts, n, kst[wave], wave == 0, lane);
 }
 
 // Reverse sweep: the adjoint of an explicit Runge-Kutta step, over the recorded accepted steps, step sizes constant.
@@ -293,43 +371,149 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rollout_adaptive_bwd_kernel(Ad
   }
 }
 
+// Reverse sweep of the dense mode.  The outputs o a step holds add their interpolation weights to the slope adjoints:
+//   G0 = sum_o g_o,  S_j = h sum_o w_j(theta_o) g_o  (j = 0..6);  w_6(1) = 0, so the seventh slope is differentiated only where a step
+//   holds an output with theta < 1:  lam += J_F(x_6)^T S_6  (x_6 = y_{n+1}, lam = the adjoint of y_{n+1})
+//   ak_j = h b_j lam + S_j (j = 0..5);  the stage loop of the landing sweep;  lam += G0
+// astage has 7 rows per step; row 6 is zero where the step holds no interior output.  The branch on that is scalar and the same in
+// the four wavefronts of a team (theta is read from memory), as the evaluation behind it carries the team's barrier.
+template <class EV, int DI, int DO, int ORDER>
+__global__ __launch_bounds__(64 * EV::kTeam) void rollout_dense_bwd_kernel(AdaptBwdDense a) {
+  static_assert(DI == ORDER * DO && DI <= KP, "state dim = order * D_out");
+  __shared__ float slots[2 * EV::kTeam * TeamCombine::DP];
+  __shared__ float akst[EV::kTeam][NDEN * KP];
+  const size_t dr = blockIdx.y, NT = (size_t)a.N;
+  const int T = a.T, K = a.K;
+  const float* pack = a.pack + dr * a.pack_stride;
+  const float* xstage = a.xstage + dr * NT * K * NDEN * DI;
+  const float* hstep = a.hstep + dr * NT * K;
+  const int* istep = a.iend + dr * NT * (T - 1);
+  const float* theta = a.theta + dr * NT * (T - 1);
+  const float* gzt = a.gzt + dr * NT * T * DI;
+  float* gz0 = a.gz0 + dr * NT * DI;
+  float* astage = a.astage + dr * NT * K * NDEN * DO;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float* ak = akst[wave];
+  EV ev;
+  ev.init(pack, a.M, a.S, slots, wave, lane);
+  for (int n = blockIdx.x; n < a.N; n += gridDim.x) {
+    const float* gz = gzt + (size_t)n * T * DI;
+    const int* is = istep + (size_t)n * (T - 1);
+    const float* th = theta + (size_t)n * (T - 1);
+    int nacc = T > 1 ? __builtin_amdgcn_readfirstlane(is[T - 2]) : 0;
+    nacc = nacc < 0 ? 0 : (nacc > K ? K : nacc);
+    float lam[DI];
+#pragma unroll
+    for (int d = 0; d < DI; ++d) lam[d] = 0.f;
+    int tq = T - 2;                                  // outputs tq + 1 and below still wait for their gradient
+    for (int i = nacc; i >= 1; --i) {
+      const size_t row = (size_t)n * K + (i - 1);
+      const float hs = uni(hstep[row]);
+      const float* xr = xstage + row * NDEN * DI;
+      float* ar = astage + row * NDEN * DO;
+      float g0[DI];
+#pragma unroll
+      for (int d = 0; d < DI; ++d) g0[d] = 0.f;
+      for (int j = 0; j < NDEN; ++j) {
+#pragma unroll
+        for (int d = 0; d < DI; ++d) ak[j * KP + d] = 0.f;
+      }
+      bool interior = false;
+      while (tq >= 0 && __builtin_amdgcn_readfirstlane(is[tq]) >= i) {
+        const float t = uni(fminf(fmaxf(th[tq], 0.f), 1.f));
+        interior = interior || t < 1.f;
+        float g[DI];
+#pragma unroll
+        for (int d = 0; d < DI; ++d) { g[d] = gz[(size_t)(tq + 1) * DI + d]; g0[d] += g[d]; }
+        for (int j = 0; j < NDEN; ++j) {
+          const float c = hs * dense_w(j, t);
+#pragma unroll
+          for (int d = 0; d < DI; ++d) ak[j * KP + d] = fmaf(c, g[d], ak[j * KP + d]);
+        }
+        --tq;
+      }
+      if (interior) {
+        float x[DI], aj[DI], g[DI], af[DO];
+#pragma unroll
+        for (int d = 0; d < DI; ++d) { x[d] = xr[(NDEN - 1) * DI + d]; aj[d] = ak[(NDEN - 1) * KP + d]; }
+        ode_vjp<EV, DI, DO, ORDER>(ev, x, aj, g, af);
+        if (wave == 0) store_state<DO>(ar + (NDEN - 1) * DO, af, lane);
+#pragma unroll
+        for (int d = 0; d < DI; ++d) lam[d] += g[d];
+      } else if (wave == 0 && lane < DO) {
+        ar[(NDEN - 1) * DO + lane] = 0.f;
+      }
+      for (int j = 0; j < NREC; ++j) {
+        const float c = hs * dp_a[6][j];
+#pragma unroll
+        for (int d = 0; d < DI; ++d) ak[j * KP + d] = fmaf(c, lam[d], ak[j * KP + d]);
+      }
+      for (int j = NREC - 1; j >= 0; --j) {
+        float x[DI], aj[DI], g[DI], af[DO];
+#pragma unroll
+        for (int d = 0; d < DI; ++d) { x[d] = xr[j * DI + d]; aj[d] = ak[j * KP + d]; }
+        ode_vjp<EV, DI, DO, ORDER>(ev, x, aj, g, af);
+        if (wave == 0) store_state<DO>(ar + j * DO, af, lane);
+#pragma unroll
+        for (int d = 0; d < DI; ++d) lam[d] += g[d];
+        for (int l = 0; l < j; ++l) {
+          const float c = hs * dp_a[j][l];
+#pragma unroll
+          for (int d = 0; d < DI; ++d) ak[l * KP + d] = fmaf(c, g[d], ak[l * KP + d]);
+        }
+      }
+#pragma unroll
+      for (int d = 0; d < DI; ++d) lam[d] += g0[d];
+    }
+    for (; tq >= -1; --tq) {                         // the initial state, and what a record without steps attributes to it
+#pragma unroll
+      for (int d = 0; d < DI; ++d) lam[d] += gz[(size_t)(tq + 1) * DI + d];
+    }
+    if (wave == 0) {
+      store_state<DI>(gz0 + (size_t)n * DI, lam, lane);
+      float* az = astage + (size_t)n * K * NDEN * DO;
+      for (size_t i = (size_t)nacc * NDEN * DO + lane; i < (size_t)K * NDEN * DO; i += 64) az[i] = 0.f;
+    }
+  }
+}
+
 // ----------------------------------------------------------------------------------------------
 // host launchers: the dispatch of the fixed-grid rollout (gp_forward.hip, gp_backward.hip)
 // ----------------------------------------------------------------------------------------------
-template <int DI, int DO, int ORDER>
-static int launch_adaptive_rbf(const AdaptFwd& a, int nd, hipStream_t st) {
+template <int DI, int DO, int ORDER, bool DENSE>
+static int launch_adaptive_rbf(const AdaptFwdArg<DENSE>& a, int nd, hipStream_t st) {
   const int N = a.N, M = a.M, S = a.S;
   int grid, block;
   grid_for(N, grid, block);
   if (N <= kTeamMaxRows && DO <= 16) {
     if (RbfTeamEval<DI, DO, 1>::fits(M, S)) {
-      hipLaunchKernelGGL((rollout_adaptive_team_kernel<RbfTeamEval<DI, DO, 1>, DI, DO, ORDER>), dim3(team_grid(N), nd), 256, 0, st, a);
+      hipLaunchKernelGGL((rollout_adaptive_team_kernel<RbfTeamEval<DI, DO, 1>, DI, DO, ORDER, DENSE>), dim3(team_grid(N), nd), 256, 0, st, a);
       return check_launch("rollout_adaptive_rbf_team");
     }
   }
   if (N <= kTeamMaxRows) {
-    hipLaunchKernelGGL((rollout_adaptive_team_kernel<RbfStreamTeam<DI, DO>, DI, DO, ORDER>), dim3(team_grid(N), nd), 256, 0, st, a);
+    hipLaunchKernelGGL((rollout_adaptive_team_kernel<RbfStreamTeam<DI, DO>, DI, DO, ORDER, DENSE>), dim3(team_grid(N), nd), 256, 0, st, a);
     return check_launch("rollout_adaptive_rbf_team_stream");
   }
   const int SJ = cdiv(S, 64), MJ = cdiv(M, 64);
   if constexpr (rbf_reg_fits<DI, DO, 4, 2>()) {
     if (SJ == 4 && MJ == 2) {
-      hipLaunchKernelGGL((rollout_adaptive_kernel<RbfRegEval<DI, DO, 4, 2>, DI, DO, ORDER, false>), dim3(grid, nd), block, 0, st, a, (size_t)0);
+      hipLaunchKernelGGL((rollout_adaptive_kernel<RbfRegEval<DI, DO, 4, 2>, DI, DO, ORDER, false, DENSE>), dim3(grid, nd), block, 0, st, a, (size_t)0);
       return check_launch("rollout_adaptive_rbf");
     }
   }
   if constexpr (rbf_reg_fits<DI, DO, 1, 1>()) {
     if (SJ == 1 && MJ == 1) {
-      hipLaunchKernelGGL((rollout_adaptive_kernel<RbfRegEval<DI, DO, 1, 1>, DI, DO, ORDER, false>), dim3(grid, nd), block, 0, st, a, (size_t)0);
+      hipLaunchKernelGGL((rollout_adaptive_kernel<RbfRegEval<DI, DO, 1, 1>, DI, DO, ORDER, false, DENSE>), dim3(grid, nd), block, 0, st, a, (size_t)0);
       return check_launch("rollout_adaptive_rbf");
     }
   }
-  hipLaunchKernelGGL((rollout_adaptive_kernel<RbfStreamEval<DI, DO>, DI, DO, ORDER, false>), dim3(grid, nd), block, 0, st, a, (size_t)0);
+  hipLaunchKernelGGL((rollout_adaptive_kernel<RbfStreamEval<DI, DO>, DI, DO, ORDER, false, DENSE>), dim3(grid, nd), block, 0, st, a, (size_t)0);
   return check_launch("rollout_adaptive_rbf");
 }
 
-template <int D>
-static int launch_adaptive_df(const AdaptFwd& a, int nd, hipStream_t st) {
+template <int D, bool DENSE>
+static int launch_adaptive_df(const AdaptFwdArg<DENSE>& a, int nd, hipStream_t st) {
   using L = DfLayout<D>;
   const int N = a.N, M = a.M, S = a.S;
   const size_t f4 = L::rff_f4(S) + L::ind_f4(M);
@@ -337,96 +521,126 @@ static int launch_adaptive_df(const AdaptFwd& a, int nd, hipStream_t st) {
   grid_for(N, grid, block);
   if constexpr (D <= 8) {
     if (N <= kTeamMaxRows && DfTeamEval<D, 1>::fits(M, S)) {
-      hipLaunchKernelGGL((rollout_adaptive_team_kernel<DfTeamEval<D, 1>, D, D, 1>), dim3(team_grid(N), nd), 256, 0, st, a);
+      hipLaunchKernelGGL((rollout_adaptive_team_kernel<DfTeamEval<D, 1>, D, D, 1, DENSE>), dim3(team_grid(N), nd), 256, 0, st, a);
       return check_launch("rollout_adaptive_df_team");
     }
   }
   if (N <= kTeamMaxRows) {
-    hipLaunchKernelGGL((rollout_adaptive_team_kernel<DfStreamTeam<D>, D, D, 1>), dim3(team_grid(N), nd), 256, 0, st, a);
+    hipLaunchKernelGGL((rollout_adaptive_team_kernel<DfStreamTeam<D>, D, D, 1, DENSE>), dim3(team_grid(N), nd), 256, 0, st, a);
     return check_launch("rollout_adaptive_df_team_stream");
   }
   if (f4 * 16 <= kLdsLimitBytes) {
     if (N <= 1024) { block = 64; grid = N < 256 ? N : 256; }
     else { block = 256; grid = 256; }
-    auto kern = rollout_adaptive_kernel<DfEval<D, true>, D, D, 1, true>;
+    auto kern = rollout_adaptive_kernel<DfEval<D, true>, D, D, 1, true, DENSE>;
     if (set_max_lds((const void*)kern, f4 * 16)) return 1;
     hipLaunchKernelGGL(kern, dim3(grid, nd), block, f4 * 16, st, a, f4);
   } else {
-    hipLaunchKernelGGL((rollout_adaptive_kernel<DfEval<D, false>, D, D, 1, false>), dim3(grid, nd), block, 0, st, a, (size_t)0);
+    hipLaunchKernelGGL((rollout_adaptive_kernel<DfEval<D, false>, D, D, 1, false, DENSE>), dim3(grid, nd), block, 0, st, a, (size_t)0);
   }
   return check_launch("rollout_adaptive_df");
 }
 
-template <int DI, int DO>
-static int adaptive_rbf_dispatch(int order, const AdaptFwd& a, int nd, hipStream_t st) {
-  if constexpr (DI == DO) { if (order == 1) return launch_adaptive_rbf<DI, DO, 1>(a, nd, st); }
-  if constexpr (DI == 2 * DO) { if (order == 2) return launch_adaptive_rbf<DI, DO, 2>(a, nd, st); }
+template <int DI, int DO, bool DENSE>
+static int adaptive_rbf_dispatch(int order, const AdaptFwdArg<DENSE>& a, int nd, hipStream_t st) {
+  if constexpr (DI == DO) { if (order == 1) return launch_adaptive_rbf<DI, DO, 1, DENSE>(a, nd, st); }
+  if constexpr (DI == 2 * DO) { if (order == 2) return launch_adaptive_rbf<DI, DO, 2, DENSE>(a, nd, st); }
   return set_error("gpode_rollout_adaptive_fwd: order=%d needs Di == order*Do (Di=%d Do=%d)", order, DI, DO);
 }
 
-int rollout_adaptive_fwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
-                         const float* z0, const float* ts, int N, int T, float rtol, float atol, int K, float* zt, float* xstage,
-                         float* hstep, int* iend, int* counts, hipStream_t st) {
-  const AdaptFwd a{pack, pack_stride, M, S, z0, ts, N, T, K, rtol, atol, zt, xstage, hstep, iend, counts};
+template <bool DENSE>
+static int adaptive_fwd(int kernel, int order, int Di, int Do, const AdaptFwdArg<DENSE>& a, int nd, hipStream_t st) {
   if (kernel == 0) {
-#define X(p, q) if (Di == p && Do == q) return adaptive_rbf_dispatch<p, q>(order, a, nd, st);
+#define X(p, q) if (Di == p && Do == q) return adaptive_rbf_dispatch<p, q, DENSE>(order, a, nd, st);
     GP_RBF_DIMS(X)
 #undef X
   } else {
     if (order != 1) return set_error("gpode_rollout_adaptive_fwd: DF kernel is first-order only (kernels.py:259-262)");
-#define X(p) if (Di == p && Do == p) return launch_adaptive_df<p>(a, nd, st);
+#define X(p) if (Di == p && Do == p) return launch_adaptive_df<p, DENSE>(a, nd, st);
     GP_DF_DIMS(X)
 #undef X
   }
   return set_error("gpode_rollout_adaptive_fwd: no specialisation for kernel=%d Di=%d Do=%d", kernel, Di, Do);
 }
 
-template <int DI, int DO, int ORDER>
-static int launch_adaptive_bwd_rbf(const AdaptBwd& a, int nd, hipStream_t st) {
+int rollout_adaptive_fwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
+                         const float* z0, const float* ts, int N, int T, float rtol, float atol, int K, float* zt, float* xstage,
+                         float* hstep, int* iend, int* counts, hipStream_t st) {
+  const AdaptFwd a{pack, pack_stride, M, S, z0, ts, N, T, K, rtol, atol, zt, xstage, hstep, iend, counts};
+  return adaptive_fwd<false>(kernel, order, Di, Do, a, nd, st);
+}
+
+int rollout_dense_fwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
+                      const float* z0, const float* ts, int N, int T, float rtol, float atol, int K, float* zt, float* xstage,
+                      float* hstep, int* istep, float* theta, int* counts, hipStream_t st) {
+  const AdaptFwdDense a{{pack, pack_stride, M, S, z0, ts, N, T, K, rtol, atol, zt, xstage, hstep, istep, counts}, theta};
+  return adaptive_fwd<true>(kernel, order, Di, Do, a, nd, st);
+}
+
+// the reverse kernel of a mode
+template <bool DENSE, class EV, int DI, int DO, int ORDER> static constexpr auto adaptive_bwd_kernel() {
+  if constexpr (DENSE) return &rollout_dense_bwd_kernel<EV, DI, DO, ORDER>;
+  else return &rollout_adaptive_bwd_kernel<EV, DI, DO, ORDER>;
+}
+
+template <int DI, int DO, int ORDER, bool DENSE>
+static int launch_adaptive_bwd_rbf(const AdaptBwdArg<DENSE>& a, int nd, hipStream_t st) {
   if constexpr (DO <= 8) {
     if (rbf_team_ok<DI, DO>(a.M, a.S)) {
-      hipLaunchKernelGGL((rollout_adaptive_bwd_kernel<RbfTeamEval<DI, DO, 1>, DI, DO, ORDER>), dim3(team_grid(a.N), nd), 256, 0, st, a);
+      hipLaunchKernelGGL((adaptive_bwd_kernel<DENSE, RbfTeamEval<DI, DO, 1>, DI, DO, ORDER>()), dim3(team_grid(a.N), nd), 256, 0, st, a);
       return check_launch("rollout_adaptive_bwd_rbf");
     }
   }
-  hipLaunchKernelGGL((rollout_adaptive_bwd_kernel<RbfStreamTeam<DI, DO>, DI, DO, ORDER>), dim3(team_grid(a.N), nd), 256, 0, st, a);
+  hipLaunchKernelGGL((adaptive_bwd_kernel<DENSE, RbfStreamTeam<DI, DO>, DI, DO, ORDER>()), dim3(team_grid(a.N), nd), 256, 0, st, a);
   return check_launch("rollout_adaptive_bwd_rbf_stream");
 }
 
-template <int D>
-static int launch_adaptive_bwd_df(const AdaptBwd& a, int nd, hipStream_t st) {
+template <int D, bool DENSE>
+static int launch_adaptive_bwd_df(const AdaptBwdArg<DENSE>& a, int nd, hipStream_t st) {
   if constexpr (D <= 8) {
     if (df_team_ok<D>(a.M, a.S)) {
-      hipLaunchKernelGGL((rollout_adaptive_bwd_kernel<DfTeamEval<D, 1>, D, D, 1>), dim3(team_grid(a.N), nd), 256, 0, st, a);
+      hipLaunchKernelGGL((adaptive_bwd_kernel<DENSE, DfTeamEval<D, 1>, D, D, 1>()), dim3(team_grid(a.N), nd), 256, 0, st, a);
       return check_launch("rollout_adaptive_bwd_df");
     }
   }
-  hipLaunchKernelGGL((rollout_adaptive_bwd_kernel<DfStreamTeam<D>, D, D, 1>), dim3(team_grid(a.N), nd), 256, 0, st, a);
+  hipLaunchKernelGGL((adaptive_bwd_kernel<DENSE, DfStreamTeam<D>, D, D, 1>()), dim3(team_grid(a.N), nd), 256, 0, st, a);
   return check_launch("rollout_adaptive_bwd_df_stream");
 }
 
-template <int DI, int DO>
-static int adaptive_bwd_rbf_dispatch(int order, const AdaptBwd& a, int nd, hipStream_t st) {
-  if constexpr (DI == DO) { if (order == 1) return launch_adaptive_bwd_rbf<DI, DO, 1>(a, nd, st); }
-  if constexpr (DI == 2 * DO) { if (order == 2) return launch_adaptive_bwd_rbf<DI, DO, 2>(a, nd, st); }
+template <int DI, int DO, bool DENSE>
+static int adaptive_bwd_rbf_dispatch(int order, const AdaptBwdArg<DENSE>& a, int nd, hipStream_t st) {
+  if constexpr (DI == DO) { if (order == 1) return launch_adaptive_bwd_rbf<DI, DO, 1, DENSE>(a, nd, st); }
+  if constexpr (DI == 2 * DO) { if (order == 2) return launch_adaptive_bwd_rbf<DI, DO, 2, DENSE>(a, nd, st); }
   return set_error("gpode_rollout_adaptive_bwd: order=%d needs Di == order*Do (Di=%d Do=%d)", order, DI, DO);
+}
+
+template <bool DENSE>
+static int adaptive_bwd(int kernel, int order, int Di, int Do, const AdaptBwdArg<DENSE>& a, int nd, hipStream_t st) {
+  if (kernel == 0) {
+#define X(p, q) if (Di == p && Do == q) return adaptive_bwd_rbf_dispatch<p, q, DENSE>(order, a, nd, st);
+    GP_RBF_DIMS(X)
+#undef X
+  } else {
+    if (order != 1) return set_error("gpode_rollout_adaptive_bwd: DF kernel is first-order only");
+#define X(p) if (Di == p && Do == p) return launch_adaptive_bwd_df<p, DENSE>(a, nd, st);
+    GP_DF_DIMS(X)
+#undef X
+  }
+  return set_error("gpode_rollout_adaptive_bwd: no specialisation for kernel=%d Di=%d Do=%d", kernel, Di, Do);
 }
 
 int rollout_adaptive_bwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
                          const float* xstage, const float* hstep, const int* iend, const float* gzt, int N, int T, int K,
                          float* gz0, float* astage, hipStream_t st) {
   const AdaptBwd a{pack, pack_stride, M, S, xstage, hstep, iend, gzt, N, T, K, gz0, astage};
-  if (kernel == 0) {
-#define X(p, q) if (Di == p && Do == q) return adaptive_bwd_rbf_dispatch<p, q>(order, a, nd, st);
-    GP_RBF_DIMS(X)
-#undef X
-  } else {
-    if (order != 1) return set_error("gpode_rollout_adaptive_bwd: DF kernel is first-order only");
-#define X(p) if (Di == p && Do == p) return launch_adaptive_bwd_df<p>(a, nd, st);
-    GP_DF_DIMS(X)
-#undef X
-  }
-  return set_error("gpode_rollout_adaptive_bwd: no specialisation for kernel=%d Di=%d Do=%d", kernel, Di, Do);
+  return adaptive_bwd<false>(kernel, order, Di, Do, a, nd, st);
+}
+
+int rollout_dense_bwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
+                      const float* xstage, const float* hstep, const int* istep, const float* theta, const float* gzt, int N, int T,
+                      int K, float* gz0, float* astage, hipStream_t st) {
+  const AdaptBwdDense a{{pack, pack_stride, M, S, xstage, hstep, istep, gzt, N, T, K, gz0, astage}, theta};
+  return adaptive_bwd<true>(kernel, order, Di, Do, a, nd, st);
 }
 
 }  // namespace gp

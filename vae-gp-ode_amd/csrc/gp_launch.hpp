@@ -97,6 +97,13 @@ int rollout_adaptive_fwd(int kernel, int order, int Di, int Do, int M, int S, in
 int rollout_adaptive_bwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
                          const float* xstage, const float* hstep, const int* iend, const float* gzt, int N, int T, int K,
                          float* gz0, float* astage, hipStream_t st);
+// the same in dense-output mode: steps cut at ts[T-1] only, interior outputs interpolated (record: 7 rows per step, istep, theta)
+int rollout_dense_fwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
+                      const float* z0, const float* ts, int N, int T, float rtol, float atol, int K, float* zt, float* xstage,
+                      float* hstep, int* istep, float* theta, int* counts, hipStream_t st);
+int rollout_dense_bwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
+                      const float* xstage, const float* hstep, const int* istep, const float* theta, const float* gzt, int N, int T,
+                      int K, float* gz0, float* astage, hipStream_t st);
 int rhs_vjp(int kernel, int Di, int Do, int M, int S, const float* pack, const float* x, const float* a, int R, float* gx,
             int prior_only, hipStream_t st, Draws dw = Draws{});
 int param_grad(int kernel, int Di, int Do, int M, int S, const float* pack, const float* xr, const float* ar, int R,

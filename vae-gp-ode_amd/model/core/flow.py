@@ -5,9 +5,13 @@ from Python.  Here ``Flow.forward`` is ONE persistent HIP kernel for all MC draw
 team of four) integrates one trajectory over the whole grid.  Solvers: the fixed-grid 'euler', 'rk4'
 (= torchdiffeq's 3/8 rule) and 'midpoint' (csrc/gp_forward.hip), and the adaptive 'dopri5'
 (csrc/gp_adaptive.hip: Dormand-Prince 5(4), one step-size controller per trajectory, steps landing
-on ``ts`` -- it agrees with torchdiffeq's to the tolerances, not step by step).  The rest of the
+on ``ts`` -- it agrees with torchdiffeq's to the tolerances, not step by step; with
+``dense_output`` the steps are free of ``ts`` and the outputs are interpolated, as torchdiffeq
+does).  The rest of the
 reference's --solver list (bdf, adams, explicit_adams, fixed_adams) is refused: ops.REFUSED_SOLVERS.
 """
+import os
+
 import torch
 import torch.nn as nn
 
@@ -79,8 +83,13 @@ class ODEfunc(nn.Module):
         return self.first_order(sv) if self.order == 1 else self.second_order(sv)
 
 
+def dense_output_default():
+    """GPODE_DOPRI5_DENSE: unset, empty or 0 -> False; anything else -> True."""
+    return os.environ.get('GPODE_DOPRI5_DENSE', '0').strip() not in ('', '0')
+
+
 class Flow(nn.Module):
-    def __init__(self, diffeq, order=2, solver='dopri5', atol=1e-6, rtol=1e-6, use_adjoint=False, max_steps=None):
+    def __init__(self, diffeq, order=2, solver='dopri5', atol=1e-6, rtol=1e-6, use_adjoint=False, max_steps=None, dense_output=None):
         super().__init__()
         self.odefunc = ODEfunc(diffeq, order)
         self.solver = solver
@@ -89,6 +98,9 @@ class Flow(nn.Module):
         self.atol, self.rtol = atol, rtol
         self.max_steps = max_steps         # dopri5: accepted steps a trajectory may take; None = 4 (T - 1)
         self.use_adjoint = use_adjoint     # same forward; gradients are discretise-then-optimise either way
+        # dopri5: steps cut at ts[-1] only, interior outputs interpolated.  None = the environment decides (GPODE_DOPRI5_DENSE,
+        # unset or 0: off), so that everything built through build_model can be switched without a flag; ignored by fixed grids
+        self.dense_output = dense_output_default() if dense_output is None else bool(dense_output)
         self._last_counts = None
 
     def forward(self, z0, ts, draws=None):
@@ -104,7 +116,8 @@ class Flow(nn.Module):
         gp = self.odefunc.diffeq
         self._last_counts = None
         if self.solver == 'dopri5':
-            return ops.flow(gp, z0, ts, self.odefunc.order, self.solver, draws, (self.rtol, self.atol, self.max_steps, self._take_counts))
+            return ops.flow(gp, z0, ts, self.odefunc.order, self.solver, draws,
+                            (self.rtol, self.atol, self.max_steps, self._take_counts, bool(self.dense_output)))
         zt = ops.flow(gp, z0, ts, self.odefunc.order, self.solver, draws)
         self.odefunc._set_evals(EVALS_PER_STEP[self.solver] * (ts.shape[0] - 1))
         return zt

@@ -305,6 +305,7 @@ def rhs(cache, x, mode=0):
 
 
 NSTAGE = {'euler': 1, 'rk4': 4, 'midpoint': 2, 'dopri5': 6}   # recorded stage inputs per step
+NSTAGE_DENSE = 7     # dopri5 with dense output: the end state of the step, where the seventh slope is evaluated, is recorded too
 
 
 _ts_checked = [None]
@@ -321,11 +322,14 @@ def _check_increasing(ts):
     _ts_checked[0] = key
 
 
-def rollout_adaptive(cache, z0, ts, order, rtol=1e-6, atol=1e-6, max_steps=None, save_stages=False):
+def rollout_adaptive(cache, z0, ts, order, rtol=1e-6, atol=1e-6, max_steps=None, save_stages=False, dense=False):
     """Adaptive Dormand-Prince 5(4) rollout (gpode_rollout_adaptive_fwd_n): one step-size controller per trajectory, steps landing
     on ts.  ``max_steps`` = accepted steps a trajectory may take (default 4 (T-1)).  -> zt ([L,] N,T,D), counts ([L,] N,4) int32
     = (accepted, rejected, status, evaluations of f); with save_stages also the record of the accepted steps: xstage
-    ([L,] N,K,6,D), hstep ([L,] N,K), iend ([L,] N,T-1) int32.  A trajectory with status != 0 is NaN from the output it missed."""
+    ([L,] N,K,6,D), hstep ([L,] N,K), iend ([L,] N,T-1) int32.  A trajectory with status != 0 is NaN from the output it missed.
+    ``dense`` (gpode_rollout_dense_fwd_n): steps are cut at ts[-1] only and the interior outputs are interpolated (4th-order
+    continuous extension, no evaluation of f); the record is then xstage ([L,] N,K,7,D), hstep, istep ([L,] N,T-1) int32 = 1-based
+    number of the accepted step that holds output t+1, theta ([L,] N,T-1) = the output's position inside that step, in (0, 1]."""
     z0 = _chk(z0, 'z0'); ts = _chk(ts, 'ts')
     N, D = z0.shape
     if D != cache.Di or D != order * cache.Do:
@@ -338,46 +342,62 @@ def rollout_adaptive(cache, z0, ts, order, rtol=1e-6, atol=1e-6, max_steps=None,
     lead, dev = cache.lead, z0.device
     zt = torch.empty(lead + (N, T, D), dtype=torch.float32, device=dev)
     counts = torch.empty(lead + (N, 4), dtype=torch.int32, device=dev)
-    xs = hs = ie = None
+    xs = hs = ie = th = None
     if save_stages:
-        xs = torch.empty(lead + (N, K, NSTAGE['dopri5'], D), dtype=torch.float32, device=dev)
+        xs = torch.empty(lead + (N, K, NSTAGE_DENSE if dense else NSTAGE['dopri5'], D), dtype=torch.float32, device=dev)
         hs = torch.empty(lead + (N, K), dtype=torch.float32, device=dev)
         ie = torch.empty(lead + (N, max(T - 1, 0)), dtype=torch.int32, device=dev)
+        th = torch.empty(lead + (N, max(T - 1, 0)), dtype=torch.float32, device=dev) if dense else None
+    if dense:
+        _lib.call('gpode_rollout_dense_fwd_n', KERNEL_ID[cache.kernel], order, METHOD_ID['dopri5'], cache.Di, cache.Do, cache.M,
+                  cache.S, cache.nd, _ptr(cache.pack), _ptr(z0), _ptr(ts), N, T, float(rtol), float(atol), K, _ptr(zt), _ptr(xs), _ptr(hs),
+                  _ptr(ie), _ptr(th), _ptr(counts), _stream())
+        return (zt, counts, xs, hs, ie, th) if save_stages else (zt, counts)
     _lib.call('gpode_rollout_adaptive_fwd_n', KERNEL_ID[cache.kernel], order, METHOD_ID['dopri5'], cache.Di, cache.Do, cache.M,
               cache.S, cache.nd, _ptr(cache.pack), _ptr(z0), _ptr(ts), N, T, float(rtol), float(atol), K, _ptr(zt), _ptr(xs), _ptr(hs),
               _ptr(ie), _ptr(counts), _stream())
     return (zt, counts, xs, hs, ie) if save_stages else (zt, counts)
 
 
-def rollout_adaptive_bwd(cache, xstage, hstep, iend, gzt, order):
-    """Reverse sweep over the recorded accepted steps: gzt ([L,] N,T,D) -> gz0 ([L,] N,D), astage ([L,] N,K,6,Do), zero past the count."""
+def rollout_adaptive_bwd(cache, xstage, hstep, iend, gzt, order, theta=None):
+    """Reverse sweep over the recorded accepted steps: gzt ([L,] N,T,D) -> gz0 ([L,] N,D), astage ([L,] N,K,6,Do), zero past the count.
+    With ``theta`` the record is a dense-output one (xstage ([L,] N,K,7,D), iend = its istep; gpode_rollout_dense_bwd_n): astage
+    ([L,] N,K,7,Do), row 6 zero in the steps that hold no interior output."""
     gzt = _chk(gzt, 'gzt')
     lead = cache.lead
     if gzt.dim() != 3 + len(lead) or tuple(gzt.shape[:len(lead)]) != lead:
         raise _lib.GpodeError('gzt: expected %s + (N,T,D), got %s' % (lead, tuple(gzt.shape)))
     N, T, D = gzt.shape[-3:]
     K = hstep.shape[-1]
-    xstage = _chk(xstage, 'xstage', lead + (N, K, NSTAGE['dopri5'], D)); hstep = _chk(hstep, 'hstep', lead + (N, K))
+    NS = NSTAGE['dopri5'] if theta is None else NSTAGE_DENSE
+    xstage = _chk(xstage, 'xstage', lead + (N, K, NS, D)); hstep = _chk(hstep, 'hstep', lead + (N, K))
     if iend.dtype != torch.int32 or tuple(iend.shape) != lead + (N, max(T - 1, 0)) or not iend.is_contiguous():
         raise _lib.GpodeError('iend: expected contiguous int32 %s, got %s %s' % (lead + (N, T - 1), iend.dtype, tuple(iend.shape)))
     gz0 = torch.empty(lead + (N, D), dtype=torch.float32, device=gzt.device)
-    ast = torch.empty(lead + (N, K, NSTAGE['dopri5'], cache.Do), dtype=torch.float32, device=gzt.device)
+    ast = torch.empty(lead + (N, K, NS, cache.Do), dtype=torch.float32, device=gzt.device)
+    if theta is not None:
+        theta = _chk(theta, 'theta', lead + (N, max(T - 1, 0)))
+        _lib.call('gpode_rollout_dense_bwd_n', KERNEL_ID[cache.kernel], order, METHOD_ID['dopri5'], cache.Di, cache.Do, cache.M,
+                  cache.S, cache.nd, _ptr(cache.pack), _ptr(xstage), _ptr(hstep), _ptr(iend), _ptr(theta), _ptr(gzt), N, T, K, _ptr(gz0),
+                  _ptr(ast), _stream())
+        return gz0, ast
     _lib.call('gpode_rollout_adaptive_bwd_n', KERNEL_ID[cache.kernel], order, METHOD_ID['dopri5'], cache.Di, cache.Do, cache.M,
               cache.S, cache.nd, _ptr(cache.pack), _ptr(xstage), _ptr(hstep), _ptr(iend), _ptr(gzt), N, T, K, _ptr(gz0), _ptr(ast),
               _stream())
     return gz0, ast
 
 
-def rollout(cache, z0, ts, order, method, save_stages=False, rtol=1e-6, atol=1e-6, max_steps=None):
+def rollout(cache, z0, ts, order, method, save_stages=False, rtol=1e-6, atol=1e-6, max_steps=None, dense=False):
     """Flow.forward (flow.py:68-86) for a built cache: z0 (N,D), ts (T,) -> zt (N,T,D); a cache of L draws integrates all L * N
     trajectories in ONE launch -> zt (L,N,T,D) (the stack of odegpvae.py:41-44).
     save_stages=True also returns the inputs of all RHS evaluations ([L,] N,T-1,NS,D) for the reverse sweep.
-    method 'dopri5' (the only one that reads rtol / atol / max_steps) is rollout_adaptive(): with save_stages the second value is its
-    record (xstage, hstep, iend, counts), which rollout_bwd takes in place of xstage."""
+    method 'dopri5' (the only one that reads rtol / atol / max_steps / dense) is rollout_adaptive(): with save_stages the second value
+    is its record (xstage, hstep, iend, counts), which rollout_bwd takes in place of xstage; in dense-output mode the record is
+    (xstage, hstep, istep, counts, theta)."""
     check_solver(method)
     if method == 'dopri5':
-        out = rollout_adaptive(cache, z0, ts, order, rtol, atol, max_steps, save_stages)
-        return (out[0], (out[2], out[3], out[4], out[1])) if save_stages else out[0]
+        out = rollout_adaptive(cache, z0, ts, order, rtol, atol, max_steps, save_stages, dense=dense)
+        return (out[0], (out[2], out[3], out[4], out[1]) + tuple(out[5:])) if save_stages else out[0]
     z0 = _chk(z0, 'z0'); ts = _chk(ts, 'ts')
     N, D = z0.shape
     if D != cache.Di or D != order * cache.Do:
@@ -393,9 +413,9 @@ def rollout(cache, z0, ts, order, method, save_stages=False, rtol=1e-6, atol=1e-
 
 def rollout_bwd(cache, xstage, gzt, ts, order, method):
     """Reverse sweep: gzt ([L,] N,T,D) -> gz0 ([L,] N,D), astage ([L,] N,T-1,NS,Do) (dopri5: xstage is rollout's record, astage
-    ([L,] N,K,6,Do))."""
+    ([L,] N,K,6,Do), or ([L,] N,K,7,Do) for a dense-output record)."""
     if method == 'dopri5':
-        return rollout_adaptive_bwd(cache, xstage[0], xstage[1], xstage[2], gzt, order)
+        return rollout_adaptive_bwd(cache, xstage[0], xstage[1], xstage[2], gzt, order, theta=xstage[4] if len(xstage) > 4 else None)
     gzt = _chk(gzt, 'gzt'); xstage = _chk(xstage, 'xstage'); ts = _chk(ts, 'ts')
     lead = cache.lead
     if gzt.dim() != 3 + len(lead) or tuple(gzt.shape[:len(lead)]) != lead:
@@ -632,9 +652,10 @@ class _Flow(torch.autograd.Function):
     reverse sweep, one parameter-sum launch and one cache backward on the gradients summed over the draws.
     Forward: gpode_cache_build_fwd_n + gpode_rollout_fwd_n.  Backward: gpode_rollout_bwd_n (reverse sweep), gpode_param_grad_n
     (pack-layout parameter gradients), gpode_cache_build_bwd_n.
-    method 'dopri5': the adaptive entry points; ``adaptive`` = (rtol, atol, max_steps, sink) -- sink(counts) is handed the counts
-    tensor of the solve.  The record (xstage, hstep, iend) takes the place of xs; its rows past a trajectory's count are zero
-    in both xstage and astage, so the parameter sums run over all K * 6 rows."""
+    method 'dopri5': the adaptive entry points; ``adaptive`` = (rtol, atol, max_steps, sink[, dense]) -- sink(counts) is handed the
+    counts tensor of the solve.  The record (xstage, hstep, iend) takes the place of xs; its rows past a trajectory's count are zero
+    in both xstage and astage, so the parameter sums run over all K * 6 rows.  ``dense``: the dense-output entry points; the record
+    is (xstage, hstep, istep, theta) with 7 rows per step, saved behind the landing mode's tensors."""
 
     @staticmethod
     def forward(ctx, z0, ts, raw_ell, raw_var, Z, Um, Us, gp, order, method, draws=None, adaptive=None):
@@ -652,10 +673,11 @@ class _Flow(torch.autograd.Function):
             side = fork_side_stream()
             with launch_on(side):
                 ctx.prepared = cache_bwd_prepare(cache)
-        hs = ie = None
+        hs = ie = th = None
         if method == 'dopri5':
-            rtol, atol, max_steps, sink = adaptive if adaptive is not None else (1e-6, 1e-6, None, None)
-            zt, counts, xs, hs, ie = (rollout_adaptive(cache, z0, ts, order, rtol, atol, max_steps, save_stages=need) + (None,) * 3)[:5]
+            rtol, atol, max_steps, sink, dense = (tuple(adaptive) + (False,))[:5] if adaptive is not None else (1e-6, 1e-6, None, None, False)
+            zt, counts, xs, hs, ie, th = (rollout_adaptive(cache, z0, ts, order, rtol, atol, max_steps, save_stages=need, dense=bool(dense))
+                                          + (None,) * 4)[:6]
             if sink is not None:
                 sink(counts)
         elif need:
@@ -663,12 +685,12 @@ class _Flow(torch.autograd.Function):
         else:
             zt, xs = rollout(cache, z0, ts, order, method), None
         ctx.cache, ctx.order, ctx.method = cache, order, method
-        ctx.save_for_backward(ts, xs, raw_ell.detach(), raw_var.detach(), Z.detach(), hs, ie)
+        ctx.save_for_backward(ts, xs, raw_ell.detach(), raw_var.detach(), Z.detach(), hs, ie, th)
         return zt
 
     @staticmethod
     def backward(ctx, gzt):
-        ts, xs, raw_ell, raw_var, Z, hs, ie = ctx.saved_tensors
+        ts, xs, raw_ell, raw_var, Z, hs, ie, th = ctx.saved_tensors
         c = ctx.cache
         lead = c.lead
         want_p = any(ctx.needs_input_grad[2:7])
@@ -679,7 +701,7 @@ class _Flow(torch.autograd.Function):
         if nch:
             gz0, ast, gpack_f = rollout_bwd_pgrad(c, xs, gzt.contiguous(), ts, ctx.order, ctx.method, nch)
         elif ctx.method == 'dopri5':
-            gz0, ast = rollout_adaptive_bwd(c, xs, hs, ie, gzt.contiguous(), ctx.order)
+            gz0, ast = rollout_adaptive_bwd(c, xs, hs, ie, gzt.contiguous(), ctx.order, theta=th)
         else:
             gz0, ast = rollout_bwd(c, xs, gzt.contiguous(), ts, ctx.order, ctx.method)
         if c.stacked:
@@ -703,7 +725,7 @@ class _Flow(torch.autograd.Function):
             # every buffer a side-stream kernel touches stays referenced until join_side_stream(): the allocator would
             # otherwise hand the block to the encoder-backward kernels the main stream launches meanwhile
             _overlap['pending'].append((ctx.params, [gg.view_as(p) for gg, p in zip(grads, ctx.params)],
-                                        (g, gpack, xs, ast, c, scratch, raw_ell, raw_var, Z, ctx.prepared, hs, ie)))
+                                        (g, gpack, xs, ast, c, scratch, raw_ell, raw_var, Z, ctx.prepared, hs, ie, th)))
             return (gz0,) + (None,) * 11
         if ctx.prepared is not None:
             torch.cuda.current_stream().wait_stream(side_stream())
@@ -714,7 +736,7 @@ class _Flow(torch.autograd.Function):
 
 def flow(gp, z0, ts, order, method, draws=None, adaptive=None):
     """One function draw -> zt (N,T,D); ``draws`` = L -> the L draws of odegpvae.py:41-44 in one pass, zt (L,N,T,D).
-    ``adaptive`` = (rtol, atol, max_steps, sink) for method 'dopri5' (see _Flow)."""
+    ``adaptive`` = (rtol, atol, max_steps, sink[, dense]) for method 'dopri5' (see _Flow)."""
     check_solver(method)
     k = gp.kern
     raw_ell, raw_var = k.raw_dimwise() if hasattr(k, 'raw_dimwise') else (k.unconstrained_lengthscales, k.unconstrained_variance)
