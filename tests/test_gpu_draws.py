@@ -20,6 +20,10 @@ from test_gpu_forward import relerr
 
 pytestmark = pytest.mark.gpu
 
+# Bit-exactness between the batched and the single-draw builds holds only while both take the SAME forward route: whether a system is
+# LDS-resident depends on the number of draws too (the rhs rows count towards np, the solution vectors towards the LDS bytes), so a
+# shape may take k_draw_lds with one draw and the launch chain with L.  Every shape below keeps one route for 1 and L draws;
+# test_gpu_gp_routes.py covers the pair that does not (RBF 16 x 8, M = 190, one against two draws), against the oracle.
 #        name            kernel Di Do  M    S    N  T  L   route through the factor
 SHAPES = [('rbf_lds', 'RBF', 6, 6, 100, 256, 8, 6, 5),      # six 128-row systems resident in LDS (BASELINE configs[0], [3])
           ('rbf2_lds', 'RBF', 6, 3, 100, 256, 8, 6, 3),     # second order (configs[2])

@@ -1366,7 +1366,7 @@ int cache_build_fwd(int kernel, int Di, int Do, int M, int S, int nd,
                          bstride, Dfac, dstride, ws + w.nu, nu, pack_ind, info, nd, MD, MD, pf);
     }
     if (Lu) hipLaunchKernelGGL(k_copy_L, dim3(cdiv(w.n, 128), w.n, w.batch), 128, 0, st, Lmat, Dfac, dstride, w.n, w.np, bstride, Lu);
-    return check_launch("cache build (LDS-resident draw)");
+    return check_launch("cache build: lds");
   }
   if (kernel == 0)
     hipLaunchKernelGGL(k_Kzz_rbf, dim3(cdiv(w.np, 128), w.np, Do), 128, 0, st, Di, Do, M, w.np, Z, ws + w.ell, ws + w.var, up, A, nd);
@@ -1377,6 +1377,7 @@ int cache_build_fwd(int kernel, int Di, int Do, int M, int S, int nd,
 
   // nu_l = L^-T (u_l - L^-1 u_prior_l), written to ws, to the optional output and into draw l's pack
   const int u_stride = kernel == 0 ? Do : 1, u_bstride = kernel == 0 ? 1 : 0;
+  const char* route = "cache build: panel";            // the route through the factor (gpode_last_launch; tests/gp_routes.py)
   if (big_factor(w.np)) {
     const int npanel = cdiv(w.n, ST);
     for (int P = npanel - 1; P >= 0; --P)
@@ -1391,7 +1392,7 @@ int cache_build_fwd(int kernel, int Di, int Do, int M, int S, int nd,
       hipLaunchKernelGGL(k_solve_back_deep, dim3(w.batch, nd), SBD_THREADS, ldsd, st, Lmat, w.n, w.np, bstride, Dfac, dstride, ws + w.u,
                          u_stride, u_bstride, ws + w.nu, nu, kernel, Di, Do, M, ws + w.var, pack_ind, MD, MD, pf);
       if (Lu) hipLaunchKernelGGL(k_copy_L, dim3(cdiv(w.n, 128), w.n, w.batch), 128, 0, st, Lmat, Dfac, dstride, w.n, w.np, bstride, Lu);
-      return check_launch("cache build");
+      return check_launch("cache build: chain32+deep");
     }
     const size_t lds = sizeof(float) * w.np;
     const int cpt = cdiv(w.n, 1024);  // 4 columns per thread per unit
@@ -1405,9 +1406,10 @@ int cache_build_fwd(int kernel, int Di, int Do, int M, int S, int nd,
     else if (cpt == 2) GP_SOLVE(2);
     else GP_SOLVE(0);
 #undef GP_SOLVE
+    route = cpt == 1 ? "cache build: chain32+back<1>" : cpt == 2 ? "cache build: chain32+back<2>" : "cache build: chain32+back<0>";
   }
   if (Lu) hipLaunchKernelGGL(k_copy_L, dim3(cdiv(w.n, 128), w.n, w.batch), 128, 0, st, Lmat, Dfac, dstride, w.n, w.np, bstride, Lu);
-  return check_launch("cache build");
+  return check_launch(route);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1487,14 +1489,15 @@ int compute_nu(int kernel, int Di, int Do, int M, const float* Ku, const float* 
       if (set_max_lds((const void*)k_solve_back_deep, ldsd)) return 1;
       hipLaunchKernelGGL(k_solve_back_deep, dim3(w.batch, 1), SBD_THREADS, ldsd, st, Lmat, w.n, w.np, bstride, Dfac, dstride, u, u_stride,
                          u_bstride, ws + w.nu, nu, kernel, Di, Do, M, (const float*)nullptr, (float*)nullptr, MD, MD, (size_t)0);
-      return check_launch("kern.compute_nu");
+      return check_launch("kern.compute_nu: chain32+deep");
     }
     const size_t lds = sizeof(float) * w.np;
     if (set_max_lds((const void*)k_solve_back<0>, lds)) return 1;
     hipLaunchKernelGGL(k_solve_back<0>, dim3(w.batch, 1), 256, lds, st, Lmat, w.n, w.np, bstride, Dfac, dstride, u, u_stride, u_bstride,
                        ws + w.nu, nu, kernel, Di, Do, M, (const float*)nullptr, (float*)nullptr, MD, MD, (size_t)0);
+    return check_launch("kern.compute_nu: chain32+back<0>");
   }
-  return check_launch("kern.compute_nu");
+  return check_launch("kern.compute_nu: panel");
 }
 
 int f_update(int kernel, int Di, int Do, int M, const float* raw_ell, const float* raw_var, const float* x2, const float* nu,
@@ -1668,7 +1671,7 @@ int conditional(int Di, int Do, int M, int N, const float* raw_ell, const float*
                      Us_packed, us_rank1, ws + c.a, ws + c.t, mean, full_cov ? nullptr : var);
   if (full_cov)
     hipLaunchKernelGGL(k_cond_cov, (unsigned)(((size_t)N * N + 3) / 4), 256, 0, st, Di, Do, M, N, raw_ell, raw_var, x, ws + c.a, ws + c.t, var);
-  return check_launch("conditional");
+  return check_launch(big_factor(c.np) ? "conditional: panel" : "conditional: chain32");
 }
 
 }  // namespace gp

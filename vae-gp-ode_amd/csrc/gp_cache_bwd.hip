@@ -1192,7 +1192,7 @@ int cache_bwd_prepare(int kernel, int Di, int Do, int M, int S, int nd, const fl
   const float* Dfac = ws + w.Dfac;
   const size_t bstride = (size_t)w.np * w.np, dstride = (size_t)w.nblk * NB * NB, dinv_stride = (size_t)b.nbn * NB * NB;
   hipLaunchKernelGGL(k_trinv_diag, dim3(b.nbn, b.batch), 64, 0, st, Dfac, dstride, b.n, bws + b.Dinv, dinv_stride);
-  if (use_trsm(b.np)) return check_launch("cache bwd: diagonal-block inverses");   // the solve-based route needs nothing else
+  if (use_trsm(b.np)) return check_launch("cache bwd prepare: solves");   // the solve-based route needs nothing else
   hipLaunchKernelGGL(k_linv_init, dim3(b.nbn, b.nbn, b.batch), 256, 0, st, b.np, bws + b.Dinv, dinv_stride, bws + b.Linv, bstride);
   for (int sb = 1; sb < b.nbn; sb *= 2) {            // T lives in the X buffer (written by k_gemm_phiX only afterwards)
     const int npairs = cdiv(b.nbn, 2 * sb);
@@ -1205,7 +1205,7 @@ int cache_bwd_prepare(int kernel, int Di, int Do, int M, int S, int nd, const fl
     hipLaunchKernelGGL(k_linv_dc, dim3(sb, sb, npairs * b.batch), 256, 0, st, 0, sb, npairs, b.nbn, b.n, b.np, Lmat, bws + b.Linv, bws + b.X, bstride);
     hipLaunchKernelGGL(k_linv_dc, dim3(sb, sb, npairs * b.batch), 256, 0, st, 1, sb, npairs, b.nbn, b.n, b.np, Lmat, bws + b.Linv, bws + b.X, bstride);
   }
-  return check_launch("cache bwd: L^-1");
+  return check_launch(big_factor(b.np) ? "cache bwd prepare: inverse_mfma" : "cache bwd prepare: inverse32");
 }
 
 // nd draws that shared one cache build: gpack, pack, eps_u are stacked along a leading draw axis; the parameter gradients
@@ -1229,6 +1229,7 @@ int cache_build_bwd(int kernel, int Di, int Do, int M, int S, int nd, const floa
   (void)MJ;
 
   const bool solves = use_trsm(b.np);
+  const int route = solves ? 0 : big_factor(b.np) ? 2 : 1;   // the tag of the last launch names it (gpode_last_launch; tests/gp_routes.py)
   if (!solves) hipLaunchKernelGGL(k_gnu, dim3(cdiv(b.np, 128), b.batch, nd), 128, 0, st, kernel, Di, Do, M, b.n, b.np, gpack_ind, ws + w.var, vec, pf);
   if (!(prepared & 1) && cache_bwd_prepare(kernel, Di, Do, M, S, nd, ws, bws, st)) return 1;
   const size_t trsm_lds = sizeof(float) * (size_t)(b.nbn + 2) * NB * TSL;
@@ -1282,7 +1283,9 @@ int cache_build_bwd(int kernel, int Di, int Do, int M, int S, int nd, const floa
                        bws + b.gZpart, bws + b.kpart);
     hipLaunchKernelGGL(k_chain_rbf, Do * Di + Do + cdiv(M * Di, 256), 256, 0, st, Di, Do, M, S, pack, gpack, raw_ell, raw_var, ws + w.nu,
                        bws + b.vjpZ, bws + b.gZpart, bws + b.kpart, g_raw_ell, g_raw_var, g_Z, nd, pf);
-    return check_launch("cache bwd: chain");
+    static const char* const tag[3] = {"cache bwd: solves (k_trsm_slab), rbf", "cache bwd: inverse32 (k_linv_dc, k_gemm_phiX), rbf",
+                                       "cache bwd: inverse_mfma (k_linv_dc_mfma, k_gemm_mfma), rbf"};
+    return check_launch(tag[route]);
   }
 #define X(D_)                                                                                                              \
   if (Do == D_) {                                                                                                          \
@@ -1291,7 +1294,9 @@ int cache_build_bwd(int kernel, int Di, int Do, int M, int S, int nd, const floa
     hipLaunchKernelGGL(k_df_gomega<D_>, dim3(S, nd), ((D_ * D_ + 63) / 64) * 64, 0, st, S, pack, gpack, ws + w.var, bws + b.gom, pf);    \
     hipLaunchKernelGGL(k_chain_df<D_>, D_ * D_ + D_ + cdiv(M * D_, 256), 256, 0, st, M, S, pack, gpack, raw_ell, raw_var, bws + b.gom, bws + b.vjpZ,      \
                        bws + b.gZpart, bws + b.kpart, g_raw_ell, g_raw_var, g_Z, nd, pf);                                  \
-    return check_launch("cache bwd: chain df");                                                                            \
+    static const char* const tag[3] = {"cache bwd: solves (k_trsm_slab), df", "cache bwd: inverse32 (k_linv_dc, k_gemm_phiX), df",       \
+                                       "cache bwd: inverse_mfma (k_linv_dc_mfma, k_gemm_mfma), df"};                       \
+    return check_launch(tag[route]);                                                                                       \
   }
   X(6) X(4) X(2) X(3) X(8) X(16) X(5) X(7) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
 #undef X
