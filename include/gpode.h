@@ -298,7 +298,9 @@ int gpode_conv2d_bwd_weight_bn(const float* x, const float* gy, const float* gy_
 /* nn.BatchNorm2d in TRAINING mode (batch statistics), optional fused ReLU (vae.py:55-59,113-120).
  * running_* may be NULL (no update); num_batches_tracked (optional, DEVICE int64 scalar, the module buffer) is incremented.
  * gx_chansum (optional, C floats): per-channel sum of gx, i.e. the bias gradient of the
- * convolution that feeds this BatchNorm, produced while gx is written instead of by a separate pass. */
+ * convolution that feeds this BatchNorm, produced while gx is written instead of by a separate pass.
+ * gpode_bn_fwd and gpode_bn_stats refuse B * HW < 2 ("Expected more than 1 value per channel when training", as nn.BatchNorm2d:
+ * the unbiased variance of one value does not exist) and write nothing; gpode_bn_moments accepts a one-element shard. */
 size_t gpode_bn_scratch(int B, int C);
 int gpode_bn_fwd(const float* x, const float* gamma, const float* beta, float* y, float* save_mean, float* save_invstd,
                  float* running_mean, float* running_var, long long* num_batches_tracked, float momentum, float eps, int B, int C,

@@ -413,7 +413,7 @@ __global__ __launch_bounds__(64) void k_bn_moments(const float* __restrict__ par
   mom[2 * c + 1] = fmaxf(s1 - s0 * d, 0.f);
 }
 
-// gathered[r][2C+1] for r < W (<= 64) ranks, combined in rank order (Chan et al.: n = sum n_r, mean = sum n_r mean_r / n,
+// gathered[r][2C+1] for r < W (<= 64) ranks, combined in rank order (Chan et al.: n = sum n_r, mean = mean_0 + sum n_r (mean_r - mean_0) / n,
 // M2 = sum M2_r + n_r (mean_r - mean)^2) -- identical on every rank, no E[x^2] - E[x]^2 cancellation.  Then exactly what
 // k_bn_table does with the batch statistics.
 __global__ __launch_bounds__(64) void k_bn_finalize(const float* __restrict__ gathered, int W, const float* __restrict__ gamma,
@@ -426,10 +426,11 @@ __global__ __launch_bounds__(64) void k_bn_finalize(const float* __restrict__ ga
   const float nr = lane < W ? gathered[lane * stride + 2 * C] : 0.f;
   const float mr = lane < W ? gathered[lane * stride + 2 * c] : 0.f;
   const float qr = lane < W ? gathered[lane * stride + 2 * c + 1] : 0.f;
-  const float in2[2] = {nr, nr * mr};
+  const float m0 = gathered[2 * c];                  // rank 0's mean as the shift: the sum rounds at the size of the spread between
+  const float in2[2] = {nr, nr * (mr - m0)};         // the ranks' means, not of the mean itself, and one rank gets its own mean back
   float out2[2];
   wave_sum_multi<2>(in2, out2);
-  const float count = out2[0], m = out2[1] / count;
+  const float count = out2[0], m = m0 + out2[1] / count;
   const float dm = mr - m;
   const float in1[1] = {fmaf(nr * dm, dm, qr)};
   float out1[1];
@@ -487,6 +488,9 @@ inline bool bn_small(size_t per_channel, size_t limit) {
   static const bool off = [] { const char* e = getenv("GPODE_BN_ONE_LAUNCH"); return e && e[0] == '0'; }();
   return !off && per_channel <= limit;
 }
+// one value per channel has no unbiased variance (count / (count - 1) = 1 / 0 would put NaN into running_var): refused in the words
+// of nn.BatchNorm2d.  gpode_bn_moments accepts such a shard, which is legitimate across ranks.
+constexpr const char* kBnOneValue = "Expected more than 1 value per channel when training";
 
 }  // namespace
 
@@ -497,6 +501,7 @@ int bn_fwd(const float* x, const float* gamma, const float* beta, float* y, floa
            float* running_mean, float* running_var, long long* num_batches_tracked, float momentum, float eps, int B, int C, int HW,
            int relu, float* scratch, hipStream_t st) {
   if ((HW & 3) == 0 && !(aligned16(x) && aligned16(y))) return set_error("gpode_bn_fwd: x / y must be 16-byte aligned");
+  if ((size_t)B * HW < 2) return set_error("gpode_bn_fwd: %s, got B * HW = %d", kBnOneValue, B * HW);
   if (bn_small((size_t)B * HW, kBnSmallFwd)) {
     hipLaunchKernelGGL(k_bn_fwd_small, C, 256, 0, st, x, gamma, beta, (float)B * HW, eps, momentum, save_mean, save_invstd, running_mean, running_var,
                        num_batches_tracked, y, (float*)nullptr, B, C, HW, relu);
@@ -514,6 +519,7 @@ int bn_stats(const float* x, const float* gamma, const float* beta, float* save_
              float* running_var, long long* num_batches_tracked, float momentum, float eps, float* table, int B, int C, int HW,
              float* scratch, hipStream_t st) {
   if ((HW & 3) == 0 && !aligned16(x)) return set_error("gpode_bn_stats: x must be 16-byte aligned");
+  if ((size_t)B * HW < 2) return set_error("gpode_bn_stats: %s, got B * HW = %d", kBnOneValue, B * HW);
   if (bn_small((size_t)B * HW, kBnSmallFwd)) {
     hipLaunchKernelGGL(k_bn_fwd_small, C, 256, 0, st, x, gamma, beta, (float)B * HW, eps, momentum, save_mean, save_invstd, running_mean, running_var,
                        num_batches_tracked, (float*)nullptr, table, B, C, HW, 0);
