@@ -392,6 +392,17 @@ int gpode_bn_eval_table(const float* gamma, const float* beta, const float* runn
  * bits as one launch.  The F frame states are combined on the host in double precision (evaluate.merge_states). */
 int gpode_dec10_predict(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th,
                         int T_obs, int done, float* pred_mean, float* pred_m2, float* se_state, void* stream);
+/* gpode_dec10_predict, which also leaves the held-out Bernoulli log-likelihood of every decoded image against its target -- the
+ * likelihood of vae.py:136-153 (`log(z) * x + log(1 - z) * (1 - x)` summed over the pixels), the term create_model.py:52-53 averages
+ * over draws and sequences.  With a = the logit of decnn.10 and x = the target as it is (not confined to [0,1]):
+ *   ell[(done + l) * F + f] = sum_p  x * a - softplus(a),   softplus(a) = max(a, 0) + log1p(exp(-|a|)),
+ * which equals the reference's expression in exact arithmetic (log z = a - softplus(a), log(1 - z) = -softplus(a)) and is finite for
+ * every finite logit; the reference's float32 form is -inf / nan once 1 - z rounds to 0.  Frames without a target (t >= T_obs) get 0.
+ * ell: [L_total][F], rows done .. done + Lc - 1 are written, every entry exactly once from one image only, so any split of the draws
+ * over launches gives the same bits.  pred_mean, pred_m2 and se_state are updated to the same bits as by gpode_dec10_predict.
+ * Refused, with nothing written: ell == NULL, done + Lc > L_total, every argument gpode_dec10_predict refuses, GPODE_CONV_VALU. */
+int gpode_dec10_predict_ll(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th,
+                           int T_obs, int done, float* pred_mean, float* pred_m2, float* se_state, float* ell, int L_total, void* stream);
 /* out[c] = sum_{b,hw} v[b,c,hw] (bias gradients); scratch: gpode_bn_scratch(B,C) floats. */
 int gpode_chan_sum(const float* v, float* out, int B, int C, int HW, float* scratch, void* stream);
 /* mode 0: ReLU, 1: sigmoid (vae.py:60,121).  Backward takes the forward OUTPUT y. */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Posterior-predictive evaluation, the route that existed before against evaluate.predict, on one GPU.
 
-    python tools/eval_bench.py [--L 128] [--N 40] [--T 16] [--Troll 1] [--windows 5] [--min_window_s 1.0]
+    python tools/eval_bench.py [--L 128] [--N 40] [--T 16] [--Troll 1] [--windows 5] [--min_window_s 1.0] [--loglik [--parent_lib SO]]
 
   baseline  model.eval(); model(X, Lc[, T_custom]) per pass of at most --images_per_pass images, then torch's var_mean of the squared
             error per pass, merged at the end (the only route before evaluate.py; in passes so that both fit the same memory)
@@ -11,7 +11,19 @@
 configs[0] model (RBF, q = 6, M = 100, S = 256, rk4), synthetic frames, device noise for both routes.  Every shape is warmed up,
 then the routes alternate in windows of whole evaluations, each window at least --min_window_s long, timed with device events around
 the window.  One JSON line: per-window ms per evaluation, medians, spread (max - min over the median) and the ratio.  Without a GPU it
-fails; `--dry` only parses, plans the passes and prints the byte counts (a rehearsal, no timing).
+fails.
+
+--loglik measures the held-out log-likelihood instead (statistics only, no predictive moments), the same alternating windows:
+  predict_plain         evaluate.predict(variance=False)                       -- k_fwd_predict<false>
+  predict_loglik        evaluate.predict(variance=False, loglik=True)          -- k_fwd_predict<true>, one more copy of L F floats
+  unfused_loglik        model.eval(); model(X, Lc) per pass, torch's var_mean of the squared error and the reference's
+                        log(z) x + log(1 - z) (1 - x) summed per sequence, then the log-mean-exp over the draws
+  predict_plain_parent  predict_plain through the library of the parent commit given with --parent_lib (loaded next to this
+                        build's, the same process and the same windows), to show that the plain route did not move
+It reports, with no target set, `loglik_cost` = predict_loglik / predict_plain - 1 beside the window spreads, and -- the condition --
+`plain_vs_parent` = predict_plain / predict_plain_parent - 1, which must not exceed the larger of the two spreads.
+
+`--dry` only parses, plans the passes and prints the byte counts (a rehearsal, no timing).
 """
 import argparse
 import json
@@ -36,6 +48,52 @@ def byte_counts(L, N, T, Th, passes):
                 dec10_predict=imgs * a7 + state)
 
 
+def loglik_routes(a, model, X, passes, Tc):
+    """the routes of --loglik: [(name, callable returning (mse, std[, nll, nlpd]))]"""
+    import ctypes
+    import torch
+    from vae_gp_ode_amd import _lib
+    from vae_gp_ode_amd.evaluate import log_mean_exp, mean_std, merge_states, predict
+
+    def plain():
+        p = predict(model, X, a.L, T_custom=Tc, images_per_pass=a.images_per_pass, variance=False)
+        return p.mse, p.std
+
+    def loglik():
+        p = predict(model, X, a.L, T_custom=Tc, images_per_pass=a.images_per_pass, variance=False, loglik=True)
+        return p.mse, p.std, p.nll, p.nlpd
+
+    def unfused():
+        model.eval()
+        parts, lls = [], []
+        with torch.no_grad():
+            for s, e in passes:
+                Xrec, _, _ = model(X, e - s, T_custom=Tc)
+                z = Xrec[:, :, :a.T]
+                se = (z - X) ** 2
+                parts.append((se.numel(),) + torch.var_mean(se, unbiased=False))
+                lls.append((torch.log(z) * X + torch.log(1 - z) * (1 - X)).sum(dim=(2, 3, 4, 5)))
+        model.train()
+        ll = torch.cat(lls).double().cpu()
+        return mean_std(merge_states([(n, m.item(), v.item() * n) for n, v, m in parts])) + (-ll.mean().item(), -log_mean_exp(ll).mean().item())
+
+    routes = [('predict_plain', plain), ('predict_loglik', loglik), ('unfused_loglik', unfused)]
+    if a.parent_lib:
+        this, parent = _lib.load(), ctypes.CDLL(os.path.abspath(a.parent_lib))
+        for name, (res, args) in _lib.SIGNATURES.items():
+            if hasattr(parent, name):                  # the parent's header is a subset of this build's
+                getattr(parent, name).restype, getattr(parent, name).argtypes = res, args
+
+        def plain_parent():
+            _lib._lib = parent
+            try:
+                return plain()
+            finally:
+                _lib._lib = this
+        routes.append(('predict_plain_parent', plain_parent))
+    return routes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--L', type=int, default=128)
@@ -47,6 +105,8 @@ def main():
     ap.add_argument('--min_window_s', type=float, default=1.0)
     ap.add_argument('--seed', type=int, default=121)
     ap.add_argument('--dry', action='store_true')
+    ap.add_argument('--loglik', action='store_true')
+    ap.add_argument('--parent_lib', default=None)
     a = ap.parse_args()
     from vae_gp_ode_amd.evaluate import plan_passes
     Th = a.Troll * a.T
@@ -98,6 +158,8 @@ def main():
         return p.mse, p.std
 
     routes = [('baseline', baseline), ('predict_stats', new_stats), ('predict_full', new_full)]
+    if a.loglik:
+        routes = loglik_routes(a, model, X, passes, Tc)
     last, reps = {}, {}
     ev = lambda: torch.cuda.Event(enable_timing=True)
     for name, fn in routes:                            # warm every shape, then size the windows
@@ -120,6 +182,19 @@ def main():
             torch.cuda.synchronize()
             times[name].append(e0.elapsed_time(e1) / reps[name])
     med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    if a.loglik:
+        spread = {k: round((max(v) - min(v)) / med[k], 4) for k, v in times.items()}
+        out = dict(cfg, device=torch.cuda.get_device_name(0), windows=a.windows, evaluations_per_window=reps,
+                   ms_per_evaluation={k: [round(t, 3) for t in v] for k, v in times.items()}, median_ms={k: round(v, 3) for k, v in med.items()},
+                   spread=spread, loglik_cost=round(med['predict_loglik'] / med['predict_plain'] - 1, 4),
+                   loglik_vs_unfused=round(med['unfused_loglik'] / med['predict_loglik'], 3),
+                   figures={k: [float(x) for x in v] for k, v in last.items()})
+        if 'predict_plain_parent' in med:
+            out['plain_vs_parent'] = round(med['predict_plain'] / med['predict_plain_parent'] - 1, 4)
+            out['plain_vs_parent_allowed'] = max(spread['predict_plain'], spread['predict_plain_parent'])
+            out['plain_not_slower_than_parent'] = out['plain_vs_parent'] <= out['plain_vs_parent_allowed']
+        print(json.dumps(out))
+        return
     out = dict(cfg, device=torch.cuda.get_device_name(0), windows=a.windows, evaluations_per_window=reps,
                ms_per_evaluation={k: [round(t, 3) for t in v] for k, v in times.items()}, median_ms={k: round(v, 3) for k, v in med.items()},
                spread={k: round((max(v) - min(v)) / med[k], 4) for k, v in times.items()},

@@ -94,6 +94,7 @@ SIGNATURES.update({
     'gpode_bn_eval': (_i, [_c_float_p] * 6 + [_f, _c_float_p, _i, _i, _i, _i, _vp]),
     'gpode_bn_eval_table': (_i, [_c_float_p] * 4 + [_f, _c_float_p, _i, _vp]),
     'gpode_dec10_predict': (_i, [_c_float_p] * 5 + [_i] * 5 + [_c_float_p] * 3 + [_vp]),
+    'gpode_dec10_predict_ll': (_i, [_c_float_p] * 5 + [_i] * 5 + [_c_float_p] * 4 + [_i, _vp]),
     'gpode_chan_sum': (_i, [_c_float_p, _c_float_p, _i, _i, _i, _c_float_p, _vp]),
     'gpode_act_fwd': (_i, [_c_float_p, _c_float_p, _sz, _i, _vp]),
     'gpode_act_bwd': (_i, [_c_float_p, _c_float_p, _c_float_p, _sz, _i, _vp]),

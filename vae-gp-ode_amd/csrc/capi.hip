@@ -455,6 +455,11 @@ int gpode_dec10_predict(const float* c, const float* table, const float* w, cons
   if (!c || !table || !w || !X || !se_state) return gp::set_error("gpode_dec10_predict: null pointer");
   return gp::dec10_predict(c, table, w, bias, X, Lc, F, Th, T_obs, done, pred_mean, pred_m2, se_state, GP_ST);
 }
+int gpode_dec10_predict_ll(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th,
+                           int T_obs, int done, float* pred_mean, float* pred_m2, float* se_state, float* ell, int L_total, void* stream) {
+  if (!c || !table || !w || !X || !se_state) return gp::set_error("gpode_dec10_predict_ll: null pointer");
+  return gp::dec10_predict_ll(c, table, w, bias, X, Lc, F, Th, T_obs, done, pred_mean, pred_m2, se_state, ell, L_total, GP_ST);
+}
 int gpode_chan_sum(const float* v, float* out, int B, int C, int HW, float* scratch, void* stream) {
   if (!v || !out || !scratch) return gp::set_error("gpode_chan_sum: null pointer");
   return gp::chan_sum(v, out, B, C, HW, scratch, GP_ST);

@@ -120,16 +120,28 @@ __global__ __launch_bounds__(512) void k_fwd(const float* __restrict__ x, const 
 // Neither logits nor reconstructions are stored.  State in global memory between launches: pred_mean / pred_m2 [F][784] (both NULL:
 // error statistics only), se_state [F][3]; `done` = draws already folded in (0: the state is initialised here, not read).
 // grid <= min(F, CUs), block 512, LDS = 25 * PST + 16 floats.
+//
+// LL = true additionally leaves the Bernoulli log-likelihood of every image against its target (vae.py:136-153, the likelihood term of
+// create_model.py:52-53):
+//   ell[(done + l) F + f] = sum_p lp,   lp = x a - softplus(a),   softplus(a) = max(a, 0) + log1p(exp(-|a|)),
+// a = the pixel's logit, x = its target as it is.  With z = sigmoid(a): log z = a - softplus(a) and log(1 - z) = -softplus(a), so
+// lp = x log z + (1 - x) log(1 - z), the reference's expression, in exact arithmetic -- but finite for every finite logit, where the
+// reference's float32 form is -inf or nan once 1 - z rounds to 0 (a logit of about 17).  The sigmoid and everything behind it are
+// computed as in LL = false, from their own expression: se_state, pred_mean and pred_m2 are the same bits.  The wavefront's sum of lp
+// rides in the first wavefront reduction (two values wide instead of one), takes one more LDS slot per wavefront (s_r: 24 floats), and
+// the eight slots are added in wavefront order behind the second barrier.  Every entry of ell is written exactly once (0 for a frame
+// without a target) and depends on one image only.  LL = false is the kernel as it was: ell is not touched, LDS = 25 * PST + 16 floats.
 // ---------------------------------------------------------------------------------------------
 // pixels owned by the 64 threads of wavefront wv in the epilogue: 64 (o = tid) plus those of o = tid + 512 below 784
 __host__ __device__ constexpr int wave_pixels(int wv) { return 64 + (NP - 512 - 64 * wv > 64 ? 64 : (NP - 512 - 64 * wv > 0 ? NP - 512 - 64 * wv : 0)); }
 
+template <bool LL>
 __global__ __launch_bounds__(512) void k_fwd_predict(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                                                      const float* __restrict__ in_bn, const float* __restrict__ X, int Lc, int F, int Th,
                                                      int T_obs, int done, float* __restrict__ pred_mean, float* __restrict__ pred_m2,
-                                                     float* __restrict__ se_state) {
+                                                     float* __restrict__ se_state, float* __restrict__ ell) {
   float* s_T = igemm_smem;                           // [25][PST], zero borders
-  float* s_r = s_T + KK * PST;                       // [8][2] the wavefronts' {mean, M2} of the current image
+  float* s_r = s_T + KK * PST;                       // [8][2] the wavefronts' {mean, M2} of the current image; LL: + [8] their sums of lp
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lr = lane & 15, lk = lane >> 4;
   constexpr int MAXT = (NTILE + 7) / 8;
@@ -205,6 +217,7 @@ __global__ __launch_bounds__(512) void k_fwd_predict(const float* __restrict__ x
       __syncthreads();
       const float kinv = 1.f / (float)(done + l + 1);
       float ev[2] = {0.f, 0.f};
+      [[maybe_unused]] float lp[2] = {0.f, 0.f};
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         const int o = tid + 512 * q;
@@ -225,18 +238,29 @@ __global__ __launch_bounds__(512) void k_fwd_predict(const float* __restrict__ x
           pq[q] = __fmaf_rn(d, z - pm[q], pq[q]);
           const float df = z - xt[q];
           ev[q] = df * df;
+          if constexpr (LL) {
+            const float a = s0 + s1;
+            lp[q] = xt[q] * a - (fmaxf(a, 0.f) + log1pf(expf(-fabsf(a))));
+          }
         }
       }
       if (has_t) {
         // this wavefront's pixels: its mean, then M2 about that mean -- two wavefront reductions, no barrier in between
-        const float in1[1] = {ev[0] + ev[1]};
-        float out1[1];
-        wave_sum_multi<1>(in1, out1);
+        constexpr int NV = LL ? 2 : 1;                // LL: the sum of lp rides along (the error's sum is the same bits either way)
+        float in1[NV], out1[NV];
+        in1[0] = ev[0] + ev[1];
+        if constexpr (LL) in1[1] = lp[0] + lp[1];
+        wave_sum_multi<NV>(in1, out1);
+        [[maybe_unused]] const float wl = out1[NV - 1];
         const float mw = out1[0] * inv_nw;
         const float d0 = ev[0] - mw, d1 = two ? ev[1] - mw : 0.f;
         const float in2[1] = {__fmaf_rn(d0, d0, d1 * d1)};
-        wave_sum_multi<1>(in2, out1);
-        if (lane == 0) { s_r[2 * wave] = mw; s_r[2 * wave + 1] = out1[0]; }
+        float out2[1];
+        wave_sum_multi<1>(in2, out2);
+        if (lane == 0) {
+          s_r[2 * wave] = mw; s_r[2 * wave + 1] = out2[0];
+          if constexpr (LL) s_r[16 + wave] = wl;
+        }
       }
       __syncthreads();                               // s_T is free again; the wavefronts' {mean, M2} are visible
       if (has_t) {
@@ -254,6 +278,14 @@ __global__ __launch_bounds__(512) void k_fwd_predict(const float* __restrict__ x
         sq = sq + aq + dl * dl * (sn * rb);
         sm = __fmaf_rn(dl, rb, sm);
         sn = nn;
+      }
+      if constexpr (LL) {
+        float el = 0.f;
+        if (has_t) {
+#pragma unroll
+          for (int wv = 0; wv < 8; ++wv) el += s_r[16 + wv];
+        }
+        if (tid == 0) ell[(size_t)(done + l) * F + f] = el;
       }
     }
     if (pred_mean) {

@@ -193,6 +193,8 @@ int bn_eval_table(const float* gamma, const float* beta, const float* running_me
 // decnn.10 of a frozen decoder fused with the predictive statistics over the draws (vae_conv_tiled.hip)
 int dec10_predict(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th, int T_obs,
                   int done, float* pred_mean, float* pred_m2, float* se_state, hipStream_t st);
+int dec10_predict_ll(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th, int T_obs,
+                     int done, float* pred_mean, float* pred_m2, float* se_state, float* ell, int L_total, hipStream_t st);
 int chan_sum(const float* v, float* out, int B, int C, int HW, float* scratch, hipStream_t st);
 int act_fwd(const float* x, float* y, size_t n, int mode, hipStream_t st);
 int act_bwd(const float* y, const float* gy, float* gx, size_t n, int mode, hipStream_t st);

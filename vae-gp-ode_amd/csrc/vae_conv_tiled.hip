@@ -615,10 +615,29 @@ int dec10_predict(const float* c, const float* table, const float* w, const floa
   if ((pred_mean == nullptr) != (pred_m2 == nullptr)) return set_error("gpode_dec10_predict: pred_mean and pred_m2 go together");
   if (!aligned16(table)) return set_error("gpode_dec10_predict: the table must be 16-byte aligned");
   const size_t lds = sizeof(float) * (dec10::KK * dec10::PST + 16);
-  if (set_max_lds((const void*)dec10::k_fwd_predict, lds)) return 1;
-  hipLaunchKernelGGL(dec10::k_fwd_predict, F < num_cus() ? F : num_cus(), 512, lds, st, c, w, bias, table, X, Lc, F, Th, T_obs, done, pred_mean,
-                     pred_m2, se_state);
+  if (set_max_lds((const void*)dec10::k_fwd_predict<false>, lds)) return 1;
+  hipLaunchKernelGGL(dec10::k_fwd_predict<false>, F < num_cus() ? F : num_cus(), 512, lds, st, c, w, bias, table, X, Lc, F, Th, T_obs, done,
+                     pred_mean, pred_m2, se_state, (float*)nullptr);
   return check_launch("dec10_predict");
+}
+
+// the same stage, which also leaves the log-likelihood of every (draw, frame) image in ell[L_total][F] (k_fwd_predict<true>): rows
+// done .. done + Lc - 1 are written, every entry once.  Nothing is launched and nothing written when an argument is refused.
+int dec10_predict_ll(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th, int T_obs,
+                     int done, float* pred_mean, float* pred_m2, float* se_state, float* ell, int L_total, hipStream_t st) {
+  if (!use_mfma()) return set_error("gpode_dec10_predict_ll: matrix-core kernel only (GPODE_CONV_VALU is set)");
+  if (Lc < 1 || F < 1 || Th < 1 || T_obs < 1 || T_obs > Th || F % Th != 0 || done < 0)
+    return set_error("gpode_dec10_predict_ll: need Lc, F >= 1, 1 <= T_obs <= Th, F a multiple of Th, done >= 0");
+  if ((pred_mean == nullptr) != (pred_m2 == nullptr)) return set_error("gpode_dec10_predict_ll: pred_mean and pred_m2 go together");
+  if (!aligned16(table)) return set_error("gpode_dec10_predict_ll: the table must be 16-byte aligned");
+  if (ell == nullptr) return set_error("gpode_dec10_predict_ll: ell is NULL");
+  if (L_total < 1 || Lc > L_total || done > L_total - Lc)
+    return set_error("gpode_dec10_predict_ll: ell has L_total rows, need done + Lc <= L_total");
+  const size_t lds = sizeof(float) * (dec10::KK * dec10::PST + 24);
+  if (set_max_lds((const void*)dec10::k_fwd_predict<true>, lds)) return 1;
+  hipLaunchKernelGGL(dec10::k_fwd_predict<true>, F < num_cus() ? F : num_cus(), 512, lds, st, c, w, bias, table, X, Lc, F, Th, T_obs, done,
+                     pred_mean, pred_m2, se_state, ell);
+  return check_launch("dec10_predict_ll");
 }
 
 // decnn.10's input gradient fused with the backward of the BatchNorm + ReLU in front of it (conv_dec10_mfma.hpp, k_bwd_data_bn).

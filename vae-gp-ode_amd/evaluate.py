@@ -9,8 +9,15 @@ pixels happen in the registers of the convolution's epilogue, so neither the (L,
 element-wise temporary exists.  The kernel leaves one {count, mean, M2} triple per frame; they are combined here, on the host, in
 double precision and in a fixed order (``merge_states``) after one copy of 3 F floats.
 
+Held-out log-likelihood (``predict(..., loglik=True)``, ``compute_nll``): the model is trained on a Bernoulli likelihood
+(vae.py:136-153, create_model.py:52-53), so the same kernel epilogue -- as ``gpode_dec10_predict_ll`` -- also leaves the
+log-likelihood of every (draw, frame) image, computed from the logit as ``x a - softplus(a)`` (finite for every finite logit; the
+reference's ``log(z) x + log(1 - z) (1 - x)`` on a float32 sigmoid is -inf / nan from a logit of about 17).  The L F floats come back
+in one copy; the sums over time and the log-mean-exp over the draws are taken here in double precision (``loglik_stats``).
+
 Command line (``python -m vae_gp_ode_amd.evaluate``, the flags of ``vae_gp_ode_amd.main`` so a training command line can be
-reused): loads ``--model_path``, evaluates the test split with L = ``--eval_sample_size`` draws, rolls ``--Troll`` * T frames out for
+reused): loads ``--model_path``, evaluates the test split with L = ``--eval_sample_size`` draws (squared error and the held-out
+log-likelihood: ``mse``, ``std``, ``mse_t``, ``nll``, ``nlpd``, ``nll_t``), rolls ``--Troll`` * T frames out for
 the first three test sequences, prints one JSON line and writes ``eval.json``, ``rollout_mean.npy``, ``rollout_var.npy`` under
 ``--save``.  The draws come from the host generators as in the reference (two of them unseeded there, SURVEY F6, so two runs differ
 by Monte-Carlo noise); ``--device_noise True`` draws on the device, reproducibly from ``--seed``.  Single process: data-parallel
@@ -27,11 +34,31 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-Prediction = namedtuple('Prediction', 'mean var mse std count mse_t state passes')
+Prediction = namedtuple('Prediction', 'mean var mse std count mse_t state passes ll nll nlpd nll_t', defaults=(None,) * 4)
 Prediction.__doc__ = """mean, var (N,Th,1,28,28): predictive mean and unbiased variance of the decoded images over the L draws (None
 without ``variance``; var is nan for L = 1, as torch.var);  mse, std: mean and unbiased standard deviation of the squared error over
 all ``count`` = L N T_obs 784 elements;  mse_t (T_obs,): error per time step;  state: the (n, mean, M2) triple behind mse / std, for
-merging over batches;  passes: draws per decoder pass."""
+merging over batches;  passes: draws per decoder pass.  With ``loglik`` (None otherwise):  ll (L,N) float64 on the CPU: log-likelihood of
+every sequence under every draw;  nll: -mean of ll, the averaged negative log-likelihood (the likelihood term of the ELBO);  nlpd: the
+negative log predictive density -mean_n log mean_l exp ll[l,n];  nll_t (T_obs,): -mean over draws and sequences per time step."""
+
+
+def log_mean_exp(ll):
+    """log(mean_l exp(ll[l, ...])) over the first axis, in double precision: the maximum over the draws is subtracted first (a plain
+    exp underflows to 0 at ll of about -745, and a sequence's ll is in the thousands).  A fixed order of operations: the same input
+    gives the same bits."""
+    ll = torch.as_tensor(ll, dtype=torch.float64)
+    top = ll.max(dim=0).values
+    return top + torch.log(torch.exp(ll - top).sum(dim=0)) - math.log(ll.shape[0])
+
+
+def loglik_stats(ell, T_obs):
+    """(ll, nll, nlpd, nll_t) from the frame log-likelihoods ell (L,N,Th) (frames t >= T_obs hold 0 and are left out):
+    ll[l,n] = sum_{t < T_obs} ell[l,n,t];  nll = -mean_{l,n} ll;  nlpd = -mean_n (logsumexp_l ll[l,n] - log L);
+    nll_t[t] = -mean_{l,n} ell[l,n,t].  Double precision, a fixed order of operations."""
+    ell = torch.as_tensor(ell, dtype=torch.float64)[:, :, :T_obs]
+    ll = ell.sum(dim=2)
+    return ll, -ll.mean().item(), -log_mean_exp(ll).mean().item(), -ell.mean(dim=(0, 1))
 
 
 def merge_states(states):
@@ -91,14 +118,18 @@ class _EvalMode:
         return False
 
 
-def predict(model, X, L=1, T_custom=None, images_per_pass=8192, variance=True):
+def predict(model, X, L=1, T_custom=None, images_per_pass=8192, variance=True, loglik=False):
     """Posterior-predictive statistics of ``model`` (ODEGPVAE) for the sequences X (N,T,1,28,28): encode once, one z0 sample per
     sequence, L function draws shared by the batch, integrate ``T_custom or T`` steps, decode (positions only for order 2) --
     the order of operations of the notebook routine -- and reduce inside the decoder's last kernel.  Frames beyond T have no
     target: they enter the predictive mean / variance and not the error.  The draws go through the decoder in passes of at most
     ``images_per_pass`` images (8192: the largest image count the decoder's parity tests cover, not a tuned value).
     ``variance=False``: the error statistics only; the roll-out then stops at T, since the first T frames of a longer one are
-    the same trajectory.  Runs without autograd and in eval mode; leaves every module buffer and ``training`` flag as it found them."""
+    the same trajectory.  ``loglik=True`` also fills ``ll``, ``nll``, ``nlpd`` and ``nll_t`` of the result (Bernoulli log-likelihood of
+    the observed frames, from the logits); every other field is the same bits as without it.  One z0 sample per sequence is shared by
+    the L draws, so ``nlpd`` is the predictive density under the GP function draws GIVEN that sample of the initial state, not the
+    marginal over the encoder's distribution.  Runs without autograd and in eval mode; leaves every module buffer and ``training`` flag
+    as it found them."""
     from . import vae_ops as V
     if X.dim() != 5 or tuple(X.shape[2:]) != (1, 28, 28):
         raise ValueError('predict: X must be (N,T,1,28,28)')
@@ -118,7 +149,7 @@ def predict(model, X, L=1, T_custom=None, images_per_pass=8192, variance=True):
         ztL = model.sample_trajectories(z0, Th, L)                     # (L,N,Th,order*q)
         lat = ztL if model.order == 1 else ztL[..., :ztL.shape[-1] // 2]
         tables = dec._frozen_tables()
-        state = V.PredictState(F, X.device, variance)
+        state = V.PredictState(F, X.device, variance, loglik=L if loglik else 0)
         for l0, l1 in passes:
             c, t8 = dec.decode_frozen_raw(lat[l0:l1], tables)
             V.dec10_predict(c, t8, dec.decnn[10].weight, dec.decnn[10].bias, X, Th, state)
@@ -131,7 +162,10 @@ def predict(model, X, L=1, T_custom=None, images_per_pass=8192, variance=True):
     total = merge_states(se.reshape(-1, 3).tolist())
     mse, std = mean_std(total)
     mse_t = se[:, :, 1].mean(0)                                        # every frame holds the same count L * 784
-    return Prediction(mean, var, mse, std, int(total[0]), mse_t, total, [b - a for a, b in passes])
+    extra = ()
+    if loglik:
+        extra = loglik_stats(state.ell.cpu().double().view(L, N, Th), T)   # one copy of L F floats
+    return Prediction(mean, var, mse, std, int(total[0]), mse_t, total, [b - a for a, b in passes], *extra)
 
 
 def compute_mse_std(model, loader, L=1, images_per_pass=8192):
@@ -141,6 +175,23 @@ def compute_mse_std(model, loader, L=1, images_per_pass=8192):
     dev = next(model.parameters()).device
     states = [predict(model, _frames(batch).to(dev), L, images_per_pass=images_per_pass, variance=False).state for batch in loader]
     return mean_std(merge_states(states))
+
+
+def compute_nll(model, loader, L=1, images_per_pass=8192):
+    """(nll, nlpd) of the held-out log-likelihood over a whole loader with L draws per batch: the batches' figures are means over
+    their sequences, so they are weighted by the sequence counts -- the mean over all sequences, not over batches."""
+    from .main import _frames
+    dev = next(model.parameters()).device
+    nseq, nll, nlpd = 0, 0.0, 0.0
+    for batch in loader:
+        X = _frames(batch).to(dev)
+        p = predict(model, X, L, images_per_pass=images_per_pass, variance=False, loglik=True)
+        nseq += X.shape[0]
+        nll += p.nll * X.shape[0]
+        nlpd += p.nlpd * X.shape[0]
+    if nseq == 0:
+        return float('nan'), float('nan')
+    return nll / nseq, nlpd / nseq
 
 
 def build_from_checkpoint(args):
@@ -182,11 +233,16 @@ def main(argv=None):
     torch.cuda.synchronize()
     t0 = time.time()
     states, per_step, nseq, first = [], None, 0, None
+    nll = nlpd = 0.0
+    nll_step = None
     for batch in testset:
         Xb = _frames(batch).to(args.device)
         first = Xb if first is None else first
-        p = predict(model, Xb, L, variance=False)
+        p = predict(model, Xb, L, variance=False, loglik=True)
         states.append(p.state)
+        nll += p.nll * Xb.shape[0]
+        nlpd += p.nlpd * Xb.shape[0]
+        nll_step = p.nll_t * Xb.shape[0] if nll_step is None else nll_step + p.nll_t * Xb.shape[0]
         per_step = p.mse_t * Xb.shape[0] if per_step is None else per_step + p.mse_t * Xb.shape[0]
         nseq += Xb.shape[0]
     total = merge_states(states)
@@ -197,7 +253,7 @@ def main(argv=None):
     ms = (time.time() - t0) * 1e3
 
     os.makedirs(args.save, exist_ok=True)
-    out = dict(mse=mse, std=std, mse_t=(per_step / nseq).tolist(), L=L, sequences=nseq, T=T, count=int(total[0]),
+    out = dict(mse=mse, std=std, mse_t=(per_step / nseq).tolist(), nll=nll / nseq, nlpd=nlpd / nseq, nll_t=(nll_step / nseq).tolist(), L=L, sequences=nseq, T=T, count=int(total[0]),
                rollout_sequences=int(roll.mean.shape[0]), rollout_T=int(roll.mean.shape[1]), rollout_mse=roll.mse, ms=ms,
                checkpoint=os.path.abspath(fname), ranks=1)
     np.save(os.path.join(args.save, 'rollout_mean.npy'), roll.mean.cpu().numpy())

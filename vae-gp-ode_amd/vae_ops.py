@@ -988,10 +988,12 @@ def table_conv_transpose2d(c, table, w, b, stride, pad, out_pad=0):
 
 class PredictState:
     """State of gpode_dec10_predict for F = N * Th frames: Welford mean / M2 of the decoded images over the draws (``variance``),
-    {count, mean, M2} of the squared error per frame, and the number of draws folded in so far."""
+    {count, mean, M2} of the squared error per frame, and the number of draws folded in so far.  ``loglik`` = L > 0 adds ``ell`` (L, F),
+    the log-likelihood of every (draw, frame) image against its target (gpode_dec10_predict_ll), for L draws in all."""
 
-    def __init__(self, F, device, variance=True):
+    def __init__(self, F, device, variance=True, loglik=0):
         self.F, self.done = int(F), 0
+        self.ell = torch.zeros(int(loglik), F, dtype=torch.float32, device=device) if loglik > 0 else None
         self.mean = torch.zeros(F, 784, dtype=torch.float32, device=device) if variance else None
         self.m2 = torch.zeros(F, 784, dtype=torch.float32, device=device) if variance else None
         self.se = torch.zeros(F, 3, dtype=torch.float32, device=device)
@@ -1000,7 +1002,8 @@ class PredictState:
 def dec10_predict(c, table, w, b, X, Th, state):
     """Fold the draws held in ``c`` -- raw decnn.7 output (Lc * F, 16, 28, 28) laid out (draw, frame) -- into ``state``:
     sigmoid(decnn.10(relu(bn(c)))) is formed in registers and only its statistics against the targets X (N, T_obs, 1, 28, 28) leave
-    the kernel (frames t >= T_obs of a sequence have no target and add nothing to the error)."""
+    the kernel (frames t >= T_obs of a sequence have no target and add nothing to the error).  A state with ``ell`` takes
+    gpode_dec10_predict_ll, which also writes the rows of ``ell`` of these draws; a state without it takes gpode_dec10_predict."""
     c, w, table, X = _chk(c.detach(), 'c'), _chk(w.detach(), 'weight'), _chk(table, 'table'), _chk(X, 'X')
     F = state.F
     N, T_obs = X.shape[0], X.shape[1]
@@ -1009,6 +1012,14 @@ def dec10_predict(c, table, w, b, X, Th, state):
     if tuple(X.shape[2:]) != (1, 28, 28) or F != N * Th or c.shape[0] % F != 0 or c.shape[0] == 0:
         raise _lib.GpodeError('dec10_predict: X (N,T_obs,1,28,28), F = N * Th frames, c a whole number of draws of F frames')
     Lc = c.shape[0] // F
+    ell = getattr(state, 'ell', None)
+    if ell is not None:
+        if ell.dim() != 2 or ell.shape[1] != F or ell.dtype != torch.float32 or not ell.is_contiguous():
+            raise _lib.GpodeError('gpode_dec10_predict_ll: ell must be a contiguous float32 (L_total, F) tensor')
+        _lib.call('gpode_dec10_predict_ll', _ptr(c), _ptr(table), _ptr(w), _ptr(None if b is None else _chk(b.detach(), 'bias')), _ptr(X),
+                  Lc, F, int(Th), T_obs, state.done, _ptr(state.mean), _ptr(state.m2), _ptr(state.se), _ptr(ell), ell.shape[0], _stream())
+        state.done += Lc
+        return state
     _lib.call('gpode_dec10_predict', _ptr(c), _ptr(table), _ptr(w), _ptr(None if b is None else _chk(b.detach(), 'bias')), _ptr(X),
               Lc, F, int(Th), T_obs, state.done, _ptr(state.mean), _ptr(state.m2), _ptr(state.se), _stream())
     state.done += Lc
