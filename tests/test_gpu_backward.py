@@ -3,14 +3,12 @@ reference's autograd results (golden) and the oracle's fp64 autograd on the same
 
 Tolerance: |hip - ref| <= 5e-4 + 3 |ref - fp64 twin| relative to max|ref| (gradients pass through the same
 ill-conditioned nu as the forward; see tests/test_gpu_forward.py)."""
-import math
-
 import pytest
 import torch
 
 from conftest import load_golden, sub
 from oracle import gpode_oracle as O
-from pack_layout import PackView
+from pack_layout import PackView, leaf_grads
 from test_gpu_forward import GP_CASES, build, relerr
 
 pytestmark = pytest.mark.gpu
@@ -64,38 +62,16 @@ def test_param_grads_in_pack_layout(name, kernel, order):
         assert relerr(view(gp2), view(gp)) < 2e-5
     tw = oracle_leaf_grads(g, kernel, order, method)
     c64 = tw['cache']
-    rff, ind, uni = pv.rff(gp), pv.ind(gp), pv.uni(gp)
-    Di, Do, S = c.Di, c.Do, c.S
-    var, ell, nu = c64['var'], c64['ell'], c64['nu']
+    got = leaf_grads(pv, gp, c64)
     tol = 2e-3
-    if kernel == 'RBF':
-        g_omega = rff[:, :, :Di].permute(2, 0, 1) / (2 * math.pi)           # (Di,S,Do)
-        assert relerr(g_omega, tw['omega']) < tol
-        aw = torch.sqrt(var / S) * c64['w']                                  # (S,Do)
-        g_var = (rff[:, :, Di + 1] * aw / (2 * var)).sum(0) + (ind[:, Di:Di + Do] * nu.squeeze(2).T).sum(0)
-        assert relerr(g_var, tw['var']) < tol
-        assert relerr(ind[:, :Di], tw['Z']) < tol
-        assert relerr((ind[:, Di:Di + Do] * var).T.unsqueeze(2), tw['nu']) < tol
-        g_ell = uni.view(Do, Di) * math.log2(math.e) / ell ** 3
-        assert relerr(g_ell, tw['ell']) < tol
-    else:
-        D = Do
-        # rff record (s,i): fields [om_k (D), ph, wc, ws, bs_j (D)]
-        g_omega = rff[:, :, :D].permute(2, 0, 1) / (2 * math.pi)             # [k, s, i]
-        assert relerr(g_omega, tw['omega']) < tol
-        sc = torch.sqrt(var / S)                                             # per column j
-        g_B = rff[:, :, D + 3:2 * D + 3] * sc                                # (S, i, j)
-        ref_B = tw['B'][:S] + tw['B'][S:]                                    # cos and sin halves share B
-        assert relerr(g_B, ref_B) < tol
-        assert relerr(ind[:, :D], tw['Z']) < tol
-        assert relerr(ind[:, D:2 * D].reshape(-1, 1), tw['nu']) < tol
-        wab, il2, gvar = uni[:D * D].view(D, D), uni[D * D:2 * D * D].view(D, D), uni[2 * D * D:]
-        # wab = -log2e/(2 l^2), il2 = 1/l^2
-        g_ell = wab * math.log2(math.e) / ell ** 3 + il2 * (-2.0) / ell ** 3
-        assert relerr(g_ell, tw['ell']) < tol
-        bs = O.df_B_omega(c64['omega'])[:S] * sc
-        g_var = gvar + (rff[:, :, D + 3:2 * D + 3] * bs / (2 * var)).sum((0, 1))
-        assert relerr(g_var, tw['var']) < tol
+    assert relerr(got['omega'], tw['omega']) < tol
+    if kernel == 'DF':
+        ref_B = tw['B'][:c.S] + tw['B'][c.S:]                                # cos and sin halves share B
+        assert relerr(got['B'], ref_B) < tol
+    assert relerr(got['var'], tw['var']) < tol
+    assert relerr(got['Z'], tw['Z']) < tol
+    assert relerr(got['nu'], tw['nu']) < tol
+    assert relerr(got['ell'], tw['ell']) < tol
 
 
 def make_layer(g, kernel, order, method):

@@ -136,8 +136,9 @@ def test_bitwise_reproducible(name, kernel, order):
                                                ('gp_df1_tiny_q4', 'DF', 1), ('gp_rbf1_tiny', 'RBF', 1)])
 def test_wave_and_team_mappings_agree(name, kernel, order):
     """Batches > 2048 rows take the one-wave-per-trajectory kernels, smaller ones the 4-wave team kernels.
-    Same cache, same rows: the two mappings must agree to summation-order round-off, and a grid-stride
-    pass (more rows than workgroups) must equal the chunked evaluation."""
+    Same cache, same rows: the two mappings must agree to summation-order round-off.  (At 2600 rows only the divergence-free
+    LDS kernel, 256 workgroups, is on its grid-stride: the RBF wave launch has 650 workgroups of 4 wavefronts, one row each, and a second
+    row per wavefront needs more than 8192 rows -- tests/test_gpu_integrator_routes.py runs those.)"""
     from vae_gp_ode_amd import ops
     g = load_golden(name)
     c = build(g, kernel, want_Lu=False)

@@ -847,8 +847,11 @@ int param_grad(int kernel, int Di, int Do, int M, int S, const float* pack, cons
   }
   if (rc < 0) return set_error("gpode_param_grad: no specialisation for kernel=%d Di=%d Do=%d", kernel, Di, Do);
   if (rc) return rc;
+  const char* route = *last_launch_slot();           // which parameter-sum kernel ran: what the entry point reports (tests/integrator_routes.py)
   hipLaunchKernelGGL(reduce_slab_kernel, dim3((unsigned)((pf + 63) / 64), dw.nd), 1024, 0, st, slab, used, pf, gpack, accumulate, dw.out, nchunk);
-  return check_launch("reduce_slab");
+  if (check_launch("reduce_slab")) return 1;
+  *last_launch_slot() = route;
+  return 0;
 }
 
 }  // namespace gp

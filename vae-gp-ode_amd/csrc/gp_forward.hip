@@ -208,17 +208,17 @@ static int launch_rhs_rbf(const float* pack, int M, int S, const float* x, int N
   if constexpr (rbf_reg_fits<DI, DO, 4, 2>()) {
     if (SJ == 4 && MJ == 2) {
       hipLaunchKernelGGL((rhs_kernel<RbfRegEval<DI, DO, 4, 2>, DI, DO, false>), dim3(grid, dw.nd), block, 0, st, pack, M, S, (size_t)0, x, N, f, mode, dw);
-      return check_launch("rhs_rbf");
+      return check_launch("rhs_rbf_reg42");
     }
   }
   if constexpr (rbf_reg_fits<DI, DO, 1, 1>()) {
     if (SJ == 1 && MJ == 1) {
       hipLaunchKernelGGL((rhs_kernel<RbfRegEval<DI, DO, 1, 1>, DI, DO, false>), dim3(grid, dw.nd), block, 0, st, pack, M, S, (size_t)0, x, N, f, mode, dw);
-      return check_launch("rhs_rbf");
+      return check_launch("rhs_rbf_reg11");
     }
   }
   hipLaunchKernelGGL((rhs_kernel<RbfStreamEval<DI, DO>, DI, DO, false>), dim3(grid, dw.nd), block, 0, st, pack, M, S, (size_t)0, x, N, f, mode, dw);
-  return check_launch("rhs_rbf");
+  return check_launch("rhs_rbf_stream");
 }
 
 template <int D>
@@ -237,16 +237,16 @@ static int launch_rhs_df(const float* pack, int M, int S, const float* x, int N,
     hipLaunchKernelGGL((rhs_team_kernel<DfStreamTeam<D>, D, D>), dim3(team_grid(N), dw.nd), 256, 0, st, pack, M, S, x, N, f, mode, dw);
     return check_launch("rhs_df_team_stream");
   }
-  // one evaluation per row: staging the pack in LDS only pays when a workgroup evaluates many rows
-  if (f4 * 16 <= kLdsLimitBytes && N >= 2048) {
+  // N > kTeamMaxRows from here on: a workgroup evaluates many rows, so staging the pack in LDS pays whenever it fits
+  if (f4 * 16 <= kLdsLimitBytes) {
     block = 256; grid = 256;
     auto kern = rhs_kernel<DfEval<D, true>, D, D, true>;
     if (set_max_lds((const void*)kern, f4 * 16)) return 1;
     hipLaunchKernelGGL(kern, dim3(grid, dw.nd), block, f4 * 16, st, pack, M, S, f4, x, N, f, mode, dw);
-  } else {
-    hipLaunchKernelGGL((rhs_kernel<DfEval<D, false>, D, D, false>), dim3(grid, dw.nd), block, 0, st, pack, M, S, (size_t)0, x, N, f, mode, dw);
+    return check_launch("rhs_df_lds");
   }
-  return check_launch("rhs_df");
+  hipLaunchKernelGGL((rhs_kernel<DfEval<D, false>, D, D, false>), dim3(grid, dw.nd), block, 0, st, pack, M, S, (size_t)0, x, N, f, mode, dw);
+  return check_launch("rhs_df_stream");
 }
 
 template <int DI, int DO, int ORDER, int METHOD>
@@ -267,17 +267,17 @@ static int launch_rollout_rbf(const float* pack, int M, int S, const float* z0, 
   if constexpr (rbf_reg_fits<DI, DO, 4, 2>()) {
     if (SJ == 4 && MJ == 2) {
       hipLaunchKernelGGL((rollout_kernel<RbfRegEval<DI, DO, 4, 2>, DI, DO, ORDER, METHOD, false>), dim3(grid, dw.nd), block, 0, st, pack, M, S, (size_t)0, z0, ts, N, T, zt, xstage, dw);
-      return check_launch("rollout_rbf");
+      return check_launch("rollout_rbf_reg42");
     }
   }
   if constexpr (rbf_reg_fits<DI, DO, 1, 1>()) {
     if (SJ == 1 && MJ == 1) {
       hipLaunchKernelGGL((rollout_kernel<RbfRegEval<DI, DO, 1, 1>, DI, DO, ORDER, METHOD, false>), dim3(grid, dw.nd), block, 0, st, pack, M, S, (size_t)0, z0, ts, N, T, zt, xstage, dw);
-      return check_launch("rollout_rbf");
+      return check_launch("rollout_rbf_reg11");
     }
   }
   hipLaunchKernelGGL((rollout_kernel<RbfStreamEval<DI, DO>, DI, DO, ORDER, METHOD, false>), dim3(grid, dw.nd), block, 0, st, pack, M, S, (size_t)0, z0, ts, N, T, zt, xstage, dw);
-  return check_launch("rollout_rbf");
+  return check_launch("rollout_rbf_stream");
 }
 
 template <int D, int METHOD>
@@ -296,16 +296,15 @@ static int launch_rollout_df(const float* pack, int M, int S, const float* z0, c
     hipLaunchKernelGGL((rollout_team_kernel<DfStreamTeam<D>, D, D, 1, METHOD>), dim3(team_grid(N), dw.nd), 256, 0, st, pack, M, S, z0, ts, N, T, zt, xstage, dw);
     return check_launch("rollout_df_team_stream");
   }
-  if (f4 * 16 <= kLdsLimitBytes) {
-    if (N <= 1024) { block = 64; grid = N < 256 ? N : 256; }
-    else { block = 256; grid = 256; }
+  if (f4 * 16 <= kLdsLimitBytes) {                 // N > kTeamMaxRows here
+    block = 256; grid = 256;
     auto kern = rollout_kernel<DfEval<D, true>, D, D, 1, METHOD, true>;
     if (set_max_lds((const void*)kern, f4 * 16)) return 1;
     hipLaunchKernelGGL(kern, dim3(grid, dw.nd), block, f4 * 16, st, pack, M, S, f4, z0, ts, N, T, zt, xstage, dw);
-  } else {
-    hipLaunchKernelGGL((rollout_kernel<DfEval<D, false>, D, D, 1, METHOD, false>), dim3(grid, dw.nd), block, 0, st, pack, M, S, (size_t)0, z0, ts, N, T, zt, xstage, dw);
+    return check_launch("rollout_df_lds");
   }
-  return check_launch("rollout_df");
+  hipLaunchKernelGGL((rollout_kernel<DfEval<D, false>, D, D, 1, METHOD, false>), dim3(grid, dw.nd), block, 0, st, pack, M, S, (size_t)0, z0, ts, N, T, zt, xstage, dw);
+  return check_launch("rollout_df_stream");
 }
 
 
