@@ -175,6 +175,22 @@ int gpode_rollout_dense_fwd_n(int kernel, int order, int method, int Di, int Do,
 int gpode_rollout_dense_bwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                               const float* pack, const float* xstage, const float* hstep, const int* istep, const float* theta,
                               const float* gzt, int N, int T, int K, float* gz0, float* astage, void* stream);
+/* The batched rollouts with an initial state PER DRAW (the joint samples (z0_l, f_l) of the importance-weighted marginal
+ * likelihood, evaluate.predict_marginal): the arguments of the `_n` twin plus `z0_per_draw`, in front of `stream`.
+ *   z0_per_draw = 0   z0 is (N,D), shared by all draws: the same launch, the same bits as the `_n` entry point
+ *   z0_per_draw = 1   z0 is (ndraws,N,D), dense: draw l starts from slab l
+ * Any other value is refused before anything is launched.  The reverse sweeps are the `_n` ones: gz0 is (L,N,D) already, and is
+ * the gradient of the per-draw z0 as it stands (not summed over the draws). */
+int gpode_rollout_fwd_nz(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                         const float* pack, const float* z0, const float* ts, int N, int T,
+                         float* zt, float* xstage, int z0_per_draw, void* stream);
+int gpode_rollout_adaptive_fwd_nz(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                                  const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
+                                  float* zt, float* xstage, float* hstep, int* iend, int* counts, int z0_per_draw, void* stream);
+int gpode_rollout_dense_fwd_nz(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                               const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
+                               float* zt, float* xstage, float* hstep, int* istep, float* theta, int* counts, int z0_per_draw,
+                               void* stream);
 /* gpode_rollout_bwd_n and gpode_param_grad_n in ONE pass: the reverse sweep visits every (stage input, adjoint) row anyway, so the
  * rows' parameter-gradient terms are accumulated on the way and come out as gpack (ndraws, pack_floats) -- what the two calls
  * produce together, with one launch and one pass over the rows less.  slab: ndraws * nchunk * pack_floats floats of scratch with
@@ -484,6 +500,15 @@ int gpode_elbo_all_bwd_ll_kl(const float* g_loss, const float* g_nll, const floa
                              const float* Um, const float* Us, float nobs, float* glrow, float* gkls, int nks, float* gklv, int nkv,
                              float* dUm, float* dUs, const float* X, const float* z, float* ga, size_t n_logits, size_t nX, void* stream);
 int gpode_reparam_fwd(const float* mu, const float* logvar, int ld, const float* eps, float* z, int N, int q, void* stream);
+/* L reparameterised draws of one encoder distribution and their importance log-weights (forward only; evaluation):
+ *   z[l,n,i]  = mu[n,i] + exp(logvar[n,i] / 2) eps[l,n,i]   -- the bits gpode_reparam_fwd gives for (mu, logvar, eps[l]) --
+ *               written at z + (l N + n) ldz + i: ldz >= q, so the caller can point z at one half of an order-2 state
+ *   lw[l,n] (+)= sum_i (eps^2 / 2 - z^2 / 2 + logvar / 2) = log N(z; 0, I) - log N(z; mu, sigma^2)   (the 2 pi terms cancel)
+ * mu, logvar (N,q) with row stride ld; eps (L,N,q) dense; lw (L,N).  accumulate = 0 writes lw, 1 adds to it (the velocity
+ * encoder's half of an order-2 state).  One lane per (l,n) row sums i = 0 .. q-1 in that order: no atomics, the same bits
+ * every run. */
+int gpode_reparam_draws_fwd(const float* mu, const float* logvar, int ld, const float* eps, float* z, int ldz, float* lw,
+                            int accumulate, int L, int N, int q, void* stream);
 int gpode_reparam_bwd(const float* gz, const float* logvar, int ld, const float* eps, float* gmu, float* glogvar, int ldg, int N, int q,
                       void* stream);
 int gpode_normal_kl_fwd(const float* mu, const float* logvar, int ld, float* klrow, int N, int q, void* stream);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Posterior-predictive evaluation, the route that existed before against evaluate.predict, on one GPU.
 
-    python tools/eval_bench.py [--L 128] [--N 40] [--T 16] [--Troll 1] [--windows 5] [--min_window_s 1.0] [--loglik [--parent_lib SO]]
+    python tools/eval_bench.py [--L 128] [--N 40] [--T 16] [--Troll 1] [--windows 5] [--min_window_s 1.0] [--loglik | --z0_draws [--parent_lib SO]]
 
   baseline  model.eval(); model(X, Lc[, T_custom]) per pass of at most --images_per_pass images, then torch's var_mean of the squared
             error per pass, merged at the end (the only route before evaluate.py; in passes so that both fit the same memory)
@@ -22,6 +22,14 @@ fails.
                         build's, the same process and the same windows), to show that the plain route did not move
 It reports, with no target set, `loglik_cost` = predict_loglik / predict_plain - 1 beside the window spreads, and -- the condition --
 `plain_vs_parent` = predict_plain / predict_plain_parent - 1, which must not exceed the larger of the two spreads.
+
+--z0_draws measures the marginal likelihood route (an initial state per draw), the same alternating windows:
+  predict_loglik        evaluate.predict(variance=False, loglik=True)          -- one z0 sample shared by the L draws
+  predict_marginal      evaluate.predict_marginal                               -- L z0 samples and their log-weights in one launch, the rollout
+                        reading its own z0 per draw; the same trajectory count and decoder work
+  predict_plain, predict_plain_parent   as under --loglik (the second with --parent_lib): the route that existed must not have moved
+It reports, with no target set, `marginal_cost` = predict_marginal / predict_loglik - 1 beside the window spreads, and `plain_vs_parent` with
+its condition as under --loglik.
 
 `--dry` only parses, plans the passes and prints the byte counts (a rehearsal, no timing).
 """
@@ -77,7 +85,14 @@ def loglik_routes(a, model, X, passes, Tc):
         ll = torch.cat(lls).double().cpu()
         return mean_std(merge_states([(n, m.item(), v.item() * n) for n, v, m in parts])) + (-ll.mean().item(), -log_mean_exp(ll).mean().item())
 
+    def marginal():
+        from vae_gp_ode_amd.evaluate import predict_marginal
+        p = predict_marginal(model, X, a.L, images_per_pass=a.images_per_pass)
+        return p.mse, p.std, p.nll, p.nlpd, p.iw_nll, float(p.ess.mean())
+
     routes = [('predict_plain', plain), ('predict_loglik', loglik), ('unfused_loglik', unfused)]
+    if a.z0_draws:
+        routes = [('predict_plain', plain), ('predict_loglik', loglik), ('predict_marginal', marginal)]
     if a.parent_lib:
         this, parent = _lib.load(), ctypes.CDLL(os.path.abspath(a.parent_lib))
         for name, (res, args) in _lib.SIGNATURES.items():
@@ -106,6 +121,7 @@ def main():
     ap.add_argument('--seed', type=int, default=121)
     ap.add_argument('--dry', action='store_true')
     ap.add_argument('--loglik', action='store_true')
+    ap.add_argument('--z0_draws', action='store_true')
     ap.add_argument('--parent_lib', default=None)
     a = ap.parse_args()
     from vae_gp_ode_amd.evaluate import plan_passes
@@ -158,7 +174,9 @@ def main():
         return p.mse, p.std
 
     routes = [('baseline', baseline), ('predict_stats', new_stats), ('predict_full', new_full)]
-    if a.loglik:
+    if a.z0_draws and Tc is not None:
+        raise SystemExit('--z0_draws: predict_marginal has no forecast frames, use --Troll 1')
+    if a.loglik or a.z0_draws:
         routes = loglik_routes(a, model, X, passes, Tc)
     last, reps = {}, {}
     ev = lambda: torch.cuda.Event(enable_timing=True)
@@ -182,13 +200,16 @@ def main():
             torch.cuda.synchronize()
             times[name].append(e0.elapsed_time(e1) / reps[name])
     med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
-    if a.loglik:
+    if a.loglik or a.z0_draws:
         spread = {k: round((max(v) - min(v)) / med[k], 4) for k, v in times.items()}
         out = dict(cfg, device=torch.cuda.get_device_name(0), windows=a.windows, evaluations_per_window=reps,
                    ms_per_evaluation={k: [round(t, 3) for t in v] for k, v in times.items()}, median_ms={k: round(v, 3) for k, v in med.items()},
                    spread=spread, loglik_cost=round(med['predict_loglik'] / med['predict_plain'] - 1, 4),
-                   loglik_vs_unfused=round(med['unfused_loglik'] / med['predict_loglik'], 3),
                    figures={k: [float(x) for x in v] for k, v in last.items()})
+        if a.z0_draws:
+            out['marginal_cost'] = round(med['predict_marginal'] / med['predict_loglik'] - 1, 4)
+        else:
+            out['loglik_vs_unfused'] = round(med['unfused_loglik'] / med['predict_loglik'], 3)
         if 'predict_plain_parent' in med:
             out['plain_vs_parent'] = round(med['predict_plain'] / med['predict_plain_parent'] - 1, 4)
             out['plain_vs_parent_allowed'] = max(spread['predict_plain'], spread['predict_plain_parent'])

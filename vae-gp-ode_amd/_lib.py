@@ -47,6 +47,10 @@ SIGNATURES = {
     'gpode_rollout_adaptive_bwd_n': (_i, [_i] * 8 + [_c_float_p] * 5 + [_i, _i, _i, _c_float_p, _c_float_p, ctypes.c_void_p]),
     'gpode_rollout_dense_fwd_n': (_i, [_i] * 8 + [_c_float_p] * 3 + [_i, _i, ctypes.c_float, ctypes.c_float, _i] + [_c_float_p] * 6 + [ctypes.c_void_p]),
     'gpode_rollout_dense_bwd_n': (_i, [_i] * 8 + [_c_float_p] * 6 + [_i, _i, _i, _c_float_p, _c_float_p, ctypes.c_void_p]),
+    # ... with an initial state per draw: the `_n` arguments plus `z0_per_draw` in front of the stream
+    'gpode_rollout_fwd_nz': (_i, [_i] * 8 + [_c_float_p, _c_float_p, _c_float_p, _i, _i, _c_float_p, _c_float_p, _i, ctypes.c_void_p]),
+    'gpode_rollout_adaptive_fwd_nz': (_i, [_i] * 8 + [_c_float_p] * 3 + [_i, _i, ctypes.c_float, ctypes.c_float, _i] + [_c_float_p] * 5 + [_i, ctypes.c_void_p]),
+    'gpode_rollout_dense_fwd_nz': (_i, [_i] * 8 + [_c_float_p] * 3 + [_i, _i, ctypes.c_float, ctypes.c_float, _i] + [_c_float_p] * 6 + [_i, ctypes.c_void_p]),
     'gpode_rollout_bwd_pgrad_chunks': (_i, [_i] * 8),
     'gpode_rollout_bwd_pgrad_n': (_i, [_i] * 8 + [_c_float_p] * 4 + [_i, _i, _c_float_p, _c_float_p, _c_float_p, _i, _c_float_p, ctypes.c_void_p]),
     'gpode_param_grad_n': (_i, [_i] * 6 + [_c_float_p, _c_float_p, _c_float_p, _i, _c_float_p, _i, _c_float_p, _i, ctypes.c_void_p]),
@@ -112,6 +116,7 @@ SIGNATURES.update({
     'gpode_elbo_all_fwd_kl': (_i, [_c_float_p, _i, _i, _c_float_p, _i, _c_float_p, _i, _i, _i, _i, _c_float_p, _c_float_p, _f, _c_float_p, _vp]),
     'gpode_elbo_all_bwd_ll_kl': (_i, [_c_float_p] * 4 + [_i, _i, _i, _i, _c_float_p, _c_float_p, _f, _c_float_p, _c_float_p, _i, _c_float_p, _i] + [_c_float_p] * 5 + [_sz, _sz, _vp]),
     'gpode_reparam_fwd': (_i, [_c_float_p, _c_float_p, _i, _c_float_p, _c_float_p, _i, _i, _vp]),
+    'gpode_reparam_draws_fwd': (_i, [_c_float_p, _c_float_p, _i, _c_float_p, _c_float_p, _i, _c_float_p, _i, _i, _i, _i, _vp]),
     'gpode_reparam_bwd': (_i, [_c_float_p, _c_float_p, _i, _c_float_p, _c_float_p, _c_float_p, _i, _i, _i, _vp]),
     'gpode_normal_kl_fwd': (_i, [_c_float_p, _c_float_p, _i, _c_float_p, _i, _i, _vp]),
     'gpode_normal_kl_bwd': (_i, [_c_float_p, _c_float_p, _c_float_p, _i, _c_float_p, _c_float_p, _i, _i, _i, _vp]),

@@ -88,16 +88,30 @@ static gp::Draws draws_of(int nd, size_t pack, size_t in, size_t out, size_t in2
 }
 static int stage_count(int method) { return method == 0 ? 1 : (method == 1 ? 4 : 2); }
 
-int gpode_rollout_fwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
-                        const float* pack, const float* z0, const float* ts, int N, int T,
-                        float* zt, float* xstage, void* stream) {
-  if (N < 0 || T < 1 || ndraws < 1 || ndraws > 65535) return gp::set_error("gpode_rollout_fwd: N=%d T=%d draws=%d", N, T, ndraws);
+// `who`: the entry point's name in the messages; z0_per_draw: 0 = z0 (N,D) shared by the draws, 1 = (ndraws,N,D)
+static int rollout_fwd_any(const char* who, int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                           const float* pack, const float* z0, const float* ts, int N, int T,
+                           float* zt, float* xstage, int z0_per_draw, void* stream) {
+  if (z0_per_draw != 0 && z0_per_draw != 1) return gp::set_error("%s: z0_per_draw=%d (0 shared, 1 one (N,D) slab per draw)", who, z0_per_draw);
+  if (N < 0 || T < 1 || ndraws < 1 || ndraws > 65535) return gp::set_error("%s: N=%d T=%d draws=%d", who, N, T, ndraws);
   if (N == 0) return 0;
-  if (!pack || !z0 || !ts || !zt) return gp::set_error("gpode_rollout_fwd: null pointer");
+  if (!pack || !z0 || !ts || !zt) return gp::set_error("%s: null pointer", who);
   size_t pf = 0;
   if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
   return gp::rollout_fwd(kernel, order, method, Di, Do, M, S, pack, z0, ts, N, T, zt, xstage, (hipStream_t)stream,
-                         draws_of(ndraws, pf, 0, (size_t)N * T * Di, 0, (size_t)N * (T - 1) * stage_count(method) * Di));
+                         draws_of(ndraws, pf, z0_per_draw ? (size_t)N * Di : 0, (size_t)N * T * Di, 0,
+                                  (size_t)N * (T - 1) * stage_count(method) * Di));
+}
+int gpode_rollout_fwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                        const float* pack, const float* z0, const float* ts, int N, int T,
+                        float* zt, float* xstage, void* stream) {
+  return rollout_fwd_any("gpode_rollout_fwd", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, zt, xstage, 0, stream);
+}
+int gpode_rollout_fwd_nz(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                         const float* pack, const float* z0, const float* ts, int N, int T,
+                         float* zt, float* xstage, int z0_per_draw, void* stream) {
+  return rollout_fwd_any("gpode_rollout_fwd_nz", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, zt, xstage, z0_per_draw,
+                         stream);
 }
 int gpode_rollout_fwd(int kernel, int order, int method, int Di, int Do, int M, int S,
                       const float* pack, const float* z0, const float* ts, int N, int T,
@@ -137,21 +151,34 @@ int gpode_rollout_bwd(int kernel, int order, int method, int Di, int Do, int M, 
   return gpode_rollout_bwd_n(kernel, order, method, Di, Do, M, S, 1, pack, xstage, gzt, ts, N, T, gz0, astage, stream);
 }
 
-int gpode_rollout_adaptive_fwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
-                                 const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
-                                 float* zt, float* xstage, float* hstep, int* iend, int* counts, void* stream) {
-  if (method != GPODE_METHOD_DOPRI5) return gp::set_error("gpode_rollout_adaptive_fwd: method %d (3 dopri5)", method);
+static int rollout_adaptive_fwd_any(const char* who, int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                                    const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
+                                    float* zt, float* xstage, float* hstep, int* iend, int* counts, int z0_per_draw, void* stream) {
+  if (z0_per_draw != 0 && z0_per_draw != 1) return gp::set_error("%s: z0_per_draw=%d (0 shared, 1 one (N,D) slab per draw)", who, z0_per_draw);
+  if (method != GPODE_METHOD_DOPRI5) return gp::set_error("%s: method %d (3 dopri5)", who, method);
   if (N < 0 || T < 1 || K < 0 || ndraws < 1 || ndraws > 65535)
-    return gp::set_error("gpode_rollout_adaptive_fwd: N=%d T=%d K=%d draws=%d", N, T, K, ndraws);
+    return gp::set_error("%s: N=%d T=%d K=%d draws=%d", who, N, T, K, ndraws);
   if (!(rtol >= 0.f) || !(atol >= 0.f) || !(rtol + atol > 0.f) || !(rtol + atol < 1e30f))
-    return gp::set_error("gpode_rollout_adaptive_fwd: rtol=%g atol=%g (both >= 0, not both 0)", rtol, atol);
+    return gp::set_error("%s: rtol=%g atol=%g (both >= 0, not both 0)", who, rtol, atol);
   if (N == 0) return 0;
-  if (!pack || !z0 || !ts || !zt || !counts) return gp::set_error("gpode_rollout_adaptive_fwd: null pointer");
-  if (xstage && T > 1 && (!iend || (K > 0 && !hstep))) return gp::set_error("gpode_rollout_adaptive_fwd: xstage without hstep / iend");
+  if (!pack || !z0 || !ts || !zt || !counts) return gp::set_error("%s: null pointer", who);
+  if (xstage && T > 1 && (!iend || (K > 0 && !hstep))) return gp::set_error("%s: xstage without hstep / iend", who);
   size_t pf = 0;
   if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
   return gp::rollout_adaptive_fwd(kernel, order, Di, Do, M, S, ndraws, pack, pf, z0, ts, N, T, rtol, atol, K, zt, xstage, hstep, iend,
-                                  counts, (hipStream_t)stream);
+                                  counts, (hipStream_t)stream, z0_per_draw ? (size_t)N * Di : 0);
+}
+int gpode_rollout_adaptive_fwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                                 const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
+                                 float* zt, float* xstage, float* hstep, int* iend, int* counts, void* stream) {
+  return rollout_adaptive_fwd_any("gpode_rollout_adaptive_fwd", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol, atol,
+                                  K, zt, xstage, hstep, iend, counts, 0, stream);
+}
+int gpode_rollout_adaptive_fwd_nz(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                                  const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
+                                  float* zt, float* xstage, float* hstep, int* iend, int* counts, int z0_per_draw, void* stream) {
+  return rollout_adaptive_fwd_any("gpode_rollout_adaptive_fwd_nz", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol,
+                                  atol, K, zt, xstage, hstep, iend, counts, z0_per_draw, stream);
 }
 int gpode_rollout_adaptive_bwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                                  const float* pack, const float* xstage, const float* hstep, const int* iend, const float* gzt,
@@ -168,22 +195,37 @@ int gpode_rollout_adaptive_bwd_n(int kernel, int order, int method, int Di, int 
                                   (hipStream_t)stream);
 }
 
-int gpode_rollout_dense_fwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
-                              const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
-                              float* zt, float* xstage, float* hstep, int* istep, float* theta, int* counts, void* stream) {
-  if (method != GPODE_METHOD_DOPRI5) return gp::set_error("gpode_rollout_dense_fwd: method %d (3 dopri5)", method);
+static int rollout_dense_fwd_any(const char* who, int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                                 const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
+                                 float* zt, float* xstage, float* hstep, int* istep, float* theta, int* counts, int z0_per_draw,
+                                 void* stream) {
+  if (z0_per_draw != 0 && z0_per_draw != 1) return gp::set_error("%s: z0_per_draw=%d (0 shared, 1 one (N,D) slab per draw)", who, z0_per_draw);
+  if (method != GPODE_METHOD_DOPRI5) return gp::set_error("%s: method %d (3 dopri5)", who, method);
   if (N < 0 || T < 1 || K < 0 || ndraws < 1 || ndraws > 65535)
-    return gp::set_error("gpode_rollout_dense_fwd: N=%d T=%d K=%d draws=%d", N, T, K, ndraws);
+    return gp::set_error("%s: N=%d T=%d K=%d draws=%d", who, N, T, K, ndraws);
   if (!(rtol >= 0.f) || !(atol >= 0.f) || !(rtol + atol > 0.f) || !(rtol + atol < 1e30f))
-    return gp::set_error("gpode_rollout_dense_fwd: rtol=%g atol=%g (both >= 0, not both 0)", rtol, atol);
+    return gp::set_error("%s: rtol=%g atol=%g (both >= 0, not both 0)", who, rtol, atol);
   if (N == 0) return 0;
-  if (!pack || !z0 || !ts || !zt || !counts) return gp::set_error("gpode_rollout_dense_fwd: null pointer");
+  if (!pack || !z0 || !ts || !zt || !counts) return gp::set_error("%s: null pointer", who);
   if (xstage && T > 1 && (!istep || !theta || (K > 0 && !hstep)))
-    return gp::set_error("gpode_rollout_dense_fwd: xstage without hstep / istep / theta");
+    return gp::set_error("%s: xstage without hstep / istep / theta", who);
   size_t pf = 0;
   if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
   return gp::rollout_dense_fwd(kernel, order, Di, Do, M, S, ndraws, pack, pf, z0, ts, N, T, rtol, atol, K, zt, xstage, hstep, istep, theta,
-                               counts, (hipStream_t)stream);
+                               counts, (hipStream_t)stream, z0_per_draw ? (size_t)N * Di : 0);
+}
+int gpode_rollout_dense_fwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                              const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
+                              float* zt, float* xstage, float* hstep, int* istep, float* theta, int* counts, void* stream) {
+  return rollout_dense_fwd_any("gpode_rollout_dense_fwd", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol, atol, K, zt,
+                               xstage, hstep, istep, theta, counts, 0, stream);
+}
+int gpode_rollout_dense_fwd_nz(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                               const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
+                               float* zt, float* xstage, float* hstep, int* istep, float* theta, int* counts, int z0_per_draw,
+                               void* stream) {
+  return rollout_dense_fwd_any("gpode_rollout_dense_fwd_nz", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol, atol, K,
+                               zt, xstage, hstep, istep, theta, counts, z0_per_draw, stream);
 }
 int gpode_rollout_dense_bwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                               const float* pack, const float* xstage, const float* hstep, const int* istep, const float* theta,
@@ -532,6 +574,14 @@ int gpode_reparam_fwd(const float* mu, const float* logvar, int ld, const float*
   if (N == 0) return 0;
   if (!mu || !logvar || !eps || !z || q < 1 || ld < q) return gp::set_error("gpode_reparam_fwd: bad argument");
   return gp::reparam_fwd(mu, logvar, ld, eps, z, N, q, GP_ST);
+}
+int gpode_reparam_draws_fwd(const float* mu, const float* logvar, int ld, const float* eps, float* z, int ldz, float* lw, int accumulate,
+                            int L, int N, int q, void* stream) {
+  if (L < 0 || N < 0 || q < 1 || q > 16 || ld < q || ldz < q || (accumulate != 0 && accumulate != 1) || (long long)L * N > 0x7fffffffLL / 16)
+    return gp::set_error("gpode_reparam_draws_fwd: bad argument (L=%d N=%d q=%d ld=%d ldz=%d accumulate=%d; q <= 16)", L, N, q, ld, ldz, accumulate);
+  if (L == 0 || N == 0) return 0;
+  if (!mu || !logvar || !eps || !z || !lw) return gp::set_error("gpode_reparam_draws_fwd: null pointer");
+  return gp::reparam_draws_fwd(mu, logvar, ld, eps, z, ldz, lw, accumulate, L, N, q, GP_ST);
 }
 int gpode_reparam_bwd(const float* gz, const float* logvar, int ld, const float* eps, float* gmu, float* glogvar, int ldg, int N, int q,
                       void* stream) {

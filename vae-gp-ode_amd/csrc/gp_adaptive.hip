@@ -74,10 +74,12 @@ struct AdaptBwd {
   const float* xstage; const float* hstep; const int* iend; const float* gzt; int N, T, K;
   float* gz0; float* astage;
 };
-// the dense mode's kernels take one pointer more; the landing kernels keep their argument block (and with it their machine code)
-struct AdaptFwdDense : AdaptFwd { float* theta; };
+// What the kernels take.  z0_stride: floats between the draws' initial states, 0 = one (N,D) block shared by all draws; it is the
+// LAST member of either block, so every other argument stays where it was.  The dense mode's kernels take one pointer more.
+struct AdaptFwdLand : AdaptFwd { size_t z0_stride; };
+struct AdaptFwdDense : AdaptFwd { float* theta; size_t z0_stride; };
 struct AdaptBwdDense : AdaptBwd { const float* theta; };
-template <bool DENSE> using AdaptFwdArg = std::conditional_t<DENSE, AdaptFwdDense, AdaptFwd>;
+template <bool DENSE> using AdaptFwdArg = std::conditional_t<DENSE, AdaptFwdDense, AdaptFwdLand>;
 template <bool DENSE> using AdaptBwdArg = std::conditional_t<DENSE, AdaptBwdDense, AdaptBwd>;
 
 // a value every lane holds identically -> a scalar: the controller's branches are then scalar branches, the same in every
@@ -256,10 +258,12 @@ __device__ __forceinline__ void dopri5_trajectory(EV& ev, const AdaptFwd& a, con
   }
 }
 
-// blockIdx.y = Monte-Carlo draw: its own pack, the shared initial states, its own trajectories and record
+// blockIdx.y = Monte-Carlo draw: its own pack, the shared initial states (z0_stride = 0) or its own slab of them, its own
+// trajectories and record.  Every offset is a scalar: blockIdx.y is.
 #define GP_ADAPT_DRAW_POINTERS                                                                                   \
   const size_t dr = blockIdx.y, NT = (size_t)a.N;                                                                \
   const float* pack = a.pack + dr * a.pack_stride;                                                               \
+  const float* z0 = a.z0 + dr * a.z0_stride;                                                                     \
   float* zt = a.zt + dr * NT * a.T * DI;                                                                         \
   float* xstage = a.xstage ? a.xstage + dr * NT * a.K * (DENSE ? NDEN : NREC) * DI : nullptr;                    \
   float* hstep = a.xstage ? a.hstep + dr * NT * a.K : nullptr;                                                   \
@@ -280,7 +284,7 @@ __global__ __launch_bounds__(256) void rollout_adaptive_kernel(AdaptFwdArg<DENSE
   EV ev;
   ev.init(pack, a.M, a.S, lane);
   for (int n = blockIdx.x * wpb + wave; n < a.N; n += gridDim.x * wpb)
-    dopri5_trajectory<EV, DI, DO, ORDER, DENSE>(ev, a, a.z0, zt, xstage, hstep, iend, theta, counts, n, kst[wave], true, lane);
+    dopri5_trajectory<EV, DI, DO, ORDER, DENSE>(ev, a, z0, zt, xstage, hstep, iend, theta, counts, n, kst[wave], true, lane);
 }
 
 // One workgroup per trajectory.  Every evaluation carries the team's barrier, so the four wavefronts must take the same steps:
@@ -295,7 +299,7 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rollout_adaptive_team_kernel(A
   EV ev;
   ev.init(pack, a.M, a.S, slots, wave, lane);
   for (int n = blockIdx.x; n < a.N; n += gridDim.x)
-    dopri5_trajectory<EV, DI, DO, ORDER, DENSE>(ev, a, a.z0, zt, xstage, hstep, iend, theta, counts, n, kst[wave], wave == 0, lane);
+    dopri5_trajectory<EV, DI, DO, ORDER, DENSE>(ev, a, z0, zt, xstage, hstep, iend, theta, counts, n, kst[wave], wave == 0, lane);
 }
 
 // Reverse sweep: the adjoint of an explicit Runge-Kutta step, over the recorded accepted steps, step sizes constant.
@@ -565,15 +569,15 @@ static int adaptive_fwd(int kernel, int order, int Di, int Do, const AdaptFwdArg
 
 int rollout_adaptive_fwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
                          const float* z0, const float* ts, int N, int T, float rtol, float atol, int K, float* zt, float* xstage,
-                         float* hstep, int* iend, int* counts, hipStream_t st) {
-  const AdaptFwd a{pack, pack_stride, M, S, z0, ts, N, T, K, rtol, atol, zt, xstage, hstep, iend, counts};
+                         float* hstep, int* iend, int* counts, hipStream_t st, size_t z0_stride) {
+  const AdaptFwdLand a{{pack, pack_stride, M, S, z0, ts, N, T, K, rtol, atol, zt, xstage, hstep, iend, counts}, z0_stride};
   return adaptive_fwd<false>(kernel, order, Di, Do, a, nd, st);
 }
 
 int rollout_dense_fwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
                       const float* z0, const float* ts, int N, int T, float rtol, float atol, int K, float* zt, float* xstage,
-                      float* hstep, int* istep, float* theta, int* counts, hipStream_t st) {
-  const AdaptFwdDense a{{pack, pack_stride, M, S, z0, ts, N, T, K, rtol, atol, zt, xstage, hstep, istep, counts}, theta};
+                      float* hstep, int* istep, float* theta, int* counts, hipStream_t st, size_t z0_stride) {
+  const AdaptFwdDense a{{pack, pack_stride, M, S, z0, ts, N, T, K, rtol, atol, zt, xstage, hstep, istep, counts}, theta, z0_stride};
   return adaptive_fwd<true>(kernel, order, Di, Do, a, nd, st);
 }
 

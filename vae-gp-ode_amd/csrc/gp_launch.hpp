@@ -90,17 +90,18 @@ int rollout_bwd_pgrad_chunks(int kernel, int order, int method, int Di, int Do, 
 int rollout_bwd_pgrad(int kernel, int order, int method, int Di, int Do, int M, int S, const float* pack, const float* xstage,
                       const float* gzt, const float* ts, int N, int T, float* gz0, float* astage, float* slab, int nchunk,
                       float* gpack, hipStream_t st, Draws dw = Draws{});
-// adaptive Dormand-Prince rollout and its reverse sweep (gp_adaptive.hip); every per-draw operand is dense, `pack_stride` apart
+// adaptive Dormand-Prince rollout and its reverse sweep (gp_adaptive.hip); every per-draw operand is dense, `pack_stride` apart;
+// z0_stride: floats between the draws' initial states, 0 = shared by all draws
 int rollout_adaptive_fwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
                          const float* z0, const float* ts, int N, int T, float rtol, float atol, int K, float* zt, float* xstage,
-                         float* hstep, int* iend, int* counts, hipStream_t st);
+                         float* hstep, int* iend, int* counts, hipStream_t st, size_t z0_stride = 0);
 int rollout_adaptive_bwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
                          const float* xstage, const float* hstep, const int* iend, const float* gzt, int N, int T, int K,
                          float* gz0, float* astage, hipStream_t st);
 // the same in dense-output mode: steps cut at ts[T-1] only, interior outputs interpolated (record: 7 rows per step, istep, theta)
 int rollout_dense_fwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
                       const float* z0, const float* ts, int N, int T, float rtol, float atol, int K, float* zt, float* xstage,
-                      float* hstep, int* istep, float* theta, int* counts, hipStream_t st);
+                      float* hstep, int* istep, float* theta, int* counts, hipStream_t st, size_t z0_stride = 0);
 int rollout_dense_bwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
                       const float* xstage, const float* hstep, const int* istep, const float* theta, const float* gzt, int N, int T,
                       int K, float* gz0, float* astage, hipStream_t st);
@@ -219,6 +220,8 @@ int elbo_all_bwd_ll_kl(const float* g0, const float* g1, const float* g2, const 
                        const float* Us, float nobs, float* glrow, float* gkls, int nks, float* gklv, int nkv, float* dUm, float* dUs,
                        const float* X, const float* z, float* ga, size_t n, size_t nX, hipStream_t st);
 int reparam_fwd(const float* mu, const float* logvar, int ld, const float* eps, float* z, int N, int q, hipStream_t st);
+int reparam_draws_fwd(const float* mu, const float* logvar, int ld, const float* eps, float* z, int ldz, float* lw, int accumulate, int L, int N,
+                      int q, hipStream_t st);
 int reparam_bwd(const float* gz, const float* logvar, int ld, const float* eps, float* gmu, float* glogvar, int ldg, int N, int q, hipStream_t st);
 int normal_kl_fwd(const float* mu, const float* logvar, int ld, float* klrow, int N, int q, hipStream_t st);
 int normal_kl_bwd(const float* grow, const float* mu, const float* logvar, int ld, float* gmu, float* glogvar, int ldg, int N, int q, hipStream_t st);

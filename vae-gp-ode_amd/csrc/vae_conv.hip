@@ -555,6 +555,28 @@ __global__ void k_reparam_fwd(const float* __restrict__ mu, const float* __restr
   const int n = e / q, d = e % q;
   z[e] = mu[(size_t)n * ld + d] + expf(0.5f * logvar[(size_t)n * ld + d]) * eps[e];
 }
+// L draws of one (mu, logvar) and their importance log-weights log p(z) - log q(z | x) (evaluate.predict_marginal).  One lane per
+// (draw, sample) row: q <= 16 terms summed serially in the order of the latent dimension -- a fixed order, no atomics.  z is the
+// expression of k_reparam_fwd, so it contracts to the same fma and gives the same bits.  Rows of z are ldz apart.
+__global__ __launch_bounds__(256) void k_reparam_draws_fwd(const float* __restrict__ mu, const float* __restrict__ logvar, int ld,
+                                                            const float* __restrict__ eps, float* __restrict__ z, int ldz,
+                                                            float* __restrict__ lw, int accumulate, int rows, int N, int q) {
+  const int r = blockIdx.x * 256 + threadIdx.x;      // r = l N + n
+  if (r >= rows) return;
+  const int n = r % N;
+  const float* m = mu + (size_t)n * ld;
+  const float* lv = logvar + (size_t)n * ld;
+  const float* e = eps + (size_t)r * q;
+  float* zr = z + (size_t)r * ldz;
+  float acc = 0.f;
+  for (int d = 0; d < q; ++d) {
+    const float ed = e[d], lvd = lv[d];
+    const float zd = m[d] + expf(0.5f * lvd) * ed;
+    zr[d] = zd;
+    acc += 0.5f * (ed * ed) - 0.5f * (zd * zd) + 0.5f * lvd;
+  }
+  lw[r] = accumulate ? lw[r] + acc : acc;
+}
 __global__ void k_reparam_bwd(const float* __restrict__ gz, const float* __restrict__ logvar, int ld, const float* __restrict__ eps,
                               float* __restrict__ gmu, float* __restrict__ glogvar, int ldg, int N, int q) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -963,6 +985,12 @@ int elbo_all_bwd_ll_kl(const float* g0, const float* g1, const float* g2, const 
 int reparam_fwd(const float* mu, const float* logvar, int ld, const float* eps, float* z, int N, int q, hipStream_t st) {
   hipLaunchKernelGGL(k_reparam_fwd, (N * q + 255) / 256, 256, 0, st, mu, logvar, ld, eps, z, N, q);
   return check_launch("reparam_fwd");
+}
+int reparam_draws_fwd(const float* mu, const float* logvar, int ld, const float* eps, float* z, int ldz, float* lw, int accumulate, int L, int N,
+                      int q, hipStream_t st) {
+  const int rows = L * N;
+  hipLaunchKernelGGL(k_reparam_draws_fwd, (rows + 255) / 256, 256, 0, st, mu, logvar, ld, eps, z, ldz, lw, accumulate, rows, N, q);
+  return check_launch("reparam_draws_fwd");
 }
 int reparam_bwd(const float* gz, const float* logvar, int ld, const float* eps, float* gmu, float* glogvar, int ldg, int N, int q,
                 hipStream_t st) {

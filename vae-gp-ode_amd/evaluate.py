@@ -15,12 +15,19 @@ log-likelihood of every (draw, frame) image, computed from the logit as ``x a - 
 reference's ``log(z) x + log(1 - z) (1 - x)`` on a float32 sigmoid is -inf / nan from a logit of about 17).  The L F floats come back
 in one copy; the sums over time and the log-mean-exp over the draws are taken here in double precision (``loglik_stats``).
 
+Marginal likelihood (``predict_marginal``, ``compute_iw_nll``, ``--eval_z0_draws True``): ``predict`` shares one sample of the initial
+state among its L function draws.  ``predict_marginal`` draws L JOINT samples (z0_l ~ q(z0 | x), f_l ~ q(f)) -- one launch for the L
+reparameterised initial states and their log-weights lw = log p(z0) - log q(z0 | x) (``gpode_reparam_draws_fwd``), one rollout launch
+in which every draw starts from its own z0 (the ``_nz`` entry points) -- and reports the importance-weighted estimate
+log p(x) ~ log (1/L) sum_l p(x | z0_l, f_l) p(z0_l) / q(z0_l | x) (``iw_stats``) with its effective sample size.
+
 Command line (``python -m vae_gp_ode_amd.evaluate``, the flags of ``vae_gp_ode_amd.main`` so a training command line can be
 reused): loads ``--model_path``, evaluates the test split with L = ``--eval_sample_size`` draws (squared error and the held-out
 log-likelihood: ``mse``, ``std``, ``mse_t``, ``nll``, ``nlpd``, ``nll_t``), rolls ``--Troll`` * T frames out for
 the first three test sequences, prints one JSON line and writes ``eval.json``, ``rollout_mean.npy``, ``rollout_var.npy`` under
 ``--save``.  The draws come from the host generators as in the reference (two of them unseeded there, SURVEY F6, so two runs differ
-by Monte-Carlo noise); ``--device_noise True`` draws on the device, reproducibly from ``--seed``.  Single process: data-parallel
+by Monte-Carlo noise); ``--device_noise True`` draws on the device, reproducibly from ``--seed``.  ``--eval_z0_draws True`` adds a second pass over the test split
+with a z0 sample per draw and reports ``iw_nll``, ``nlpd_marginal``, ``ess_mean``, ``ess_min``; every other figure is unchanged.  Single process: data-parallel
 evaluation is not built.  No plots.
 """
 import json
@@ -41,6 +48,27 @@ all ``count`` = L N T_obs 784 elements;  mse_t (T_obs,): error per time step;  s
 merging over batches;  passes: draws per decoder pass.  With ``loglik`` (None otherwise):  ll (L,N) float64 on the CPU: log-likelihood of
 every sequence under every draw;  nll: -mean of ll, the averaged negative log-likelihood (the likelihood term of the ELBO);  nlpd: the
 negative log predictive density -mean_n log mean_l exp ll[l,n];  nll_t (T_obs,): -mean over draws and sequences per time step."""
+
+
+MarginalPrediction = namedtuple('MarginalPrediction', 'll lw nll nlpd iw_ll iw_nll ess nll_t mse std state passes')
+MarginalPrediction.__doc__ = """ll (L,N) float64 on the CPU: log p(x_n | z0_l, f_l) of every sequence under every JOINT draw of the initial state
+and the function;  lw (L,N) float64: log p(z0_l) - log q(z0_l | x_n);  nll: -mean of ll;  nlpd: -mean_n log mean_l exp ll[l,n], the
+predictive density with the initial state marginalised under q(z0 | x) (not under the prior);  iw_ll (N,), iw_nll: the
+importance-weighted estimate of log p(x_n) and minus its mean over the sequences;  ess (N,): effective sample size of the L weights,
+in [1, L];  nll_t (T,);  mse, std, state, passes: as in Prediction, over the same joint draws."""
+
+
+def iw_stats(ll, lw):
+    """(iw_ll, iw_nll, ess) of the importance-weighted marginal likelihood from ll, lw (L,N):
+    iw_ll[n] = log mean_l exp(ll[l,n] + lw[l,n]);  iw_nll = -mean_n iw_ll;  ess[n] = (sum_l w)^2 / sum_l w^2 with
+    w = exp(ll + lw - max_l(ll + lw)) -- the maximum cancels in the ratio.  Double precision on the CPU, the maximum subtracted as in
+    log_mean_exp, a fixed order of operations: the same input gives the same bits."""
+    a = torch.as_tensor(ll, dtype=torch.float64).cpu() + torch.as_tensor(lw, dtype=torch.float64).cpu()
+    top = a.max(dim=0).values
+    w = torch.exp(a - top)
+    s1, s2 = w.sum(dim=0), (w * w).sum(dim=0)
+    iw_ll = top + torch.log(s1) - math.log(a.shape[0])
+    return iw_ll, -iw_ll.mean().item(), s1 * s1 / s2
 
 
 def log_mean_exp(ll):
@@ -168,6 +196,58 @@ def predict(model, X, L=1, T_custom=None, images_per_pass=8192, variance=True, l
     return Prediction(mean, var, mse, std, int(total[0]), mse_t, total, [b - a for a, b in passes], *extra)
 
 
+def predict_marginal(model, X, L, images_per_pass=8192):
+    """``predict(variance=False, loglik=True)`` with the initial state sampled PER DRAW: ``encode_initial_state(X, draws=L)`` gives
+    z0 (L,N,order*q) and the log-weights lw (L,N), draw l integrates from z0[l] under function draw l (one rollout launch over L N
+    trajectories), and the decoder passes and the fused last kernel are predict's.  -> MarginalPrediction.  Runs without autograd and
+    in eval mode; leaves every module buffer and ``training`` flag as it found them."""
+    from . import vae_ops as V
+    if X.dim() != 5 or tuple(X.shape[2:]) != (1, 28, 28):
+        raise ValueError('predict_marginal: X must be (N,T,1,28,28)')
+    N, T = X.shape[0], X.shape[1]
+    L = int(L)
+    F = N * T
+    passes = plan_passes(L, F, int(images_per_pass))
+    dec = model.vae.decoder
+    with torch.no_grad(), _EvalMode(model):
+        X = X.contiguous().float()
+        z0, lw, _, _ = model.encode_initial_state(X, draws=L)          # (L,N,order*q), (L,N)
+        ztL = model.sample_trajectories(z0, T, L)                      # (L,N,T,order*q)
+        lat = ztL if model.order == 1 else ztL[..., :ztL.shape[-1] // 2]
+        tables = dec._frozen_tables()
+        state = V.PredictState(F, X.device, False, loglik=L)
+        for l0, l1 in passes:
+            c, t8 = dec.decode_frozen_raw(lat[l0:l1], tables)
+            V.dec10_predict(c, t8, dec.decnn[10].weight, dec.decnn[10].bias, X, T, state)
+            del c
+        se = state.se.double().cpu().view(N, T, 3)
+        ell = state.ell.cpu().double().view(L, N, T)
+        lw = lw.cpu().double()
+    total = merge_states(se.reshape(-1, 3).tolist())
+    mse, std = mean_std(total)
+    ll, nll, nlpd, nll_t = loglik_stats(ell, T)
+    iw_ll, iw_nll, ess = iw_stats(ll, lw)
+    return MarginalPrediction(ll, lw, nll, nlpd, iw_ll, iw_nll, ess, nll_t, mse, std, total, [b - a for a, b in passes])
+
+
+def compute_iw_nll(model, loader, L, images_per_pass=8192):
+    """(iw_nll, nlpd, mean ess) over a whole loader with L joint draws per batch (predict_marginal): means over all sequences, the
+    batches weighted by their sequence counts."""
+    from .main import _frames
+    dev = next(model.parameters()).device
+    nseq, iw, nlpd, ess = 0, 0.0, 0.0, 0.0
+    for batch in loader:
+        X = _frames(batch).to(dev)
+        p = predict_marginal(model, X, L, images_per_pass=images_per_pass)
+        nseq += X.shape[0]
+        iw += p.iw_nll * X.shape[0]
+        nlpd += p.nlpd * X.shape[0]
+        ess += p.ess.sum().item()
+    if nseq == 0:
+        return float('nan'), float('nan'), float('nan')
+    return iw / nseq, nlpd / nseq, ess / nseq
+
+
 def compute_mse_std(model, loader, L=1, images_per_pass=8192):
     """(mse, std) of the squared reconstruction error over a whole loader with L draws per batch -- ``compute_mse_std`` of the
     evaluation notebook: the batches' (n, mean, M2) triples are merged, so the result is the mean / std over all elements."""
@@ -219,8 +299,19 @@ def build_from_checkpoint(args):
     return model, testset, fname
 
 
+def make_parser():
+    """The training command line (``vae_gp_ode_amd.main.make_parser``, whose flag list is the reference's) plus what only the
+    evaluation reads."""
+    from .main import make_parser as train_parser
+    p = train_parser()
+    p.add_argument('--eval_z0_draws', type=eval, default=False,
+                   help='also report the importance-weighted marginal likelihood: a second pass over the test split in which every one of '
+                        'the --eval_sample_size draws samples its own initial state (iw_nll, nlpd_marginal, ess_mean, ess_min)')
+    return p
+
+
 def main(argv=None):
-    from .main import _frames, make_parser
+    from .main import _frames
     args = make_parser().parse_args(argv)
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
         raise SystemExit('vae_gp_ode_amd.evaluate is a single-process tool: data-parallel evaluation is not built '
@@ -249,6 +340,17 @@ def main(argv=None):
     mse, std = mean_std(total)
     T = first.shape[1]
     roll = predict(model, first[:3].contiguous(), L, T_custom=args.Troll * T)
+    marginal = None
+    if args.eval_z0_draws:                           # behind everything else: the figures above see the draws they see without it
+        iw = nlpd_m = ess_sum = 0.0
+        ess_min = float('inf')
+        for batch in testset:
+            pm = predict_marginal(model, _frames(batch).to(args.device), L)
+            iw += pm.iw_nll * pm.ll.shape[1]
+            nlpd_m += pm.nlpd * pm.ll.shape[1]
+            ess_sum += pm.ess.sum().item()
+            ess_min = min(ess_min, pm.ess.min().item())
+        marginal = dict(iw_nll=iw / nseq, nlpd_marginal=nlpd_m / nseq, ess_mean=ess_sum / nseq, ess_min=ess_min)
     torch.cuda.synchronize()
     ms = (time.time() - t0) * 1e3
 
@@ -256,6 +358,8 @@ def main(argv=None):
     out = dict(mse=mse, std=std, mse_t=(per_step / nseq).tolist(), nll=nll / nseq, nlpd=nlpd / nseq, nll_t=(nll_step / nseq).tolist(), L=L, sequences=nseq, T=T, count=int(total[0]),
                rollout_sequences=int(roll.mean.shape[0]), rollout_T=int(roll.mean.shape[1]), rollout_mse=roll.mse, ms=ms,
                checkpoint=os.path.abspath(fname), ranks=1)
+    if marginal is not None:
+        out.update(marginal)
     np.save(os.path.join(args.save, 'rollout_mean.npy'), roll.mean.cpu().numpy())
     np.save(os.path.join(args.save, 'rollout_var.npy'), roll.var.cpu().numpy())
     with open(os.path.join(args.save, 'eval.json'), 'w') as f:

@@ -106,7 +106,7 @@ class Flow(nn.Module):
     def forward(self, z0, ts, draws=None):
         """z0 (N,D), ts (T,) -> zt (N,T,D) for a fresh function draw (flow.py:68-86).  ``draws`` = L: L fresh draws integrated in
         one pass -> (L,N,T,D), the stack ODEGPVAE.sample_trajectories builds from L calls (odegpvae.py:41-44); ``_num_evals`` ends
-        at the count of ONE solve, as it does after the reference's last call.
+        at the count of ONE solve, as it does after the reference's last call.  z0 (L,N,D): draw l starts from z0[l].
         'dopri5': a trajectory that exhausts ``max_steps`` or whose step underflows is NaN from the output it missed (status in
         ``last_counts``); the others are unaffected."""
         try:

@@ -20,18 +20,21 @@ class ODEGPVAE(nn.Module):
         return (self.vae.decoder(lat, logits=True) if logits else self.vae.decoder(lat)).view([L, N, T, nc, d, d])
 
     def sample_trajectories(self, z0, T, L=1):
-        """L independent function draws, each shared by the whole minibatch (odegpvae.py:37-45)."""
+        """L independent function draws, each shared by the whole minibatch (odegpvae.py:37-45).  z0 (L,N,D): draw l starts from
+        its own sample z0[l] of the initial states (encode_initial_state(X, draws=L))."""
+        if z0.dim() == 3 and z0.shape[0] != L:
+            raise ValueError('sample_trajectories: z0 holds initial states for %d draws, L = %d' % (z0.shape[0], L))
         key = (T, str(z0.device))
         if getattr(self, '_ts_key', None) != key:            # the grid dt * arange(T) is a constant of the run: build it once
             self._ts, self._ts_key = self.dt * torch.arange(T, dtype=torch.float, device=z0.device), key
         ts = self._ts
         if L == 1:
-            return self.flow(z0, ts).unsqueeze(0)
+            return self.flow(z0[0] if z0.dim() == 3 else z0, ts).unsqueeze(0)
         field = self.flow.odefunc.diffeq
         if getattr(field, 'batched_draws_supported', lambda: False)():
             # the L draws in ONE pass: K_uu factored once, one rollout launch over L * N trajectories, one reverse sweep
             return self.flow(z0, ts, draws=L)
-        return torch.stack([self.flow(z0, ts) for _ in range(L)], 0)
+        return torch.stack([self.flow(z0[l] if z0.dim() == 3 else z0, ts) for l in range(L)], 0)
 
     def _pair_encoders(self):
         from ... import vae_ops
@@ -39,10 +42,24 @@ class ODEGPVAE(nn.Module):
         return (vae_ops.pack_bn_gathers() and enc.training and vel.training and
                 all(m.training for m in (enc.cnn[1], enc.cnn[4], vel.cnn[1], vel.cnn[4])))
 
-    def encode_initial_state(self, X):
+    def encode_initial_state(self, X, draws=None):
         """q(z0 | X): position code from the first frame, velocity code (order 2) from the first ``v_steps`` frames stacked as
-        channels; returns the reparameterised sample and the (mean, log-variance) pairs the ELBO needs (odegpvae.py:55-63)."""
+        channels; returns the reparameterised sample and the (mean, log-variance) pairs the ELBO needs (odegpvae.py:55-63).
+        ``draws`` = L (evaluation; forward only): L samples per sequence instead of one, z0 (L,N,order*q), and their importance
+        log-weights lw (L,N) = log p(z0) - log q(z0 | X) under the standard-normal prior -> (z0, lw, code_s, code_v)."""
         pos = self.vae.encoder
+        if draws is not None:
+            L = int(draws)
+            mu_s, logv_s = pos(X[:, 0])
+            N, q = mu_s.shape
+            z0 = torch.empty((L, N, self.order * q), dtype=torch.float32, device=mu_s.device)
+            _, lw = pos.sample_draws(mu_s, logv_s, L, out=z0, col=0)
+            if self.order == 1:
+                return z0, lw, (mu_s, logv_s), (None, None)
+            vel = self.vae.encoder_v
+            mu_v, logv_v = vel(X[:, 0:self.v_steps].squeeze(2))   # the frames as channels; a batch of one sequence keeps its axis
+            vel.sample_draws(mu_v, logv_v, L, out=z0, col=q, lw=lw)
+            return z0, lw, (mu_s, logv_s), (mu_v, logv_v)
         if self.order == 2 and self._pair_encoders():
             # data parallelism with global-minibatch BatchNorm: the two encoders run in lockstep and share their statistics exchanges
             vel = self.vae.encoder_v

@@ -77,6 +77,20 @@ class Encoder(nn.Module):
         self.next_eps = None
         return V.reparam(mu, logvar, eps.to(mu))     # mu + exp(logvar / 2) * eps, one launch
 
+    def sample_draws(self, mu, logvar, L, out=None, col=0, lw=None):
+        """L reparameterised draws and their importance log-weights log p(z) - log q(z | x), one launch (V.reparam_draws):
+        -> (z (L,N,q), lw (L,N)).  ``next_eps`` (L,N,q), if set, replaces the N(0,1) draw once.  ``out`` (L,N,W) / ``col``: z goes
+        into columns col .. col+q-1 of it; ``lw``: this encoder's sum is added to it.  Forward only."""
+        shape = (int(L),) + tuple(mu.shape)
+        eps = getattr(self, 'next_eps', None)
+        if eps is None:
+            src = getattr(self, 'eps_source', None)
+            eps = src.normal(shape, mu.device) if src is not None and mu.is_cuda else torch.randn(shape, dtype=mu.dtype, device=mu.device)
+        elif tuple(eps.shape) != shape:
+            raise ValueError('sample_draws: next_eps must be %s, got %s' % (shape, tuple(eps.shape)))
+        self.next_eps = None
+        return V.reparam_draws(mu, logvar, eps.to(mu), out=out, col=col, lw=lw)
+
     def kl_rows(self, mu_s, logvar_s, mu_v=None, logvar_v=None):
         """kl_divergence(q_dist(...), N(0, I)).sum(-1) (create_model.py:47-49) without building the distributions: (N,)."""
         kl = V.normal_kl_rows(mu_s, logvar_s)         # the KL of a factorised Gaussian is additive over (s, v)

@@ -322,6 +322,16 @@ def _check_increasing(ts):
     _ts_checked[0] = key
 
 
+def _z0_per_draw(cache, z0):
+    """0 for initial states (N,D) shared by the draws of the cache, 1 for (L,N,D) with L = cache.nd: one slab per draw."""
+    if z0.dim() == 2:
+        return 0
+    if z0.dim() != 3 or not cache.stacked or z0.shape[0] != cache.nd:
+        raise _lib.GpodeError('z0 must be (N,D), or (L,N,D) with L = the %s of the cache; got %s'
+                              % ('%d draws' % cache.nd if cache.stacked else 'draws (this cache holds a single, unstacked one)', tuple(z0.shape)))
+    return 1
+
+
 def rollout_adaptive(cache, z0, ts, order, rtol=1e-6, atol=1e-6, max_steps=None, save_stages=False, dense=False):
     """Adaptive Dormand-Prince 5(4) rollout (gpode_rollout_adaptive_fwd_n): one step-size controller per trajectory, steps landing
     on ts.  ``max_steps`` = accepted steps a trajectory may take (default 4 (T-1)).  -> zt ([L,] N,T,D), counts ([L,] N,4) int32
@@ -329,9 +339,11 @@ def rollout_adaptive(cache, z0, ts, order, rtol=1e-6, atol=1e-6, max_steps=None,
     ([L,] N,K,6,D), hstep ([L,] N,K), iend ([L,] N,T-1) int32.  A trajectory with status != 0 is NaN from the output it missed.
     ``dense`` (gpode_rollout_dense_fwd_n): steps are cut at ts[-1] only and the interior outputs are interpolated (4th-order
     continuous extension, no evaluation of f); the record is then xstage ([L,] N,K,7,D), hstep, istep ([L,] N,T-1) int32 = 1-based
-    number of the accepted step that holds output t+1, theta ([L,] N,T-1) = the output's position inside that step, in (0, 1]."""
+    number of the accepted step that holds output t+1, theta ([L,] N,T-1) = the output's position inside that step, in (0, 1].
+    z0 (L,N,D) with L = cache.nd gives every draw its own initial states (gpode_rollout_adaptive_fwd_nz / _dense_fwd_nz)."""
     z0 = _chk(z0, 'z0'); ts = _chk(ts, 'ts')
-    N, D = z0.shape
+    zpd = _z0_per_draw(cache, z0)
+    N, D = z0.shape[-2:]
     if D != cache.Di or D != order * cache.Do:
         raise _lib.GpodeError('state dim %d must equal D_in=%d = order*D_out=%d' % (D, cache.Di, order * cache.Do))
     T = ts.shape[0]
@@ -349,13 +361,19 @@ def rollout_adaptive(cache, z0, ts, order, rtol=1e-6, atol=1e-6, max_steps=None,
         ie = torch.empty(lead + (N, max(T - 1, 0)), dtype=torch.int32, device=dev)
         th = torch.empty(lead + (N, max(T - 1, 0)), dtype=torch.float32, device=dev) if dense else None
     if dense:
-        _lib.call('gpode_rollout_dense_fwd_n', KERNEL_ID[cache.kernel], order, METHOD_ID['dopri5'], cache.Di, cache.Do, cache.M,
-                  cache.S, cache.nd, _ptr(cache.pack), _ptr(z0), _ptr(ts), N, T, float(rtol), float(atol), K, _ptr(zt), _ptr(xs), _ptr(hs),
-                  _ptr(ie), _ptr(th), _ptr(counts), _stream())
+        head = (KERNEL_ID[cache.kernel], order, METHOD_ID['dopri5'], cache.Di, cache.Do, cache.M, cache.S, cache.nd, _ptr(cache.pack),
+                _ptr(z0), _ptr(ts), N, T, float(rtol), float(atol), K, _ptr(zt), _ptr(xs), _ptr(hs), _ptr(ie), _ptr(th), _ptr(counts))
+        if zpd:
+            _lib.call('gpode_rollout_dense_fwd_nz', *head, zpd, _stream())
+        else:
+            _lib.call('gpode_rollout_dense_fwd_n', *head, _stream())
         return (zt, counts, xs, hs, ie, th) if save_stages else (zt, counts)
-    _lib.call('gpode_rollout_adaptive_fwd_n', KERNEL_ID[cache.kernel], order, METHOD_ID['dopri5'], cache.Di, cache.Do, cache.M,
-              cache.S, cache.nd, _ptr(cache.pack), _ptr(z0), _ptr(ts), N, T, float(rtol), float(atol), K, _ptr(zt), _ptr(xs), _ptr(hs),
-              _ptr(ie), _ptr(counts), _stream())
+    head = (KERNEL_ID[cache.kernel], order, METHOD_ID['dopri5'], cache.Di, cache.Do, cache.M, cache.S, cache.nd, _ptr(cache.pack),
+            _ptr(z0), _ptr(ts), N, T, float(rtol), float(atol), K, _ptr(zt), _ptr(xs), _ptr(hs), _ptr(ie), _ptr(counts))
+    if zpd:
+        _lib.call('gpode_rollout_adaptive_fwd_nz', *head, zpd, _stream())
+    else:
+        _lib.call('gpode_rollout_adaptive_fwd_n', *head, _stream())
     return (zt, counts, xs, hs, ie) if save_stages else (zt, counts)
 
 
@@ -389,7 +407,8 @@ def rollout_adaptive_bwd(cache, xstage, hstep, iend, gzt, order, theta=None):
 
 def rollout(cache, z0, ts, order, method, save_stages=False, rtol=1e-6, atol=1e-6, max_steps=None, dense=False):
     """Flow.forward (flow.py:68-86) for a built cache: z0 (N,D), ts (T,) -> zt (N,T,D); a cache of L draws integrates all L * N
-    trajectories in ONE launch -> zt (L,N,T,D) (the stack of odegpvae.py:41-44).
+    trajectories in ONE launch -> zt (L,N,T,D) (the stack of odegpvae.py:41-44).  z0 (L,N,D) with L = the draws of the cache: draw l
+    starts from z0[l] (gpode_rollout_fwd_nz) -- joint samples of the initial state and the function.
     save_stages=True also returns the inputs of all RHS evaluations ([L,] N,T-1,NS,D) for the reverse sweep.
     method 'dopri5' (the only one that reads rtol / atol / max_steps / dense) is rollout_adaptive(): with save_stages the second value
     is its record (xstage, hstep, iend, counts), which rollout_bwd takes in place of xstage; in dense-output mode the record is
@@ -399,15 +418,20 @@ def rollout(cache, z0, ts, order, method, save_stages=False, rtol=1e-6, atol=1e-
         out = rollout_adaptive(cache, z0, ts, order, rtol, atol, max_steps, save_stages, dense=dense)
         return (out[0], (out[2], out[3], out[4], out[1]) + tuple(out[5:])) if save_stages else out[0]
     z0 = _chk(z0, 'z0'); ts = _chk(ts, 'ts')
-    N, D = z0.shape
+    zpd = _z0_per_draw(cache, z0)
+    N, D = z0.shape[-2:]
     if D != cache.Di or D != order * cache.Do:
         raise _lib.GpodeError('state dim %d must equal D_in=%d = order*D_out=%d' % (D, cache.Di, order * cache.Do))
     T = ts.shape[0]
     lead = cache.lead
     zt = torch.empty(lead + (N, T, D), dtype=torch.float32, device=z0.device)
     xs = torch.empty(lead + (N, max(T - 1, 0), NSTAGE[method], D), dtype=torch.float32, device=z0.device) if save_stages else None
-    _lib.call('gpode_rollout_fwd_n', KERNEL_ID[cache.kernel], order, METHOD_ID[method], cache.Di, cache.Do, cache.M,
-              cache.S, cache.nd, _ptr(cache.pack), _ptr(z0), _ptr(ts), N, T, _ptr(zt), _ptr(xs), _stream())
+    head = (KERNEL_ID[cache.kernel], order, METHOD_ID[method], cache.Di, cache.Do, cache.M, cache.S, cache.nd, _ptr(cache.pack), _ptr(z0),
+            _ptr(ts), N, T, _ptr(zt), _ptr(xs))
+    if zpd:
+        _lib.call('gpode_rollout_fwd_nz', *head, zpd, _stream())
+    else:
+        _lib.call('gpode_rollout_fwd_n', *head, _stream())
     return (zt, xs) if save_stages else zt
 
 
@@ -655,7 +679,9 @@ class _Flow(torch.autograd.Function):
     method 'dopri5': the adaptive entry points; ``adaptive`` = (rtol, atol, max_steps, sink[, dense]) -- sink(counts) is handed the
     counts tensor of the solve.  The record (xstage, hstep, iend) takes the place of xs; its rows past a trajectory's count are zero
     in both xstage and astage, so the parameter sums run over all K * 6 rows.  ``dense``: the dense-output entry points; the record
-    is (xstage, hstep, istep, theta) with 7 rows per step, saved behind the landing mode's tensors."""
+    is (xstage, hstep, istep, theta) with 7 rows per step, saved behind the landing mode's tensors.
+    z0 (L,N,D) with ``draws`` = L: every draw starts from its own slab (the `_nz` entry points); the gradient of z0 is then the
+    reverse sweep's gz0 (L,N,D) as it stands, where a shared z0 takes its sum over the draws."""
 
     @staticmethod
     def forward(ctx, z0, ts, raw_ell, raw_var, Z, Um, Us, gp, order, method, draws=None, adaptive=None):
@@ -684,7 +710,7 @@ class _Flow(torch.autograd.Function):
             zt, xs = rollout(cache, z0, ts, order, method, save_stages=True)
         else:
             zt, xs = rollout(cache, z0, ts, order, method), None
-        ctx.cache, ctx.order, ctx.method = cache, order, method
+        ctx.cache, ctx.order, ctx.method, ctx.z0_per_draw = cache, order, method, z0.dim() == 3
         ctx.save_for_backward(ts, xs, raw_ell.detach(), raw_var.detach(), Z.detach(), hs, ie, th)
         return zt
 
@@ -704,7 +730,7 @@ class _Flow(torch.autograd.Function):
             gz0, ast = rollout_adaptive_bwd(c, xs, hs, ie, gzt.contiguous(), ctx.order, theta=th)
         else:
             gz0, ast = rollout_bwd(c, xs, gzt.contiguous(), ts, ctx.order, ctx.method)
-        if c.stacked:
+        if c.stacked and not ctx.z0_per_draw:
             gz0 = gz0.sum(0)                         # every draw starts from the same z0 (odegpvae.py:42)
         if not want_p:
             return (gz0,) + (None,) * 11
@@ -736,8 +762,16 @@ class _Flow(torch.autograd.Function):
 
 def flow(gp, z0, ts, order, method, draws=None, adaptive=None):
     """One function draw -> zt (N,T,D); ``draws`` = L -> the L draws of odegpvae.py:41-44 in one pass, zt (L,N,T,D).
-    ``adaptive`` = (rtol, atol, max_steps, sink[, dense]) for method 'dopri5' (see _Flow)."""
+    ``adaptive`` = (rtol, atol, max_steps, sink[, dense]) for method 'dopri5' (see _Flow).
+    z0 (L,N,D): draw l starts from z0[l].  With ``draws`` = L on a layer that batches its draws this is still one pass; otherwise
+    (``draws`` None, or a zero-padded width, whose draws are built one by one) it is L single-draw flows, stacked -- the sink of an
+    adaptive solve then sees the counts of the last one, as after the reference's loop."""
     check_solver(method)
+    if z0.dim() == 3:
+        if draws is not None and draws != z0.shape[0]:
+            raise _lib.GpodeError('z0 holds initial states for %d draws, the flow was asked for %d' % (z0.shape[0], draws))
+        if draws is None or not getattr(gp, 'batched_draws_supported', lambda: True)():
+            return torch.stack([flow(gp, z0[l], ts, order, method, None, adaptive) for l in range(z0.shape[0])], 0)
     k = gp.kern
     raw_ell, raw_var = k.raw_dimwise() if hasattr(k, 'raw_dimwise') else (k.unconstrained_lengthscales, k.unconstrained_variance)
     params = (raw_ell, raw_var, gp.inducing_loc.optvar, gp.Um.optvar, gp.us_packed() if hasattr(gp, 'us_packed') else gp.Us_sqrt.optvar)

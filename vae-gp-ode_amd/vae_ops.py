@@ -877,6 +877,33 @@ def reparam(mu, logvar, eps):
     return _Reparam.apply(_pack(mu, logvar), eps)
 
 
+def reparam_draws(mu, logvar, eps, out=None, col=0, lw=None):
+    """L reparameterised draws of one N(mu, exp(logvar)) (N,q) and their importance log-weights, one launch (gpode_reparam_draws_fwd):
+    eps (L,N,q) -> z[l] = mu + exp(logvar / 2) eps[l] -- the bits reparam() gives draw by draw -- and
+    lw[l,n] = sum_i log N(z; 0, 1) - log N(z; mu, sigma^2) (L,N).  ``out`` (L,N,W) with ``col``: z is written into columns
+    col .. col+q-1 of it (one half of an order-2 state) and that view is returned; ``lw``: the sum is ADDED to it (the other half's).
+    Forward only: evaluation, not training."""
+    h = _chk(_pack(mu, logvar).detach(), 'h')
+    N, q = h.shape[0], h.shape[1] // 2
+    if eps.dim() != 3:
+        raise _lib.GpodeError('reparam_draws: eps must be (L,N,q), got %s' % (tuple(eps.shape),))
+    L = eps.shape[0]
+    eps = _chk(eps, 'eps', (L, N, q))
+    if out is None:
+        out, col = _new((L, N, q), h), 0
+    W = out.shape[-1]
+    if tuple(out.shape) != (L, N, W) or not out.is_contiguous() or out.dtype != torch.float32 or not out.is_cuda or col < 0 or col + q > W:
+        raise _lib.GpodeError('reparam_draws: out must be a contiguous float32 (L,N,W) with col + q <= W, got %s, col %d' % (tuple(out.shape), col))
+    acc = 1 if lw is not None else 0
+    if lw is None:
+        lw = _new((L, N), h)
+    elif tuple(lw.shape) != (L, N) or not lw.is_contiguous() or lw.dtype != torch.float32 or not lw.is_cuda:
+        raise _lib.GpodeError('reparam_draws: lw must be a contiguous float32 (L,N), got %s' % (tuple(lw.shape),))
+    _lib.call('gpode_reparam_draws_fwd', _ptr(h), ctypes.c_void_p(h.data_ptr() + 4 * q), 2 * q, _ptr(eps),
+              ctypes.c_void_p(out.data_ptr() + 4 * col), W, _ptr(lw), acc, L, N, q, _stream())
+    return out[..., col:col + q], lw
+
+
 def normal_kl_rows(mu, logvar):
     return _NormalKL.apply(_pack(mu, logvar))
 
