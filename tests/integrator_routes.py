@@ -1,6 +1,8 @@
 """Every route of the fixed-grid integrator and of its reverse sweep -- rhs_fwd and rollout_fwd (csrc/gp_forward.hip), rollout_bwd, rhs_vjp,
 param_grad and rollout_bwd_pgrad (csrc/gp_backward.hip), with the evaluators they select from gp_rollout.hpp and gp_team.hpp -- shared
-by test_gpu_integrator_routes.py and test_integrator_routes_host.py.
+by test_gpu_integrator_routes.py and test_integrator_routes_host.py.  The library holds the ladder once (forward_route / reverse_route
+in gp_rollout.hpp), and the adaptive launchers of csrc/gp_adaptive.hip take it from there: forward_route() and backward_resident()
+below cover dopri5, landing and dense, too -- test_gpu_z0_draws.py runs it on the first 'full' case of every forward route.
 
 A case is (kernel, Di, Do, order, M, S, N, T, method, nd, kind): the kernel family, the widths, the inducing points and Fourier
 features, the trajectories, the output times, the solver and the Monte-Carlo draws.  kind: 'full' (everything), 'fused' (also the

@@ -4,7 +4,8 @@ routing through ops.rollout / ops.flow, and evaluate.predict_marginal (the impor
 What is held, and to what:
   * one `_nz` launch over L draws with z0 (L,N,D) against L single-draw launches on (pack[l], z0[l]): BITS (torch.equal) -- the property
     test_gpu_draws.py holds for a shared z0; every forward route of the fixed-grid dispatch (shapes of integrator_routes.py, route read
-    back from gpode_last_launch()), and dopri5 landing / dense on the team and on the wave mapping;
+    back from gpode_last_launch()), and dopri5 landing / dense with its reverse sweep on the team and on the wave mapping and on the same
+    route shapes;
   * z0_per_draw = 0, and z0_per_draw = 1 on L copies of one z0, against the `_n` entry point: BITS;
   * the gradient of a (L,N,D) leaf against ops.rollout_bwd on the same record: BITS; GP parameter gradients with L copies against the
     shared flow: BITS;
@@ -133,38 +134,84 @@ def test_fixed_grid_per_draw_launch_equals_single_draw_launches(route, c):
 
 # ---- 2. dopri5, landing and dense -----------------------------------------------------------------------------------------------------
 ADAPT = [('rbf1', 'RBF', 6, 6, 24, 32), ('rbf2', 'RBF', 6, 3, 24, 32), ('df', 'DF', 4, 4, 16, 32)]
+ANCHOR_ROWS, ANCHOR_TOL, ANCHOR_BOUND = 683, 1e-5, 3e-4 + 2e-4
 
 
-@pytest.mark.parametrize('dense', [False, True], ids=['landing', 'dense'])
-@pytest.mark.parametrize('N', [1, 5, 300, 2049])
-@pytest.mark.parametrize('name,kernel,Di,Do,M,S', ADAPT, ids=[a[0] for a in ADAPT])
-def test_dopri5_per_draw_launch_equals_single_draw_launches(name, kernel, Di, Do, M, S, N, dense):
-    """N = 1, 5, 300: one workgroup per trajectory (the team mapping, up to 2048 rows); N = 2049: one wavefront per trajectory"""
+def _dopri5_cases():
+    """The small caches of ADAPT at 1, 5, 300 and 2049 rows, then the nine route shapes of _route_cases() (their fixed-grid method is
+    not used), each in landing and in dense mode: (id, (route, kernel, Di, Do, M, S, N, dense, table case))"""
+    out = []
+    for name, kernel, Di, Do, M, S in ADAPT:
+        for N in (1, 5, 300, 2049):
+            for dense in (False, True):
+                out.append(('%s-%d-%s' % (name, N, 'dense' if dense else 'landing'), (None, kernel, Di, Do, M, S, N, dense, None)))
+    for route, c in _route_cases():
+        for dense in (False, True):
+            out.append(('%s-%s' % (route, 'dense' if dense else 'landing'), (route, c.kernel, c.Di, c.Do, c.M, c.S, c.N, dense, c)))
+    return out
+
+
+def _dopri5_setup(route, kernel, Di, Do, M, S, N, c):
+    """the cache of L draws, the initial states (N,Di) on the CPU, the tag of the forward launch and the tag of the reverse sweep"""
     from vae_gp_ode_amd import ops
+    k = kernel.lower()
+    if c is None:                                                       # M <= 24, S = 32, Do <= 6: register-resident on either side
+        p = {kk: v.cuda() for kk, v in _params(kernel, Di, Do, M, 3).items()}
+        nz = {kk: v.cuda() for kk, v in _noise(kernel, Di, Do, M, S, L, 4).items()}
+        cb = _build(ops, kernel, p, nz)
+        cb.check_factorisation()
+        z0 = torch.randn(N, Di, generator=torch.Generator().manual_seed(50 + N))
+        return cb, z0, 'rollout_adaptive_%s%s' % (k, '_team' if N <= 2048 else ''), 'rollout_adaptive_bwd_' + k
+    assert IR.forward_route(c) == route
+    p, nz, z0, _, _ = IR.inputs(c)
+    cb = IR.build(c, ({kk: v.cuda() for kk, v in p.items()}, {kk: v.cuda() for kk, v in nz.items()}))
+    mapping = route[len(k):] if 'team' in route else ''                 # _team, _team_stream; every wave route reports the family alone
+    return cb, z0, 'rollout_adaptive_' + k + mapping, 'rollout_adaptive_bwd_%s%s' % (k, '' if IR.backward_resident(c) else '_stream')
+
+
+def _solve_all(ops, cb, z0, ts, order, tol, dense, save):
+    """ops.rollout_adaptive with a budget no trajectory exhausts: (its outputs, the budget)"""
+    K = 4 * (T - 1)
+    while True:
+        out = ops.rollout_adaptive(cb, z0, ts, order, tol, tol, K, save_stages=save, dense=dense)
+        if int(out[1][..., 2].max()) == 0 or K >= 512:
+            return out, K
+        K *= 2
+
+
+@pytest.mark.parametrize('case', [v for _, v in _dopri5_cases()], ids=[i for i, _ in _dopri5_cases()])
+def test_dopri5_per_draw_launch_equals_single_draw_launches(case):
+    """N = 1, 5, 300: one workgroup per trajectory (the team mapping, up to 2048 rows); N = 2049: one wavefront per trajectory.
+    The route shapes run dopri5 and its reverse sweep on every evaluator of the forward dispatch and on both reverse ones.  On the
+    wave routes the first 683 rows, solved on their own by the team kernels, anchor the values: the bound and tolerance of
+    test_gpu_dopri5.test_wave_and_team_mappings_agree (3e-4 + 2e-4 at rtol = atol = 1e-5).  Measured on an MI355X with the dispatch
+    as it was before the launchers shared one selector, landing / dense: rbf_reg42 3.9e-6 / 9.1e-6, rbf_reg11 2.9e-6 / 1.5e-5, rbf_stream
+    2.2e-6 / 1.7e-5, df_lds 1.8e-5 / 1.2e-5, df_stream 6.0e-6 / 2.7e-5 -- no case needs a bound of its own."""
+    from vae_gp_ode_amd import ops
+    route, kernel, Di, Do, M, S, N, dense, c = case
+    name = route or kernel
     order = Di // Do
-    p = {k: v.cuda() for k, v in _params(kernel, Di, Do, M, 3).items()}
-    nz = {k: v.cuda() for k, v in _noise(kernel, Di, Do, M, S, L, 4).items()}
-    cb = _build(ops, kernel, p, nz)
-    cb.check_factorisation()
-    g = torch.Generator().manual_seed(50 + N)
-    z0 = torch.randn(N, Di, generator=g)
+    cb, z0, want, want_bwd = _dopri5_setup(route, kernel, Di, Do, M, S, N, c)
     z0L = _per_draw_states(z0, 8)
     ts = torch.tensor(TS4).cuda() * 4                                   # long enough intervals for more than one step each
-    K = 4 * (T - 1)
-    while True:                                                         # a budget no trajectory exhausts
-        out = ops.rollout_adaptive(cb, z0L, ts, order, 1e-4, 1e-4, K, save_stages=True, dense=dense)
-        if int(out[1][..., 2].max()) == 0 or K >= 512:
-            break
-        K *= 2
-    want = 'rollout_adaptive_%s%s' % (kernel.lower(), '_team' if N <= 2048 else '')
+    out, K = _solve_all(ops, cb, z0L, ts, order, 1e-4, dense, True)
     assert _tag() == want, (_tag(), want)
     assert int(out[1][..., 2].max()) == 0 and len(out) == (6 if dense else 5)
     assert not torch.isnan(out[0]).any() and int(out[1][..., 0].min()) >= 1
+    # the reverse sweep on the record, all draws in one launch
+    gzt = torch.randn(L, N, T, Di, generator=torch.Generator().manual_seed(60 + N)).cuda()
+    bwd = ops.rollout_adaptive_bwd(cb, out[2], out[3], out[4], gzt, order, theta=out[5] if dense else None)
+    assert _tag() == want_bwd, (_tag(), want_bwd)
+    assert not torch.isnan(bwd[0]).any() and not torch.isnan(bwd[1]).any()
     for l in range(L):
-        one = ops.rollout_adaptive(_one_draw(cb, l), z0L[l], ts, order, 1e-4, 1e-4, K, save_stages=True, dense=dense)
+        c1 = _one_draw(cb, l)
+        one = ops.rollout_adaptive(c1, z0L[l], ts, order, 1e-4, 1e-4, K, save_stages=True, dense=dense)
         assert _tag() == want
         for i, (a, b) in enumerate(zip(out, one)):
             assert torch.equal(a[l], b), (name, N, 'draw', l, 'output', i)
+        bwd1 = ops.rollout_adaptive_bwd(c1, one[2], one[3], one[4], gzt[l], order, theta=one[5] if dense else None)
+        assert _tag() == want_bwd
+        assert torch.equal(bwd[0][l], bwd1[0]) and torch.equal(bwd[1][l], bwd1[1]), (name, N, 'draw', l, 'reverse sweep')
     assert not torch.equal(out[0][0], out[0][1])
     # shared form, through the C ABI on NaN-filled buffers
     z0s = z0.cuda()
@@ -178,6 +225,16 @@ def test_dopri5_per_draw_launch_equals_single_draw_launches(name, kernel, Di, Do
     # without the record
     zt, counts = ops.rollout_adaptive(cb, z0L, ts, order, 1e-4, 1e-4, K, dense=dense)
     assert torch.equal(zt, out[0]) and torch.equal(counts, out[1])
+    # the values of a wave route against the team kernels, which the fixed-grid route tests hold to fp64
+    if c is not None and N > IR.TEAM_MAX_ROWS:
+        (zw, cw), _ = _solve_all(ops, cb, z0L, ts, order, ANCHOR_TOL, dense, False)
+        (zq, cq), _ = _solve_all(ops, cb, z0L[:, :ANCHOR_ROWS].contiguous(), ts, order, ANCHOR_TOL, dense, False)
+        assert _tag() in ('rollout_adaptive_%s_team' % kernel.lower(), 'rollout_adaptive_%s_team_stream' % kernel.lower())
+        assert int(cw[..., 2].max()) == 0 and int(cq[..., 2].max()) == 0
+        e = relerr(zq, zw[:, :ANCHOR_ROWS])
+        print('%s %s: first %d rows on the team kernels vs the wave route %.2e  bound %.2e' %
+              (route, 'dense' if dense else 'landing', ANCHOR_ROWS, e, ANCHOR_BOUND))
+        assert e < ANCHOR_BOUND, (route, e)
 
 
 # ---- 3. gradients ---------------------------------------------------------------------------------------------------------------------

@@ -151,17 +151,34 @@ int gpode_rollout_bwd(int kernel, int order, int method, int Di, int Do, int M, 
   return gpode_rollout_bwd_n(kernel, order, method, Di, Do, M, S, 1, pack, xstage, gzt, ts, N, T, gz0, astage, stream);
 }
 
-static int rollout_adaptive_fwd_any(const char* who, int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
-                                    const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
-                                    float* zt, float* xstage, float* hstep, int* iend, int* counts, int z0_per_draw, void* stream) {
+// The argument checks of the dopri5 entry points, landing and dense alike.  who: the entry point the error names.
+// -> 1 refused (the error is set), -1 nothing to integrate (N = 0), 0 go on.
+static int adaptive_fwd_args(const char* who, int method, int ndraws, const float* pack, const float* z0, const float* ts, int N, int T,
+                             float rtol, float atol, int K, const float* zt, const int* counts, int z0_per_draw) {
   if (z0_per_draw != 0 && z0_per_draw != 1) return gp::set_error("%s: z0_per_draw=%d (0 shared, 1 one (N,D) slab per draw)", who, z0_per_draw);
   if (method != GPODE_METHOD_DOPRI5) return gp::set_error("%s: method %d (3 dopri5)", who, method);
   if (N < 0 || T < 1 || K < 0 || ndraws < 1 || ndraws > 65535)
     return gp::set_error("%s: N=%d T=%d K=%d draws=%d", who, N, T, K, ndraws);
   if (!(rtol >= 0.f) || !(atol >= 0.f) || !(rtol + atol > 0.f) || !(rtol + atol < 1e30f))
     return gp::set_error("%s: rtol=%g atol=%g (both >= 0, not both 0)", who, rtol, atol);
-  if (N == 0) return 0;
+  if (N == 0) return -1;
   if (!pack || !z0 || !ts || !zt || !counts) return gp::set_error("%s: null pointer", who);
+  return 0;
+}
+// index: the mode's index of the record is there (iend; istep and theta)
+static int adaptive_bwd_args(const char* who, int method, int ndraws, const float* pack, const float* xstage, const float* hstep, bool index,
+                             const float* gzt, int N, int T, int K, const float* gz0, const float* astage) {
+  if (method != GPODE_METHOD_DOPRI5) return gp::set_error("%s: method %d (3 dopri5)", who, method);
+  if (N < 0 || T < 1 || K < 0 || ndraws < 1 || ndraws > 65535) return gp::set_error("%s: N=%d T=%d K=%d draws=%d", who, N, T, K, ndraws);
+  if (N == 0) return -1;
+  if (!pack || !gzt || !gz0 || (T > 1 && !index) || (T > 1 && K > 0 && (!xstage || !hstep || !astage))) return gp::set_error("%s: null pointer", who);
+  return 0;
+}
+
+static int rollout_adaptive_fwd_any(const char* who, int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                                    const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
+                                    float* zt, float* xstage, float* hstep, int* iend, int* counts, int z0_per_draw, void* stream) {
+  if (const int rc = adaptive_fwd_args(who, method, ndraws, pack, z0, ts, N, T, rtol, atol, K, zt, counts, z0_per_draw)) return rc > 0;
   if (xstage && T > 1 && (!iend || (K > 0 && !hstep))) return gp::set_error("%s: xstage without hstep / iend", who);
   size_t pf = 0;
   if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
@@ -183,12 +200,8 @@ int gpode_rollout_adaptive_fwd_nz(int kernel, int order, int method, int Di, int
 int gpode_rollout_adaptive_bwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                                  const float* pack, const float* xstage, const float* hstep, const int* iend, const float* gzt,
                                  int N, int T, int K, float* gz0, float* astage, void* stream) {
-  if (method != GPODE_METHOD_DOPRI5) return gp::set_error("gpode_rollout_adaptive_bwd: method %d (3 dopri5)", method);
-  if (N < 0 || T < 1 || K < 0 || ndraws < 1 || ndraws > 65535)
-    return gp::set_error("gpode_rollout_adaptive_bwd: N=%d T=%d K=%d draws=%d", N, T, K, ndraws);
-  if (N == 0) return 0;
-  if (!pack || !gzt || !gz0 || (T > 1 && !iend) || (T > 1 && K > 0 && (!xstage || !hstep || !astage)))
-    return gp::set_error("gpode_rollout_adaptive_bwd: null pointer");
+  if (const int rc = adaptive_bwd_args("gpode_rollout_adaptive_bwd", method, ndraws, pack, xstage, hstep, iend != nullptr, gzt, N, T, K, gz0, astage))
+    return rc > 0;
   size_t pf = 0;
   if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
   return gp::rollout_adaptive_bwd(kernel, order, Di, Do, M, S, ndraws, pack, pf, xstage, hstep, iend, gzt, N, T, K, gz0, astage,
@@ -199,14 +212,7 @@ static int rollout_dense_fwd_any(const char* who, int kernel, int order, int met
                                  const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
                                  float* zt, float* xstage, float* hstep, int* istep, float* theta, int* counts, int z0_per_draw,
                                  void* stream) {
-  if (z0_per_draw != 0 && z0_per_draw != 1) return gp::set_error("%s: z0_per_draw=%d (0 shared, 1 one (N,D) slab per draw)", who, z0_per_draw);
-  if (method != GPODE_METHOD_DOPRI5) return gp::set_error("%s: method %d (3 dopri5)", who, method);
-  if (N < 0 || T < 1 || K < 0 || ndraws < 1 || ndraws > 65535)
-    return gp::set_error("%s: N=%d T=%d K=%d draws=%d", who, N, T, K, ndraws);
-  if (!(rtol >= 0.f) || !(atol >= 0.f) || !(rtol + atol > 0.f) || !(rtol + atol < 1e30f))
-    return gp::set_error("%s: rtol=%g atol=%g (both >= 0, not both 0)", who, rtol, atol);
-  if (N == 0) return 0;
-  if (!pack || !z0 || !ts || !zt || !counts) return gp::set_error("%s: null pointer", who);
+  if (const int rc = adaptive_fwd_args(who, method, ndraws, pack, z0, ts, N, T, rtol, atol, K, zt, counts, z0_per_draw)) return rc > 0;
   if (xstage && T > 1 && (!istep || !theta || (K > 0 && !hstep)))
     return gp::set_error("%s: xstage without hstep / istep / theta", who);
   size_t pf = 0;
@@ -230,12 +236,8 @@ int gpode_rollout_dense_fwd_nz(int kernel, int order, int method, int Di, int Do
 int gpode_rollout_dense_bwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                               const float* pack, const float* xstage, const float* hstep, const int* istep, const float* theta,
                               const float* gzt, int N, int T, int K, float* gz0, float* astage, void* stream) {
-  if (method != GPODE_METHOD_DOPRI5) return gp::set_error("gpode_rollout_dense_bwd: method %d (3 dopri5)", method);
-  if (N < 0 || T < 1 || K < 0 || ndraws < 1 || ndraws > 65535)
-    return gp::set_error("gpode_rollout_dense_bwd: N=%d T=%d K=%d draws=%d", N, T, K, ndraws);
-  if (N == 0) return 0;
-  if (!pack || !gzt || !gz0 || (T > 1 && (!istep || !theta)) || (T > 1 && K > 0 && (!xstage || !hstep || !astage)))
-    return gp::set_error("gpode_rollout_dense_bwd: null pointer");
+  if (const int rc = adaptive_bwd_args("gpode_rollout_dense_bwd", method, ndraws, pack, xstage, hstep, istep && theta, gzt, N, T, K, gz0, astage))
+    return rc > 0;
   size_t pf = 0;
   if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
   return gp::rollout_dense_bwd(kernel, order, Di, Do, M, S, ndraws, pack, pf, xstage, hstep, istep, theta, gzt, N, T, K, gz0, astage,

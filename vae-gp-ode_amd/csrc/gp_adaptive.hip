@@ -482,89 +482,32 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rollout_dense_bwd_kernel(Adapt
 }
 
 // ----------------------------------------------------------------------------------------------
-// host launchers: the dispatch of the fixed-grid rollout (gp_forward.hip, gp_backward.hip)
+// host side: the evaluators and grids of the fixed-grid rollout and of its reverse sweep (forward_route, reverse_route of gp_rollout.hpp)
 // ----------------------------------------------------------------------------------------------
-template <int DI, int DO, int ORDER, bool DENSE>
-static int launch_adaptive_rbf(const AdaptFwdArg<DENSE>& a, int nd, hipStream_t st) {
-  const int N = a.N, M = a.M, S = a.S;
-  int grid, block;
-  grid_for(N, grid, block);
-  if (N <= kTeamMaxRows && DO <= 16) {
-    if (RbfTeamEval<DI, DO, 1>::fits(M, S)) {
-      hipLaunchKernelGGL((rollout_adaptive_team_kernel<RbfTeamEval<DI, DO, 1>, DI, DO, ORDER, DENSE>), dim3(team_grid(N), nd), 256, 0, st, a);
-      return check_launch("rollout_adaptive_rbf_team");
-    }
-  }
-  if (N <= kTeamMaxRows) {
-    hipLaunchKernelGGL((rollout_adaptive_team_kernel<RbfStreamTeam<DI, DO>, DI, DO, ORDER, DENSE>), dim3(team_grid(N), nd), 256, 0, st, a);
-    return check_launch("rollout_adaptive_rbf_team_stream");
-  }
-  const int SJ = cdiv(S, 64), MJ = cdiv(M, 64);
-  if constexpr (rbf_reg_fits<DI, DO, 4, 2>()) {
-    if (SJ == 4 && MJ == 2) {
-      hipLaunchKernelGGL((rollout_adaptive_kernel<RbfRegEval<DI, DO, 4, 2>, DI, DO, ORDER, false, DENSE>), dim3(grid, nd), block, 0, st, a, (size_t)0);
-      return check_launch("rollout_adaptive_rbf");
-    }
-  }
-  if constexpr (rbf_reg_fits<DI, DO, 1, 1>()) {
-    if (SJ == 1 && MJ == 1) {
-      hipLaunchKernelGGL((rollout_adaptive_kernel<RbfRegEval<DI, DO, 1, 1>, DI, DO, ORDER, false, DENSE>), dim3(grid, nd), block, 0, st, a, (size_t)0);
-      return check_launch("rollout_adaptive_rbf");
-    }
-  }
-  hipLaunchKernelGGL((rollout_adaptive_kernel<RbfStreamEval<DI, DO>, DI, DO, ORDER, false, DENSE>), dim3(grid, nd), block, 0, st, a, (size_t)0);
-  return check_launch("rollout_adaptive_rbf");
-}
-
-template <int D, bool DENSE>
-static int launch_adaptive_df(const AdaptFwdArg<DENSE>& a, int nd, hipStream_t st) {
-  using L = DfLayout<D>;
-  const int N = a.N, M = a.M, S = a.S;
-  const size_t f4 = L::rff_f4(S) + L::ind_f4(M);
-  int grid, block;
-  grid_for(N, grid, block);
-  if constexpr (D <= 8) {
-    if (N <= kTeamMaxRows && DfTeamEval<D, 1>::fits(M, S)) {
-      hipLaunchKernelGGL((rollout_adaptive_team_kernel<DfTeamEval<D, 1>, D, D, 1, DENSE>), dim3(team_grid(N), nd), 256, 0, st, a);
-      return check_launch("rollout_adaptive_df_team");
-    }
-  }
-  if (N <= kTeamMaxRows) {
-    hipLaunchKernelGGL((rollout_adaptive_team_kernel<DfStreamTeam<D>, D, D, 1, DENSE>), dim3(team_grid(N), nd), 256, 0, st, a);
-    return check_launch("rollout_adaptive_df_team_stream");
-  }
-  if (f4 * 16 <= kLdsLimitBytes) {
-    if (N <= 1024) { block = 64; grid = N < 256 ? N : 256; }
-    else { block = 256; grid = 256; }
-    auto kern = rollout_adaptive_kernel<DfEval<D, true>, D, D, 1, true, DENSE>;
-    if (set_max_lds((const void*)kern, f4 * 16)) return 1;
-    hipLaunchKernelGGL(kern, dim3(grid, nd), block, f4 * 16, st, a, f4);
-  } else {
-    hipLaunchKernelGGL((rollout_adaptive_kernel<DfEval<D, false>, D, D, 1, false, DENSE>), dim3(grid, nd), block, 0, st, a, (size_t)0);
-  }
-  return check_launch("rollout_adaptive_df");
-}
-
-template <int DI, int DO, bool DENSE>
-static int adaptive_rbf_dispatch(int order, const AdaptFwdArg<DENSE>& a, int nd, hipStream_t st) {
-  if constexpr (DI == DO) { if (order == 1) return launch_adaptive_rbf<DI, DO, 1, DENSE>(a, nd, st); }
-  if constexpr (DI == 2 * DO) { if (order == 2) return launch_adaptive_rbf<DI, DO, 2, DENSE>(a, nd, st); }
-  return set_error("gpode_rollout_adaptive_fwd: order=%d needs Di == order*Do (Di=%d Do=%d)", order, DI, DO);
-}
-
 template <bool DENSE>
 static int adaptive_fwd(int kernel, int order, int Di, int Do, const AdaptFwdArg<DENSE>& a, int nd, hipStream_t st) {
-  if (kernel == 0) {
-#define X(p, q) if (Di == p && Do == q) return adaptive_rbf_dispatch<p, q, DENSE>(order, a, nd, st);
-    GP_RBF_DIMS(X)
-#undef X
-  } else {
-    if (order != 1) return set_error("gpode_rollout_adaptive_fwd: DF kernel is first-order only (kernels.py:259-262)");
-#define X(p) if (Di == p && Do == p) return launch_adaptive_df<p, DENSE>(a, nd, st);
-    GP_DF_DIMS(X)
-#undef X
-  }
-  return set_error("gpode_rollout_adaptive_fwd: no specialisation for kernel=%d Di=%d Do=%d", kernel, Di, Do);
+  static const char* const who = "gpode_rollout_adaptive_fwd";
+  // the wave routes report the family alone
+  static const char* const tags[2][kRoutes] = {
+      {"rollout_adaptive_rbf_team", "rollout_adaptive_rbf_team_stream", "rollout_adaptive_rbf", "rollout_adaptive_rbf", "rollout_adaptive_rbf"},
+      {"rollout_adaptive_df_team", "rollout_adaptive_df_team_stream", "rollout_adaptive_df", "rollout_adaptive_df"}};
+  if (kernel != 0 && order != 1) return set_error("gpode_rollout_adaptive_fwd: DF kernel is first-order only (kernels.py:259-262)");
+  return dispatch_dims(who, kernel, Di, Do, [&](auto k, auto di, auto dO) {
+    constexpr int KERNEL = decltype(k)::value, DI = decltype(di)::value, DO = decltype(dO)::value;
+    return dispatch_order<DI, DO>(who, order, [&](auto o) {
+      constexpr int ORDER = decltype(o)::value;
+      return forward_route<KERNEL, DI, DO>(a.N, a.M, a.S, [&](auto ev, auto map, const LaunchGeom& g) {
+        using EV = typename decltype(ev)::type;
+        constexpr int MAP = decltype(map)::value;
+        if constexpr (MAP == kTeam) {
+          if (launch_route(rollout_adaptive_team_kernel<EV, DI, DO, ORDER, DENSE>, g, nd, st, a)) return 1;
+        } else {
+          if (launch_route(rollout_adaptive_kernel<EV, DI, DO, ORDER, MAP == kWaveLds, DENSE>, g, nd, st, a, g.lds_f4)) return 1;
+        }
+        return check_launch(tags[KERNEL][g.route]);
+      });
+    });
+  });
 }
 
 int rollout_adaptive_fwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
@@ -587,50 +530,23 @@ template <bool DENSE, class EV, int DI, int DO, int ORDER> static constexpr auto
   else return &rollout_adaptive_bwd_kernel<EV, DI, DO, ORDER>;
 }
 
-template <int DI, int DO, int ORDER, bool DENSE>
-static int launch_adaptive_bwd_rbf(const AdaptBwdArg<DENSE>& a, int nd, hipStream_t st) {
-  if constexpr (DO <= 8) {
-    if (rbf_team_ok<DI, DO>(a.M, a.S)) {
-      hipLaunchKernelGGL((adaptive_bwd_kernel<DENSE, RbfTeamEval<DI, DO, 1>, DI, DO, ORDER>()), dim3(team_grid(a.N), nd), 256, 0, st, a);
-      return check_launch("rollout_adaptive_bwd_rbf");
-    }
-  }
-  hipLaunchKernelGGL((adaptive_bwd_kernel<DENSE, RbfStreamTeam<DI, DO>, DI, DO, ORDER>()), dim3(team_grid(a.N), nd), 256, 0, st, a);
-  return check_launch("rollout_adaptive_bwd_rbf_stream");
-}
-
-template <int D, bool DENSE>
-static int launch_adaptive_bwd_df(const AdaptBwdArg<DENSE>& a, int nd, hipStream_t st) {
-  if constexpr (D <= 8) {
-    if (df_team_ok<D>(a.M, a.S)) {
-      hipLaunchKernelGGL((adaptive_bwd_kernel<DENSE, DfTeamEval<D, 1>, D, D, 1>()), dim3(team_grid(a.N), nd), 256, 0, st, a);
-      return check_launch("rollout_adaptive_bwd_df");
-    }
-  }
-  hipLaunchKernelGGL((adaptive_bwd_kernel<DENSE, DfStreamTeam<D>, D, D, 1>()), dim3(team_grid(a.N), nd), 256, 0, st, a);
-  return check_launch("rollout_adaptive_bwd_df_stream");
-}
-
-template <int DI, int DO, bool DENSE>
-static int adaptive_bwd_rbf_dispatch(int order, const AdaptBwdArg<DENSE>& a, int nd, hipStream_t st) {
-  if constexpr (DI == DO) { if (order == 1) return launch_adaptive_bwd_rbf<DI, DO, 1, DENSE>(a, nd, st); }
-  if constexpr (DI == 2 * DO) { if (order == 2) return launch_adaptive_bwd_rbf<DI, DO, 2, DENSE>(a, nd, st); }
-  return set_error("gpode_rollout_adaptive_bwd: order=%d needs Di == order*Do (Di=%d Do=%d)", order, DI, DO);
-}
-
 template <bool DENSE>
 static int adaptive_bwd(int kernel, int order, int Di, int Do, const AdaptBwdArg<DENSE>& a, int nd, hipStream_t st) {
-  if (kernel == 0) {
-#define X(p, q) if (Di == p && Do == q) return adaptive_bwd_rbf_dispatch<p, q, DENSE>(order, a, nd, st);
-    GP_RBF_DIMS(X)
-#undef X
-  } else {
-    if (order != 1) return set_error("gpode_rollout_adaptive_bwd: DF kernel is first-order only");
-#define X(p) if (Di == p && Do == p) return launch_adaptive_bwd_df<p, DENSE>(a, nd, st);
-    GP_DF_DIMS(X)
-#undef X
-  }
-  return set_error("gpode_rollout_adaptive_bwd: no specialisation for kernel=%d Di=%d Do=%d", kernel, Di, Do);
+  static const char* const who = "gpode_rollout_adaptive_bwd";
+  static const char* const tags[2][2] = {{"rollout_adaptive_bwd_rbf", "rollout_adaptive_bwd_rbf_stream"},
+                                         {"rollout_adaptive_bwd_df", "rollout_adaptive_bwd_df_stream"}};
+  if (kernel != 0 && order != 1) return set_error("gpode_rollout_adaptive_bwd: DF kernel is first-order only");
+  return dispatch_dims(who, kernel, Di, Do, [&](auto k, auto di, auto dO) {
+    constexpr int KERNEL = decltype(k)::value, DI = decltype(di)::value, DO = decltype(dO)::value;
+    return dispatch_order<DI, DO>(who, order, [&](auto o) {
+      constexpr int ORDER = decltype(o)::value;
+      return reverse_route<KERNEL, DI, DO>(a.N, a.M, a.S, [&](auto ev, const LaunchGeom& g) {
+        using EV = typename decltype(ev)::type;
+        if (launch_route(adaptive_bwd_kernel<DENSE, EV, DI, DO, ORDER>(), g, nd, st, a)) return 1;
+        return check_launch(tags[KERNEL][g.route]);
+      });
+    });
+  });
 }
 
 int rollout_adaptive_bwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,

@@ -640,74 +640,28 @@ __global__ __launch_bounds__(1024) void reduce_slab_kernel(const float* __restri
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static inline int team_grid_b(int N) { return N < 2048 ? N : 2048; }
-
-
-template <int DI, int DO, int ORDER, int METHOD>
-static int launch_bwd_rbf(const float* pack, int M, int S, const float* xstage, const float* gzt, const float* ts, int N, int T,
-                          float* gz0, float* astage, hipStream_t st, Draws dw) {
-  if constexpr (DO <= 8) {
-    if (rbf_team_ok<DI, DO>(M, S)) {
-      hipLaunchKernelGGL((rollout_bwd_team_kernel<RbfTeamEval<DI, DO, 1>, DI, DO, ORDER, METHOD>), dim3(team_grid_b(N), dw.nd), 256, 0, st,
-                         pack, M, S, xstage, gzt, ts, N, T, gz0, astage, dw);
-      return check_launch("rollout_bwd_rbf");
-    }
-  }
-  hipLaunchKernelGGL((rollout_bwd_team_kernel<RbfStreamTeam<DI, DO>, DI, DO, ORDER, METHOD>), dim3(team_grid_b(N), dw.nd), 256, 0, st,
-                     pack, M, S, xstage, gzt, ts, N, T, gz0, astage, dw);
-  return check_launch("rollout_bwd_rbf_stream");
-}
-
-template <int D, int METHOD>
-static int launch_bwd_df(const float* pack, int M, int S, const float* xstage, const float* gzt, const float* ts, int N, int T,
-                         float* gz0, float* astage, hipStream_t st, Draws dw) {
-  if constexpr (D <= 8) {
-    if (df_team_ok<D>(M, S)) {
-      hipLaunchKernelGGL((rollout_bwd_team_kernel<DfTeamEval<D, 1>, D, D, 1, METHOD>), dim3(team_grid_b(N), dw.nd), 256, 0, st,
-                         pack, M, S, xstage, gzt, ts, N, T, gz0, astage, dw);
-      return check_launch("rollout_bwd_df");
-    }
-  }
-  hipLaunchKernelGGL((rollout_bwd_team_kernel<DfStreamTeam<D>, D, D, 1, METHOD>), dim3(team_grid_b(N), dw.nd), 256, 0, st,
-                     pack, M, S, xstage, gzt, ts, N, T, gz0, astage, dw);
-  return check_launch("rollout_bwd_df_stream");
-}
-
-#define GP_BWD_RBF_DIMS(X) X(6, 6) X(6, 3) X(4, 4) X(4, 2) X(2, 2) X(2, 1) X(8, 8) X(8, 4) X(3, 3) X(16, 16) X(16, 8) X(12, 6)
-#define GP_BWD_DF_DIMS(X) X(6) X(4) X(2) X(3) X(8) X(16) X(5) X(7) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
-
-template <int DI, int DO>
-static int bwd_rbf_dispatch(int order, int method, const float* pack, int M, int S, const float* xstage, const float* gzt,
-                            const float* ts, int N, int T, float* gz0, float* astage, hipStream_t st, Draws dw) {
-  if constexpr (DI == DO) {
-    if (order == 1 && method == 0) return launch_bwd_rbf<DI, DO, 1, 0>(pack, M, S, xstage, gzt, ts, N, T, gz0, astage, st, dw);
-    if (order == 1 && method == 1) return launch_bwd_rbf<DI, DO, 1, 1>(pack, M, S, xstage, gzt, ts, N, T, gz0, astage, st, dw);
-    if (order == 1 && method == 2) return launch_bwd_rbf<DI, DO, 1, 2>(pack, M, S, xstage, gzt, ts, N, T, gz0, astage, st, dw);
-  }
-  if constexpr (DI == 2 * DO) {
-    if (order == 2 && method == 0) return launch_bwd_rbf<DI, DO, 2, 0>(pack, M, S, xstage, gzt, ts, N, T, gz0, astage, st, dw);
-    if (order == 2 && method == 1) return launch_bwd_rbf<DI, DO, 2, 1>(pack, M, S, xstage, gzt, ts, N, T, gz0, astage, st, dw);
-    if (order == 2 && method == 2) return launch_bwd_rbf<DI, DO, 2, 2>(pack, M, S, xstage, gzt, ts, N, T, gz0, astage, st, dw);
-  }
-  return set_error("gpode_rollout_bwd: order=%d needs Di == order*Do (Di=%d Do=%d)", order, DI, DO);
-}
-
+// The register-resident or the streamed team, and the grid: reverse_route (gp_rollout.hpp).
 int rollout_bwd(int kernel, int order, int method, int Di, int Do, int M, int S, const float* pack, const float* xstage,
                 const float* gzt, const float* ts, int N, int T, float* gz0, float* astage, hipStream_t st, Draws dw) {
+  static const char* const who = "gpode_rollout_bwd";
+  static const char* const tags[2][2] = {{"rollout_bwd_rbf", "rollout_bwd_rbf_stream"}, {"rollout_bwd_df", "rollout_bwd_df_stream"}};
   if (method < 0 || method > 2) return set_error("gpode_rollout_bwd: method %d (0 euler, 1 rk4, 2 midpoint; 3 dopri5: gpode_rollout_adaptive_bwd_n)", method);
-  if (kernel == 0) {
-#define X(a, b) if (Di == a && Do == b) return bwd_rbf_dispatch<a, b>(order, method, pack, M, S, xstage, gzt, ts, N, T, gz0, astage, st, dw);
-    GP_BWD_RBF_DIMS(X)
-#undef X
-  } else {
-    if (order != 1) return set_error("gpode_rollout_bwd: DF kernel is first-order only");
-#define X(a) if (Di == a && Do == a) return method == 0 ? launch_bwd_df<a, 0>(pack, M, S, xstage, gzt, ts, N, T, gz0, astage, st, dw) \
-                                            : method == 1 ? launch_bwd_df<a, 1>(pack, M, S, xstage, gzt, ts, N, T, gz0, astage, st, dw) \
-                                                          : launch_bwd_df<a, 2>(pack, M, S, xstage, gzt, ts, N, T, gz0, astage, st, dw);
-    GP_BWD_DF_DIMS(X)
-#undef X
-  }
-  return set_error("gpode_rollout_bwd: no specialisation for kernel=%d Di=%d Do=%d", kernel, Di, Do);
+  if (kernel != 0 && order != 1) return set_error("gpode_rollout_bwd: DF kernel is first-order only");
+  return dispatch_dims(who, kernel, Di, Do, [&](auto k, auto di, auto dO) {
+    constexpr int KERNEL = decltype(k)::value, DI = decltype(di)::value, DO = decltype(dO)::value;
+    return dispatch_order<DI, DO>(who, order, [&](auto o) {
+      return dispatch_method(method, [&](auto m) {
+        constexpr int ORDER = decltype(o)::value, METHOD = decltype(m)::value;
+        return reverse_route<KERNEL, DI, DO>(N, M, S, [&](auto ev, const LaunchGeom& g) {
+          using EV = typename decltype(ev)::type;
+          if (launch_route(rollout_bwd_team_kernel<EV, DI, DO, ORDER, METHOD>, g, dw.nd, st, pack, M, S, xstage, gzt, ts, N, T, gz0, astage, dw,
+                           (float*)nullptr, (size_t)0))
+            return 1;
+          return check_launch(tags[KERNEL][g.route]);
+        });
+      });
+    });
+  });
 }
 
 // ---- reverse sweep + parameter sums in one pass (rollout_bwd_team_kernel<..., PG = true>) --------------------------------------
@@ -717,14 +671,18 @@ int rollout_bwd(int kernel, int order, int method, int Di, int Do, int M, int S,
 //  parameter-sum kernel alone takes 432, spills 945 -- besides, at configs[1] its sums (168 us) sit on the side branch, and moving them
 //  into the main branch's sweep lengthens the chain the encoder's backward follows by about what the side branch gets shorter)
 #define GP_PGRAD_RBF_DIMS(X) X(6) X(4) X(2) X(3)
-int rollout_bwd_pgrad_chunks(int kernel, int order, int method, int Di, int Do, int M, int S, int N) {
-  if (order != 1 || Di != Do || (method != 0 && method != 1) || N < 1) return 0;
+// f(int_c<D>) for a width the fused form is built for, 0 for every other
+template <class F> static int pgrad_width(int kernel, int Do, F&& f) {
   if (kernel == 0) {
-#define X(d) if (Do == d) return rbf_team_ok<d, d>(M, S) ? team_grid_b(N) : 0;
+#define X(d) if (Do == d) return f(int_c<d>{});
     GP_PGRAD_RBF_DIMS(X)
 #undef X
   }
   return 0;
+}
+int rollout_bwd_pgrad_chunks(int kernel, int order, int method, int Di, int Do, int M, int S, int N) {
+  if (order != 1 || Di != Do || (method != 0 && method != 1) || N < 1) return 0;
+  return pgrad_width(kernel, Do, [&](auto d) { return rbf_team_ok<decltype(d)::value, decltype(d)::value>(M, S) ? team_grid(N) : 0; });
 }
 int rollout_bwd_pgrad(int kernel, int order, int method, int Di, int Do, int M, int S, const float* pack, const float* xstage,
                       const float* gzt, const float* ts, int N, int T, float* gz0, float* astage, float* slab, int nchunk,
@@ -735,19 +693,14 @@ int rollout_bwd_pgrad(int kernel, int order, int method, int Di, int Do, int M, 
   if (nchunk != grid) return set_error("gpode_rollout_bwd_pgrad: slab for %d chunks, the launch has %d", nchunk, grid);
   size_t pf = 0;
   if (cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
-  bool done = false;
-  if (kernel == 0) {
-#define X(d)                                                                                                                         \
-  if (Do == d) {                                                                                                                     \
-    if (method == 0) hipLaunchKernelGGL((rollout_bwd_team_kernel<RbfTeamEval<d, d, 1>, d, d, 1, 0, true>), dim3(grid, dw.nd), 256, 0, st, \
-                                        pack, M, S, xstage, gzt, ts, N, T, gz0, astage, dw, slab, pf);                               \
-    else hipLaunchKernelGGL((rollout_bwd_team_kernel<RbfTeamEval<d, d, 1>, d, d, 1, 1, true>), dim3(grid, dw.nd), 256, 0, st,        \
-                            pack, M, S, xstage, gzt, ts, N, T, gz0, astage, dw, slab, pf);                                           \
-    done = true;                                                                                                                     \
-  }
-    GP_PGRAD_RBF_DIMS(X)
-#undef X
-  }
+  const int done = pgrad_width(kernel, Do, [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    if (method == 0) hipLaunchKernelGGL((rollout_bwd_team_kernel<RbfTeamEval<D, D, 1>, D, D, 1, 0, true>), dim3(grid, dw.nd), 256, 0, st,
+                                        pack, M, S, xstage, gzt, ts, N, T, gz0, astage, dw, slab, pf);
+    else hipLaunchKernelGGL((rollout_bwd_team_kernel<RbfTeamEval<D, D, 1>, D, D, 1, 1, true>), dim3(grid, dw.nd), 256, 0, st,
+                            pack, M, S, xstage, gzt, ts, N, T, gz0, astage, dw, slab, pf);
+    return 1;
+  });
   if (!done) return set_error("gpode_rollout_bwd_pgrad: width %d not built", Do);
   if (check_launch("rollout_bwd_pgrad")) return 1;
   // the chunk slabs -> the pack-layout gradient of every draw (dw.out2 is astage's draw stride; gpack is dense per draw)
@@ -755,43 +708,18 @@ int rollout_bwd_pgrad(int kernel, int order, int method, int Di, int Do, int M, 
   return check_launch("reduce_slab");
 }
 
-template <int DI, int DO>
-static int launch_vjp_rbf(const float* pack, int M, int S, const float* x, const float* a, int R, float* gx, int prior_only, hipStream_t st, Draws dw) {
-  if constexpr (DO <= 8) {
-    if (rbf_team_ok<DI, DO>(M, S)) {
-      hipLaunchKernelGGL((rhs_vjp_team_kernel<RbfTeamEval<DI, DO, 1>, DI, DO>), dim3(team_grid_b(R), dw.nd), 256, 0, st, pack, M, S, x, a, R, gx, prior_only, dw);
-      return check_launch("rhs_vjp_rbf");
-    }
-  }
-  hipLaunchKernelGGL((rhs_vjp_team_kernel<RbfStreamTeam<DI, DO>, DI, DO>), dim3(team_grid_b(R), dw.nd), 256, 0, st, pack, M, S, x, a, R, gx, prior_only, dw);
-  return check_launch("rhs_vjp_rbf_stream");
-}
-
-template <int D>
-static int launch_vjp_df(const float* pack, int M, int S, const float* x, const float* a, int R, float* gx, int prior_only, hipStream_t st, Draws dw) {
-  if constexpr (D <= 8) {
-    if (df_team_ok<D>(M, S)) {
-      hipLaunchKernelGGL((rhs_vjp_team_kernel<DfTeamEval<D, 1>, D, D>), dim3(team_grid_b(R), dw.nd), 256, 0, st, pack, M, S, x, a, R, gx, prior_only, dw);
-      return check_launch("rhs_vjp_df");
-    }
-  }
-  hipLaunchKernelGGL((rhs_vjp_team_kernel<DfStreamTeam<D>, D, D>), dim3(team_grid_b(R), dw.nd), 256, 0, st, pack, M, S, x, a, R, gx, prior_only, dw);
-  return check_launch("rhs_vjp_df_stream");
-}
-
 int rhs_vjp(int kernel, int Di, int Do, int M, int S, const float* pack, const float* x, const float* a, int R, float* gx,
             int prior_only, hipStream_t st, Draws dw) {
+  static const char* const tags[2][2] = {{"rhs_vjp_rbf", "rhs_vjp_rbf_stream"}, {"rhs_vjp_df", "rhs_vjp_df_stream"}};
   if (R <= 0) return 0;
-  if (kernel == 0) {
-#define X(p, q) if (Di == p && Do == q) return launch_vjp_rbf<p, q>(pack, M, S, x, a, R, gx, prior_only, st, dw);
-    GP_BWD_RBF_DIMS(X)
-#undef X
-  } else {
-#define X(p) if (Di == p && Do == p) return launch_vjp_df<p>(pack, M, S, x, a, R, gx, prior_only, st, dw);
-    GP_BWD_DF_DIMS(X)
-#undef X
-  }
-  return set_error("gpode_rhs_vjp: no specialisation for kernel=%d Di=%d Do=%d", kernel, Di, Do);
+  return dispatch_dims("gpode_rhs_vjp", kernel, Di, Do, [&](auto k, auto di, auto dO) {
+    constexpr int KERNEL = decltype(k)::value, DI = decltype(di)::value, DO = decltype(dO)::value;
+    return reverse_route<KERNEL, DI, DO>(R, M, S, [&](auto ev, const LaunchGeom& g) {
+      using EV = typename decltype(ev)::type;
+      if (launch_route(rhs_vjp_team_kernel<EV, DI, DO>, g, dw.nd, st, pack, M, S, x, a, R, gx, prior_only, dw)) return 1;
+      return check_launch(tags[KERNEL][g.route]);
+    });
+  });
 }
 
 // rows (R,Di) x adjoints (R,Do) -> gpack (pack layout).  slab: nchunk * pack_floats floats of scratch.
@@ -835,17 +763,12 @@ int param_grad(int kernel, int Di, int Do, int M, int S, const float* pack, cons
   if (R <= 0 || nchunk <= 0) return set_error("gpode_param_grad: R=%d nchunk=%d", R, nchunk);
   const int rpc = cdiv(R, nchunk);
   const int used = cdiv(R, rpc);
-  int rc = -1;
-  if (kernel == 0) {
-#define X(p, q) if (Di == p && Do == q) rc = launch_pgrad_rbf<p, q>(pack, M, S, xr, ar, R, rpc, used, slab, pf, prior_only, st, dw, nchunk);
-    GP_BWD_RBF_DIMS(X)
-#undef X
-  } else {
-#define X(p) if (Di == p && Do == p) rc = launch_pgrad_df<p>(pack, M, S, xr, ar, R, rpc, used, slab, pf, prior_only, st, dw, nchunk);
-    GP_BWD_DF_DIMS(X)
-#undef X
-  }
-  if (rc < 0) return set_error("gpode_param_grad: no specialisation for kernel=%d Di=%d Do=%d", kernel, Di, Do);
+  // the parameter-sum kernels are not templated on an evaluator: their own choice, on the predicate of the reverse side
+  const int rc = dispatch_dims("gpode_param_grad", kernel, Di, Do, [&](auto k, auto di, auto dO) {
+    constexpr int DI = decltype(di)::value, DO = decltype(dO)::value;
+    if constexpr (decltype(k)::value == 0) return launch_pgrad_rbf<DI, DO>(pack, M, S, xr, ar, R, rpc, used, slab, pf, prior_only, st, dw, nchunk);
+    else return launch_pgrad_df<DO>(pack, M, S, xr, ar, R, rpc, used, slab, pf, prior_only, st, dw, nchunk);
+  });
   if (rc) return rc;
   const char* route = *last_launch_slot();           // which parameter-sum kernel ran: what the entry point reports (tests/integrator_routes.py)
   hipLaunchKernelGGL(reduce_slab_kernel, dim3((unsigned)((pf + 63) / 64), dw.nd), 1024, 0, st, slab, used, pf, gpack, accumulate, dw.out, nchunk);

@@ -190,181 +190,58 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rollout_team_kernel(const floa
 }
 
 
-template <int DI, int DO>
-static int launch_rhs_rbf(const float* pack, int M, int S, const float* x, int N, float* f, int mode, hipStream_t st, Draws dw) {
-  int grid, block;
-  grid_for(N, grid, block);
-  if (N <= kTeamMaxRows && DO <= 16) {
-    if (RbfTeamEval<DI, DO, 1>::fits(M, S)) {
-      hipLaunchKernelGGL((rhs_team_kernel<RbfTeamEval<DI, DO, 1>, DI, DO>), dim3(team_grid(N), dw.nd), 256, 0, st, pack, M, S, x, N, f, mode, dw);
-      return check_launch("rhs_rbf_team");
-    }
-  }
-  if (N <= kTeamMaxRows) {     // past the register-resident quarter pack: the same team, records streamed from L2
-    hipLaunchKernelGGL((rhs_team_kernel<RbfStreamTeam<DI, DO>, DI, DO>), dim3(team_grid(N), dw.nd), 256, 0, st, pack, M, S, x, N, f, mode, dw);
-    return check_launch("rhs_rbf_team_stream");
-  }
-  const int SJ = cdiv(S, 64), MJ = cdiv(M, 64);
-  if constexpr (rbf_reg_fits<DI, DO, 4, 2>()) {
-    if (SJ == 4 && MJ == 2) {
-      hipLaunchKernelGGL((rhs_kernel<RbfRegEval<DI, DO, 4, 2>, DI, DO, false>), dim3(grid, dw.nd), block, 0, st, pack, M, S, (size_t)0, x, N, f, mode, dw);
-      return check_launch("rhs_rbf_reg42");
-    }
-  }
-  if constexpr (rbf_reg_fits<DI, DO, 1, 1>()) {
-    if (SJ == 1 && MJ == 1) {
-      hipLaunchKernelGGL((rhs_kernel<RbfRegEval<DI, DO, 1, 1>, DI, DO, false>), dim3(grid, dw.nd), block, 0, st, pack, M, S, (size_t)0, x, N, f, mode, dw);
-      return check_launch("rhs_rbf_reg11");
-    }
-  }
-  hipLaunchKernelGGL((rhs_kernel<RbfStreamEval<DI, DO>, DI, DO, false>), dim3(grid, dw.nd), block, 0, st, pack, M, S, (size_t)0, x, N, f, mode, dw);
-  return check_launch("rhs_rbf_stream");
-}
-
-template <int D>
-static int launch_rhs_df(const float* pack, int M, int S, const float* x, int N, float* f, int mode, hipStream_t st, Draws dw) {
-  using L = DfLayout<D>;
-  const size_t f4 = L::rff_f4(S) + L::ind_f4(M);
-  int grid, block;
-  grid_for(N, grid, block);
-  if constexpr (D <= 8) {
-    if (N <= kTeamMaxRows && DfTeamEval<D, 1>::fits(M, S)) {
-      hipLaunchKernelGGL((rhs_team_kernel<DfTeamEval<D, 1>, D, D>), dim3(team_grid(N), dw.nd), 256, 0, st, pack, M, S, x, N, f, mode, dw);
-      return check_launch("rhs_df_team");
-    }
-  }
-  if (N <= kTeamMaxRows) {
-    hipLaunchKernelGGL((rhs_team_kernel<DfStreamTeam<D>, D, D>), dim3(team_grid(N), dw.nd), 256, 0, st, pack, M, S, x, N, f, mode, dw);
-    return check_launch("rhs_df_team_stream");
-  }
-  // N > kTeamMaxRows from here on: a workgroup evaluates many rows, so staging the pack in LDS pays whenever it fits
-  if (f4 * 16 <= kLdsLimitBytes) {
-    block = 256; grid = 256;
-    auto kern = rhs_kernel<DfEval<D, true>, D, D, true>;
-    if (set_max_lds((const void*)kern, f4 * 16)) return 1;
-    hipLaunchKernelGGL(kern, dim3(grid, dw.nd), block, f4 * 16, st, pack, M, S, f4, x, N, f, mode, dw);
-    return check_launch("rhs_df_lds");
-  }
-  hipLaunchKernelGGL((rhs_kernel<DfEval<D, false>, D, D, false>), dim3(grid, dw.nd), block, 0, st, pack, M, S, (size_t)0, x, N, f, mode, dw);
-  return check_launch("rhs_df_stream");
-}
-
-template <int DI, int DO, int ORDER, int METHOD>
-static int launch_rollout_rbf(const float* pack, int M, int S, const float* z0, const float* ts, int N, int T, float* zt, float* xstage, hipStream_t st, Draws dw) {
-  int grid, block;
-  grid_for(N, grid, block);
-  if (N <= kTeamMaxRows && DO <= 16) {
-    if (RbfTeamEval<DI, DO, 1>::fits(M, S)) {
-      hipLaunchKernelGGL((rollout_team_kernel<RbfTeamEval<DI, DO, 1>, DI, DO, ORDER, METHOD>), dim3(team_grid(N), dw.nd), 256, 0, st, pack, M, S, z0, ts, N, T, zt, xstage, dw);
-      return check_launch("rollout_rbf_team");
-    }
-  }
-  if (N <= kTeamMaxRows) {
-    hipLaunchKernelGGL((rollout_team_kernel<RbfStreamTeam<DI, DO>, DI, DO, ORDER, METHOD>), dim3(team_grid(N), dw.nd), 256, 0, st, pack, M, S, z0, ts, N, T, zt, xstage, dw);
-    return check_launch("rollout_rbf_team_stream");
-  }
-  const int SJ = cdiv(S, 64), MJ = cdiv(M, 64);
-  if constexpr (rbf_reg_fits<DI, DO, 4, 2>()) {
-    if (SJ == 4 && MJ == 2) {
-      hipLaunchKernelGGL((rollout_kernel<RbfRegEval<DI, DO, 4, 2>, DI, DO, ORDER, METHOD, false>), dim3(grid, dw.nd), block, 0, st, pack, M, S, (size_t)0, z0, ts, N, T, zt, xstage, dw);
-      return check_launch("rollout_rbf_reg42");
-    }
-  }
-  if constexpr (rbf_reg_fits<DI, DO, 1, 1>()) {
-    if (SJ == 1 && MJ == 1) {
-      hipLaunchKernelGGL((rollout_kernel<RbfRegEval<DI, DO, 1, 1>, DI, DO, ORDER, METHOD, false>), dim3(grid, dw.nd), block, 0, st, pack, M, S, (size_t)0, z0, ts, N, T, zt, xstage, dw);
-      return check_launch("rollout_rbf_reg11");
-    }
-  }
-  hipLaunchKernelGGL((rollout_kernel<RbfStreamEval<DI, DO>, DI, DO, ORDER, METHOD, false>), dim3(grid, dw.nd), block, 0, st, pack, M, S, (size_t)0, z0, ts, N, T, zt, xstage, dw);
-  return check_launch("rollout_rbf_stream");
-}
-
-template <int D, int METHOD>
-static int launch_rollout_df(const float* pack, int M, int S, const float* z0, const float* ts, int N, int T, float* zt, float* xstage, hipStream_t st, Draws dw) {
-  using L = DfLayout<D>;
-  const size_t f4 = L::rff_f4(S) + L::ind_f4(M);
-  int grid, block;
-  grid_for(N, grid, block);
-  if constexpr (D <= 8) {
-    if (N <= kTeamMaxRows && DfTeamEval<D, 1>::fits(M, S)) {
-      hipLaunchKernelGGL((rollout_team_kernel<DfTeamEval<D, 1>, D, D, 1, METHOD>), dim3(team_grid(N), dw.nd), 256, 0, st, pack, M, S, z0, ts, N, T, zt, xstage, dw);
-      return check_launch("rollout_df_team");
-    }
-  }
-  if (N <= kTeamMaxRows) {     // e.g. BASELINE configs[4] (D = 16, M = 512): 4 wavefronts per trajectory, records streamed from L2
-    hipLaunchKernelGGL((rollout_team_kernel<DfStreamTeam<D>, D, D, 1, METHOD>), dim3(team_grid(N), dw.nd), 256, 0, st, pack, M, S, z0, ts, N, T, zt, xstage, dw);
-    return check_launch("rollout_df_team_stream");
-  }
-  if (f4 * 16 <= kLdsLimitBytes) {                 // N > kTeamMaxRows here
-    block = 256; grid = 256;
-    auto kern = rollout_kernel<DfEval<D, true>, D, D, 1, METHOD, true>;
-    if (set_max_lds((const void*)kern, f4 * 16)) return 1;
-    hipLaunchKernelGGL(kern, dim3(grid, dw.nd), block, f4 * 16, st, pack, M, S, f4, z0, ts, N, T, zt, xstage, dw);
-    return check_launch("rollout_df_lds");
-  }
-  hipLaunchKernelGGL((rollout_kernel<DfEval<D, false>, D, D, 1, METHOD, false>), dim3(grid, dw.nd), block, 0, st, pack, M, S, (size_t)0, z0, ts, N, T, zt, xstage, dw);
-  return check_launch("rollout_df_stream");
-}
-
-
+// The evaluator and the grid of either entry point come from forward_route (gp_rollout.hpp); what is left here is the kernel
+// template, its arguments and the tag per route, in the order of LaunchGeom::route.
 int rhs_fwd(int kernel, int Di, int Do, int M, int S, const float* pack, const float* x, int N, float* f, int mode, hipStream_t st, Draws dw) {
-  if (kernel == 0) {
-#define X(a, b) if (Di == a && Do == b) return launch_rhs_rbf<a, b>(pack, M, S, x, N, f, mode, st, dw);
-    GP_RBF_DIMS(X)
-#undef X
-  } else {
-#define X(a) if (Di == a && Do == a) return launch_rhs_df<a>(pack, M, S, x, N, f, mode, st, dw);
-    GP_DF_DIMS(X)
-#undef X
-  }
-  return set_error("gpode_rhs_fwd: no specialisation for kernel=%d Di=%d Do=%d", kernel, Di, Do);
-}
-
-template <int DI, int DO>
-static int rollout_rbf_dispatch(int order, int method, const float* pack, int M, int S, const float* z0, const float* ts, int N, int T, float* zt, float* xstage, hipStream_t st, Draws dw) {
-  if constexpr (DI == DO) {
-    if (order == 1 && method == 0) return launch_rollout_rbf<DI, DO, 1, 0>(pack, M, S, z0, ts, N, T, zt, xstage, st, dw);
-    if (order == 1 && method == 1) return launch_rollout_rbf<DI, DO, 1, 1>(pack, M, S, z0, ts, N, T, zt, xstage, st, dw);
-    if (order == 1 && method == 2) return launch_rollout_rbf<DI, DO, 1, 2>(pack, M, S, z0, ts, N, T, zt, xstage, st, dw);
-  }
-  if constexpr (DI == 2 * DO) {
-    if (order == 2 && method == 0) return launch_rollout_rbf<DI, DO, 2, 0>(pack, M, S, z0, ts, N, T, zt, xstage, st, dw);
-    if (order == 2 && method == 1) return launch_rollout_rbf<DI, DO, 2, 1>(pack, M, S, z0, ts, N, T, zt, xstage, st, dw);
-    if (order == 2 && method == 2) return launch_rollout_rbf<DI, DO, 2, 2>(pack, M, S, z0, ts, N, T, zt, xstage, st, dw);
-  }
-  return set_error("gpode_rollout_fwd: order=%d needs Di == order*Do (Di=%d Do=%d)", order, DI, DO);
+  static const char* const tags[2][kRoutes] = {{"rhs_rbf_team", "rhs_rbf_team_stream", "rhs_rbf_reg42", "rhs_rbf_reg11", "rhs_rbf_stream"},
+                                               {"rhs_df_team", "rhs_df_team_stream", "rhs_df_lds", "rhs_df_stream"}};
+  return dispatch_dims("gpode_rhs_fwd", kernel, Di, Do, [&](auto k, auto di, auto dO) {
+    constexpr int KERNEL = decltype(k)::value, DI = decltype(di)::value, DO = decltype(dO)::value;
+    return forward_route<KERNEL, DI, DO>(N, M, S, [&](auto ev, auto map, const LaunchGeom& g) {
+      using EV = typename decltype(ev)::type;
+      constexpr int MAP = decltype(map)::value;
+      if constexpr (MAP == kTeam) {
+        if (launch_route(rhs_team_kernel<EV, DI, DO>, g, dw.nd, st, pack, M, S, x, N, f, mode, dw)) return 1;
+      } else {
+        if (launch_route(rhs_kernel<EV, DI, DO, MAP == kWaveLds>, g, dw.nd, st, pack, M, S, g.lds_f4, x, N, f, mode, dw)) return 1;
+      }
+      return check_launch(tags[KERNEL][g.route]);
+    });
+  });
 }
 
 int rollout_fwd(int kernel, int order, int method, int Di, int Do, int M, int S, const float* pack,
                 const float* z0, const float* ts, int N, int T, float* zt, float* xstage, hipStream_t st, Draws dw) {
+  static const char* const who = "gpode_rollout_fwd";
+  static const char* const tags[2][kRoutes] = {
+      {"rollout_rbf_team", "rollout_rbf_team_stream", "rollout_rbf_reg42", "rollout_rbf_reg11", "rollout_rbf_stream"},
+      {"rollout_df_team", "rollout_df_team_stream", "rollout_df_lds", "rollout_df_stream"}};
   if (method < 0 || method > 2) return set_error("gpode_rollout_fwd: method %d (0 euler, 1 rk4, 2 midpoint; 3 dopri5: gpode_rollout_adaptive_fwd_n)", method);
-  if (kernel == 0) {
-#define X(a, b) if (Di == a && Do == b) return rollout_rbf_dispatch<a, b>(order, method, pack, M, S, z0, ts, N, T, zt, xstage, st, dw);
-    GP_RBF_DIMS(X)
-#undef X
-  } else {
-    if (order != 1) return set_error("gpode_rollout_fwd: DF kernel is first-order only (kernels.py:259-262)");
-#define X(a) if (Di == a && Do == a) return method == 0 ? launch_rollout_df<a, 0>(pack, M, S, z0, ts, N, T, zt, xstage, st, dw) \
-                                            : method == 1 ? launch_rollout_df<a, 1>(pack, M, S, z0, ts, N, T, zt, xstage, st, dw) \
-                                                          : launch_rollout_df<a, 2>(pack, M, S, z0, ts, N, T, zt, xstage, st, dw);
-    GP_DF_DIMS(X)
-#undef X
-  }
-  return set_error("gpode_rollout_fwd: no specialisation for kernel=%d Di=%d Do=%d", kernel, Di, Do);
+  if (kernel != 0 && order != 1) return set_error("gpode_rollout_fwd: DF kernel is first-order only (kernels.py:259-262)");
+  return dispatch_dims(who, kernel, Di, Do, [&](auto k, auto di, auto dO) {
+    constexpr int KERNEL = decltype(k)::value, DI = decltype(di)::value, DO = decltype(dO)::value;
+    return dispatch_order<DI, DO>(who, order, [&](auto o) {
+      return dispatch_method(method, [&](auto m) {
+        constexpr int ORDER = decltype(o)::value, METHOD = decltype(m)::value;
+        return forward_route<KERNEL, DI, DO>(N, M, S, [&](auto ev, auto map, const LaunchGeom& g) {
+          using EV = typename decltype(ev)::type;
+          constexpr int MAP = decltype(map)::value;
+          if constexpr (MAP == kTeam) {
+            if (launch_route(rollout_team_kernel<EV, DI, DO, ORDER, METHOD>, g, dw.nd, st, pack, M, S, z0, ts, N, T, zt, xstage, dw)) return 1;
+          } else {
+            if (launch_route(rollout_kernel<EV, DI, DO, ORDER, METHOD, MAP == kWaveLds>, g, dw.nd, st, pack, M, S, g.lds_f4, z0, ts, N, T, zt,
+                             xstage, dw))
+              return 1;
+          }
+          return check_launch(tags[KERNEL][g.route]);
+        });
+      });
+    });
+  });
 }
 
 int dims_supported(int kernel, int Di, int Do) {
-  if (kernel == 0) {
-#define X(a, b) if (Di == a && Do == b) return 1;
-    GP_RBF_DIMS(X)
-#undef X
-  } else if (kernel == 1) {
-#define X(a) if (Di == a && Do == a) return 1;
-    GP_DF_DIMS(X)
-#undef X
-  }
-  return 0;
+  return (kernel == 0 || kernel == 1) && for_dims(kernel, Di, Do, [](auto, auto, auto) { return 0; }) == 0;
 }
 
 }  // namespace gp

@@ -1,6 +1,6 @@
 // gp_rollout.hpp -- what the persistent rollout kernels share: the wave-mapped evaluators (policy objects), the ODE right-hand side on
 // the state, the state store, and the host-side launch policy (grid shapes, the team / wave threshold, the compiled widths).
-// Used by gp_forward.hip (fixed-grid solvers) and gp_adaptive.hip (Dormand-Prince).
+// Used by gp_forward.hip (fixed-grid solvers), gp_adaptive.hip (Dormand-Prince) and gp_backward.hip (reverse sweep).
 #pragma once
 #include "gp_eval.hpp"
 #include "gp_team.hpp"
@@ -191,7 +191,9 @@ __device__ __forceinline__ void ode_vjp(EV& ev, const float (&x)[DI], const floa
 }
 
 // ----------------------------------------------------------------------------------------------
-// host-side launch policy
+// host-side launch policy: which evaluator a launch runs on, and its grid.  The ONE place that knows it -- rhs_fwd and rollout_fwd
+// (gp_forward.hip), the landing and dense dopri5 (gp_adaptive.hip) and the reverse sweeps (gp_backward.hip, gp_adaptive.hip) hand
+// forward_route / reverse_route a callable and supply only their kernel template, its arguments and their tags.
 // ----------------------------------------------------------------------------------------------
 static const size_t kLdsLimitBytes = 150 * 1024;  // 160 KiB per CU; leave headroom
 
@@ -220,8 +222,107 @@ template <int D> static bool df_team_ok(int M, int S) {
   return false;
 }
 
+template <int V> using int_c = std::integral_constant<int, V>;
+template <class T> struct type_c { using type = T; };
+
+// A route: the evaluator (a type), the mapping (a type) and this.  `route` numbers the family's routes in the order of the ladder
+// below -- the index into a consumer's table of tags.  lds_f4: float4 of pack a wave kernel stages in LDS, 0 on every other route.
+enum Mapping { kTeam, kWave, kWaveLds };             // one workgroup of four wavefronts per row / one wavefront per row (pack in LDS)
+using team_c = int_c<kTeam>;
+using wave_c = int_c<kWave>;
+using wave_lds_c = int_c<kWaveLds>;
+struct LaunchGeom { int route, grid, block; size_t lds_f4; };
+enum { kRouteTeam, kRouteTeamStream, kRouteRbfReg42, kRouteRbfReg11, kRouteRbfStream, kRouteDfLds = 2, kRouteDfStream, kRoutes = 5 };
+
+// The forward ladder of a kernel family (KERNEL 0: RBF, 1: divergence-free, DI = DO) at N rows: f(type_c<EV>, mapping, geometry).
+template <int KERNEL, int DI, int DO, class F> static int forward_route(int N, int M, int S, F&& f) {
+  int grid, block;
+  grid_for(N, grid, block);
+  if constexpr (KERNEL == 0) {
+    if (N <= kTeamMaxRows && DO <= 16) {
+      if (RbfTeamEval<DI, DO, 1>::fits(M, S)) return f(type_c<RbfTeamEval<DI, DO, 1>>{}, team_c{}, LaunchGeom{kRouteTeam, team_grid(N), 256, 0});
+    }
+    if (N <= kTeamMaxRows)       // past the register-resident quarter pack: the same team, records streamed from L2
+      return f(type_c<RbfStreamTeam<DI, DO>>{}, team_c{}, LaunchGeom{kRouteTeamStream, team_grid(N), 256, 0});
+    const int SJ = cdiv(S, 64), MJ = cdiv(M, 64);
+    if constexpr (rbf_reg_fits<DI, DO, 4, 2>()) {
+      if (SJ == 4 && MJ == 2) return f(type_c<RbfRegEval<DI, DO, 4, 2>>{}, wave_c{}, LaunchGeom{kRouteRbfReg42, grid, block, 0});
+    }
+    if constexpr (rbf_reg_fits<DI, DO, 1, 1>()) {
+      if (SJ == 1 && MJ == 1) return f(type_c<RbfRegEval<DI, DO, 1, 1>>{}, wave_c{}, LaunchGeom{kRouteRbfReg11, grid, block, 0});
+    }
+    return f(type_c<RbfStreamEval<DI, DO>>{}, wave_c{}, LaunchGeom{kRouteRbfStream, grid, block, 0});
+  } else {
+    static_assert(DI == DO, "the divergence-free kernel maps R^D to R^D");
+    using L = DfLayout<DO>;
+    const size_t f4 = L::rff_f4(S) + L::ind_f4(M);
+    if constexpr (DO <= 8) {
+      if (N <= kTeamMaxRows && DfTeamEval<DO, 1>::fits(M, S)) return f(type_c<DfTeamEval<DO, 1>>{}, team_c{}, LaunchGeom{kRouteTeam, team_grid(N), 256, 0});
+    }
+    if (N <= kTeamMaxRows)       // e.g. BASELINE configs[4] (D = 16, M = 512): 4 wavefronts per trajectory, records streamed from L2
+      return f(type_c<DfStreamTeam<DO>>{}, team_c{}, LaunchGeom{kRouteTeamStream, team_grid(N), 256, 0});
+    // N > kTeamMaxRows from here on: a workgroup evaluates many rows, so staging the pack in LDS pays whenever it fits
+    if (f4 * 16 <= kLdsLimitBytes) return f(type_c<DfEval<DO, true>>{}, wave_lds_c{}, LaunchGeom{kRouteDfLds, 256, 256, f4});
+    return f(type_c<DfEval<DO, false>>{}, wave_c{}, LaunchGeom{kRouteDfStream, grid, block, 0});
+  }
+}
+
+// The reverse side (rollout_bwd, rhs_vjp, the dopri5 sweeps) runs on a team at any number of rows: register-resident (route 0) when
+// the quarter pack fits and D <= 8 -- a narrower limit than the forward team's, the sweep holds the adjoints as well -- streamed
+// (route 1) otherwise: f(type_c<EV>, geometry).
+template <int KERNEL, int DI, int DO, class F> static int reverse_route(int rows, int M, int S, F&& f) {
+  if constexpr (DO <= 8) {
+    if constexpr (KERNEL == 0) {
+      if (rbf_team_ok<DI, DO>(M, S)) return f(type_c<RbfTeamEval<DI, DO, 1>>{}, LaunchGeom{kRouteTeam, team_grid(rows), 256, 0});
+    } else {
+      if (df_team_ok<DO>(M, S)) return f(type_c<DfTeamEval<DO, 1>>{}, LaunchGeom{kRouteTeam, team_grid(rows), 256, 0});
+    }
+  }
+  using Stream = std::conditional_t<KERNEL == 0, RbfStreamTeam<DI, DO>, DfStreamTeam<DO>>;
+  return f(type_c<Stream>{}, LaunchGeom{kRouteTeamStream, team_grid(rows), 256, 0});
+}
+
+// The launch of a route, draws on gridDim.y.  A pack staged in LDS may pass the 64 KB a kernel gets by default: set_max_lds.
+template <class... P, class... A> static int launch_route(void (*kern)(P...), const LaunchGeom& g, int nd, hipStream_t st, A... args) {
+  if (set_max_lds((const void*)kern, g.lds_f4 * 16)) return 1;
+  hipLaunchKernelGGL(kern, dim3(g.grid, nd), g.block, g.lds_f4 * 16, st, args...);
+  return 0;
+}
+
 // dispatch tables -----------------------------------------------------------------------------
 #define GP_RBF_DIMS(X) X(6, 6) X(6, 3) X(4, 4) X(4, 2) X(2, 2) X(2, 1) X(8, 8) X(8, 4) X(16, 16) X(16, 8) X(3, 3) X(12, 6)
 #define GP_DF_DIMS(X) X(6) X(4) X(2) X(3) X(8) X(16) X(5) X(7) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
+
+// The compiled widths of a kernel family (0: RBF, anything else: divergence-free): f(int_c<KERNEL>, int_c<DI>, int_c<DO>), which
+// returns 0 or 1; -1 for a width that is not compiled.
+template <class F> static int for_dims(int kernel, int Di, int Do, F&& f) {
+  if (kernel == 0) {
+#define X(a, b) if (Di == a && Do == b) return f(int_c<0>{}, int_c<a>{}, int_c<b>{});
+    GP_RBF_DIMS(X)
+#undef X
+  } else {
+#define X(a) if (Di == a && Do == a) return f(int_c<1>{}, int_c<a>{}, int_c<a>{});
+    GP_DF_DIMS(X)
+#undef X
+  }
+  return -1;
+}
+// the same for an entry point: who names it in the error text
+template <class F> static int dispatch_dims(const char* who, int kernel, int Di, int Do, F&& f) {
+  const int rc = for_dims(kernel, Di, Do, f);
+  return rc < 0 ? set_error("%s: no specialisation for kernel=%d Di=%d Do=%d", who, kernel, Di, Do) : rc;
+}
+
+// Order 1 or 2 of a compiled width, whichever DI == ORDER * DO allows: f(int_c<ORDER>).
+template <int DI, int DO, class F> static int dispatch_order(const char* who, int order, F&& f) {
+  if constexpr (DI == DO) { if (order == 1) return f(int_c<1>{}); }
+  if constexpr (DI == 2 * DO) { if (order == 2) return f(int_c<2>{}); }
+  return set_error("%s: order=%d needs Di == order*Do (Di=%d Do=%d)", who, order, DI, DO);
+}
+
+// The fixed-grid solver, 0 euler, 1 rk4, 2 midpoint (the caller has refused every other value): f(int_c<METHOD>).
+template <class F> static int dispatch_method(int method, F&& f) {
+  return method == 0 ? f(int_c<0>{}) : method == 1 ? f(int_c<1>{}) : f(int_c<2>{});
+}
 
 }  // namespace gp

@@ -332,6 +332,25 @@ def _z0_per_draw(cache, z0):
     return 1
 
 
+def _rollout_args(cache, z0, ts, order):
+    """What rollout and rollout_adaptive check alike: z0, ts (contiguous), the z0_per_draw flag, N and the state dimension."""
+    z0 = _chk(z0, 'z0'); ts = _chk(ts, 'ts')
+    zpd = _z0_per_draw(cache, z0)
+    N, D = z0.shape[-2:]
+    if D != cache.Di or D != order * cache.Do:
+        raise _lib.GpodeError('state dim %d must equal D_in=%d = order*D_out=%d' % (D, cache.Di, order * cache.Do))
+    return z0, ts, zpd, N, D
+
+
+def _gzt_lead(cache, gzt):
+    """gzt ([L,] N,T,D) of rollout_bwd and rollout_adaptive_bwd, contiguous, and the leading draw axis of the cache it must carry"""
+    gzt = _chk(gzt, 'gzt')
+    lead = cache.lead
+    if gzt.dim() != 3 + len(lead) or tuple(gzt.shape[:len(lead)]) != lead:
+        raise _lib.GpodeError('gzt: expected %s + (N,T,D), got %s' % (lead, tuple(gzt.shape)))
+    return gzt, lead
+
+
 def rollout_adaptive(cache, z0, ts, order, rtol=1e-6, atol=1e-6, max_steps=None, save_stages=False, dense=False):
     """Adaptive Dormand-Prince 5(4) rollout (gpode_rollout_adaptive_fwd_n): one step-size controller per trajectory, steps landing
     on ts.  ``max_steps`` = accepted steps a trajectory may take (default 4 (T-1)).  -> zt ([L,] N,T,D), counts ([L,] N,4) int32
@@ -341,11 +360,7 @@ def rollout_adaptive(cache, z0, ts, order, rtol=1e-6, atol=1e-6, max_steps=None,
     continuous extension, no evaluation of f); the record is then xstage ([L,] N,K,7,D), hstep, istep ([L,] N,T-1) int32 = 1-based
     number of the accepted step that holds output t+1, theta ([L,] N,T-1) = the output's position inside that step, in (0, 1].
     z0 (L,N,D) with L = cache.nd gives every draw its own initial states (gpode_rollout_adaptive_fwd_nz / _dense_fwd_nz)."""
-    z0 = _chk(z0, 'z0'); ts = _chk(ts, 'ts')
-    zpd = _z0_per_draw(cache, z0)
-    N, D = z0.shape[-2:]
-    if D != cache.Di or D != order * cache.Do:
-        raise _lib.GpodeError('state dim %d must equal D_in=%d = order*D_out=%d' % (D, cache.Di, order * cache.Do))
+    z0, ts, zpd, N, D = _rollout_args(cache, z0, ts, order)
     T = ts.shape[0]
     K = 4 * max(T - 1, 0) if max_steps is None else int(max_steps)
     if K < 0:
@@ -360,31 +375,22 @@ def rollout_adaptive(cache, z0, ts, order, rtol=1e-6, atol=1e-6, max_steps=None,
         hs = torch.empty(lead + (N, K), dtype=torch.float32, device=dev)
         ie = torch.empty(lead + (N, max(T - 1, 0)), dtype=torch.int32, device=dev)
         th = torch.empty(lead + (N, max(T - 1, 0)), dtype=torch.float32, device=dev) if dense else None
-    if dense:
-        head = (KERNEL_ID[cache.kernel], order, METHOD_ID['dopri5'], cache.Di, cache.Do, cache.M, cache.S, cache.nd, _ptr(cache.pack),
-                _ptr(z0), _ptr(ts), N, T, float(rtol), float(atol), K, _ptr(zt), _ptr(xs), _ptr(hs), _ptr(ie), _ptr(th), _ptr(counts))
-        if zpd:
-            _lib.call('gpode_rollout_dense_fwd_nz', *head, zpd, _stream())
-        else:
-            _lib.call('gpode_rollout_dense_fwd_n', *head, _stream())
-        return (zt, counts, xs, hs, ie, th) if save_stages else (zt, counts)
     head = (KERNEL_ID[cache.kernel], order, METHOD_ID['dopri5'], cache.Di, cache.Do, cache.M, cache.S, cache.nd, _ptr(cache.pack),
-            _ptr(z0), _ptr(ts), N, T, float(rtol), float(atol), K, _ptr(zt), _ptr(xs), _ptr(hs), _ptr(ie), _ptr(counts))
+            _ptr(z0), _ptr(ts), N, T, float(rtol), float(atol), K, _ptr(zt), _ptr(xs), _ptr(hs), _ptr(ie))
+    head += (_ptr(th), _ptr(counts)) if dense else (_ptr(counts),)
+    name = 'gpode_rollout_dense_fwd' if dense else 'gpode_rollout_adaptive_fwd'
     if zpd:
-        _lib.call('gpode_rollout_adaptive_fwd_nz', *head, zpd, _stream())
+        _lib.call(name + '_nz', *head, zpd, _stream())
     else:
-        _lib.call('gpode_rollout_adaptive_fwd_n', *head, _stream())
-    return (zt, counts, xs, hs, ie) if save_stages else (zt, counts)
+        _lib.call(name + '_n', *head, _stream())
+    return ((zt, counts, xs, hs, ie) + ((th,) if dense else ())) if save_stages else (zt, counts)
 
 
 def rollout_adaptive_bwd(cache, xstage, hstep, iend, gzt, order, theta=None):
     """Reverse sweep over the recorded accepted steps: gzt ([L,] N,T,D) -> gz0 ([L,] N,D), astage ([L,] N,K,6,Do), zero past the count.
     With ``theta`` the record is a dense-output one (xstage ([L,] N,K,7,D), iend = its istep; gpode_rollout_dense_bwd_n): astage
     ([L,] N,K,7,Do), row 6 zero in the steps that hold no interior output."""
-    gzt = _chk(gzt, 'gzt')
-    lead = cache.lead
-    if gzt.dim() != 3 + len(lead) or tuple(gzt.shape[:len(lead)]) != lead:
-        raise _lib.GpodeError('gzt: expected %s + (N,T,D), got %s' % (lead, tuple(gzt.shape)))
+    gzt, lead = _gzt_lead(cache, gzt)
     N, T, D = gzt.shape[-3:]
     K = hstep.shape[-1]
     NS = NSTAGE['dopri5'] if theta is None else NSTAGE_DENSE
@@ -417,11 +423,7 @@ def rollout(cache, z0, ts, order, method, save_stages=False, rtol=1e-6, atol=1e-
     if method == 'dopri5':
         out = rollout_adaptive(cache, z0, ts, order, rtol, atol, max_steps, save_stages, dense=dense)
         return (out[0], (out[2], out[3], out[4], out[1]) + tuple(out[5:])) if save_stages else out[0]
-    z0 = _chk(z0, 'z0'); ts = _chk(ts, 'ts')
-    zpd = _z0_per_draw(cache, z0)
-    N, D = z0.shape[-2:]
-    if D != cache.Di or D != order * cache.Do:
-        raise _lib.GpodeError('state dim %d must equal D_in=%d = order*D_out=%d' % (D, cache.Di, order * cache.Do))
+    z0, ts, zpd, N, D = _rollout_args(cache, z0, ts, order)
     T = ts.shape[0]
     lead = cache.lead
     zt = torch.empty(lead + (N, T, D), dtype=torch.float32, device=z0.device)
@@ -440,10 +442,7 @@ def rollout_bwd(cache, xstage, gzt, ts, order, method):
     ([L,] N,K,6,Do), or ([L,] N,K,7,Do) for a dense-output record)."""
     if method == 'dopri5':
         return rollout_adaptive_bwd(cache, xstage[0], xstage[1], xstage[2], gzt, order, theta=xstage[4] if len(xstage) > 4 else None)
-    gzt = _chk(gzt, 'gzt'); xstage = _chk(xstage, 'xstage'); ts = _chk(ts, 'ts')
-    lead = cache.lead
-    if gzt.dim() != 3 + len(lead) or tuple(gzt.shape[:len(lead)]) != lead:
-        raise _lib.GpodeError('gzt: expected %s + (N,T,D), got %s' % (lead, tuple(gzt.shape)))
+    (gzt, lead), xstage, ts = _gzt_lead(cache, gzt), _chk(xstage, 'xstage'), _chk(ts, 'ts')
     N, T, D = gzt.shape[-3:]
     gz0 = torch.empty(lead + (N, D), dtype=torch.float32, device=gzt.device)
     ast = torch.empty(lead + (N, T - 1, NSTAGE[method], cache.Do), dtype=torch.float32, device=gzt.device)
