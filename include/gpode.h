@@ -425,7 +425,8 @@ int gpode_chan_sum(const float* v, float* out, int B, int C, int HW, float* scra
 int gpode_act_fwd(const float* x, float* y, size_t n, int mode, void* stream);
 int gpode_act_bwd(const float* y, const float* gy, float* gx, size_t n, int mode, void* stream);
 /* nn.Linear (vae.py:64,107): x (B,In), w (Out,In).  scratch: gpode_linear_bwd_scratch(B, In, Out) floats, or NULL (the weight
- * gradient of a narrow, tall layer -- the decoder's fc at thousands of rows -- is then summed without row slabs, ~3x slower). */
+ * gradient of a narrow, tall layer -- the decoder's fc at thousands of rows -- is then summed without row slabs, ~3x slower).
+ * Each of gx, gw, gb may be NULL: that gradient is not computed, the others are (gb without gw included). */
 int gpode_linear_fwd(const float* x, const float* w, const float* bias, float* y, int B, int In, int Out, void* stream);
 size_t gpode_linear_bwd_scratch(int B, int In, int Out);
 int gpode_linear_bwd(const float* x, const float* w, const float* gy, float* gx, float* gw, float* gb, int B, int In, int Out,

@@ -180,6 +180,7 @@ __global__ __launch_bounds__(256) void k_linear_bwd_w(const float* __restrict__ 
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
   if (wave >= Out * (In + 1)) return;
   const int o = wave / (In + 1), i = wave % (In + 1);
+  if (i < In ? !gw : !gb) return;                    // gw == NULL: only the bias column is summed
   float acc = 0.f;
   for (int b = lane; b < B; b += 64) {
     float xv = i < In ? x[(size_t)b * In + i] : 1.f;
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(256) void k_linear_bwd_w(const float* __restrict__ 
   }
   float in1[1] = {acc}, out1[1];
   wave_sum_multi<1>(in1, out1);
-  if (lane == 0) { if (i < In) gw[(size_t)o * In + i] = out1[0]; else if (gb) gb[o] = out1[0]; }
+  if (lane == 0) { if (i < In) gw[(size_t)o * In + i] = out1[0]; else gb[o] = out1[0]; }
 }
 
 // The same sums for the decoder's fc layer at thousands of rows (q -> 512 on batch x T latent states, vae.py:101): a workgroup owns 64
@@ -487,8 +488,10 @@ int linear_bwd(const float* x, const float* w, const float* gy, float* gx, float
 #undef X
       }
     }
-    if (gw) {
-      if (scratch && In <= 8 && B >= 1024) {
+    bool slabs = false;
+    if (gw || gb) {
+      if (gw && scratch && In <= 8 && B >= 1024) {
+        slabs = true;
         const int rps = (B + LINW_SLABS - 1) / LINW_SLABS, used = (B + rps - 1) / rps;
         float* partW = scratch;
         float* partB = scratch + (size_t)LINW_SLABS * Out * In;
@@ -499,10 +502,10 @@ int linear_bwd(const float* x, const float* w, const float* gy, float* gx, float
         hipLaunchKernelGGL(k_linear_bwd_w, (unsigned)(((size_t)Out * (In + 1) * 64 + 255) / 256), 256, 0, st, x, gy, gw, gb, B, In, Out, 0);
       }
     }
-    return check_launch("linear_bwd_fanout");
+    return check_launch(slabs ? "linear_bwd_fanout (row slabs)" : "linear_bwd_fanout");
   }
   if (gx) hipLaunchKernelGGL(k_linear_bwd_x, (unsigned)(((size_t)B * In + 255) / 256), 256, 0, st, gy, w, gx, B, In, Out, (const float*)nullptr);
-  if (gw) hipLaunchKernelGGL(k_linear_bwd_w, (unsigned)(((size_t)Out * (In + 1) * 64 + 255) / 256), 256, 0, st, x, gy, gw, gb, B, In, Out, 0);
+  if (gw || gb) hipLaunchKernelGGL(k_linear_bwd_w, (unsigned)(((size_t)Out * (In + 1) * 64 + 255) / 256), 256, 0, st, x, gy, gw, gb, B, In, Out, 0);
   return check_launch("linear_bwd");
 }
 
@@ -516,7 +519,7 @@ int linear_relu_fwd(const float* x, const float* w, const float* bias, float* y,
 int linear_relu_bwd(const float* x, const float* w, const float* gy, float* gx, float* gw, float* gb, int B, int In, int Out, hipStream_t st) {
   if (In < 128) return set_error("gpode_linear_relu_bwd: built for wide fan-in layers (In >= 128)");
   if (gx) hipLaunchKernelGGL(k_linear_bwd_x, (unsigned)(((size_t)B * In + 255) / 256), 256, 0, st, gy, w, gx, B, In, Out, x);
-  if (gw) hipLaunchKernelGGL(k_linear_bwd_w, (unsigned)(((size_t)Out * (In + 1) * 64 + 255) / 256), 256, 0, st, x, gy, gw, gb, B, In, Out, 1);
+  if (gw || gb) hipLaunchKernelGGL(k_linear_bwd_w, (unsigned)(((size_t)Out * (In + 1) * 64 + 255) / 256), 256, 0, st, x, gy, gw, gb, B, In, Out, 1);
   return check_launch("linear_relu_bwd");
 }
 
@@ -890,6 +893,7 @@ __global__ void k_elbo_loglik_bwd(const float* __restrict__ g0p, const float* __
 }
 
 int sigmoid_loglik_splits(size_t rows, size_t inner) {
+  if (rows == 0 || inner == 0) return 1;             // nothing to split (and no division by rows)
   size_t ns = (1024 + rows - 1) / rows, cap = (inner + 1023) / 1024;
   if (ns > cap) ns = cap;
   if (ns > 64) ns = 64;
@@ -920,7 +924,7 @@ int elbo_all_fwd(const float* lpart, int nl_rows, int nl_values, const float* hs
     usq = out + 4;
   }
   hipLaunchKernelGGL(k_elbo_all_fwd, 1, 1024, 0, st, lpart, nl_rows, nl_values, hs, hv, N, q, M, Do, Um, Us, nobs, out, usq, (const float*)nullptr, 0, (const float*)nullptr, 0);
-  return check_launch("elbo_all_fwd");
+  return check_launch(usq ? "elbo_all_fwd (Us in parts)" : "elbo_all_fwd");
 }
 int elbo_all_bwd(const float* g0, const float* g1, const float* g2, const float* g3, int nl_rows, const float* hs, const float* hv, int N,
                  int q, int M, int Do, const float* Um, const float* Us, float nobs, float* glrow, float* ghs, float* ghv, float* dUm,
@@ -966,7 +970,7 @@ int elbo_all_fwd_kl(const float* lpart, int nl_rows, int nl_values, const float*
   }
   hipLaunchKernelGGL(k_elbo_all_fwd, 1, 1024, 0, st, lpart, nl_rows, nl_values, (const float*)nullptr, (const float*)nullptr, N, 1, M, Do, Um, Us, nobs,
                      out, usq, kls, nks, klv, nkv);
-  return check_launch("elbo_all_fwd_kl");
+  return check_launch(usq ? "elbo_all_fwd_kl (Us in parts)" : "elbo_all_fwd_kl");
 }
 int elbo_all_bwd_ll_kl(const float* g0, const float* g1, const float* g2, const float* g3, int nl_rows, int N, int M, int Do, const float* Um,
                        const float* Us, float nobs, float* glrow, float* gkls, int nks, float* gklv, int nkv, float* dUm, float* dUs,
