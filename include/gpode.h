@@ -191,6 +191,38 @@ int gpode_rollout_dense_fwd_nz(int kernel, int order, int method, int Di, int Do
                                const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
                                float* zt, float* xstage, float* hstep, int* istep, float* theta, int* counts, int z0_per_draw,
                                void* stream);
+/* The rollouts and the fixed-grid reverse sweeps with a time grid PER TRAJECTORY (sequences observed at their own times): the
+ * arguments of the twin named plus `ts_per_traj`, directly in front of `stream`.
+ *   gpode_rollout_fwd_nt           gpode_rollout_fwd_nz             gpode_rollout_bwd_nt         gpode_rollout_bwd_n
+ *   gpode_rollout_adaptive_fwd_nt  gpode_rollout_adaptive_fwd_nz    gpode_rollout_bwd_pgrad_nt   gpode_rollout_bwd_pgrad_n
+ *   gpode_rollout_dense_fwd_nt     gpode_rollout_dense_fwd_nz
+ *   ts_per_traj = 0   ts is (T,), shared by all trajectories: the same launch, the same bits as the twin
+ *   ts_per_traj = 1   ts is (N,T), dense: row n is the grid of trajectory n of EVERY draw -- a grid belongs to the sequence, not to
+ *                     the function draw, so it has no draw axis
+ * Any other value is refused before anything is launched (gpode_last_error() says so).  The route, and with it the tag
+ * gpode_last_launch() returns, does not depend on the grid.  Every other operand keeps the layout of the twin; T is the same for all
+ * trajectories (sequences with different numbers of observations are not covered).  The adaptive reverse sweeps read the recorded
+ * step sizes and theta only, never ts: gpode_rollout_adaptive_bwd_n / gpode_rollout_dense_bwd_n serve either kind of grid.
+ * Status 3 of the adaptive rollouts is per trajectory here: only the trajectory whose own row is not strictly increasing stops
+ * (landing mode: at the first interval that is not; dense mode: before its first step) and turns NaN from the first output it did
+ * not reach; every other trajectory of the launch is unaffected. */
+int gpode_rollout_fwd_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                         const float* pack, const float* z0, const float* ts, int N, int T,
+                         float* zt, float* xstage, int z0_per_draw, int ts_per_traj, void* stream);
+int gpode_rollout_adaptive_fwd_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                                  const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
+                                  float* zt, float* xstage, float* hstep, int* iend, int* counts, int z0_per_draw, int ts_per_traj,
+                                  void* stream);
+int gpode_rollout_dense_fwd_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                               const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
+                               float* zt, float* xstage, float* hstep, int* istep, float* theta, int* counts, int z0_per_draw,
+                               int ts_per_traj, void* stream);
+int gpode_rollout_bwd_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                         const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
+                         float* gz0, float* astage, int ts_per_traj, void* stream);
+int gpode_rollout_bwd_pgrad_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                               const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
+                               float* gz0, float* astage, float* slab, int nchunk, float* gpack, int ts_per_traj, void* stream);
 /* gpode_rollout_bwd_n and gpode_param_grad_n in ONE pass: the reverse sweep visits every (stage input, adjoint) row anyway, so the
  * rows' parameter-gradient terms are accumulated on the way and come out as gpack (ndraws, pack_floats) -- what the two calls
  * produce together, with one launch and one pass over the rows less.  slab: ndraws * nchunk * pack_floats floats of scratch with

@@ -9,8 +9,20 @@ variant between two events; the variants take turns, ``--reps`` windows each, an
 the time per call.
 
     python tools/time_dopri5.py [--workload cfg1] [--reps 20] [--window 10] [--tol 1e-3 1e-5] [--dense] [--out FILE.json]
+
+--per_traj_ts measures what a time grid per trajectory costs instead: rk4, dopri5 landing and dopri5 dense (at the first --tol), each as
+rollout, rollout with record and reverse sweep, in three variants that take turns window by window --
+  shared    ts (T,), the launches as they always were
+  per_traj  the same grid values expanded to (N,T): the `_nt` entry points, the same arithmetic, one row pointer per trajectory
+  parent    `shared` through the library of the parent commit given with --parent_lib SO (loaded next to this build's, the same process)
+and reports per entry the medians, the window spreads (max - min over the median), `shared_vs_parent` = shared / parent - 1 with its
+condition -- not beyond the larger of the two spreads -- and `per_traj_vs_shared` = per_traj / shared - 1, which is reported, not gated.
+(The adaptive reverse sweeps never read ts: their two variants of this build are the same launch and measure the windows' noise.)
+
+    python tools/time_dopri5.py --per_traj_ts [--parent_lib SO] [--workload cfg1] [--reps 20] [--window 10] [--tol 1e-4] [--out FILE.json]
 """
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -40,6 +52,79 @@ def timed_together(fns, reps, window):
     return {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
 
 
+def timed_windows(fns, reps, window):
+    """timed_together, keeping every window: {name: [ms per call, one per window]}"""
+    for f in fns.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, f in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(window):
+                f()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / window)
+    return ms
+
+
+def time_grids(a, ops, c, z0, ts, order, gw, res):
+    """--per_traj_ts: shared against per-trajectory grids, and against the parent's library (see the module docstring)"""
+    from vae_gp_ode_amd import _lib
+    N, tol = z0.shape[0], a.tol[0]
+    rows = ts[None].expand(N, -1).contiguous()
+    this, parent = _lib.load(), None
+    if a.parent_lib:
+        parent = ctypes.CDLL(os.path.abspath(a.parent_lib))
+        for name, (rt, args) in _lib.SIGNATURES.items():
+            if hasattr(parent, name):                  # the parent's header is a subset of this build's
+                getattr(parent, name).restype, getattr(parent, name).argtypes = rt, args
+
+    def through_parent(f):
+        def g():
+            _lib._lib = parent
+            try:
+                return f()
+            finally:
+                _lib._lib = this
+        return g
+    _, xs4 = ops.rollout(c, z0, ts, order, 'rk4', save_stages=True)
+    entries = {}                                       # entry -> grid -> callable
+    entries['rk4.fwd'] = lambda t: (lambda: ops.rollout(c, z0, t, order, 'rk4'))
+    entries['rk4.fwd_record'] = lambda t: (lambda: ops.rollout(c, z0, t, order, 'rk4', save_stages=True))
+    entries['rk4.bwd'] = lambda t: (lambda: ops.rollout_bwd(c, xs4, gw, t, order, 'rk4'))
+    for name, dense in (('landing', False), ('dense', True)):
+        rec = ops.rollout_adaptive(c, z0, ts, order, tol, tol, save_stages=True, dense=dense)
+        rec_t = ops.rollout_adaptive(c, z0, rows, order, tol, tol, save_stages=True, dense=dense)
+        res[name + '_same_bits'] = all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(rec, rec_t))
+        res[name] = stats(rec[1], rec[3].shape[-1])
+        entries[name + '.fwd'] = lambda t, dense=dense: (lambda: ops.rollout_adaptive(c, z0, t, order, tol, tol, dense=dense))
+        entries[name + '.fwd_record'] = lambda t, dense=dense: (lambda: ops.rollout_adaptive(c, z0, t, order, tol, tol, save_stages=True, dense=dense))
+        entries[name + '.bwd'] = lambda t, rec=rec: (lambda: ops.rollout_adaptive_bwd(c, rec[2], rec[3], rec[4], gw, order,
+                                                                                       theta=rec[5] if len(rec) > 5 else None))
+    res['tol'], res['parent_lib'] = tol, bool(parent)
+    ok = True
+    for entry, make in entries.items():
+        fns = {'shared': make(ts), 'per_traj': make(rows)}
+        if parent is not None:
+            fns['parent'] = through_parent(make(ts))
+        win = timed_windows(fns, a.reps, a.window)
+        med = {k: sorted(v)[len(v) // 2] for k, v in win.items()}
+        spread = {k: round((max(v) - min(v)) / med[k], 4) for k, v in win.items()}
+        r = dict(ms={k: round(v, 5) for k, v in med.items()}, spread=spread, per_traj_vs_shared=round(med['per_traj'] / med['shared'] - 1, 4))
+        if parent is not None:
+            r['shared_vs_parent'] = round(med['shared'] / med['parent'] - 1, 4)
+            r['shared_vs_parent_allowed'] = max(spread['shared'], spread['parent'])
+            r['shared_not_slower_than_parent'] = r['shared_vs_parent'] <= r['shared_vs_parent_allowed']
+            ok = ok and r['shared_not_slower_than_parent']
+        res[entry] = r
+    if parent is not None:
+        res['shared_not_slower_than_parent'] = ok
+
+
 def stats(cnt, budget):
     cnt = cnt.cpu().long()
     return dict(accepted_mean=cnt[:, 0].float().mean().item(), accepted_max=int(cnt[:, 0].max()), rejected_mean=cnt[:, 1].float().mean().item(),
@@ -56,6 +141,9 @@ def main():
     ap.add_argument('--tol', type=float, nargs='+', default=[1e-3, 1e-5])
     ap.add_argument('--dense', action='store_true', help='time the dense-output mode next to the landing mode and rk4')
     ap.add_argument('--out', default=None, help='also write the JSON result to this file')
+    ap.add_argument('--per_traj_ts', action='store_true', help='time a time grid per trajectory (the same grid values, expanded to (N,T)) '
+                                                              'against the shared grid, rk4 and dopri5 landing / dense')
+    ap.add_argument('--parent_lib', default=None, help="with --per_traj_ts: the parent commit's libgpode_hip.so, timed in the same windows")
     a = ap.parse_args()
     w = bench.WORKLOADS[a.workload]
     dev = torch.device('cuda:0')
@@ -70,6 +158,13 @@ def main():
 
     res = {'workload': w['desc'], 'reps': a.reps, 'window': a.window, 'N': int(z0.shape[0]), 'T': int(ts.shape[0]),
            'rk4_evals': 4 * (ts.shape[0] - 1)}
+    if a.per_traj_ts:
+        time_grids(a, ops, c, z0, ts, order, gw, res)
+        print(json.dumps(res))
+        if a.out:
+            with open(a.out, 'w') as f:
+                f.write(json.dumps(res, indent=1) + '\n')
+        return
     _, xs4 = ops.rollout(c, z0, ts, order, 'rk4', save_stages=True)
     rk4 = {'rk4_fwd_ms': lambda: ops.rollout(c, z0, ts, order, 'rk4'),
            'rk4_fwd_record_ms': lambda: ops.rollout(c, z0, ts, order, 'rk4', save_stages=True),

@@ -51,6 +51,12 @@ SIGNATURES = {
     'gpode_rollout_fwd_nz': (_i, [_i] * 8 + [_c_float_p, _c_float_p, _c_float_p, _i, _i, _c_float_p, _c_float_p, _i, ctypes.c_void_p]),
     'gpode_rollout_adaptive_fwd_nz': (_i, [_i] * 8 + [_c_float_p] * 3 + [_i, _i, ctypes.c_float, ctypes.c_float, _i] + [_c_float_p] * 5 + [_i, ctypes.c_void_p]),
     'gpode_rollout_dense_fwd_nz': (_i, [_i] * 8 + [_c_float_p] * 3 + [_i, _i, ctypes.c_float, ctypes.c_float, _i] + [_c_float_p] * 6 + [_i, ctypes.c_void_p]),
+    # ... with a time grid per trajectory: the twin's arguments plus `ts_per_traj` in front of the stream
+    'gpode_rollout_fwd_nt': (_i, [_i] * 8 + [_c_float_p, _c_float_p, _c_float_p, _i, _i, _c_float_p, _c_float_p, _i, _i, ctypes.c_void_p]),
+    'gpode_rollout_adaptive_fwd_nt': (_i, [_i] * 8 + [_c_float_p] * 3 + [_i, _i, ctypes.c_float, ctypes.c_float, _i] + [_c_float_p] * 5 + [_i, _i, ctypes.c_void_p]),
+    'gpode_rollout_dense_fwd_nt': (_i, [_i] * 8 + [_c_float_p] * 3 + [_i, _i, ctypes.c_float, ctypes.c_float, _i] + [_c_float_p] * 6 + [_i, _i, ctypes.c_void_p]),
+    'gpode_rollout_bwd_nt': (_i, [_i] * 8 + [_c_float_p] * 4 + [_i, _i, _c_float_p, _c_float_p, _i, ctypes.c_void_p]),
+    'gpode_rollout_bwd_pgrad_nt': (_i, [_i] * 8 + [_c_float_p] * 4 + [_i, _i, _c_float_p, _c_float_p, _c_float_p, _i, _c_float_p, _i, ctypes.c_void_p]),
     'gpode_rollout_bwd_pgrad_chunks': (_i, [_i] * 8),
     'gpode_rollout_bwd_pgrad_n': (_i, [_i] * 8 + [_c_float_p] * 4 + [_i, _i, _c_float_p, _c_float_p, _c_float_p, _i, _c_float_p, ctypes.c_void_p]),
     'gpode_param_grad_n': (_i, [_i] * 6 + [_c_float_p, _c_float_p, _c_float_p, _i, _c_float_p, _i, _c_float_p, _i, ctypes.c_void_p]),

@@ -88,19 +88,30 @@ static gp::Draws draws_of(int nd, size_t pack, size_t in, size_t out, size_t in2
 }
 static int stage_count(int method) { return method == 0 ? 1 : (method == 1 ? 4 : 2); }
 
+// ts_per_traj of the `_nt` entry points: 0 = ts (T,) shared by the trajectories, 1 = (N,T), row n for trajectory n of every draw
+static int ts_flag_refused(const char* who, int ts_per_traj) {
+  if (ts_per_traj == 0 || ts_per_traj == 1) return 0;
+  return gp::set_error("%s: ts_per_traj=%d (0 one (T,) grid shared, 1 one row of (N,T) per trajectory)", who, ts_per_traj);
+}
+static gp::Draws with_ts(gp::Draws d, int ts_per_traj, int T) {
+  d.ts = ts_per_traj ? (size_t)T : 0;
+  return d;
+}
+
 // `who`: the entry point's name in the messages; z0_per_draw: 0 = z0 (N,D) shared by the draws, 1 = (ndraws,N,D)
 static int rollout_fwd_any(const char* who, int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                            const float* pack, const float* z0, const float* ts, int N, int T,
-                           float* zt, float* xstage, int z0_per_draw, void* stream) {
+                           float* zt, float* xstage, int z0_per_draw, void* stream, int ts_per_traj = 0) {
   if (z0_per_draw != 0 && z0_per_draw != 1) return gp::set_error("%s: z0_per_draw=%d (0 shared, 1 one (N,D) slab per draw)", who, z0_per_draw);
+  if (ts_flag_refused(who, ts_per_traj)) return 1;
   if (N < 0 || T < 1 || ndraws < 1 || ndraws > 65535) return gp::set_error("%s: N=%d T=%d draws=%d", who, N, T, ndraws);
   if (N == 0) return 0;
   if (!pack || !z0 || !ts || !zt) return gp::set_error("%s: null pointer", who);
   size_t pf = 0;
   if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
   return gp::rollout_fwd(kernel, order, method, Di, Do, M, S, pack, z0, ts, N, T, zt, xstage, (hipStream_t)stream,
-                         draws_of(ndraws, pf, z0_per_draw ? (size_t)N * Di : 0, (size_t)N * T * Di, 0,
-                                  (size_t)N * (T - 1) * stage_count(method) * Di));
+                         with_ts(draws_of(ndraws, pf, z0_per_draw ? (size_t)N * Di : 0, (size_t)N * T * Di, 0,
+                                          (size_t)N * (T - 1) * stage_count(method) * Di), ts_per_traj, T));
 }
 int gpode_rollout_fwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                         const float* pack, const float* z0, const float* ts, int N, int T,
@@ -113,15 +124,22 @@ int gpode_rollout_fwd_nz(int kernel, int order, int method, int Di, int Do, int 
   return rollout_fwd_any("gpode_rollout_fwd_nz", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, zt, xstage, z0_per_draw,
                          stream);
 }
+int gpode_rollout_fwd_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                         const float* pack, const float* z0, const float* ts, int N, int T,
+                         float* zt, float* xstage, int z0_per_draw, int ts_per_traj, void* stream) {
+  return rollout_fwd_any("gpode_rollout_fwd_nt", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, zt, xstage, z0_per_draw,
+                         stream, ts_per_traj);
+}
 int gpode_rollout_fwd(int kernel, int order, int method, int Di, int Do, int M, int S,
                       const float* pack, const float* z0, const float* ts, int N, int T,
                       float* zt, float* xstage, void* stream) {
   return gpode_rollout_fwd_n(kernel, order, method, Di, Do, M, S, 1, pack, z0, ts, N, T, zt, xstage, stream);
 }
 
-int gpode_rollout_bwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
-                        const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
-                        float* gz0, float* astage, void* stream) {
+int gpode_rollout_bwd_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                         const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
+                         float* gz0, float* astage, int ts_per_traj, void* stream) {
+  if (ts_flag_refused("gpode_rollout_bwd", ts_per_traj)) return 1;
   if (N < 0 || T < 1 || ndraws < 1 || ndraws > 65535) return gp::set_error("gpode_rollout_bwd: N=%d T=%d draws=%d", N, T, ndraws);
   if (N == 0) return 0;
   if (!pack || !gzt || !ts || !gz0 || (T > 1 && (!xstage || !astage))) return gp::set_error("gpode_rollout_bwd: null pointer");
@@ -129,21 +147,34 @@ int gpode_rollout_bwd_n(int kernel, int order, int method, int Di, int Do, int M
   if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
   const size_t rows = (size_t)N * (T - 1) * stage_count(method);
   return gp::rollout_bwd(kernel, order, method, Di, Do, M, S, pack, xstage, gzt, ts, N, T, gz0, astage, (hipStream_t)stream,
-                         draws_of(ndraws, pf, rows * Di, (size_t)N * Di, (size_t)N * T * Di, rows * Do));
+                         with_ts(draws_of(ndraws, pf, rows * Di, (size_t)N * Di, (size_t)N * T * Di, rows * Do), ts_per_traj, T));
+}
+int gpode_rollout_bwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                        const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
+                        float* gz0, float* astage, void* stream) {
+  return gpode_rollout_bwd_nt(kernel, order, method, Di, Do, M, S, ndraws, pack, xstage, gzt, ts, N, T, gz0, astage, 0, stream);
 }
 int gpode_rollout_bwd_pgrad_chunks(int kernel, int order, int method, int Di, int Do, int M, int S, int N) {
   return gp::rollout_bwd_pgrad_chunks(kernel, order, method, Di, Do, M, S, N);
 }
-int gpode_rollout_bwd_pgrad_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
-                              const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
-                              float* gz0, float* astage, float* slab, int nchunk, float* gpack, void* stream) {
+int gpode_rollout_bwd_pgrad_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                               const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
+                               float* gz0, float* astage, float* slab, int nchunk, float* gpack, int ts_per_traj, void* stream) {
+  if (ts_flag_refused("gpode_rollout_bwd_pgrad", ts_per_traj)) return 1;
   if (N < 1 || T < 2 || ndraws < 1 || ndraws > 65535) return gp::set_error("gpode_rollout_bwd_pgrad: N=%d T=%d draws=%d", N, T, ndraws);
   if (!pack || !gzt || !ts || !gz0 || !xstage || !astage || !slab || !gpack) return gp::set_error("gpode_rollout_bwd_pgrad: null pointer");
   size_t pf = 0;
   if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
   const size_t rows = (size_t)N * (T - 1) * stage_count(method);
   return gp::rollout_bwd_pgrad(kernel, order, method, Di, Do, M, S, pack, xstage, gzt, ts, N, T, gz0, astage, slab, nchunk, gpack,
-                               (hipStream_t)stream, draws_of(ndraws, pf, rows * Di, (size_t)N * Di, (size_t)N * T * Di, rows * Do));
+                               (hipStream_t)stream,
+                               with_ts(draws_of(ndraws, pf, rows * Di, (size_t)N * Di, (size_t)N * T * Di, rows * Do), ts_per_traj, T));
+}
+int gpode_rollout_bwd_pgrad_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                              const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
+                              float* gz0, float* astage, float* slab, int nchunk, float* gpack, void* stream) {
+  return gpode_rollout_bwd_pgrad_nt(kernel, order, method, Di, Do, M, S, ndraws, pack, xstage, gzt, ts, N, T, gz0, astage, slab, nchunk,
+                                    gpack, 0, stream);
 }
 int gpode_rollout_bwd(int kernel, int order, int method, int Di, int Do, int M, int S,
                       const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
@@ -177,13 +208,15 @@ static int adaptive_bwd_args(const char* who, int method, int ndraws, const floa
 
 static int rollout_adaptive_fwd_any(const char* who, int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                                     const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
-                                    float* zt, float* xstage, float* hstep, int* iend, int* counts, int z0_per_draw, void* stream) {
+                                    float* zt, float* xstage, float* hstep, int* iend, int* counts, int z0_per_draw, void* stream,
+                                    int ts_per_traj = 0) {
+  if (ts_flag_refused(who, ts_per_traj)) return 1;
   if (const int rc = adaptive_fwd_args(who, method, ndraws, pack, z0, ts, N, T, rtol, atol, K, zt, counts, z0_per_draw)) return rc > 0;
   if (xstage && T > 1 && (!iend || (K > 0 && !hstep))) return gp::set_error("%s: xstage without hstep / iend", who);
   size_t pf = 0;
   if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
   return gp::rollout_adaptive_fwd(kernel, order, Di, Do, M, S, ndraws, pack, pf, z0, ts, N, T, rtol, atol, K, zt, xstage, hstep, iend,
-                                  counts, (hipStream_t)stream, z0_per_draw ? (size_t)N * Di : 0);
+                                  counts, (hipStream_t)stream, z0_per_draw ? (size_t)N * Di : 0, ts_per_traj ? (size_t)T : 0);
 }
 int gpode_rollout_adaptive_fwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                                  const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
@@ -196,6 +229,13 @@ int gpode_rollout_adaptive_fwd_nz(int kernel, int order, int method, int Di, int
                                   float* zt, float* xstage, float* hstep, int* iend, int* counts, int z0_per_draw, void* stream) {
   return rollout_adaptive_fwd_any("gpode_rollout_adaptive_fwd_nz", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol,
                                   atol, K, zt, xstage, hstep, iend, counts, z0_per_draw, stream);
+}
+int gpode_rollout_adaptive_fwd_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                                  const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
+                                  float* zt, float* xstage, float* hstep, int* iend, int* counts, int z0_per_draw, int ts_per_traj,
+                                  void* stream) {
+  return rollout_adaptive_fwd_any("gpode_rollout_adaptive_fwd_nt", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol,
+                                  atol, K, zt, xstage, hstep, iend, counts, z0_per_draw, stream, ts_per_traj);
 }
 int gpode_rollout_adaptive_bwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                                  const float* pack, const float* xstage, const float* hstep, const int* iend, const float* gzt,
@@ -211,14 +251,15 @@ int gpode_rollout_adaptive_bwd_n(int kernel, int order, int method, int Di, int 
 static int rollout_dense_fwd_any(const char* who, int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                                  const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
                                  float* zt, float* xstage, float* hstep, int* istep, float* theta, int* counts, int z0_per_draw,
-                                 void* stream) {
+                                 void* stream, int ts_per_traj = 0) {
+  if (ts_flag_refused(who, ts_per_traj)) return 1;
   if (const int rc = adaptive_fwd_args(who, method, ndraws, pack, z0, ts, N, T, rtol, atol, K, zt, counts, z0_per_draw)) return rc > 0;
   if (xstage && T > 1 && (!istep || !theta || (K > 0 && !hstep)))
     return gp::set_error("%s: xstage without hstep / istep / theta", who);
   size_t pf = 0;
   if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
   return gp::rollout_dense_fwd(kernel, order, Di, Do, M, S, ndraws, pack, pf, z0, ts, N, T, rtol, atol, K, zt, xstage, hstep, istep, theta,
-                               counts, (hipStream_t)stream, z0_per_draw ? (size_t)N * Di : 0);
+                               counts, (hipStream_t)stream, z0_per_draw ? (size_t)N * Di : 0, ts_per_traj ? (size_t)T : 0);
 }
 int gpode_rollout_dense_fwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                               const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
@@ -232,6 +273,13 @@ int gpode_rollout_dense_fwd_nz(int kernel, int order, int method, int Di, int Do
                                void* stream) {
   return rollout_dense_fwd_any("gpode_rollout_dense_fwd_nz", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol, atol, K,
                                zt, xstage, hstep, istep, theta, counts, z0_per_draw, stream);
+}
+int gpode_rollout_dense_fwd_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                               const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
+                               float* zt, float* xstage, float* hstep, int* istep, float* theta, int* counts, int z0_per_draw,
+                               int ts_per_traj, void* stream) {
+  return rollout_dense_fwd_any("gpode_rollout_dense_fwd_nt", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol, atol, K,
+                               zt, xstage, hstep, istep, theta, counts, z0_per_draw, stream, ts_per_traj);
 }
 int gpode_rollout_dense_bwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                               const float* pack, const float* xstage, const float* hstep, const int* istep, const float* theta,

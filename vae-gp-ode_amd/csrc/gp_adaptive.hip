@@ -75,9 +75,11 @@ struct AdaptBwd {
   float* gz0; float* astage;
 };
 // What the kernels take.  z0_stride: floats between the draws' initial states, 0 = one (N,D) block shared by all draws; it is the
-// LAST member of either block, so every other argument stays where it was.  The dense mode's kernels take one pointer more.
-struct AdaptFwdLand : AdaptFwd { size_t z0_stride; };
-struct AdaptFwdDense : AdaptFwd { float* theta; size_t z0_stride; };
+// member after the mode's own pointers, so every other argument stays where it was.  ts_stride follows it: floats between the
+// trajectories' time grids, 0 = the one (T,) grid all of them share, T = row n of a dense (N,T) block for trajectory n of every draw.
+// The dense mode's kernels take one pointer more.
+struct AdaptFwdLand : AdaptFwd { size_t z0_stride, ts_stride; };
+struct AdaptFwdDense : AdaptFwd { float* theta; size_t z0_stride, ts_stride; };
 struct AdaptBwdDense : AdaptBwd { const float* theta; };
 template <bool DENSE> using AdaptFwdArg = std::conditional_t<DENSE, AdaptFwdDense, AdaptFwdLand>;
 template <bool DENSE> using AdaptBwdArg = std::conditional_t<DENSE, AdaptBwdDense, AdaptBwd>;
@@ -108,13 +110,13 @@ __device__ __forceinline__ float dense_w(int j, float th) {
 }
 
 // One trajectory, start to end.  kst: this wavefront's 7 x KP floats of LDS.  wr: this wavefront writes the outputs (in a team all
-// four compute the same values).  Pointers are the draw's.
+// four compute the same values).  Pointers are the draw's; ts is the trajectory's own grid (a scalar pointer: ts_row).
 // DENSE: one "interval" from ts[0] to ts[T-1]; the outputs inside it are interpolated when the step that holds them is accepted.
 template <class EV, int DI, int DO, int ORDER, bool DENSE>
 __device__ __forceinline__ void dopri5_trajectory(EV& ev, const AdaptFwd& a, const float* __restrict__ z0, float* __restrict__ zt,
                                                   float* __restrict__ xstage, float* __restrict__ hstep, int* __restrict__ iend,
                                                   float* __restrict__ theta, int* __restrict__ counts, int n, float* __restrict__ kst,
-                                                  bool wr, int lane) {
+                                                  bool wr, int lane, const float* __restrict__ ts) {
   constexpr int NR = DENSE ? NDEN : NREC;
   const int T = a.T, K = a.K;
   const float rtol = a.rtol, atol = a.atol;
@@ -138,15 +140,15 @@ __device__ __forceinline__ void dopri5_trajectory(EV& ev, const AdaptFwd& a, con
     const float d0 = scaled_rms<DI>(y, y, y, rtol, atol), d1 = scaled_rms<DI>(kv, y, y, rtol, atol);
     const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
     const float h1 = d1 <= 1e-15f ? fmaxf(1e-6f, h0 * 1e-3f) : powf(0.01f / d1, 0.2f);
-    h = uni(fminf(fminf(100.f * h0, h1), a.ts[DENSE ? T - 1 : 1] - a.ts[0]));
+    h = uni(fminf(fminf(100.f * h0, h1), ts[DENSE ? T - 1 : 1] - ts[0]));
   }
   if constexpr (DENSE) {
     for (int i = 0; i + 1 < T; ++i)
-      if (!(a.ts[i + 1] - a.ts[i] > 0.f)) status = 3;
+      if (!(ts[i + 1] - ts[i] > 0.f)) status = 3;
     if (status) t = T;                               // nothing is integrated
   }
   for (; t + 1 < T; ++t) {
-    const float t0 = a.ts[t], t1 = a.ts[DENSE ? T - 1 : t + 1];
+    const float t0 = ts[t], t1 = ts[DENSE ? T - 1 : t + 1];
     const float dt = t1 - t0, tabs = fmaxf(fabsf(t0), fabsf(t1));
     if (!(dt > 0.f)) { status = 3; break; }
     float rem = dt;
@@ -193,7 +195,7 @@ __device__ __forceinline__ void dopri5_trajectory(EV& ev, const AdaptFwd& a, con
           // the slope block are k_1..k_7 of this step, y its start
           const float tnew = tn + hs;
           while (jout < T) {
-            const float to = uni(a.ts[jout] - t0);
+            const float to = uni(ts[jout] - t0);
             if (!(cut || to <= tnew)) break;
             const bool last = jout == T - 1;
             const float th = last ? 1.f : uni(fminf(fmaxf((to - tn) / hs, 1.1920929e-7f), 1.f));
@@ -284,7 +286,8 @@ __global__ __launch_bounds__(256) void rollout_adaptive_kernel(AdaptFwdArg<DENSE
   EV ev;
   ev.init(pack, a.M, a.S, lane);
   for (int n = blockIdx.x * wpb + wave; n < a.N; n += gridDim.x * wpb)
-    dopri5_trajectory<EV, DI, DO, ORDER, DENSE>(ev, a, z0, zt, xstage, hstep, iend, theta, counts, n, kst[wave], true, lane);
+    dopri5_trajectory<EV, DI, DO, ORDER, DENSE>(ev, a, z0, zt, xstage, hstep, iend, theta, counts, n, kst[wave], true, lane,
+                                                ts_row(a.ts, n, a.ts_stride));
 }
 
 // One workgroup per trajectory.  Every evaluation carries the team's barrier, so the four wavefronts must take the same steps:
@@ -299,7 +302,8 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rollout_adaptive_team_kernel(A
   EV ev;
   ev.init(pack, a.M, a.S, slots, wave, lane);
   for (int n = blockIdx.x; n < a.N; n += gridDim.x)
-    dopri5_trajectory<EV, DI, DO, ORDER, DENSE>(ev, a, z0, zt, xstage, hstep, iend, theta, counts, n, kst[wave], wave == 0, lane);
+    dopri5_trajectory<EV, DI, DO, ORDER, DENSE>(ev, a, z0, zt, xstage, hstep, iend, theta, counts, n, kst[wave], wave == 0, lane,
+                                                ts_row(a.ts, n, a.ts_stride));
 }
 
 // Reverse sweep: the adjoint of an explicit Runge-Kutta step, over the recorded accepted steps, step sizes constant.
@@ -512,15 +516,15 @@ static int adaptive_fwd(int kernel, int order, int Di, int Do, const AdaptFwdArg
 
 int rollout_adaptive_fwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
                          const float* z0, const float* ts, int N, int T, float rtol, float atol, int K, float* zt, float* xstage,
-                         float* hstep, int* iend, int* counts, hipStream_t st, size_t z0_stride) {
-  const AdaptFwdLand a{{pack, pack_stride, M, S, z0, ts, N, T, K, rtol, atol, zt, xstage, hstep, iend, counts}, z0_stride};
+                         float* hstep, int* iend, int* counts, hipStream_t st, size_t z0_stride, size_t ts_stride) {
+  const AdaptFwdLand a{{pack, pack_stride, M, S, z0, ts, N, T, K, rtol, atol, zt, xstage, hstep, iend, counts}, z0_stride, ts_stride};
   return adaptive_fwd<false>(kernel, order, Di, Do, a, nd, st);
 }
 
 int rollout_dense_fwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
                       const float* z0, const float* ts, int N, int T, float rtol, float atol, int K, float* zt, float* xstage,
-                      float* hstep, int* istep, float* theta, int* counts, hipStream_t st, size_t z0_stride) {
-  const AdaptFwdDense a{{pack, pack_stride, M, S, z0, ts, N, T, K, rtol, atol, zt, xstage, hstep, istep, counts}, theta, z0_stride};
+                      float* hstep, int* istep, float* theta, int* counts, hipStream_t st, size_t z0_stride, size_t ts_stride) {
+  const AdaptFwdDense a{{pack, pack_stride, M, S, z0, ts, N, T, K, rtol, atol, zt, xstage, hstep, istep, counts}, theta, z0_stride, ts_stride};
   return adaptive_fwd<true>(kernel, order, Di, Do, a, nd, st);
 }
 

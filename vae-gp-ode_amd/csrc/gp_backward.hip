@@ -66,8 +66,9 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rollout_bwd_team_kernel(const 
     float lam[DI];
 #pragma unroll
     for (int i = 0; i < DI; ++i) lam[i] = gz[(size_t)(T - 1) * DI + i];
+    const float* tn = ts_row(ts, n, dw.ts);          // this trajectory's grid (dw.ts = 0: the shared one)
     for (int t = T - 2; t >= 0; --t) {
-      const float dt = ts[t + 1] - ts[t];
+      const float dt = tn[t + 1] - tn[t];
       const float* xt = xs + (size_t)t * NS * DI;
       float* at = as + (size_t)t * NS * DO;
       float x[DI], g[DI], af[DO];

@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void rhs_kernel(const float* __restrict__ pack
 }
 
 
-// z0 (N,DI), ts (T) -> zt (N,T,DI).  One wave per trajectory, persistent over the T-1 steps.
+// z0 (N,DI), ts (T) or (N,T) [dw.ts = T] -> zt (N,T,DI).  One wave per trajectory, persistent over the T-1 steps.
 // Stage algebra follows torchdiffeq's fixed-grid solvers at flow.py:76-85 (3/8-rule rk4).
 template <class EV, int DI, int DO, int ORDER, int METHOD, bool USE_LDS>
 __global__ __launch_bounds__(256) void rollout_kernel(const float* __restrict__ pack, int M, int S, size_t lds_f4,
@@ -67,8 +67,9 @@ __global__ __launch_bounds__(256) void rollout_kernel(const float* __restrict__ 
     float* out = zt + (size_t)n * T * DI;
     float* xs_out = xstage ? xstage + (size_t)n * (T - 1) * NS * DI : nullptr;
     store_state<DI>(out, y, lane);
+    const float* tn = ts_row(ts, n, dw.ts);
     for (int t = 0; t + 1 < T; ++t) {
-      const float dt = ts[t + 1] - ts[t];
+      const float dt = tn[t + 1] - tn[t];
       float k1[DI];
       if (xs_out) store_state<DI>(xs_out + (size_t)(t * NS) * DI, y, lane);
       ode_rhs<EV, DI, DO, ORDER>(ev, y, k1);
@@ -151,8 +152,9 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rollout_team_kernel(const floa
     float* out = zt + (size_t)n * T * DI;
     float* xs_out = (xstage && wave == 0) ? xstage + (size_t)n * (T - 1) * NS * DI : nullptr;
     if (wave == 0) store_state<DI>(out, y, lane);
+    const float* tn = ts_row(ts, n, dw.ts);
     for (int t = 0; t + 1 < T; ++t) {
-      const float dt = ts[t + 1] - ts[t];
+      const float dt = tn[t + 1] - tn[t];
       float k1[DI];
       if (xs_out) store_state<DI>(xs_out + (size_t)(t * NS) * DI, y, lane);
       ode_rhs_mut<EV, DI, DO, ORDER>(ev, y, k1);

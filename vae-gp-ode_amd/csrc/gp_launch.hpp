@@ -70,9 +70,12 @@ inline int num_cus() {
 // Monte-Carlo draws batched into ONE launch (the reference loops `for l in range(L)` over whole flow calls, odegpvae.py:41-43):
 // blockIdx.y = draw.  Strides in floats of the operands that differ per draw -- 0 = shared by all draws (the inducing locations
 // handed to the prior-only rhs, the initial states z0 of a rollout).  Which operand each stride belongs to is listed per entry point.
+// ts: floats between the time grids of consecutive TRAJECTORIES (not draws: a grid belongs to the sequence), 0 = one (T,) grid shared
+// by all of them, T = one row of a dense (N,T) block each.  Read by the fixed-grid rollout and its reverse sweep only.
 struct Draws {
   int nd = 1;
   size_t pack = 0, in = 0, out = 0, in2 = 0, out2 = 0;
+  size_t ts = 0;
 };
 
 // entry points implemented across the .hip files
@@ -91,17 +94,18 @@ int rollout_bwd_pgrad(int kernel, int order, int method, int Di, int Do, int M, 
                       const float* gzt, const float* ts, int N, int T, float* gz0, float* astage, float* slab, int nchunk,
                       float* gpack, hipStream_t st, Draws dw = Draws{});
 // adaptive Dormand-Prince rollout and its reverse sweep (gp_adaptive.hip); every per-draw operand is dense, `pack_stride` apart;
-// z0_stride: floats between the draws' initial states, 0 = shared by all draws
+// z0_stride: floats between the draws' initial states, 0 = shared by all draws; ts_stride: floats between the trajectories' time
+// grids, 0 = one (T,) grid shared by all trajectories
 int rollout_adaptive_fwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
                          const float* z0, const float* ts, int N, int T, float rtol, float atol, int K, float* zt, float* xstage,
-                         float* hstep, int* iend, int* counts, hipStream_t st, size_t z0_stride = 0);
+                         float* hstep, int* iend, int* counts, hipStream_t st, size_t z0_stride = 0, size_t ts_stride = 0);
 int rollout_adaptive_bwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
                          const float* xstage, const float* hstep, const int* iend, const float* gzt, int N, int T, int K,
                          float* gz0, float* astage, hipStream_t st);
 // the same in dense-output mode: steps cut at ts[T-1] only, interior outputs interpolated (record: 7 rows per step, istep, theta)
 int rollout_dense_fwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
                       const float* z0, const float* ts, int N, int T, float rtol, float atol, int K, float* zt, float* xstage,
-                      float* hstep, int* istep, float* theta, int* counts, hipStream_t st, size_t z0_stride = 0);
+                      float* hstep, int* istep, float* theta, int* counts, hipStream_t st, size_t z0_stride = 0, size_t ts_stride = 0);
 int rollout_dense_bwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
                       const float* xstage, const float* hstep, const int* istep, const float* theta, const float* gzt, int N, int T,
                       int K, float* gz0, float* astage, hipStream_t st);

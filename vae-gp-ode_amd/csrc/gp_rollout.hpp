@@ -153,6 +153,13 @@ __device__ __forceinline__ void ode_rhs(const EV& ev, const float (&y)[DI], floa
   }
 }
 
+// The time grid of trajectory n: ts + n * stride (stride 0: the one grid every trajectory shares).  n is the same in every lane of a
+// wavefront but lives in a vector register where it derives from threadIdx; read through the first lane it is a scalar, so the row
+// pointer is one and the grid's entries stay scalar loads -- the step size multiplies the stage algebra as a scalar either way.
+__device__ __forceinline__ const float* ts_row(const float* __restrict__ ts, int n, size_t stride) {
+  return ts + (size_t)__builtin_amdgcn_readfirstlane(n) * stride;
+}
+
 template <int DI> __device__ __forceinline__ void store_state(float* __restrict__ dst, const float (&y)[DI], int lane) {
   if (lane < DI) {
     float v = y[0];

@@ -7,6 +7,9 @@
 ``ResidentLoader``: rotating MNIST is 360 x 16 x 784 floats = 18 MB -- nothing on a 288 GB device.  The normalised set is
 uploaded once; an epoch is a device-side permutation and every minibatch one ``index_select`` on the current stream, so the
 training step (a replayed HIP graph reading a static input buffer) never waits for a host copy.
+
+``subsample_frames``: irregularly observed sequences out of regularly sampled ones -- every sequence keeps its own sorted subset
+of the frames, and the kept indices are its observation times in units of ``dt`` (``--subsample_frames``).
 """
 import torch
 from torch.utils import data
@@ -16,6 +19,25 @@ MNIST_MEAN, MNIST_STD = 0.1307, 0.3081
 
 def normalise(frames):
     return (frames - MNIST_MEAN) / MNIST_STD
+
+
+def subsample_frames(X, keep, lead, generator):
+    """X (N,T,...) -> (X[:, idx] (N,keep,...), idx (N,keep) int64): per sequence a sorted set of ``keep`` distinct frame indices that
+    always holds 0 .. lead-1 (the frames the encoders read: 1 for a first-order model, the velocity encoder's ``frames`` for a
+    second-order one, which takes them to be consecutive); the other keep - lead are drawn uniformly without replacement from
+    lead .. T-1.  Drawn on X's device from ``generator`` alone (a torch.Generator of that device): the global generators are
+    not touched.  The time grid of sequence n is dt * idx[n]."""
+    N, T = X.shape[0], X.shape[1]
+    keep, lead = int(keep), int(lead)
+    if lead < 1 or keep <= lead or keep > T:
+        raise ValueError('subsample_frames: keep=%d must lie in (lead, T] = (%d, %d]: the first %d frame(s) are always kept and at '
+                         'least one later frame is drawn' % (keep, lead, T, lead))
+    # the keep - lead smallest of T - lead uniform scores: a uniform subset; sorted, and behind the leading frames
+    scores = torch.rand((N, T - lead), device=X.device, generator=generator)
+    tail = scores.argsort(dim=1)[:, :keep - lead].sort(dim=1).values + lead
+    head = torch.arange(lead, device=X.device).expand(N, lead)
+    idx = torch.cat((head, tail), dim=1)
+    return X[torch.arange(N, device=X.device)[:, None], idx], idx
 
 
 class Dataset(data.Dataset):

@@ -26,7 +26,9 @@ reused): loads ``--model_path``, evaluates the test split with L = ``--eval_samp
 log-likelihood: ``mse``, ``std``, ``mse_t``, ``nll``, ``nlpd``, ``nll_t``), rolls ``--Troll`` * T frames out for
 the first three test sequences, prints one JSON line and writes ``eval.json``, ``rollout_mean.npy``, ``rollout_var.npy`` under
 ``--save``.  The draws come from the host generators as in the reference (two of them unseeded there, SURVEY F6, so two runs differ
-by Monte-Carlo noise); ``--device_noise True`` draws on the device, reproducibly from ``--seed``.  ``--eval_z0_draws True`` adds a second pass over the test split
+by Monte-Carlo noise); ``--device_noise True`` draws on the device, reproducibly from ``--seed``.  ``--subsample_frames K``: every test
+sequence keeps K of its frames (drawn per sequence, reproducibly from ``--seed``) and is evaluated on its own time grid
+(``predict(..., ts=)``); the long roll-out stays on the uniform grid.  ``--eval_z0_draws True`` adds a second pass over the test split
 with a z0 sample per draw and reports ``iw_nll``, ``nlpd_marginal``, ``ess_mean``, ``ess_min``; every other figure is unchanged.  Single process: data-parallel
 evaluation is not built.  No plots.
 """
@@ -146,7 +148,32 @@ class _EvalMode:
         return False
 
 
-def predict(model, X, L=1, T_custom=None, images_per_pass=8192, variance=True, loglik=False):
+def _grid(ts, N, Th, T, who):
+    """``ts`` of predict / predict_marginal: None, or (N,Th) observation times per sequence (a grid over the T observed frames alone is
+    enough when the roll-out stops there)"""
+    if ts is None:
+        return None
+    if ts.dim() != 2 or ts.shape[0] != N or ts.shape[1] not in (Th, T):
+        raise ValueError('%s: ts must be (N,T\') = (%d,%d), one row of observation times per sequence; got %s' % (who, N, Th, tuple(ts.shape)))
+    if ts.shape[1] != Th:
+        raise ValueError('%s: ts covers %d frames, the roll-out %d: give the times of the forecast frames as well' % (who, ts.shape[1], Th))
+    return ts
+
+
+def _grid_kw(ts):
+    """ts= for predict / predict_marginal when the loader item carries a grid; nothing otherwise -- the call as it always was"""
+    return {} if ts is None else {'ts': ts}
+
+
+def _frames_ts(batch):
+    """(X, ts) of a loader item: a loader that yields (X, ts (N,T)) pairs carries the observation times of its sequences; every
+    other item (the tensor itself, a TensorDataset 1-tuple) has none"""
+    if isinstance(batch, (list, tuple)):
+        return batch[0], (batch[1] if len(batch) > 1 else None)
+    return batch, None
+
+
+def predict(model, X, L=1, T_custom=None, images_per_pass=8192, variance=True, loglik=False, ts=None):
     """Posterior-predictive statistics of ``model`` (ODEGPVAE) for the sequences X (N,T,1,28,28): encode once, one z0 sample per
     sequence, L function draws shared by the batch, integrate ``T_custom or T`` steps, decode (positions only for order 2) --
     the order of operations of the notebook routine -- and reduce inside the decoder's last kernel.  Frames beyond T have no
@@ -156,8 +183,10 @@ def predict(model, X, L=1, T_custom=None, images_per_pass=8192, variance=True, l
     the same trajectory.  ``loglik=True`` also fills ``ll``, ``nll``, ``nlpd`` and ``nll_t`` of the result (Bernoulli log-likelihood of
     the observed frames, from the logits); every other field is the same bits as without it.  One z0 sample per sequence is shared by
     the L draws, so ``nlpd`` is the predictive density under the GP function draws GIVEN that sample of the initial state, not the
-    marginal over the encoder's distribution.  Runs without autograd and in eval mode; leaves every module buffer and ``training`` flag
-    as it found them."""
+    marginal over the encoder's distribution.  ``ts`` (N,T'), T' = ``T_custom or T``: the observation (and forecast) times of every
+    sequence instead of the uniform grid dt * arange(T'); with ``variance=False`` the first T columns are read.  ``mse_t`` and ``nll_t``
+    stay indexed by FRAME: entry t averages frame t of every sequence, whatever time each of them was observed at.  Runs without
+    autograd and in eval mode; leaves every module buffer and ``training`` flag as it found them."""
     from . import vae_ops as V
     if X.dim() != 5 or tuple(X.shape[2:]) != (1, 28, 28):
         raise ValueError('predict: X must be (N,T,1,28,28)')
@@ -165,8 +194,11 @@ def predict(model, X, L=1, T_custom=None, images_per_pass=8192, variance=True, l
     Th = int(T_custom) if T_custom else T
     if Th < T:
         raise ValueError('predict: T_custom (%d) must be at least the observed length (%d)' % (Th, T))
+    if ts is not None and not variance and ts.dim() == 2 and ts.shape[1] == Th:
+        ts = ts[:, :T]
     if not variance:
         Th = T              # forecast frames have no target: without the moments over the draws nothing would come of them
+    ts = _grid(ts, N, Th, T, 'predict')
     L = int(L)
     F = N * Th
     passes = plan_passes(L, F, int(images_per_pass))
@@ -174,7 +206,7 @@ def predict(model, X, L=1, T_custom=None, images_per_pass=8192, variance=True, l
     with torch.no_grad(), _EvalMode(model):
         X = X.contiguous().float()
         z0, _, _ = model.encode_initial_state(X)
-        ztL = model.sample_trajectories(z0, Th, L)                     # (L,N,Th,order*q)
+        ztL = model.sample_trajectories(z0, Th, L) if ts is None else model.sample_trajectories(z0, Th, L, ts=ts.to(X.device))
         lat = ztL if model.order == 1 else ztL[..., :ztL.shape[-1] // 2]
         tables = dec._frozen_tables()
         state = V.PredictState(F, X.device, variance, loglik=L if loglik else 0)
@@ -196,23 +228,25 @@ def predict(model, X, L=1, T_custom=None, images_per_pass=8192, variance=True, l
     return Prediction(mean, var, mse, std, int(total[0]), mse_t, total, [b - a for a, b in passes], *extra)
 
 
-def predict_marginal(model, X, L, images_per_pass=8192):
+def predict_marginal(model, X, L, images_per_pass=8192, ts=None):
     """``predict(variance=False, loglik=True)`` with the initial state sampled PER DRAW: ``encode_initial_state(X, draws=L)`` gives
     z0 (L,N,order*q) and the log-weights lw (L,N), draw l integrates from z0[l] under function draw l (one rollout launch over L N
-    trajectories), and the decoder passes and the fused last kernel are predict's.  -> MarginalPrediction.  Runs without autograd and
-    in eval mode; leaves every module buffer and ``training`` flag as it found them."""
+    trajectories), and the decoder passes and the fused last kernel are predict's.  -> MarginalPrediction.  ``ts`` (N,T): the
+    observation times of every sequence, shared by its L draws; ``nll_t`` stays indexed by frame, as in predict.  Runs without autograd
+    and in eval mode; leaves every module buffer and ``training`` flag as it found them."""
     from . import vae_ops as V
     if X.dim() != 5 or tuple(X.shape[2:]) != (1, 28, 28):
         raise ValueError('predict_marginal: X must be (N,T,1,28,28)')
     N, T = X.shape[0], X.shape[1]
     L = int(L)
     F = N * T
+    ts = _grid(ts, N, T, T, 'predict_marginal')
     passes = plan_passes(L, F, int(images_per_pass))
     dec = model.vae.decoder
     with torch.no_grad(), _EvalMode(model):
         X = X.contiguous().float()
         z0, lw, _, _ = model.encode_initial_state(X, draws=L)          # (L,N,order*q), (L,N)
-        ztL = model.sample_trajectories(z0, T, L)                      # (L,N,T,order*q)
+        ztL = model.sample_trajectories(z0, T, L) if ts is None else model.sample_trajectories(z0, T, L, ts=ts.to(X.device))
         lat = ztL if model.order == 1 else ztL[..., :ztL.shape[-1] // 2]
         tables = dec._frozen_tables()
         state = V.PredictState(F, X.device, False, loglik=L)
@@ -232,13 +266,13 @@ def predict_marginal(model, X, L, images_per_pass=8192):
 
 def compute_iw_nll(model, loader, L, images_per_pass=8192):
     """(iw_nll, nlpd, mean ess) over a whole loader with L joint draws per batch (predict_marginal): means over all sequences, the
-    batches weighted by their sequence counts."""
-    from .main import _frames
+    batches weighted by their sequence counts.  A loader that yields (X, ts) pairs is evaluated on its time grids."""
     dev = next(model.parameters()).device
     nseq, iw, nlpd, ess = 0, 0.0, 0.0, 0.0
     for batch in loader:
-        X = _frames(batch).to(dev)
-        p = predict_marginal(model, X, L, images_per_pass=images_per_pass)
+        X, ts = _frames_ts(batch)
+        X = X.to(dev)
+        p = predict_marginal(model, X, L, images_per_pass=images_per_pass, **_grid_kw(ts))
         nseq += X.shape[0]
         iw += p.iw_nll * X.shape[0]
         nlpd += p.nlpd * X.shape[0]
@@ -250,22 +284,26 @@ def compute_iw_nll(model, loader, L, images_per_pass=8192):
 
 def compute_mse_std(model, loader, L=1, images_per_pass=8192):
     """(mse, std) of the squared reconstruction error over a whole loader with L draws per batch -- ``compute_mse_std`` of the
-    evaluation notebook: the batches' (n, mean, M2) triples are merged, so the result is the mean / std over all elements."""
-    from .main import _frames
+    evaluation notebook: the batches' (n, mean, M2) triples are merged, so the result is the mean / std over all elements.
+    A loader that yields (X, ts) pairs is evaluated on its time grids."""
     dev = next(model.parameters()).device
-    states = [predict(model, _frames(batch).to(dev), L, images_per_pass=images_per_pass, variance=False).state for batch in loader]
+    states = []
+    for batch in loader:
+        X, ts = _frames_ts(batch)
+        states.append(predict(model, X.to(dev), L, images_per_pass=images_per_pass, variance=False, **_grid_kw(ts)).state)
     return mean_std(merge_states(states))
 
 
 def compute_nll(model, loader, L=1, images_per_pass=8192):
     """(nll, nlpd) of the held-out log-likelihood over a whole loader with L draws per batch: the batches' figures are means over
-    their sequences, so they are weighted by the sequence counts -- the mean over all sequences, not over batches."""
-    from .main import _frames
+    their sequences, so they are weighted by the sequence counts -- the mean over all sequences, not over batches.
+    A loader that yields (X, ts) pairs is evaluated on its time grids."""
     dev = next(model.parameters()).device
     nseq, nll, nlpd = 0, 0.0, 0.0
     for batch in loader:
-        X = _frames(batch).to(dev)
-        p = predict(model, X, L, images_per_pass=images_per_pass, variance=False, loglik=True)
+        X, ts = _frames_ts(batch)
+        X = X.to(dev)
+        p = predict(model, X, L, images_per_pass=images_per_pass, variance=False, loglik=True, **_grid_kw(ts))
         nseq += X.shape[0]
         nll += p.nll * X.shape[0]
         nlpd += p.nlpd * X.shape[0]
@@ -310,9 +348,28 @@ def make_parser():
     return p
 
 
+def _subsampled(args, loader):
+    """The loader's items as (all frames, X, ts): with --subsample_frames K every sequence keeps K frames, drawn per batch from a
+    generator of its own seeded from --seed (so a second pass sees the same subsets), ts = dt * (kept indices); without it X is all
+    frames and ts None."""
+    from .main import _frames, subsample_generator, subsample_lead
+    if not args.subsample_frames:
+        for batch in loader:
+            X = _frames(batch).to(args.device)
+            yield X, X, None
+        return
+    from .data.utils import subsample_frames
+    gen = subsample_generator(args)
+    for batch in loader:
+        full = _frames(batch).to(args.device)
+        X, kept = subsample_frames(full, args.subsample_frames, subsample_lead(args), gen)
+        yield full, X, args.dt * kept.to(torch.float32)
+
+
 def main(argv=None):
-    from .main import _frames
+    from .main import check_subsample
     args = make_parser().parse_args(argv)
+    check_subsample(args)
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
         raise SystemExit('vae_gp_ode_amd.evaluate is a single-process tool: data-parallel evaluation is not built '
                          '(start it without torchrun, or with one rank)')
@@ -326,10 +383,9 @@ def main(argv=None):
     states, per_step, nseq, first = [], None, 0, None
     nll = nlpd = 0.0
     nll_step = None
-    for batch in testset:
-        Xb = _frames(batch).to(args.device)
-        first = Xb if first is None else first
-        p = predict(model, Xb, L, variance=False, loglik=True)
+    for full, Xb, tsb in _subsampled(args, testset):
+        first = full if first is None else first     # the roll-out below: all frames, the uniform grid
+        p = predict(model, Xb, L, variance=False, loglik=True, **_grid_kw(tsb))
         states.append(p.state)
         nll += p.nll * Xb.shape[0]
         nlpd += p.nlpd * Xb.shape[0]
@@ -340,12 +396,14 @@ def main(argv=None):
     mse, std = mean_std(total)
     T = first.shape[1]
     roll = predict(model, first[:3].contiguous(), L, T_custom=args.Troll * T)
+    if args.subsample_frames:
+        T = args.subsample_frames                    # the frames per sequence behind every figure but the roll-out's
     marginal = None
     if args.eval_z0_draws:                           # behind everything else: the figures above see the draws they see without it
         iw = nlpd_m = ess_sum = 0.0
         ess_min = float('inf')
-        for batch in testset:
-            pm = predict_marginal(model, _frames(batch).to(args.device), L)
+        for _, Xb, tsb in _subsampled(args, testset):
+            pm = predict_marginal(model, Xb, L, **_grid_kw(tsb))
             iw += pm.iw_nll * pm.ll.shape[1]
             nlpd_m += pm.nlpd * pm.ll.shape[1]
             ess_sum += pm.ess.sum().item()
@@ -358,6 +416,8 @@ def main(argv=None):
     out = dict(mse=mse, std=std, mse_t=(per_step / nseq).tolist(), nll=nll / nseq, nlpd=nlpd / nseq, nll_t=(nll_step / nseq).tolist(), L=L, sequences=nseq, T=T, count=int(total[0]),
                rollout_sequences=int(roll.mean.shape[0]), rollout_T=int(roll.mean.shape[1]), rollout_mse=roll.mse, ms=ms,
                checkpoint=os.path.abspath(fname), ranks=1)
+    if args.subsample_frames:
+        out['subsample_frames'] = args.subsample_frames
     if marginal is not None:
         out.update(marginal)
     np.save(os.path.join(args.save, 'rollout_mean.npy'), roll.mean.cpu().numpy())

@@ -65,6 +65,9 @@ EXT_FLAGS = [
                                          'rank-deficient K_uu), never, adaptive (auto, switched to always for the next epoch once the '
                                          "factor's pivots span more than 200x, i.e. approach the jitter floor)"),
     ('gp_side_stream', eval, False, 'GP cache build / cache backward on a side stream next to the encoder, without --hip_graph'),
+    ('subsample_frames', int, 0, 'K > 0: every sequence of a minibatch keeps K of its T frames, drawn per sequence (the first one always; '
+                                 'the first --frames for --ode 2), and is integrated over its own time grid dt * (kept indices); 0: off, '
+                                 'the uniform grid.  Drawn per minibatch from a generator of its own, seeded from --seed'),
     ('sync_bn', eval, True, 'data parallel: BatchNorm normalises with the statistics of the GLOBAL minibatch (all ranks), as the '
                             'single-process reference does (vae.py:55,58,113,116,119)'),
 ]
@@ -118,6 +121,26 @@ def synthetic_sequences(n, T, seed):
 def _frames(batch):
     """a loader item: the tensor itself (reference loaders, ResidentLoader) or a TensorDataset 1-tuple"""
     return batch[0] if isinstance(batch, (list, tuple)) else batch
+
+
+def subsample_lead(args):
+    """frames every subsampled sequence keeps at its head: the position encoder reads frame 0, the velocity encoder of a
+    second-order model the first --frames frames, as consecutive ones"""
+    return 1 if args.ode == 1 else args.frames
+
+
+def check_subsample(args):
+    """--subsample_frames K: 0 (off) or lead < K <= T, refused with a message otherwise"""
+    K, lead = args.subsample_frames, subsample_lead(args)
+    if K and (K > args.T or K <= lead):
+        raise SystemExit('--subsample_frames %d: must be 0 (off) or more than the %d leading frame(s) the encoders read (--ode %d) and '
+                         'at most --T %d' % (K, lead, args.ode, args.T))
+
+
+def subsample_generator(args):
+    """The generator of the frame subsets: its own, on the device, seeded from --seed alone -- identical on every rank, so the ranks
+    draw the same subsets for the global minibatch before they take their shards."""
+    return torch.Generator(device=args.device).manual_seed(args.seed + 104729)
 
 
 def load_data(args):
@@ -191,6 +214,7 @@ def cache_results(logger, args, ep, build_model):
 
 def main(argv=None):
     args = make_parser().parse_args(argv)
+    check_subsample(args)
     from .model.core.initialization import initialize_and_fix_kernel_parameters
     from .model.create_model import build_model, compute_loss, compute_test_error, backward
     from .model.misc.torch_utils import seed_everything
@@ -269,14 +293,15 @@ def main(argv=None):
     if args.hip_graph and not capture_ok:
         logger.info('cross-rank BatchNorm over {}: steps are launched eagerly (device noise and side stream stay on)'.format(dist.get_backend()))
 
-    def graphed_step(minibatch, L):
-        key = (L, tuple(minibatch.shape), bn_sync.shares if bn_sync is not None else None)
+    def graphed_step(minibatch, L, ts=None):
+        key = (L, tuple(minibatch.shape), bn_sync.shares if bn_sync is not None else None, None if ts is None else tuple(ts.shape))
         if key not in graphs:
             buf = torch.empty_like(minibatch)
+            tbuf = None if ts is None else torch.empty_like(ts)     # the time grids: a second static input of the captured step
 
             def step():
                 optimizer.zero_grad()
-                out = compute_loss(model, buf, L)
+                out = compute_loss(model, buf, L) if tbuf is None else compute_loss(model, buf, L, ts=tbuf)
                 backward(out[0])
                 if sync is None:
                     optimizer.step()
@@ -284,28 +309,43 @@ def main(argv=None):
                     ops.join_side_stream()
                 return out
             buf.copy_(minibatch)
+            if tbuf is not None:
+                tbuf.copy_(ts)
             gs = GraphedStep(step, generators=device_generators(model), warmup=1,
                              grad_params=optimizer.params if sync is not None else None)
-            graphs[key] = (buf, gs)
+            graphs[key] = (buf, tbuf, gs)
             if sync is not None:                     # the gradients the gather / all-reduce below must see are the warm-up's
                 gs.bind_warm_grads()
             return gs.warm_out                       # the capture warm-up already took this minibatch's (eager) step
-        buf, g = graphs[key]
+        buf, tbuf, g = graphs[key]
         buf.copy_(minibatch, non_blocking=True)
+        if tbuf is not None:
+            tbuf.copy_(ts, non_blocking=True)
         return g()
 
     from . import ops as gp_ops
     solves_mode = 'auto' if args.backward_solves == 'adaptive' else args.backward_solves
     gp_ops.set_backward_solves(solves_mode)
+    sub_gen = None
+    if args.subsample_frames:                        # off: no generator exists and no launch below changes
+        from .data.utils import subsample_frames
+        sub_gen = subsample_generator(args)
+        logger.info('Every sequence keeps {} of its frames, drawn per minibatch; time grids per sequence'.format(args.subsample_frames))
     logger.info('********** Started Training **********')
     begin = time.time()
     for ep in range(args.Nepoch):
         L = 1 if ep < args.Nepoch // 2 else 5
         for itr, local_batch in enumerate(trainset):
             minibatch = _frames(local_batch).to(args.device)
+            ts = None
+            if sub_gen is not None:                  # the global minibatch's subsets, the same on every rank, ahead of the shards
+                minibatch, kept = subsample_frames(minibatch, args.subsample_frames, subsample_lead(args), sub_gen)
+                ts = args.dt * kept.to(torch.float32)
             if sync is not None and minibatch.shape[0] >= world:     # this rank's shard; its share weights the gradient mean
                 n_global = minibatch.shape[0]
                 minibatch = shard_batch(minibatch, rank, world)
+                if ts is not None:
+                    ts = shard_batch(ts, rank, world).contiguous()   # the rows follow their sequences
                 sync.weight = minibatch.shape[0] / n_global
                 if bn_sync is not None:
                     bn_sync.set_shares([hi - lo for lo, hi in (shard_bounds(n_global, r, world) for r in range(world))])
@@ -314,9 +354,11 @@ def main(argv=None):
                 if bn_sync is not None:
                     bn_sync.set_shares(None)
             if args.hip_graph and capture_ok:
-                loss, nlhood, kl_reg, kl_u = graphed_step(minibatch, L)
-            else:
+                loss, nlhood, kl_reg, kl_u = graphed_step(minibatch, L, ts)
+            elif ts is None:
                 loss, nlhood, kl_reg, kl_u = compute_loss(model, minibatch, L)
+            else:
+                loss, nlhood, kl_reg, kl_u = compute_loss(model, minibatch, L, ts=ts)
             terms = torch.stack([t.detach().reshape(()) for t in (loss, nlhood, kl_reg, kl_u)])
             if sync is not None:                     # the global-batch values: shard means weighted by shard size
                 terms = terms * sync.weight

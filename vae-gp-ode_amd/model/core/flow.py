@@ -107,6 +107,8 @@ class Flow(nn.Module):
         """z0 (N,D), ts (T,) -> zt (N,T,D) for a fresh function draw (flow.py:68-86).  ``draws`` = L: L fresh draws integrated in
         one pass -> (L,N,T,D), the stack ODEGPVAE.sample_trajectories builds from L calls (odegpvae.py:41-44); ``_num_evals`` ends
         at the count of ONE solve, as it does after the reference's last call.  z0 (L,N,D): draw l starts from z0[l].
+        ts (N,T): sequence n of every draw is integrated over its own output times ts[n] -- the same launch with a row stride
+        on the grid; a first axis other than N is refused (ops.GpodeError).
         'dopri5': a trajectory that exhausts ``max_steps`` or whose step underflows is NaN from the output it missed (status in
         ``last_counts``); the others are unaffected."""
         try:
@@ -119,7 +121,7 @@ class Flow(nn.Module):
             return ops.flow(gp, z0, ts, self.odefunc.order, self.solver, draws,
                             (self.rtol, self.atol, self.max_steps, self._take_counts, bool(self.dense_output)))
         zt = ops.flow(gp, z0, ts, self.odefunc.order, self.solver, draws)
-        self.odefunc._set_evals(EVALS_PER_STEP[self.solver] * (ts.shape[0] - 1))
+        self.odefunc._set_evals(EVALS_PER_STEP[self.solver] * (ts.shape[-1] - 1))
         return zt
 
     def _take_counts(self, counts):

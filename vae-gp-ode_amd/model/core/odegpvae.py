@@ -19,15 +19,23 @@ class ODEGPVAE(nn.Module):
         lat = ztL if self.order == 1 else ztL[..., :ztL.shape[-1] // 2]
         return (self.vae.decoder(lat, logits=True) if logits else self.vae.decoder(lat)).view([L, N, T, nc, d, d])
 
-    def sample_trajectories(self, z0, T, L=1):
+    def sample_trajectories(self, z0, T, L=1, ts=None):
         """L independent function draws, each shared by the whole minibatch (odegpvae.py:37-45).  z0 (L,N,D): draw l starts from
-        its own sample z0[l] of the initial states (encode_initial_state(X, draws=L))."""
+        its own sample z0[l] of the initial states (encode_initial_state(X, draws=L)).
+        ``ts`` (N,T): the observation times of every sequence (shared by the draws); None = the uniform grid dt * arange(T)."""
         if z0.dim() == 3 and z0.shape[0] != L:
             raise ValueError('sample_trajectories: z0 holds initial states for %d draws, L = %d' % (z0.shape[0], L))
-        key = (T, str(z0.device))
-        if getattr(self, '_ts_key', None) != key:            # the grid dt * arange(T) is a constant of the run: build it once
-            self._ts, self._ts_key = self.dt * torch.arange(T, dtype=torch.float, device=z0.device), key
-        ts = self._ts
+        if ts is not None:
+            N = z0.shape[-2]
+            if ts.dim() != 2 or tuple(ts.shape) != (N, T):
+                raise ValueError('sample_trajectories: ts must be (N,T) = (%d,%d), one row of observation times per sequence; got %s'
+                                 % (N, T, tuple(ts.shape)))
+            ts = ts.to(device=z0.device, dtype=torch.float32).contiguous()
+        else:
+            key = (T, str(z0.device))
+            if getattr(self, '_ts_key', None) != key:        # the grid dt * arange(T) is a constant of the run: build it once
+                self._ts, self._ts_key = self.dt * torch.arange(T, dtype=torch.float, device=z0.device), key
+            ts = self._ts
         if L == 1:
             return self.flow(z0[0] if z0.dim() == 3 else z0, ts).unsqueeze(0)
         field = self.flow.odefunc.diffeq
@@ -74,10 +82,16 @@ class ODEGPVAE(nn.Module):
         mu_v, logv_v = vel(torch.squeeze(X[:, 0:self.v_steps]))
         return torch.concat([z0, vel.sample(mu=mu_v, logvar=logv_v)], dim=1), (mu_s, logv_s), (mu_v, logv_v)
 
-    def forward(self, X, L=1, T_custom=None, logits=False):
-        """X (N,T,nc,d,d) -> (Xrec (L,N,T',nc,d,d), (mu_s, logv_s), (mu_v, logv_v)); T' = T_custom or T (odegpvae.py:48-70)."""
+    def forward(self, X, L=1, T_custom=None, logits=False, ts=None):
+        """X (N,T,nc,d,d) -> (Xrec (L,N,T',nc,d,d), (mu_s, logv_s), (mu_v, logv_v)); T' = T_custom or T (odegpvae.py:48-70).
+        ``ts`` (N,T'): the time at which frame t of sequence n was observed -- the latent state is integrated to those times and
+        decoded there; None = the uniform grid dt * arange(T').  The encoders read the leading frames as they stand: for a
+        second-order model the first ``v_steps`` frames are taken to be consecutive."""
         N, T, nc, d, _ = X.shape
         horizon = T_custom if T_custom else T
+        if ts is not None and (ts.dim() != 2 or tuple(ts.shape) != (N, horizon)):
+            raise ValueError('forward: ts must be (N,T\') = (%d,%d), one row of observation times per sequence; got %s'
+                             % (N, horizon, tuple(ts.shape)))
         field = self.flow.odefunc.diffeq
         src = getattr(self.vae.encoder, 'eps_source', None)
         if src is not None and src is getattr(field, 'noise_source', None) and hasattr(field, 'predraw'):
@@ -88,5 +102,5 @@ class ODEGPVAE(nn.Module):
         if hasattr(field, 'prebuild_cache') and (L == 1 or field.batched_draws_supported()):
             field.prebuild_cache(None if L == 1 else L)   # overlap mode only: the cache of the draw(s) builds next to the encoder
         z0, code_s, code_v = self.encode_initial_state(X)
-        ztL = self.sample_trajectories(z0, horizon, L)
+        ztL = self.sample_trajectories(z0, horizon, L, ts=ts)
         return self.build_decoding(ztL, (L, N, horizon, nc, d, d), logits), code_s, code_v

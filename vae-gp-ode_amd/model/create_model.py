@@ -32,18 +32,21 @@ def elbo(model, X, Xrec, s0_mu, s0_logv, v0_mu, v0_logv, L):
     return lhood.mean(), kl_reg.mean(), model.flow.kl()
 
 
-def compute_loss(model, data, L):
+def compute_loss(model, data, L, ts=None):
     """-> (loss, nll, kl_reg, kl_u) (create_model.py:61-73).  Same terms as elbo() above; the per-row pieces go through
-    three fused launches (KL rows, likelihood row sums, loss algebra) instead of ~25 elementwise ones."""
+    three fused launches (KL rows, likelihood row sums, loss algebra) instead of ~25 elementwise ones.
+    ``ts`` (N,T): the observation time of every frame of every sequence (ODEGPVAE.forward); None = the uniform grid, the call as
+    it always was.  Every sequence still has T frames: the loss stage has no frame mask."""
     from .. import vae_ops as V
     field = model.flow.odefunc.diffeq
+    grid = {} if ts is None else {'ts': ts}
     if _FUSED_LOSS and hasattr(field, 'us_packed') and model.vae.decoder.distribution == 'bernoulli':
         # the decoder stops at its logits; sigmoid + likelihood row sums are one pass over them, and the three KL / mean / loss
         # launches one more (gpode_sigmoid_loglik_fwd, gpode_elbo_all_fwd)
-        logits, (s0_mu, s0_logv), (v0_mu, v0_logv) = model(data, L, logits=True)
+        logits, (s0_mu, s0_logv), (v0_mu, v0_logv) = model(data, L, logits=True, **grid)
         lpart, _ = V.sigmoid_loglik_parts(data, logits, L * data.shape[0])
         return V.elbo_all(lpart, s0_mu, s0_logv, v0_mu, v0_logv, field.Um.optvar, field.us_packed(), field.M, model.num_observations)
-    Xrec, (s0_mu, s0_logv), (v0_mu, v0_logv) = model(data, L)
+    Xrec, (s0_mu, s0_logv), (v0_mu, v0_logv) = model(data, L, **grid)
     kl_rows = model.vae.encoder.kl_rows(s0_mu, s0_logv, v0_mu, v0_logv)               # (N,)
     lhood_rows = model.vae.decoder.log_prob_rowsum(data, Xrec, L)                     # (L, N)
     out = V.elbo_terms(lhood_rows, kl_rows, model.flow.kl(), model.num_observations)

@@ -312,14 +312,27 @@ _ts_checked = [None]
 
 
 def _check_increasing(ts):
-    """Refuse output times that are not strictly increasing.  Reads the device, so it is skipped while the stream is being
-    captured into a graph and remembered per tensor (the kernel itself gives such a trajectory status 3 and NaN)."""
-    key = (ts.data_ptr(), ts._version, ts.shape[0])
-    if ts.shape[0] < 2 or _ts_checked[0] == key or torch.cuda.is_current_stream_capturing():
+    """Refuse output times that are not strictly increasing -- row by row for a grid per trajectory (N,T).  Reads the device, so it
+    is skipped while the stream is being captured into a graph and remembered per tensor (the kernel itself gives such a trajectory
+    status 3 and NaN)."""
+    key = (ts.data_ptr(), ts._version, tuple(ts.shape))
+    if ts.shape[-1] < 2 or _ts_checked[0] == key or torch.cuda.is_current_stream_capturing():
         return
-    if not bool((ts[1:] > ts[:-1]).all()):
-        raise _lib.GpodeError('dopri5: ts must be strictly increasing')
+    if not bool((ts[..., 1:] > ts[..., :-1]).all()):
+        raise _lib.GpodeError('dopri5: ts must be strictly increasing' + (' in every row' if ts.dim() == 2 else ''))
     _ts_checked[0] = key
+
+
+def _ts_per_traj(ts, N, T=None, rows='z0'):
+    """0 for a grid ts (T,) shared by all trajectories, 1 for (N,T): row n is the grid of trajectory n of every draw (the `_nt` entry
+    points).  Anything else is refused here, before any library call; ``rows`` names the operand N (and T) were read from."""
+    if ts.dim() == 1:
+        return 0
+    if ts.dim() != 2 or ts.shape[0] != N or (T is not None and ts.shape[1] != T):
+        want = '(%d,%s)' % (N, 'T' if T is None else T)
+        raise _lib.GpodeError('ts must be (%s,), or %s with one row per trajectory of %s; got ts %s'
+                              % ('T' if T is None else T, want, rows, tuple(ts.shape)))
+    return 1
 
 
 def _z0_per_draw(cache, z0):
@@ -333,13 +346,15 @@ def _z0_per_draw(cache, z0):
 
 
 def _rollout_args(cache, z0, ts, order):
-    """What rollout and rollout_adaptive check alike: z0, ts (contiguous), the z0_per_draw flag, N and the state dimension."""
+    """What rollout and rollout_adaptive check alike: z0, ts (contiguous), the z0_per_draw and ts_per_traj flags, N and the state
+    dimension."""
     z0 = _chk(z0, 'z0'); ts = _chk(ts, 'ts')
     zpd = _z0_per_draw(cache, z0)
     N, D = z0.shape[-2:]
     if D != cache.Di or D != order * cache.Do:
         raise _lib.GpodeError('state dim %d must equal D_in=%d = order*D_out=%d' % (D, cache.Di, order * cache.Do))
-    return z0, ts, zpd, N, D
+    tpt = _ts_per_traj(ts, N, rows='z0 %s' % (tuple(z0.shape),))
+    return z0, ts, zpd, tpt, N, D
 
 
 def _gzt_lead(cache, gzt):
@@ -359,9 +374,11 @@ def rollout_adaptive(cache, z0, ts, order, rtol=1e-6, atol=1e-6, max_steps=None,
     ``dense`` (gpode_rollout_dense_fwd_n): steps are cut at ts[-1] only and the interior outputs are interpolated (4th-order
     continuous extension, no evaluation of f); the record is then xstage ([L,] N,K,7,D), hstep, istep ([L,] N,T-1) int32 = 1-based
     number of the accepted step that holds output t+1, theta ([L,] N,T-1) = the output's position inside that step, in (0, 1].
-    z0 (L,N,D) with L = cache.nd gives every draw its own initial states (gpode_rollout_adaptive_fwd_nz / _dense_fwd_nz)."""
-    z0, ts, zpd, N, D = _rollout_args(cache, z0, ts, order)
-    T = ts.shape[0]
+    z0 (L,N,D) with L = cache.nd gives every draw its own initial states (gpode_rollout_adaptive_fwd_nz / _dense_fwd_nz).
+    ts (N,T) gives every trajectory its own output times (gpode_rollout_adaptive_fwd_nt / _dense_fwd_nt); a row that is not
+    strictly increasing is refused here, or -- under capture -- stops that trajectory alone with status 3."""
+    z0, ts, zpd, tpt, N, D = _rollout_args(cache, z0, ts, order)
+    T = ts.shape[-1]
     K = 4 * max(T - 1, 0) if max_steps is None else int(max_steps)
     if K < 0:
         raise _lib.GpodeError('max_steps must be >= 0, got %d' % K)
@@ -379,7 +396,9 @@ def rollout_adaptive(cache, z0, ts, order, rtol=1e-6, atol=1e-6, max_steps=None,
             _ptr(z0), _ptr(ts), N, T, float(rtol), float(atol), K, _ptr(zt), _ptr(xs), _ptr(hs), _ptr(ie))
     head += (_ptr(th), _ptr(counts)) if dense else (_ptr(counts),)
     name = 'gpode_rollout_dense_fwd' if dense else 'gpode_rollout_adaptive_fwd'
-    if zpd:
+    if tpt:
+        _lib.call(name + '_nt', *head, zpd, tpt, _stream())
+    elif zpd:
         _lib.call(name + '_nz', *head, zpd, _stream())
     else:
         _lib.call(name + '_n', *head, _stream())
@@ -415,6 +434,7 @@ def rollout(cache, z0, ts, order, method, save_stages=False, rtol=1e-6, atol=1e-
     """Flow.forward (flow.py:68-86) for a built cache: z0 (N,D), ts (T,) -> zt (N,T,D); a cache of L draws integrates all L * N
     trajectories in ONE launch -> zt (L,N,T,D) (the stack of odegpvae.py:41-44).  z0 (L,N,D) with L = the draws of the cache: draw l
     starts from z0[l] (gpode_rollout_fwd_nz) -- joint samples of the initial state and the function.
+    ts (N,T): trajectory n of every draw is integrated over its own grid ts[n] (gpode_rollout_fwd_nt).
     save_stages=True also returns the inputs of all RHS evaluations ([L,] N,T-1,NS,D) for the reverse sweep.
     method 'dopri5' (the only one that reads rtol / atol / max_steps / dense) is rollout_adaptive(): with save_stages the second value
     is its record (xstage, hstep, iend, counts), which rollout_bwd takes in place of xstage; in dense-output mode the record is
@@ -423,14 +443,16 @@ def rollout(cache, z0, ts, order, method, save_stages=False, rtol=1e-6, atol=1e-
     if method == 'dopri5':
         out = rollout_adaptive(cache, z0, ts, order, rtol, atol, max_steps, save_stages, dense=dense)
         return (out[0], (out[2], out[3], out[4], out[1]) + tuple(out[5:])) if save_stages else out[0]
-    z0, ts, zpd, N, D = _rollout_args(cache, z0, ts, order)
-    T = ts.shape[0]
+    z0, ts, zpd, tpt, N, D = _rollout_args(cache, z0, ts, order)
+    T = ts.shape[-1]
     lead = cache.lead
     zt = torch.empty(lead + (N, T, D), dtype=torch.float32, device=z0.device)
     xs = torch.empty(lead + (N, max(T - 1, 0), NSTAGE[method], D), dtype=torch.float32, device=z0.device) if save_stages else None
     head = (KERNEL_ID[cache.kernel], order, METHOD_ID[method], cache.Di, cache.Do, cache.M, cache.S, cache.nd, _ptr(cache.pack), _ptr(z0),
             _ptr(ts), N, T, _ptr(zt), _ptr(xs))
-    if zpd:
+    if tpt:
+        _lib.call('gpode_rollout_fwd_nt', *head, zpd, tpt, _stream())
+    elif zpd:
         _lib.call('gpode_rollout_fwd_nz', *head, zpd, _stream())
     else:
         _lib.call('gpode_rollout_fwd_n', *head, _stream())
@@ -439,15 +461,20 @@ def rollout(cache, z0, ts, order, method, save_stages=False, rtol=1e-6, atol=1e-
 
 def rollout_bwd(cache, xstage, gzt, ts, order, method):
     """Reverse sweep: gzt ([L,] N,T,D) -> gz0 ([L,] N,D), astage ([L,] N,T-1,NS,Do) (dopri5: xstage is rollout's record, astage
-    ([L,] N,K,6,Do), or ([L,] N,K,7,Do) for a dense-output record)."""
+    ([L,] N,K,6,Do), or ([L,] N,K,7,Do) for a dense-output record).  ts (T,) or (N,T) as in rollout (gpode_rollout_bwd_nt)."""
     if method == 'dopri5':
         return rollout_adaptive_bwd(cache, xstage[0], xstage[1], xstage[2], gzt, order, theta=xstage[4] if len(xstage) > 4 else None)
     (gzt, lead), xstage, ts = _gzt_lead(cache, gzt), _chk(xstage, 'xstage'), _chk(ts, 'ts')
     N, T, D = gzt.shape[-3:]
+    tpt = _ts_per_traj(ts, N, T, rows='gzt %s' % (tuple(gzt.shape),))
     gz0 = torch.empty(lead + (N, D), dtype=torch.float32, device=gzt.device)
     ast = torch.empty(lead + (N, T - 1, NSTAGE[method], cache.Do), dtype=torch.float32, device=gzt.device)
-    _lib.call('gpode_rollout_bwd_n', KERNEL_ID[cache.kernel], order, METHOD_ID[method], cache.Di, cache.Do, cache.M,
-              cache.S, cache.nd, _ptr(cache.pack), _ptr(xstage), _ptr(gzt), _ptr(ts), N, T, _ptr(gz0), _ptr(ast), _stream())
+    head = (KERNEL_ID[cache.kernel], order, METHOD_ID[method], cache.Di, cache.Do, cache.M, cache.S, cache.nd, _ptr(cache.pack),
+            _ptr(xstage), _ptr(gzt), _ptr(ts), N, T, _ptr(gz0), _ptr(ast))
+    if tpt:
+        _lib.call('gpode_rollout_bwd_nt', *head, tpt, _stream())
+    else:
+        _lib.call('gpode_rollout_bwd_n', *head, _stream())
     return gz0, ast
 
 
@@ -467,18 +494,23 @@ def pgrad_chunks(cache, N, order, method, force=False):
 
 
 def rollout_bwd_pgrad(cache, xstage, gzt, ts, order, method, nchunk, keep=None):
-    """rollout_bwd() and param_grad() in one pass over the rows (gpode_rollout_bwd_pgrad_n): -> gz0, astage, gpack ([L,] pack_floats)."""
+    """rollout_bwd() and param_grad() in one pass over the rows (gpode_rollout_bwd_pgrad_n; ts (N,T): gpode_rollout_bwd_pgrad_nt):
+    -> gz0, astage, gpack ([L,] pack_floats)."""
     gzt = _chk(gzt, 'gzt'); xstage = _chk(xstage, 'xstage'); ts = _chk(ts, 'ts')
     lead = cache.lead
     N, T, D = gzt.shape[-3:]
+    tpt = _ts_per_traj(ts, N, T, rows='gzt %s' % (tuple(gzt.shape),))
     pf = cache.pack.shape[-1]
     gz0 = torch.empty(lead + (N, D), dtype=torch.float32, device=gzt.device)
     ast = torch.empty(lead + (N, T - 1, NSTAGE[method], cache.Do), dtype=torch.float32, device=gzt.device)
     slab = torch.empty(cache.nd * nchunk * pf, dtype=torch.float32, device=gzt.device)
     gpack = torch.empty(lead + (pf,), dtype=torch.float32, device=gzt.device)
-    _lib.call('gpode_rollout_bwd_pgrad_n', KERNEL_ID[cache.kernel], order, METHOD_ID[method], cache.Di, cache.Do, cache.M, cache.S,
-              cache.nd, _ptr(cache.pack), _ptr(xstage), _ptr(gzt), _ptr(ts), N, T, _ptr(gz0), _ptr(ast), _ptr(slab), nchunk, _ptr(gpack),
-              _stream())
+    head = (KERNEL_ID[cache.kernel], order, METHOD_ID[method], cache.Di, cache.Do, cache.M, cache.S, cache.nd, _ptr(cache.pack),
+            _ptr(xstage), _ptr(gzt), _ptr(ts), N, T, _ptr(gz0), _ptr(ast), _ptr(slab), nchunk, _ptr(gpack))
+    if tpt:
+        _lib.call('gpode_rollout_bwd_pgrad_nt', *head, tpt, _stream())
+    else:
+        _lib.call('gpode_rollout_bwd_pgrad_n', *head, _stream())
     if keep is not None:
         keep.append(slab)
     return gz0, ast, gpack
@@ -680,7 +712,8 @@ class _Flow(torch.autograd.Function):
     in both xstage and astage, so the parameter sums run over all K * 6 rows.  ``dense``: the dense-output entry points; the record
     is (xstage, hstep, istep, theta) with 7 rows per step, saved behind the landing mode's tensors.
     z0 (L,N,D) with ``draws`` = L: every draw starts from its own slab (the `_nz` entry points); the gradient of z0 is then the
-    reverse sweep's gz0 (L,N,D) as it stands, where a shared z0 takes its sum over the draws."""
+    reverse sweep's gz0 (L,N,D) as it stands, where a shared z0 takes its sum over the draws.
+    ts (N,T): a time grid per trajectory, shared by the draws (the `_nt` entry points); ts carries no gradient either way."""
 
     @staticmethod
     def forward(ctx, z0, ts, raw_ell, raw_var, Z, Um, Us, gp, order, method, draws=None, adaptive=None):
@@ -762,6 +795,7 @@ class _Flow(torch.autograd.Function):
 def flow(gp, z0, ts, order, method, draws=None, adaptive=None):
     """One function draw -> zt (N,T,D); ``draws`` = L -> the L draws of odegpvae.py:41-44 in one pass, zt (L,N,T,D).
     ``adaptive`` = (rtol, atol, max_steps, sink[, dense]) for method 'dopri5' (see _Flow).
+    ts (T,), or (N,T): one grid per trajectory (row n for trajectory n of every draw).
     z0 (L,N,D): draw l starts from z0[l].  With ``draws`` = L on a layer that batches its draws this is still one pass; otherwise
     (``draws`` None, or a zero-padded width, whose draws are built one by one) it is L single-draw flows, stacked -- the sink of an
     adaptive solve then sees the counts of the last one, as after the reference's loop."""
