@@ -451,6 +451,17 @@ int gpode_dec10_predict(const float* c, const float* table, const float* w, cons
  * Refused, with nothing written: ell == NULL, done + Lc > L_total, every argument gpode_dec10_predict refuses, GPODE_CONV_VALU. */
 int gpode_dec10_predict_ll(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th,
                            int T_obs, int done, float* pred_mean, float* pred_m2, float* se_state, float* ell, int L_total, void* stream);
+/* gpode_dec10_predict and gpode_dec10_predict_ll for ragged sequences: n_obs[N] (int32, device) is the frame count of every sequence,
+ * X stays (N, T_obs, 1, 28, 28) with T_obs the padded width, and frame n * Th + t has a target iff t < min(T_obs, n_obs[n]).  A frame
+ * without one is treated as a forecast frame t >= T_obs: count 0 in se_state, 0 in ell, and what its padded target holds is never
+ * loaded; pred_mean / pred_m2 do not depend on n_obs.  Frames with a target get the twin's bits, n_obs[n] >= T_obs for all n gives the
+ * twin's bits everywhere, and a split of the draws over launches gives the bits of one launch.  gpode_last_launch(): the twin's tag
+ * + "_len".  Refused, with nothing written: n_obs == NULL and every argument the twin refuses. */
+int gpode_dec10_predict_len(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th,
+                            int T_obs, int done, float* pred_mean, float* pred_m2, float* se_state, const int* n_obs, void* stream);
+int gpode_dec10_predict_ll_len(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th,
+                               int T_obs, int done, float* pred_mean, float* pred_m2, float* se_state, float* ell, int L_total,
+                               const int* n_obs, void* stream);
 /* out[c] = sum_{b,hw} v[b,c,hw] (bias gradients); scratch: gpode_bn_scratch(B,C) floats. */
 int gpode_chan_sum(const float* v, float* out, int B, int C, int HW, float* scratch, void* stream);
 /* mode 0: ReLU, 1: sigmoid (vae.py:60,121).  Backward takes the forward OUTPUT y. */
@@ -477,6 +488,14 @@ int gpode_loglik_bwd(const float* X, const float* z, const float* g, float* gz, 
 int gpode_loglik_rowsum_fwd(const float* X, const float* z, float* out, size_t rows, size_t inner, size_t nX, void* stream);
 int gpode_loglik_rowsum_bwd(const float* X, const float* z, const float* grow, float* gz, size_t rows, size_t inner, size_t nX,
                             void* stream);
+
+/* The row sum and its adjoint for ragged sequences (the separate-kernel form of the *_len entries below, and their A/B reference): a row
+ * is T frames of `frame` elements, sequence n = row % (nX / inner) owns the frames t < n_obs[n].  out[row] sums the observed terms only;
+ * gz = 0 on padded elements, whose X and z are not read.  Refusals and tags as described below. */
+int gpode_loglik_rowsum_fwd_len(const float* X, const float* z, float* out, size_t rows, size_t inner, size_t nX, const int* n_obs, int T,
+                                size_t frame, void* stream);
+int gpode_loglik_rowsum_bwd_len(const float* X, const float* z, const float* grow, float* gz, size_t rows, size_t inner, size_t nX,
+                                const int* n_obs, int T, size_t frame, void* stream);
 
 /* The last two stages of the training step's forward pass, fused (and their adjoints):
  *   gpode_sigmoid_loglik_fwd  z = sigmoid(a) (vae.py:84, the decoder's nn.Sigmoid) and the Bernoulli log-likelihood of X under z
@@ -506,6 +525,26 @@ int gpode_elbo_all_bwd_ll(const float* g_loss, const float* g_nll, const float* 
                           const float* hv, int N, int q, int M, int Do, const float* Um, const float* Us, float nobs, float* glrow, float* ghs,
                           float* ghv, float* dUm, float* dUs, const float* X, const float* z, float* ga, size_t n_logits, size_t nX,
                           void* stream);
+/* Ragged minibatches: the loss stage with a frame count per sequence.  A ragged minibatch is a padded one -- X (N,T,...), n_obs[N]
+ * (int32, device); rows are (draw, sequence), sequence n = row % N with N = nX / inner, frame t = p / frame for offset p inside the row
+ * (`frame` = elements per frame, inner = T * frame), and frame t of sequence n is observed iff t < n_obs[n] (<= 0: none, >= T: all).
+ * Each entry takes its twin's arguments plus n_obs, T and frame:
+ *   gpode_sigmoid_loglik_fwd_len  z is written for every element with the twin's bits; part[row][split] sums the observed terms only
+ *                                 (a row without a frame gives exactly 0).  The 16-byte path is taken only when frame % 4 == 0.
+ *   gpode_sigmoid_loglik_bwd_len, gpode_elbo_all_bwd_ll_len, gpode_elbo_all_bwd_ll_kl_len
+ *                                 ga = 0 on padded elements, whose X and z are not read; the twin's expression on observed ones; every
+ *                                 other output of the two fused launches is the twin's, bit for bit.
+ * The mask is a select, not a multiply: NaN or Inf in a padded target or logit reaches no sum and no gradient.  With n_obs[n] >= T for
+ * all n every output has the twin's bits.  The KL terms have no mask: gpode_elbo_all_fwd / _fwd_kl serve both.  gpode_last_launch():
+ * the twin's tag + "_len".  Refused, with nothing written: n_obs == NULL, inner != T * frame, nX % inner != 0, and what the twin refuses. */
+int gpode_sigmoid_loglik_fwd_len(const float* X, const float* a, float* z, float* part, size_t rows, size_t inner, size_t nX, int nsplit,
+                                 const int* n_obs, int T, size_t frame, void* stream);
+int gpode_sigmoid_loglik_bwd_len(const float* X, const float* z, const float* grow, float* ga, size_t rows, size_t inner, size_t nX,
+                                 const int* n_obs, int T, size_t frame, void* stream);
+int gpode_elbo_all_bwd_ll_len(const float* g_loss, const float* g_nll, const float* g_kl, const float* g_klu, int nl_rows, const float* hs,
+                              const float* hv, int N, int q, int M, int Do, const float* Um, const float* Us, float nobs, float* glrow, float* ghs,
+                              float* ghv, float* dUm, float* dUs, const float* X, const float* z, float* ga, size_t n_logits, size_t nX,
+                              const int* n_obs, int T, size_t frame, void* stream);
 /* All device-side noise of a step in one launch (the reference draws on the host with numpy -- kernels.py:13-26,134-137,
  * svpy.py:12-27,94 -- and with torch.randn_like, vae.py:76; `--device_noise` / DeviceNoise draws here instead):
  *   out[0 .. n_normal) ~ N(0,1), out[n_normal .. n_normal + n_uniform) ~ U[0,1): Philox4x32-10 keyed by `seed`, counter = (element
@@ -532,6 +571,11 @@ int gpode_elbo_all_fwd_kl(const float* lpart, int nl_rows, int nl_values, const 
 int gpode_elbo_all_bwd_ll_kl(const float* g_loss, const float* g_nll, const float* g_kl, const float* g_klu, int nl_rows, int N, int M, int Do,
                              const float* Um, const float* Us, float nobs, float* glrow, float* gkls, int nks, float* gklv, int nkv,
                              float* dUm, float* dUs, const float* X, const float* z, float* ga, size_t n_logits, size_t nX, void* stream);
+/* gpode_elbo_all_bwd_ll_kl for ragged minibatches (see gpode_sigmoid_loglik_fwd_len) */
+int gpode_elbo_all_bwd_ll_kl_len(const float* g_loss, const float* g_nll, const float* g_kl, const float* g_klu, int nl_rows, int N, int M,
+                                 int Do, const float* Um, const float* Us, float nobs, float* glrow, float* gkls, int nks, float* gklv, int nkv,
+                                 float* dUm, float* dUs, const float* X, const float* z, float* ga, size_t n_logits, size_t nX,
+                                 const int* n_obs, int T, size_t frame, void* stream);
 int gpode_reparam_fwd(const float* mu, const float* logvar, int ld, const float* eps, float* z, int N, int q, void* stream);
 /* L reparameterised draws of one encoder distribution and their importance log-weights (forward only; evaluation):
  *   z[l,n,i]  = mu[n,i] + exp(logvar[n,i] / 2) eps[l,n,i]   -- the bits gpode_reparam_fwd gives for (mu, logvar, eps[l]) --

@@ -137,6 +137,15 @@ SIGNATURES.update({
     'gpode_gather_multi': (_i, [_vp, _vp, _i, ctypes.c_longlong, _c_float_p, _vp]),
     'gpode_adam_multi': (_i, [_vp, _vp, _vp, _vp, _vp, _i, ctypes.c_longlong, _f, _f, _f, _f, _i, _vp, _vp]),
     'gpode_loglik_rowsum_bwd': (_i, [_c_float_p] * 4 + [_sz, _sz, _sz, _vp]),
+    # ragged minibatches: the twins' arguments + n_obs (int32 device pointer) [+ T, frame]
+    'gpode_sigmoid_loglik_fwd_len': (_i, [_c_float_p] * 4 + [_sz, _sz, _sz, _i, _vp, _i, _sz, _vp]),
+    'gpode_sigmoid_loglik_bwd_len': (_i, [_c_float_p] * 4 + [_sz, _sz, _sz, _vp, _i, _sz, _vp]),
+    'gpode_loglik_rowsum_fwd_len': (_i, [_c_float_p] * 3 + [_sz, _sz, _sz, _vp, _i, _sz, _vp]),
+    'gpode_loglik_rowsum_bwd_len': (_i, [_c_float_p] * 4 + [_sz, _sz, _sz, _vp, _i, _sz, _vp]),
+    'gpode_elbo_all_bwd_ll_len': (_i, [_c_float_p] * 4 + [_i, _c_float_p, _c_float_p, _i, _i, _i, _i, _c_float_p, _c_float_p, _f] + [_c_float_p] * 8 + [_sz, _sz, _vp, _i, _sz, _vp]),
+    'gpode_elbo_all_bwd_ll_kl_len': (_i, [_c_float_p] * 4 + [_i, _i, _i, _i, _c_float_p, _c_float_p, _f, _c_float_p, _c_float_p, _i, _c_float_p, _i] + [_c_float_p] * 5 + [_sz, _sz, _vp, _i, _sz, _vp]),
+    'gpode_dec10_predict_len': (_i, [_c_float_p] * 5 + [_i] * 5 + [_c_float_p] * 3 + [_vp, _vp]),
+    'gpode_dec10_predict_ll_len': (_i, [_c_float_p] * 5 + [_i] * 5 + [_c_float_p] * 4 + [_i, _vp, _vp]),
 })
 
 _lib = None

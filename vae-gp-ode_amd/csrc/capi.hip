@@ -552,6 +552,17 @@ int gpode_dec10_predict_ll(const float* c, const float* table, const float* w, c
   if (!c || !table || !w || !X || !se_state) return gp::set_error("gpode_dec10_predict_ll: null pointer");
   return gp::dec10_predict_ll(c, table, w, bias, X, Lc, F, Th, T_obs, done, pred_mean, pred_m2, se_state, ell, L_total, GP_ST);
 }
+int gpode_dec10_predict_len(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th,
+                            int T_obs, int done, float* pred_mean, float* pred_m2, float* se_state, const int* n_obs, void* stream) {
+  if (!c || !table || !w || !X || !se_state) return gp::set_error("gpode_dec10_predict_len: null pointer");
+  return gp::dec10_predict_len(c, table, w, bias, X, Lc, F, Th, T_obs, done, pred_mean, pred_m2, se_state, n_obs, GP_ST);
+}
+int gpode_dec10_predict_ll_len(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th,
+                               int T_obs, int done, float* pred_mean, float* pred_m2, float* se_state, float* ell, int L_total,
+                               const int* n_obs, void* stream) {
+  if (!c || !table || !w || !X || !se_state) return gp::set_error("gpode_dec10_predict_ll_len: null pointer");
+  return gp::dec10_predict_ll_len(c, table, w, bias, X, Lc, F, Th, T_obs, done, pred_mean, pred_m2, se_state, ell, L_total, n_obs, GP_ST);
+}
 int gpode_chan_sum(const float* v, float* out, int B, int C, int HW, float* scratch, void* stream) {
   if (!v || !out || !scratch) return gp::set_error("gpode_chan_sum: null pointer");
   return gp::chan_sum(v, out, B, C, HW, scratch, GP_ST);
@@ -588,6 +599,18 @@ int gpode_loglik_rowsum_bwd(const float* X, const float* z, const float* grow, f
                             void* stream) {
   return gp::loglik_rowsum_bwd(X, z, grow, gz, rows, inner, nX, GP_ST);
 }
+int gpode_loglik_rowsum_fwd_len(const float* X, const float* z, float* out, size_t rows, size_t inner, size_t nX, const int* n_obs, int T,
+                                size_t frame, void* stream) {
+  if (!X || !z || !out) return gp::set_error("gpode_loglik_rowsum_fwd_len: null pointer");
+  if (!rows || !inner || !nX) return gp::set_error("gpode_loglik_rowsum_fwd_len: empty input");
+  return gp::loglik_rowsum_fwd_len(X, z, out, rows, inner, nX, n_obs, T, frame, GP_ST);
+}
+int gpode_loglik_rowsum_bwd_len(const float* X, const float* z, const float* grow, float* gz, size_t rows, size_t inner, size_t nX,
+                                const int* n_obs, int T, size_t frame, void* stream) {
+  if (!X || !z || !grow || !gz) return gp::set_error("gpode_loglik_rowsum_bwd_len: null pointer");
+  if (!rows || !inner || !nX) return gp::set_error("gpode_loglik_rowsum_bwd_len: empty input");
+  return gp::loglik_rowsum_bwd_len(X, z, grow, gz, rows, inner, nX, n_obs, T, frame, GP_ST);
+}
 int gpode_noise_fill(float* out, long long n_normal, long long n_uniform, unsigned long long seed, unsigned long long* state, void* stream) {
   if (n_normal < 0 || n_uniform < 0) return gp::set_error("gpode_noise_fill: negative count");
   if (n_normal + n_uniform == 0) return 0;
@@ -619,6 +642,16 @@ int gpode_elbo_all_bwd_ll_kl(const float* g_loss, const float* g_nll, const floa
     return gp::set_error("gpode_elbo_all_bwd_ll_kl: bad sizes");
   return gp::elbo_all_bwd_ll_kl(g_loss, g_nll, g_kl, g_klu, nl_rows, N, M, Do, Um, Us, nobs, glrow, gkls, nks, gklv, nkv, dUm, dUs, X, z, ga,
                                 n_logits, nX, GP_ST);
+}
+int gpode_elbo_all_bwd_ll_kl_len(const float* g_loss, const float* g_nll, const float* g_kl, const float* g_klu, int nl_rows, int N, int M,
+                                 int Do, const float* Um, const float* Us, float nobs, float* glrow, float* gkls, int nks, float* gklv, int nkv,
+                                 float* dUm, float* dUs, const float* X, const float* z, float* ga, size_t n_logits, size_t nX,
+                                 const int* n_obs, int T, size_t frame, void* stream) {
+  if (!Um || !Us || !glrow || !gkls || !dUm || !dUs || (nkv > 0 && !gklv) || !X || !z || !ga) return gp::set_error("gpode_elbo_all_bwd_ll_kl_len: null pointer");
+  if (nl_rows < 1 || N < 1 || M < 1 || Do < 1 || nks < 1 || nkv < 0 || n_logits < 1 || nX < 1 || n_logits % nX != 0)
+    return gp::set_error("gpode_elbo_all_bwd_ll_kl_len: bad sizes");
+  return gp::elbo_all_bwd_ll_kl_len(g_loss, g_nll, g_kl, g_klu, nl_rows, N, M, Do, Um, Us, nobs, glrow, gkls, nks, gklv, nkv, dUm, dUs, X, z, ga,
+                                    n_logits, nX, n_obs, T, frame, GP_ST);
 }
 int gpode_reparam_fwd(const float* mu, const float* logvar, int ld, const float* eps, float* z, int N, int q, void* stream) {
   if (N == 0) return 0;
@@ -663,6 +696,18 @@ int gpode_sigmoid_loglik_bwd(const float* X, const float* z, const float* grow, 
   if (!rows || !inner || !nX) return gp::set_error("gpode_sigmoid_loglik_bwd: empty input");
   return gp::sigmoid_loglik_bwd(X, z, grow, ga, rows, inner, nX, GP_ST);
 }
+int gpode_sigmoid_loglik_fwd_len(const float* X, const float* a, float* z, float* part, size_t rows, size_t inner, size_t nX, int nsplit,
+                                 const int* n_obs, int T, size_t frame, void* stream) {
+  if (!X || !a || !z || !part) return gp::set_error("gpode_sigmoid_loglik_fwd_len: null pointer");
+  if (!rows || !inner || !nX) return gp::set_error("gpode_sigmoid_loglik_fwd_len: empty input");
+  return gp::sigmoid_loglik_fwd_len(X, a, z, part, rows, inner, nX, nsplit, n_obs, T, frame, GP_ST);
+}
+int gpode_sigmoid_loglik_bwd_len(const float* X, const float* z, const float* grow, float* ga, size_t rows, size_t inner, size_t nX,
+                                 const int* n_obs, int T, size_t frame, void* stream) {
+  if (!X || !z || !grow || !ga) return gp::set_error("gpode_sigmoid_loglik_bwd_len: null pointer");
+  if (!rows || !inner || !nX) return gp::set_error("gpode_sigmoid_loglik_bwd_len: empty input");
+  return gp::sigmoid_loglik_bwd_len(X, z, grow, ga, rows, inner, nX, n_obs, T, frame, GP_ST);
+}
 int gpode_elbo_all_fwd(const float* lpart, int nl_rows, int nl_values, const float* hs, const float* hv, int N, int q, int M, int Do,
                        const float* Um, const float* Us, float nobs, float* out, void* stream) {
   if (!lpart || !hs || !Um || !Us || !out) return gp::set_error("gpode_elbo_all_fwd: null pointer");
@@ -684,6 +729,15 @@ int gpode_elbo_all_bwd_ll(const float* g_loss, const float* g_nll, const float* 
   if (nl_rows < 1 || N < 1 || q < 1 || M < 1 || Do < 1 || n_logits < 1 || nX < 1 || n_logits % nX != 0) return gp::set_error("gpode_elbo_all_bwd_ll: bad sizes");
   return gp::elbo_all_bwd_ll(g_loss, g_nll, g_kl, g_klu, nl_rows, hs, hv, N, q, M, Do, Um, Us, nobs, glrow, ghs, ghv, dUm, dUs, X, z, ga, n_logits,
                              nX, GP_ST);
+}
+int gpode_elbo_all_bwd_ll_len(const float* g_loss, const float* g_nll, const float* g_kl, const float* g_klu, int nl_rows, const float* hs,
+                              const float* hv, int N, int q, int M, int Do, const float* Um, const float* Us, float nobs, float* glrow, float* ghs,
+                              float* ghv, float* dUm, float* dUs, const float* X, const float* z, float* ga, size_t n_logits, size_t nX,
+                              const int* n_obs, int T, size_t frame, void* stream) {
+  if (!hs || !Um || !Us || !glrow || !ghs || !dUm || !dUs || (hv && !ghv) || !X || !z || !ga) return gp::set_error("gpode_elbo_all_bwd_ll_len: null pointer");
+  if (nl_rows < 1 || N < 1 || q < 1 || M < 1 || Do < 1 || n_logits < 1 || nX < 1 || n_logits % nX != 0) return gp::set_error("gpode_elbo_all_bwd_ll_len: bad sizes");
+  return gp::elbo_all_bwd_ll_len(g_loss, g_nll, g_kl, g_klu, nl_rows, hs, hv, N, q, M, Do, Um, Us, nobs, glrow, ghs, ghv, dUm, dUs, X, z, ga,
+                                 n_logits, nX, n_obs, T, frame, GP_ST);
 }
 int gpode_elbo_fwd(const float* lhood, int nl, const float* klrow, int nk, const float* kl_u, float nobs, float* out, void* stream) {
   if (!lhood || !klrow || !kl_u || !out || nl < 1 || nk < 1) return gp::set_error("gpode_elbo_fwd: bad argument");

@@ -131,15 +131,21 @@ __global__ __launch_bounds__(512) void k_fwd(const float* __restrict__ x, const 
 // rides in the first wavefront reduction (two values wide instead of one), takes one more LDS slot per wavefront (s_r: 24 floats), and
 // the eight slots are added in wavefront order behind the second barrier.  Every entry of ell is written exactly once (0 for a frame
 // without a target) and depends on one image only.  LL = false is the kernel as it was: ell is not touched, LDS = 25 * PST + 16 floats.
+//
+// LEN = true (gpode_dec10_predict_len / _ll_len, ragged sequences): sequence n has a target for frame t iff t < min(T_obs, n_obs[n]);
+// X stays (N, T_obs, ...) with T_obs the padded width, and what its padded frames hold is never loaded.  The test is still
+// workgroup-uniform (a workgroup owns a frame), so a frame past its sequence's count is treated exactly as a forecast frame t >= T_obs:
+// count 0 in se_state, 0 in ell, pred_mean / pred_m2 as ever.  LEN = false does not read n_obs.
 // ---------------------------------------------------------------------------------------------
 // pixels owned by the 64 threads of wavefront wv in the epilogue: 64 (o = tid) plus those of o = tid + 512 below 784
 __host__ __device__ constexpr int wave_pixels(int wv) { return 64 + (NP - 512 - 64 * wv > 64 ? 64 : (NP - 512 - 64 * wv > 0 ? NP - 512 - 64 * wv : 0)); }
 
-template <bool LL>
+template <bool LL, bool LEN = false>
 __global__ __launch_bounds__(512) void k_fwd_predict(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                                                      const float* __restrict__ in_bn, const float* __restrict__ X, int Lc, int F, int Th,
                                                      int T_obs, int done, float* __restrict__ pred_mean, float* __restrict__ pred_m2,
-                                                     float* __restrict__ se_state, float* __restrict__ ell) {
+                                                     float* __restrict__ se_state, float* __restrict__ ell,
+                                                     const int* __restrict__ n_obs = nullptr) {
   float* s_T = igemm_smem;                           // [25][PST], zero borders
   float* s_r = s_T + KK * PST;                       // [8][2] the wavefronts' {mean, M2} of the current image; LL: + [8] their sums of lp
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -177,7 +183,8 @@ __global__ __launch_bounds__(512) void k_fwd_predict(const float* __restrict__ x
   const float inv_nw = 1.f / (float)wave_pixels(wave);
   for (int f = blockIdx.x; f < F; f += gridDim.x) {
     const int n = f / Th, t = f % Th;
-    const bool has_t = t < T_obs;                    // workgroup-uniform
+    bool has_t = t < T_obs;                          // workgroup-uniform
+    if constexpr (LEN) has_t = has_t && t < n_obs[n];
     float xt[2] = {0.f, 0.f}, pm[2] = {0.f, 0.f}, pq[2] = {0.f, 0.f};
     if (has_t) {
       const float* Xp = X + ((size_t)n * T_obs + t) * NP;

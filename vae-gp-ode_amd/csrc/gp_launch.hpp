@@ -237,6 +237,28 @@ int elbo_all_fwd(const float* lpart, int nl_rows, int nl_values, const float* hs
 int elbo_all_bwd(const float* g0, const float* g1, const float* g2, const float* g3, int nl_rows, const float* hs, const float* hv, int N,
                  int q, int M, int Do, const float* Um, const float* Us, float nobs, float* glrow, float* ghs, float* ghv, float* dUm,
                  float* dUs, hipStream_t st);
+// ragged minibatches: the twins above with a frame count per sequence (n_obs[n], frame t observed iff t < n_obs[n]); vae_conv.hip
+int sigmoid_loglik_fwd_len(const float* X, const float* a, float* z, float* part, size_t rows, size_t inner, size_t nX, int nsplit,
+                           const int* n_obs, int T, size_t frame, hipStream_t st);
+int sigmoid_loglik_bwd_len(const float* X, const float* z, const float* grow, float* ga, size_t rows, size_t inner, size_t nX,
+                           const int* n_obs, int T, size_t frame, hipStream_t st);
+int loglik_rowsum_fwd_len(const float* X, const float* z, float* out, size_t rows, size_t inner, size_t nX, const int* n_obs, int T,
+                          size_t frame, hipStream_t st);
+int loglik_rowsum_bwd_len(const float* X, const float* z, const float* grow, float* gz, size_t rows, size_t inner, size_t nX,
+                          const int* n_obs, int T, size_t frame, hipStream_t st);
+int elbo_all_bwd_ll_len(const float* g0, const float* g1, const float* g2, const float* g3, int nl_rows, const float* hs, const float* hv, int N,
+                        int q, int M, int Do, const float* Um, const float* Us, float nobs, float* glrow, float* ghs, float* ghv, float* dUm,
+                        float* dUs, const float* X, const float* z, float* ga, size_t n, size_t nX, const int* n_obs, int T, size_t frame,
+                        hipStream_t st);
+int elbo_all_bwd_ll_kl_len(const float* g0, const float* g1, const float* g2, const float* g3, int nl_rows, int N, int M, int Do, const float* Um,
+                           const float* Us, float nobs, float* glrow, float* gkls, int nks, float* gklv, int nkv, float* dUm, float* dUs,
+                           const float* X, const float* z, float* ga, size_t n, size_t nX, const int* n_obs, int T, size_t frame,
+                           hipStream_t st);
+int dec10_predict_len(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th, int T_obs,
+                      int done, float* pred_mean, float* pred_m2, float* se_state, const int* n_obs, hipStream_t st);
+int dec10_predict_ll_len(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th, int T_obs,
+                         int done, float* pred_mean, float* pred_m2, float* se_state, float* ell, int L_total, const int* n_obs,
+                         hipStream_t st);
 int elbo_fwd(const float* lhood, int nl, const float* klrow, int nk, const float* kl_u, float nobs, float* out, hipStream_t st);
 int elbo_bwd(const float* gout, int nl, int nk, float nobs, float* glhood, float* gklrow, float* gklu, hipStream_t st);
 int gather_multi(const float* const* grads, const long long* offs, int ntensors, long long total, float* flat, hipStream_t st);

@@ -315,13 +315,24 @@ __global__ void k_loglik_bwd(const float* __restrict__ X, const float* __restric
     gz[e] = g[e] * (xv / zv - (1.f - xv) / (1.f - zv));
   }
 }
+// Ragged minibatches (the *_len entry points): a row is (draw, sequence), sequence n = row % N owns the frames t < n_obs[n] of its T
+// padded ones, `frame` elements each, so offset p of a row is observed iff p < obs_limit(...) -- a select, never a multiply: what a
+// padded target or logit holds (NaN, Inf) reaches no sum and no gradient.  Counts <= 0 mean no frame, counts >= T all of them.
+__device__ __forceinline__ size_t obs_limit(const int* __restrict__ n_obs, size_t seq, int T, size_t frame) {
+  const int k = n_obs[seq];
+  return (size_t)(k < 0 ? 0 : (k > T ? T : k)) * frame;
+}
 // fused reduction used by the ELBO (create_model.py:52-53): out[row] = sum over `inner` of ll; row = (l,n)
+// MASK: the observed terms only (k_loglik_rowsum<false> is the kernel as it was; n_obs, T, frame are not read)
+template <bool MASK>
 __global__ __launch_bounds__(256) void k_loglik_rowsum(const float* __restrict__ X, const float* __restrict__ z, float* __restrict__ out,
-                                                        size_t inner, size_t nX) {
+                                                        size_t inner, size_t nX, const int* __restrict__ n_obs, int T, size_t frame) {
   __shared__ float red[4];
   const size_t row = blockIdx.x;
+  size_t lim = inner;
+  if constexpr (MASK) lim = obs_limit(n_obs, row % (nX / inner), T, frame);
   float acc = 0.f;
-  for (size_t p = threadIdx.x; p < inner; p += 256) {
+  for (size_t p = threadIdx.x; p < lim; p += 256) {
     const size_t e = row * inner + p;
     const float xv = X[e % nX], zv = z[e];
     acc += logf(zv) * xv + logf(1.f - zv) * (1.f - xv);
@@ -332,9 +343,15 @@ __global__ __launch_bounds__(256) void k_loglik_rowsum(const float* __restrict__
   __syncthreads();
   if (threadIdx.x == 0) out[row] = red[0] + red[1] + red[2] + red[3];
 }
+template <bool MASK>
 __global__ void k_loglik_rowsum_bwd(const float* __restrict__ X, const float* __restrict__ z, const float* __restrict__ grow,
-                                    float* __restrict__ gz, size_t n, size_t inner, size_t nX) {
+                                    float* __restrict__ gz, size_t n, size_t inner, size_t nX, const int* __restrict__ n_obs, int T,
+                                    size_t frame) {
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+    if constexpr (MASK) {
+      const size_t ex = e % nX;
+      if (ex % inner >= obs_limit(n_obs, ex / inner, T, frame)) { gz[e] = 0.f; continue; }   // padded: X and z are not read
+    }
     const float xv = X[e % nX], zv = z[e];
     gz[e] = grow[e / inner] * (xv / zv - (1.f - xv) / (1.f - zv));
   }
@@ -532,13 +549,35 @@ int loglik_bwd(const float* X, const float* z, const float* g, float* gz, size_t
   return check_launch("loglik_bwd");
 }
 int loglik_rowsum_fwd(const float* X, const float* z, float* out, size_t rows, size_t inner, size_t nX, hipStream_t st) {
-  hipLaunchKernelGGL(k_loglik_rowsum, (unsigned)rows, 256, 0, st, X, z, out, inner, nX);
+  hipLaunchKernelGGL(k_loglik_rowsum<false>, (unsigned)rows, 256, 0, st, X, z, out, inner, nX, (const int*)nullptr, 0, (size_t)0);
   return check_launch("loglik_rowsum");
+}
+// what every *_len launcher refuses, with nothing written: rows of T frames of `frame` elements, X a whole number of them
+static const char* len_refusal(size_t inner, size_t nX, const int* n_obs, int T, size_t frame) {
+  if (n_obs == nullptr) return "n_obs is NULL";
+  if (T < 1 || frame < 1 || inner != (size_t)T * frame) return "inner must be T * frame";
+  if (nX < inner || nX % inner != 0) return "X must hold a whole number of sequences (nX a multiple of inner)";
+  return nullptr;
+}
+int loglik_rowsum_fwd_len(const float* X, const float* z, float* out, size_t rows, size_t inner, size_t nX, const int* n_obs, int T,
+                          size_t frame, hipStream_t st) {
+  if (const char* why = len_refusal(inner, nX, n_obs, T, frame)) return set_error("gpode_loglik_rowsum_fwd_len: %s", why);
+  if (rows == 0 || (rows * inner) % nX != 0) return set_error("gpode_loglik_rowsum_fwd_len: X must tile the rows");
+  hipLaunchKernelGGL(k_loglik_rowsum<true>, (unsigned)rows, 256, 0, st, X, z, out, inner, nX, n_obs, T, frame);
+  return check_launch("loglik_rowsum_len");
 }
 int loglik_rowsum_bwd(const float* X, const float* z, const float* grow, float* gz, size_t rows, size_t inner, size_t nX, hipStream_t st) {
   const size_t n = rows * inner;
-  hipLaunchKernelGGL(k_loglik_rowsum_bwd, ew_grid(n), 256, 0, st, X, z, grow, gz, n, inner, nX);
+  hipLaunchKernelGGL(k_loglik_rowsum_bwd<false>, ew_grid(n), 256, 0, st, X, z, grow, gz, n, inner, nX, (const int*)nullptr, 0, (size_t)0);
   return check_launch("loglik_rowsum_bwd");
+}
+int loglik_rowsum_bwd_len(const float* X, const float* z, const float* grow, float* gz, size_t rows, size_t inner, size_t nX,
+                          const int* n_obs, int T, size_t frame, hipStream_t st) {
+  if (const char* why = len_refusal(inner, nX, n_obs, T, frame)) return set_error("gpode_loglik_rowsum_bwd_len: %s", why);
+  if (rows == 0 || (rows * inner) % nX != 0) return set_error("gpode_loglik_rowsum_bwd_len: X must tile the rows");
+  const size_t n = rows * inner;
+  hipLaunchKernelGGL(k_loglik_rowsum_bwd<true>, ew_grid(n), 256, 0, st, X, z, grow, gz, n, inner, nX, n_obs, T, frame);
+  return check_launch("loglik_rowsum_bwd_len");
 }
 
 
@@ -683,28 +722,79 @@ __global__ void k_elbo_bwd(const float* __restrict__ gout, int nl, int nk, float
 // z = sigmoid(a) (vae.py:84, nn.Sigmoid) and sum over a row slice of log(z) X + log(1 - z)(1 - X) (vae.py:136-153 summed as
 // create_model.py:49 does): grid (nsplit, rows); part[row][split].  Same expressions as k_act_fwd / k_loglik_rowsum, so z and
 // every term are bit-identical to the separate kernels; only the order of the row sum differs.
+// MASK (gpode_sigmoid_loglik_fwd_len): z is written for every element as ever, the sum takes the observed terms only (obs_limit above):
+// a select, so what a padded target or logit holds reaches nothing, and the padded targets are not loaded.  With full lengths part has
+// the unmasked kernel's bits, which takes two things.  (1) The 16-byte path keeps its element-to-thread assignment, and so the order of
+// the sum, whatever the frame size; its float4 LOADS are used only where a float4 cannot straddle two frames (frame % 4 == 0), otherwise
+// the four elements are loaded one by one.  (2) The roundings of a term are spelt out as the compiler contracts them in the unmasked
+// kernel (-ffp-contract=fast): fma(log z, x, log(1 - z) (1 - x)) on the 16-byte path, two products and a sum on the scalar path;
+// tests/test_gpu_ragged_loss.py (full lengths) holds the two kernels together.  A slice boundary inside a frame and a mask boundary
+// inside a slice need nothing special.  <false> is the kernel as it was (n_obs, T, frame are not read).
+template <bool MASK>
 __global__ __launch_bounds__(256) void k_sigmoid_loglik_fwd(const float* __restrict__ X, const float* __restrict__ a, float* __restrict__ z,
-                                                             float* __restrict__ part, size_t inner, size_t nX, size_t chunk) {
+                                                             float* __restrict__ part, size_t inner, size_t nX, size_t chunk,
+                                                             const int* __restrict__ n_obs, int T, size_t frame) {
   __shared__ float red[4];
   const size_t row = blockIdx.y, p0 = (size_t)blockIdx.x * chunk, p1 = p0 + chunk < inner ? p0 + chunk : inner;
   float acc = 0.f;
-  auto one = [&](float av, float xv) {
-    const float zv = 1.f / (1.f + expf(-av));
-    acc += logf(zv) * xv + logf(1.f - zv) * (1.f - xv);
-    return zv;
-  };
-  if (((inner | nX | chunk) & 3) == 0) {             // rows, wraps of X and slices all start on 16-byte boundaries
-    for (size_t p = p0 + 4 * threadIdx.x; p < p1; p += 1024) {
-      const size_t e = row * inner + p;
-      const float4 av = *reinterpret_cast<const float4*>(a + e), xv = *reinterpret_cast<const float4*>(X + e % nX);
-      float4 zv;
-      zv.x = one(av.x, xv.x); zv.y = one(av.y, xv.y); zv.z = one(av.z, xv.z); zv.w = one(av.w, xv.w);
-      *reinterpret_cast<float4*>(z + e) = zv;
+  if constexpr (!MASK) {
+    auto one = [&](float av, float xv) {
+      const float zv = 1.f / (1.f + expf(-av));
+      acc += logf(zv) * xv + logf(1.f - zv) * (1.f - xv);
+      return zv;
+    };
+    if (((inner | nX | chunk) & 3) == 0) {           // rows, wraps of X and slices all start on 16-byte boundaries
+      for (size_t p = p0 + 4 * threadIdx.x; p < p1; p += 1024) {
+        const size_t e = row * inner + p;
+        const float4 av = *reinterpret_cast<const float4*>(a + e), xv = *reinterpret_cast<const float4*>(X + e % nX);
+        float4 zv;
+        zv.x = one(av.x, xv.x); zv.y = one(av.y, xv.y); zv.z = one(av.z, xv.z); zv.w = one(av.w, xv.w);
+        *reinterpret_cast<float4*>(z + e) = zv;
+      }
+    } else {
+      for (size_t p = p0 + threadIdx.x; p < p1; p += 256) {
+        const size_t e = row * inner + p;
+        z[e] = one(a[e], X[e % nX]);
+      }
     }
   } else {
-    for (size_t p = p0 + threadIdx.x; p < p1; p += 256) {
-      const size_t e = row * inner + p;
-      z[e] = one(a[e], X[e % nX]);
+    const size_t lim = obs_limit(n_obs, row % (nX / inner), T, frame);
+    if (((inner | nX | chunk) & 3) == 0) {
+      auto one = [&](float av, float xv, bool obs) {
+        const float zv = 1.f / (1.f + expf(-av));
+        const float t = __fmaf_rn(logf(zv), xv, __fmul_rn(logf(1.f - zv), 1.f - xv));
+        acc = obs ? __fadd_rn(acc, t) : acc;
+        return zv;
+      };
+      const bool whole = (frame & 3) == 0;           // a float4 lies in one frame: observed or padded as a whole
+      for (size_t p = p0 + 4 * threadIdx.x; p < p1; p += 1024) {
+        const size_t e = row * inner + p;
+        const float* xp = X + e % nX;
+        float4 av, xv = {0.f, 0.f, 0.f, 0.f}, zv;
+        if (whole) {
+          av = *reinterpret_cast<const float4*>(a + e);
+          if (p < lim) xv = *reinterpret_cast<const float4*>(xp);
+        } else {
+          av = float4{a[e], a[e + 1], a[e + 2], a[e + 3]};
+          if (p + 0 < lim) xv.x = xp[0];
+          if (p + 1 < lim) xv.y = xp[1];
+          if (p + 2 < lim) xv.z = xp[2];
+          if (p + 3 < lim) xv.w = xp[3];
+        }
+        zv.x = one(av.x, xv.x, p + 0 < lim); zv.y = one(av.y, xv.y, p + 1 < lim);
+        zv.z = one(av.z, xv.z, p + 2 < lim); zv.w = one(av.w, xv.w, p + 3 < lim);
+        *reinterpret_cast<float4*>(z + e) = zv;
+      }
+    } else {
+      for (size_t p = p0 + threadIdx.x; p < p1; p += 256) {
+        const size_t e = row * inner + p;
+        const bool obs = p < lim;
+        const float xv = obs ? X[e % nX] : 0.f;
+        const float zv = 1.f / (1.f + expf(-a[e]));
+        const float t = __fadd_rn(__fmul_rn(logf(zv), xv), __fmul_rn(logf(1.f - zv), 1.f - xv));
+        acc = obs ? __fadd_rn(acc, t) : acc;
+        z[e] = zv;
+      }
     }
   }
   float in1[1] = {acc}, out1[1];
@@ -714,9 +804,16 @@ __global__ __launch_bounds__(256) void k_sigmoid_loglik_fwd(const float* __restr
   if (threadIdx.x == 0) part[row * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 // ga = d/da: k_loglik_rowsum_bwd followed by k_act_bwd (sigmoid), same expressions in the same order
+// MASK: ga = 0 on padded elements, whose X and z are not read (<false> is the kernel as it was)
+template <bool MASK>
 __global__ void k_sigmoid_loglik_bwd(const float* __restrict__ X, const float* __restrict__ z, const float* __restrict__ grow,
-                                     float* __restrict__ ga, size_t n, size_t inner, size_t nX) {
+                                     float* __restrict__ ga, size_t n, size_t inner, size_t nX, const int* __restrict__ n_obs, int T,
+                                     size_t frame) {
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+    if constexpr (MASK) {
+      const size_t ex = e % nX;
+      if (ex % inner >= obs_limit(n_obs, ex / inner, T, frame)) { ga[e] = 0.f; continue; }
+    }
     const float xv = X[e % nX], zv = z[e];
     const float gz = grow[e / inner] * (xv / zv - (1.f - xv) / (1.f - zv));
     ga[e] = gz * zv * (1.f - zv);
@@ -845,13 +942,16 @@ __global__ void k_elbo_all_bwd(const float* __restrict__ g0p, const float* __res
 
 // k_elbo_all_bwd and k_sigmoid_loglik_bwd in ONE launch: every likelihood row receives the same gradient (-g0 nobs - g1) / rows, so the
 // logit gradients need no row-gradient tensor in between -- blocks [0, nb_small) do the (N,q)- and (M,D)-sized outputs, the rest the logits.
+// MASK (the *_len entry points): ga = 0 on padded elements, whose X and z are not read; everything else is untouched, and <false>
+// is the kernel as it was (inner, n_obs, T, frame are not read).
+template <bool MASK>
 __global__ void k_elbo_loglik_bwd(const float* __restrict__ g0p, const float* __restrict__ g1p, const float* __restrict__ g2p,
                                   const float* __restrict__ g3p, int nl_rows, const float* __restrict__ hs, const float* __restrict__ hv, int N,
                                   int q, int M, int Do, const float* __restrict__ Um, const float* __restrict__ Us, float nobs,
                                   float* __restrict__ glrow, float* __restrict__ ghs, float* __restrict__ ghv, float* __restrict__ dUm,
                                   float* __restrict__ dUs, int nb_small, const float* __restrict__ X, const float* __restrict__ z,
-                                  float* __restrict__ ga, size_t n, size_t nX, float* __restrict__ gkls = nullptr, int nks = 0,
-                                  float* __restrict__ gklv = nullptr, int nkv = 0) {
+                                  float* __restrict__ ga, size_t n, size_t nX, float* __restrict__ gkls, int nks,
+                                  float* __restrict__ gklv, int nkv, size_t inner, const int* __restrict__ n_obs, int T, size_t frame) {
   const float g0 = g0p ? *g0p : 0.f, g1 = g1p ? *g1p : 0.f, g2 = g2p ? *g2p : 0.f, g3 = g3p ? *g3p : 0.f;
   if ((int)blockIdx.x < nb_small) {
     const size_t P = (size_t)M * (M + 1) / 2;
@@ -886,6 +986,10 @@ __global__ void k_elbo_loglik_bwd(const float* __restrict__ g0p, const float* __
   const float gl = (-g0 * nobs - g1) / (float)nl_rows;
   const size_t nb = gridDim.x - nb_small;
   for (size_t e = ((size_t)blockIdx.x - nb_small) * blockDim.x + threadIdx.x; e < n; e += nb * blockDim.x) {
+    if constexpr (MASK) {
+      const size_t ex = e % nX;
+      if (ex % inner >= obs_limit(n_obs, ex / inner, T, frame)) { ga[e] = 0.f; continue; }
+    }
     const float xv = X[e % nX], zv = z[e];
     const float gz = gl * (xv / zv - (1.f - xv) / (1.f - zv));
     ga[e] = gz * zv * (1.f - zv);
@@ -906,13 +1010,33 @@ int sigmoid_loglik_fwd(const float* X, const float* a, float* z, float* part, si
   size_t chunk = (inner + nsplit - 1) / nsplit;
   chunk = (chunk + 3) & ~(size_t)3;
   if (!aligned16(X, a, z)) chunk |= 1;   // scalar path
-  hipLaunchKernelGGL(k_sigmoid_loglik_fwd, dim3(nsplit, (unsigned)rows), 256, 0, st, X, a, z, part, inner, nX, chunk);
+  hipLaunchKernelGGL(k_sigmoid_loglik_fwd<false>, dim3(nsplit, (unsigned)rows), 256, 0, st, X, a, z, part, inner, nX, chunk,
+                     (const int*)nullptr, 0, (size_t)0);
   return check_launch("sigmoid_loglik_fwd");
+}
+int sigmoid_loglik_fwd_len(const float* X, const float* a, float* z, float* part, size_t rows, size_t inner, size_t nX, int nsplit,
+                           const int* n_obs, int T, size_t frame, hipStream_t st) {
+  if (nsplit < 1 || rows > 65535) return set_error("gpode_sigmoid_loglik_fwd_len: nsplit >= 1, rows <= 65535");
+  if (const char* why = len_refusal(inner, nX, n_obs, T, frame)) return set_error("gpode_sigmoid_loglik_fwd_len: %s", why);
+  if ((rows * inner) % nX != 0) return set_error("gpode_sigmoid_loglik_fwd_len: X must tile the rows");
+  size_t chunk = (inner + nsplit - 1) / nsplit;
+  chunk = (chunk + 3) & ~(size_t)3;
+  if (!aligned16(X, a, z)) chunk |= 1;   // scalar path, as the twin takes it; the kernel loads element-wise where frame % 4 != 0
+  hipLaunchKernelGGL(k_sigmoid_loglik_fwd<true>, dim3(nsplit, (unsigned)rows), 256, 0, st, X, a, z, part, inner, nX, chunk, n_obs, T, frame);
+  return check_launch("sigmoid_loglik_fwd_len");
 }
 int sigmoid_loglik_bwd(const float* X, const float* z, const float* grow, float* ga, size_t rows, size_t inner, size_t nX, hipStream_t st) {
   const size_t n = rows * inner;
-  hipLaunchKernelGGL(k_sigmoid_loglik_bwd, ew_grid(n), 256, 0, st, X, z, grow, ga, n, inner, nX);
+  hipLaunchKernelGGL(k_sigmoid_loglik_bwd<false>, ew_grid(n), 256, 0, st, X, z, grow, ga, n, inner, nX, (const int*)nullptr, 0, (size_t)0);
   return check_launch("sigmoid_loglik_bwd");
+}
+int sigmoid_loglik_bwd_len(const float* X, const float* z, const float* grow, float* ga, size_t rows, size_t inner, size_t nX,
+                           const int* n_obs, int T, size_t frame, hipStream_t st) {
+  if (const char* why = len_refusal(inner, nX, n_obs, T, frame)) return set_error("gpode_sigmoid_loglik_bwd_len: %s", why);
+  if ((rows * inner) % nX != 0) return set_error("gpode_sigmoid_loglik_bwd_len: X must tile the rows");
+  const size_t n = rows * inner;
+  hipLaunchKernelGGL(k_sigmoid_loglik_bwd<true>, ew_grid(n), 256, 0, st, X, z, grow, ga, n, inner, nX, n_obs, T, frame);
+  return check_launch("sigmoid_loglik_bwd_len");
 }
 int elbo_all_fwd(const float* lpart, int nl_rows, int nl_values, const float* hs, const float* hv, int N, int q, int M, int Do,
                  const float* Um, const float* Us, float nobs, float* out, hipStream_t st) {
@@ -938,17 +1062,40 @@ int elbo_all_bwd(const float* g0, const float* g1, const float* g2, const float*
   return check_launch("elbo_all_bwd");
 }
 
-int elbo_all_bwd_ll(const float* g0, const float* g1, const float* g2, const float* g3, int nl_rows, const float* hs, const float* hv, int N,
-                    int q, int M, int Do, const float* Um, const float* Us, float nobs, float* glrow, float* ghs, float* ghv, float* dUm,
-                    float* dUs, const float* X, const float* z, float* ga, size_t n, size_t nX, hipStream_t st) {
+// n_obs != nullptr: the masked instantiation (gpode_elbo_all_bwd_ll_len), rows of T frames of `frame` elements
+static int elbo_all_bwd_ll_any(const float* g0, const float* g1, const float* g2, const float* g3, int nl_rows, const float* hs, const float* hv,
+                               int N, int q, int M, int Do, const float* Um, const float* Us, float nobs, float* glrow, float* ghs, float* ghv,
+                               float* dUm, float* dUs, const float* X, const float* z, float* ga, size_t n, size_t nX, const int* n_obs, int T,
+                               size_t frame, hipStream_t st) {
   size_t ns = (size_t)M * (M + 1) / 2 * Do;
   if ((size_t)N * q > ns) ns = (size_t)N * q;
   if ((size_t)nl_rows > ns) ns = nl_rows;
   if ((size_t)M * Do > ns) ns = (size_t)M * Do;
   const int nb_small = (int)((ns + 255) / 256);
-  hipLaunchKernelGGL(k_elbo_loglik_bwd, (unsigned)(nb_small + ew_grid(n)), 256, 0, st, g0, g1, g2, g3, nl_rows, hs, hv, N, q, M, Do, Um, Us, nobs,
-                     glrow, ghs, ghv, dUm, dUs, nb_small, X, z, ga, n, nX, (float*)nullptr, 0, (float*)nullptr, 0);
+  if (n_obs) {
+    hipLaunchKernelGGL(k_elbo_loglik_bwd<true>, (unsigned)(nb_small + ew_grid(n)), 256, 0, st, g0, g1, g2, g3, nl_rows, hs, hv, N, q, M, Do, Um, Us,
+                       nobs, glrow, ghs, ghv, dUm, dUs, nb_small, X, z, ga, n, nX, (float*)nullptr, 0, (float*)nullptr, 0, (size_t)T * frame,
+                       n_obs, T, frame);
+    return check_launch("elbo_loglik_bwd_len");
+  }
+  hipLaunchKernelGGL(k_elbo_loglik_bwd<false>, (unsigned)(nb_small + ew_grid(n)), 256, 0, st, g0, g1, g2, g3, nl_rows, hs, hv, N, q, M, Do, Um, Us,
+                     nobs, glrow, ghs, ghv, dUm, dUs, nb_small, X, z, ga, n, nX, (float*)nullptr, 0, (float*)nullptr, 0, (size_t)0,
+                     (const int*)nullptr, 0, (size_t)0);
   return check_launch("elbo_loglik_bwd");
+}
+int elbo_all_bwd_ll(const float* g0, const float* g1, const float* g2, const float* g3, int nl_rows, const float* hs, const float* hv, int N,
+                    int q, int M, int Do, const float* Um, const float* Us, float nobs, float* glrow, float* ghs, float* ghv, float* dUm,
+                    float* dUs, const float* X, const float* z, float* ga, size_t n, size_t nX, hipStream_t st) {
+  return elbo_all_bwd_ll_any(g0, g1, g2, g3, nl_rows, hs, hv, N, q, M, Do, Um, Us, nobs, glrow, ghs, ghv, dUm, dUs, X, z, ga, n, nX, nullptr, 0, 0,
+                             st);
+}
+int elbo_all_bwd_ll_len(const float* g0, const float* g1, const float* g2, const float* g3, int nl_rows, const float* hs, const float* hv, int N,
+                        int q, int M, int Do, const float* Um, const float* Us, float nobs, float* glrow, float* ghs, float* ghv, float* dUm,
+                        float* dUs, const float* X, const float* z, float* ga, size_t n, size_t nX, const int* n_obs, int T, size_t frame,
+                        hipStream_t st) {
+  if (const char* why = len_refusal((size_t)(T > 0 ? T : 0) * frame, nX, n_obs, T, frame)) return set_error("gpode_elbo_all_bwd_ll_len: %s", why);
+  return elbo_all_bwd_ll_any(g0, g1, g2, g3, nl_rows, hs, hv, N, q, M, Do, Um, Us, nobs, glrow, ghs, ghv, dUm, dUs, X, z, ga, n, nX, n_obs, T,
+                             frame, st);
 }
 
 int reparam_kl_fwd(const float* mu, const float* logvar, int ld, const float* eps, float* z, float* klpart, int N, int q, hipStream_t st) {
@@ -972,9 +1119,10 @@ int elbo_all_fwd_kl(const float* lpart, int nl_rows, int nl_values, const float*
                      out, usq, kls, nks, klv, nkv);
   return check_launch(usq ? "elbo_all_fwd_kl (Us in parts)" : "elbo_all_fwd_kl");
 }
-int elbo_all_bwd_ll_kl(const float* g0, const float* g1, const float* g2, const float* g3, int nl_rows, int N, int M, int Do, const float* Um,
-                       const float* Us, float nobs, float* glrow, float* gkls, int nks, float* gklv, int nkv, float* dUm, float* dUs,
-                       const float* X, const float* z, float* ga, size_t n, size_t nX, hipStream_t st) {
+static int elbo_all_bwd_ll_kl_any(const float* g0, const float* g1, const float* g2, const float* g3, int nl_rows, int N, int M, int Do,
+                                  const float* Um, const float* Us, float nobs, float* glrow, float* gkls, int nks, float* gklv, int nkv,
+                                  float* dUm, float* dUs, const float* X, const float* z, float* ga, size_t n, size_t nX, const int* n_obs,
+                                  int T, size_t frame, hipStream_t st) {
   size_t ns = (size_t)M * (M + 1) / 2 * Do;
   if ((size_t)nl_rows > ns) ns = nl_rows;
   if ((size_t)M * Do > ns) ns = (size_t)M * Do;
@@ -982,9 +1130,30 @@ int elbo_all_bwd_ll_kl(const float* g0, const float* g1, const float* g2, const 
   if ((size_t)nkv > ns) ns = nkv;
   const int nb_small = (int)((ns + 255) / 256);
   float* nf = nullptr;
-  hipLaunchKernelGGL(k_elbo_loglik_bwd, (unsigned)(nb_small + ew_grid(n)), 256, 0, st, g0, g1, g2, g3, nl_rows, (const float*)nullptr,
-                     (const float*)nullptr, N, 1, M, Do, Um, Us, nobs, glrow, nf, nf, dUm, dUs, nb_small, X, z, ga, n, nX, gkls, nks, gklv, nkv);
+  if (n_obs) {
+    hipLaunchKernelGGL(k_elbo_loglik_bwd<true>, (unsigned)(nb_small + ew_grid(n)), 256, 0, st, g0, g1, g2, g3, nl_rows, (const float*)nullptr,
+                       (const float*)nullptr, N, 1, M, Do, Um, Us, nobs, glrow, nf, nf, dUm, dUs, nb_small, X, z, ga, n, nX, gkls, nks, gklv, nkv,
+                       (size_t)T * frame, n_obs, T, frame);
+    return check_launch("elbo_loglik_bwd_kl_len");
+  }
+  hipLaunchKernelGGL(k_elbo_loglik_bwd<false>, (unsigned)(nb_small + ew_grid(n)), 256, 0, st, g0, g1, g2, g3, nl_rows, (const float*)nullptr,
+                     (const float*)nullptr, N, 1, M, Do, Um, Us, nobs, glrow, nf, nf, dUm, dUs, nb_small, X, z, ga, n, nX, gkls, nks, gklv, nkv,
+                     (size_t)0, (const int*)nullptr, 0, (size_t)0);
   return check_launch("elbo_loglik_bwd_kl");
+}
+int elbo_all_bwd_ll_kl(const float* g0, const float* g1, const float* g2, const float* g3, int nl_rows, int N, int M, int Do, const float* Um,
+                       const float* Us, float nobs, float* glrow, float* gkls, int nks, float* gklv, int nkv, float* dUm, float* dUs,
+                       const float* X, const float* z, float* ga, size_t n, size_t nX, hipStream_t st) {
+  return elbo_all_bwd_ll_kl_any(g0, g1, g2, g3, nl_rows, N, M, Do, Um, Us, nobs, glrow, gkls, nks, gklv, nkv, dUm, dUs, X, z, ga, n, nX, nullptr,
+                                0, 0, st);
+}
+int elbo_all_bwd_ll_kl_len(const float* g0, const float* g1, const float* g2, const float* g3, int nl_rows, int N, int M, int Do, const float* Um,
+                           const float* Us, float nobs, float* glrow, float* gkls, int nks, float* gklv, int nkv, float* dUm, float* dUs,
+                           const float* X, const float* z, float* ga, size_t n, size_t nX, const int* n_obs, int T, size_t frame,
+                           hipStream_t st) {
+  if (const char* why = len_refusal((size_t)(T > 0 ? T : 0) * frame, nX, n_obs, T, frame)) return set_error("gpode_elbo_all_bwd_ll_kl_len: %s", why);
+  return elbo_all_bwd_ll_kl_any(g0, g1, g2, g3, nl_rows, N, M, Do, Um, Us, nobs, glrow, gkls, nks, gklv, nkv, dUm, dUs, X, z, ga, n, nX, n_obs, T,
+                                frame, st);
 }
 int reparam_fwd(const float* mu, const float* logvar, int ld, const float* eps, float* z, int N, int q, hipStream_t st) {
   hipLaunchKernelGGL(k_reparam_fwd, (N * q + 255) / 256, 256, 0, st, mu, logvar, ld, eps, z, N, q);

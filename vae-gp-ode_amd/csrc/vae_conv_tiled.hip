@@ -640,6 +640,40 @@ int dec10_predict_ll(const float* c, const float* table, const float* w, const f
   return check_launch("dec10_predict_ll");
 }
 
+// ragged sequences: the two launchers above with a frame count per sequence, n_obs[N] (k_fwd_predict<LL, true>); same refusals
+int dec10_predict_len(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th, int T_obs,
+                      int done, float* pred_mean, float* pred_m2, float* se_state, const int* n_obs, hipStream_t st) {
+  if (!use_mfma()) return set_error("gpode_dec10_predict_len: matrix-core kernel only (GPODE_CONV_VALU is set)");
+  if (Lc < 1 || F < 1 || Th < 1 || T_obs < 1 || T_obs > Th || F % Th != 0 || done < 0)
+    return set_error("gpode_dec10_predict_len: need Lc, F >= 1, 1 <= T_obs <= Th, F a multiple of Th, done >= 0");
+  if ((pred_mean == nullptr) != (pred_m2 == nullptr)) return set_error("gpode_dec10_predict_len: pred_mean and pred_m2 go together");
+  if (!aligned16(table)) return set_error("gpode_dec10_predict_len: the table must be 16-byte aligned");
+  if (n_obs == nullptr) return set_error("gpode_dec10_predict_len: n_obs is NULL");
+  const size_t lds = sizeof(float) * (dec10::KK * dec10::PST + 16);
+  if (set_max_lds((const void*)dec10::k_fwd_predict<false, true>, lds)) return 1;
+  hipLaunchKernelGGL((dec10::k_fwd_predict<false, true>), F < num_cus() ? F : num_cus(), 512, lds, st, c, w, bias, table, X, Lc, F, Th, T_obs, done,
+                     pred_mean, pred_m2, se_state, (float*)nullptr, n_obs);
+  return check_launch("dec10_predict_len");
+}
+int dec10_predict_ll_len(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th, int T_obs,
+                         int done, float* pred_mean, float* pred_m2, float* se_state, float* ell, int L_total, const int* n_obs,
+                         hipStream_t st) {
+  if (!use_mfma()) return set_error("gpode_dec10_predict_ll_len: matrix-core kernel only (GPODE_CONV_VALU is set)");
+  if (Lc < 1 || F < 1 || Th < 1 || T_obs < 1 || T_obs > Th || F % Th != 0 || done < 0)
+    return set_error("gpode_dec10_predict_ll_len: need Lc, F >= 1, 1 <= T_obs <= Th, F a multiple of Th, done >= 0");
+  if ((pred_mean == nullptr) != (pred_m2 == nullptr)) return set_error("gpode_dec10_predict_ll_len: pred_mean and pred_m2 go together");
+  if (!aligned16(table)) return set_error("gpode_dec10_predict_ll_len: the table must be 16-byte aligned");
+  if (ell == nullptr) return set_error("gpode_dec10_predict_ll_len: ell is NULL");
+  if (L_total < 1 || Lc > L_total || done > L_total - Lc)
+    return set_error("gpode_dec10_predict_ll_len: ell has L_total rows, need done + Lc <= L_total");
+  if (n_obs == nullptr) return set_error("gpode_dec10_predict_ll_len: n_obs is NULL");
+  const size_t lds = sizeof(float) * (dec10::KK * dec10::PST + 24);
+  if (set_max_lds((const void*)dec10::k_fwd_predict<true, true>, lds)) return 1;
+  hipLaunchKernelGGL((dec10::k_fwd_predict<true, true>), F < num_cus() ? F : num_cus(), 512, lds, st, c, w, bias, table, X, Lc, F, Th, T_obs, done,
+                     pred_mean, pred_m2, se_state, ell, n_obs);
+  return check_launch("dec10_predict_ll_len");
+}
+
 // decnn.10's input gradient fused with the backward of the BatchNorm + ReLU in front of it (conv_dec10_mfma.hpp, k_bwd_data_bn).
 // scratch: part[nwg][16][2] | part_gx[nwg][16][2], nwg <= kDec10BnMaxWg.  The grid is a function of B alone, so the two
 // passes (and the partials they exchange through scratch) agree.

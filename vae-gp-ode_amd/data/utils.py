@@ -10,6 +10,9 @@ training step (a replayed HIP graph reading a static input buffer) never waits f
 
 ``subsample_frames``: irregularly observed sequences out of regularly sampled ones -- every sequence keeps its own sorted subset
 of the frames, and the kept indices are its observation times in units of ``dt`` (``--subsample_frames``).
+
+``ragged_frames``: the same with a different NUMBER of kept frames per sequence, as a padded minibatch with its frame counts
+(``--ragged_frames``).
 """
 import torch
 from torch.utils import data
@@ -38,6 +41,34 @@ def subsample_frames(X, keep, lead, generator):
     head = torch.arange(lead, device=X.device).expand(N, lead)
     idx = torch.cat((head, tail), dim=1)
     return X[torch.arange(N, device=X.device)[:, None], idx], idx
+
+
+def ragged_frames(X, kmin, kmax, lead, generator):
+    """X (N,T,...) -> (Xpad (N,kmax,...), idx (N,kmax) int64, n_obs (N,) int32): sequences with different NUMBERS of observations,
+    as a padded minibatch.  Sequence n keeps k_n frames, k_n uniform in kmin .. kmax: a sorted set of distinct indices that always
+    holds 0 .. lead-1, drawn as in ``subsample_frames`` (the k_n - lead smallest of T - lead uniform scores).  Behind them the target frames are zeros and the indices go on as idx[k_n-1] + 1, + 2, ...: they are times only --
+    the padding keeps every row strictly increasing (an adaptive solver refuses a row that is not) and may exceed T-1.  Frame t of
+    sequence n is observed iff t < n_obs[n].  Drawn on X's device from ``generator`` alone."""
+    N, T = X.shape[0], X.shape[1]
+    kmin, kmax, lead = int(kmin), int(kmax), int(lead)
+    if lead < 1 or kmin <= lead or kmin > kmax or kmax > T:
+        raise ValueError('ragged_frames: need lead < kmin <= kmax <= T, got lead=%d kmin=%d kmax=%d T=%d: the first %d frame(s) are '
+                         'always kept and at least one later frame is drawn' % (lead, kmin, kmax, T, lead))
+    dev = X.device
+    k = torch.randint(kmin, kmax + 1, (N,), device=dev, generator=generator)
+    # the k_n - lead smallest of T - lead uniform scores: a uniform subset, as in subsample_frames; a stable sort on "dropped" then
+    # lists the kept frames first, in increasing order
+    scores = torch.rand((N, T - lead), device=dev, generator=generator)
+    rank = scores.argsort(dim=1).argsort(dim=1)
+    keep = torch.cat((torch.ones((N, lead), dtype=torch.bool, device=dev), rank < (k[:, None] - lead)), dim=1)
+    idx = (~keep).to(torch.int8).sort(dim=1, stable=True).indices[:, :kmax]
+    col = torch.arange(kmax, device=dev)[None, :]
+    obs = col < k[:, None]
+    last = idx.gather(1, (k - 1)[:, None])             # idx[n, k_n - 1]
+    idx = torch.where(obs, idx, last + (col - (k[:, None] - 1)))
+    Xpad = X[torch.arange(N, device=dev)[:, None], idx.clamp(max=T - 1)]
+    Xpad = torch.where(obs.view(N, kmax, *([1] * (X.dim() - 2))), Xpad, torch.zeros((), dtype=X.dtype, device=dev))
+    return Xpad, idx, k.to(torch.int32)
 
 
 class Dataset(data.Dataset):

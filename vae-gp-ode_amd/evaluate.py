@@ -26,7 +26,10 @@ reused): loads ``--model_path``, evaluates the test split with L = ``--eval_samp
 log-likelihood: ``mse``, ``std``, ``mse_t``, ``nll``, ``nlpd``, ``nll_t``), rolls ``--Troll`` * T frames out for
 the first three test sequences, prints one JSON line and writes ``eval.json``, ``rollout_mean.npy``, ``rollout_var.npy`` under
 ``--save``.  The draws come from the host generators as in the reference (two of them unseeded there, SURVEY F6, so two runs differ
-by Monte-Carlo noise); ``--device_noise True`` draws on the device, reproducibly from ``--seed``.  ``--subsample_frames K``: every test
+by Monte-Carlo noise); ``--device_noise True`` draws on the device, reproducibly from ``--seed``.  ``--ragged_frames KMIN``: every test
+sequence keeps between KMIN and K (``--subsample_frames``, else T) of its frames and is padded to K; the error and the likelihood
+take its observed frames only (``predict(..., n_obs=)``), ``mse_t`` / ``nll_t`` are means over the sequences that have the frame and
+``count`` is L 784 times the number of observed frames.  ``--subsample_frames K``: every test
 sequence keeps K of its frames (drawn per sequence, reproducibly from ``--seed``) and is evaluated on its own time grid
 (``predict(..., ts=)``); the long roll-out stays on the uniform grid.  ``--eval_z0_draws True`` adds a second pass over the test split
 with a z0 sample per draw and reports ``iw_nll``, ``nlpd_marginal``, ``ess_mean``, ``ess_min``; every other figure is unchanged.  Single process: data-parallel
@@ -82,13 +85,34 @@ def log_mean_exp(ll):
     return top + torch.log(torch.exp(ll - top).sum(dim=0)) - math.log(ll.shape[0])
 
 
-def loglik_stats(ell, T_obs):
+def _observed(n_obs, N, T):
+    """(N,T) bool on the CPU: frame t of sequence n is observed iff t < n_obs[n] (counts <= 0: none, >= T: all)"""
+    k = torch.as_tensor(n_obs).detach().cpu().to(torch.int64).reshape(N)
+    return torch.arange(T)[None, :] < k[:, None]
+
+
+def frame_means(v, obs):
+    """Per-frame mean of v (N,T) float64 over the sequences that have the frame (obs (N,T) bool): (T,), nan where none has it.
+    The entries of v behind a False are not read."""
+    v = torch.where(obs, v, torch.zeros((), dtype=v.dtype))
+    return v.sum(0) / obs.sum(0).to(v.dtype)           # 0 / 0 = nan: no sequence has the frame
+
+
+def loglik_stats(ell, T_obs, n_obs=None):
     """(ll, nll, nlpd, nll_t) from the frame log-likelihoods ell (L,N,Th) (frames t >= T_obs hold 0 and are left out):
     ll[l,n] = sum_{t < T_obs} ell[l,n,t];  nll = -mean_{l,n} ll;  nlpd = -mean_n (logsumexp_l ll[l,n] - log L);
-    nll_t[t] = -mean_{l,n} ell[l,n,t].  Double precision, a fixed order of operations."""
+    nll_t[t] = -mean_{l,n} ell[l,n,t].  Double precision, a fixed order of operations.
+    ``n_obs`` (N,): ragged sequences -- ll[l,n] sums the frames t < min(T_obs, n_obs[n]) (the others hold 0 and are left out by a
+    select), nll and nlpd stay means over the sequences, and nll_t[t] is the mean over the draws and the sequences that HAVE frame t
+    (nan where none has it).  None: the same bits as ever."""
     ell = torch.as_tensor(ell, dtype=torch.float64)[:, :, :T_obs]
+    if n_obs is None:
+        ll = ell.sum(dim=2)
+        return ll, -ll.mean().item(), -log_mean_exp(ll).mean().item(), -ell.mean(dim=(0, 1))
+    obs = _observed(n_obs, ell.shape[1], ell.shape[2])
+    ell = torch.where(obs[None], ell, torch.zeros((), dtype=torch.float64))
     ll = ell.sum(dim=2)
-    return ll, -ll.mean().item(), -log_mean_exp(ll).mean().item(), -ell.mean(dim=(0, 1))
+    return ll, -ll.mean().item(), -log_mean_exp(ll).mean().item(), -frame_means(ell.mean(dim=0), obs)
 
 
 def merge_states(states):
@@ -160,20 +184,33 @@ def _grid(ts, N, Th, T, who):
     return ts
 
 
-def _grid_kw(ts):
-    """ts= for predict / predict_marginal when the loader item carries a grid; nothing otherwise -- the call as it always was"""
-    return {} if ts is None else {'ts': ts}
+def _grid_kw(ts, n_obs=None):
+    """ts= / n_obs= for predict / predict_marginal when the loader item carries them; nothing otherwise -- the call as it always was"""
+    kw = {} if ts is None else {'ts': ts}
+    if n_obs is not None:
+        kw['n_obs'] = n_obs
+    return kw
 
 
 def _frames_ts(batch):
-    """(X, ts) of a loader item: a loader that yields (X, ts (N,T)) pairs carries the observation times of its sequences; every
-    other item (the tensor itself, a TensorDataset 1-tuple) has none"""
+    """(X, ts, n_obs) of a loader item: a loader that yields (X, ts (N,T)) pairs carries the observation times of its sequences, one
+    that yields (X, ts, n_obs (N,)) triples their frame counts as well (ragged sequences, padded to T); every other item (the tensor
+    itself, a TensorDataset 1-tuple) has neither"""
     if isinstance(batch, (list, tuple)):
-        return batch[0], (batch[1] if len(batch) > 1 else None)
-    return batch, None
+        return batch[0], (batch[1] if len(batch) > 1 else None), (batch[2] if len(batch) > 2 else None)
+    return batch, None, None
 
 
-def predict(model, X, L=1, T_custom=None, images_per_pass=8192, variance=True, loglik=False, ts=None):
+def _counts(n_obs, X, who):
+    """``n_obs`` of predict / predict_marginal on X's device: None, or (N,) int32 (shape and dtype are checked by vae_ops)"""
+    if n_obs is None:
+        return None
+    if not torch.is_tensor(n_obs):
+        raise ValueError('%s: n_obs must be an int32 tensor (N,), one frame count per sequence' % who)
+    return n_obs.to(X.device)
+
+
+def predict(model, X, L=1, T_custom=None, images_per_pass=8192, variance=True, loglik=False, ts=None, n_obs=None):
     """Posterior-predictive statistics of ``model`` (ODEGPVAE) for the sequences X (N,T,1,28,28): encode once, one z0 sample per
     sequence, L function draws shared by the batch, integrate ``T_custom or T`` steps, decode (positions only for order 2) --
     the order of operations of the notebook routine -- and reduce inside the decoder's last kernel.  Frames beyond T have no
@@ -185,11 +222,16 @@ def predict(model, X, L=1, T_custom=None, images_per_pass=8192, variance=True, l
     the L draws, so ``nlpd`` is the predictive density under the GP function draws GIVEN that sample of the initial state, not the
     marginal over the encoder's distribution.  ``ts`` (N,T'), T' = ``T_custom or T``: the observation (and forecast) times of every
     sequence instead of the uniform grid dt * arange(T'); with ``variance=False`` the first T columns are read.  ``mse_t`` and ``nll_t``
-    stay indexed by FRAME: entry t averages frame t of every sequence, whatever time each of them was observed at.  Runs without
+    stay indexed by FRAME: entry t averages frame t of every sequence, whatever time each of them was observed at.
+    ``n_obs`` (N,) int32: ragged sequences, X padded to T frames -- frame t of sequence n has a target iff t < n_obs[n]; the padded
+    frames are integrated and decoded like forecast frames (they enter mean / var) and add nothing to the error or the likelihood,
+    whatever the padded targets hold.  ``count`` is then L 784 sum_n min(n_obs[n], T), and ``mse_t`` / ``nll_t`` average over the
+    sequences that have the frame (nan where none has it).  None: every field the same bits as ever.  Runs without
     autograd and in eval mode; leaves every module buffer and ``training`` flag as it found them."""
     from . import vae_ops as V
     if X.dim() != 5 or tuple(X.shape[2:]) != (1, 28, 28):
         raise ValueError('predict: X must be (N,T,1,28,28)')
+    n_obs = _counts(n_obs, X, 'predict')
     N, T = X.shape[0], X.shape[1]
     Th = int(T_custom) if T_custom else T
     if Th < T:
@@ -212,7 +254,10 @@ def predict(model, X, L=1, T_custom=None, images_per_pass=8192, variance=True, l
         state = V.PredictState(F, X.device, variance, loglik=L if loglik else 0)
         for l0, l1 in passes:
             c, t8 = dec.decode_frozen_raw(lat[l0:l1], tables)
-            V.dec10_predict(c, t8, dec.decnn[10].weight, dec.decnn[10].bias, X, Th, state)
+            if n_obs is None:
+                V.dec10_predict(c, t8, dec.decnn[10].weight, dec.decnn[10].bias, X, Th, state)
+            else:
+                V.dec10_predict(c, t8, dec.decnn[10].weight, dec.decnn[10].bias, X, Th, state, n_obs=n_obs)
             del c
         se = state.se.double().cpu().view(N, Th, 3)[:, :T]            # one copy of 3 F floats; frames t >= T hold zeros
         mean = var = None
@@ -221,22 +266,27 @@ def predict(model, X, L=1, T_custom=None, images_per_pass=8192, variance=True, l
             var = (state.m2 / (L - 1) if L > 1 else torch.full_like(state.m2, float('nan'))).view(N, Th, 1, 28, 28)
     total = merge_states(se.reshape(-1, 3).tolist())
     mse, std = mean_std(total)
-    mse_t = se[:, :, 1].mean(0)                                        # every frame holds the same count L * 784
+    if n_obs is None:
+        mse_t = se[:, :, 1].mean(0)                                    # every frame holds the same count L * 784
+    else:
+        mse_t = frame_means(se[:, :, 1], _observed(n_obs, N, T))       # a frame with a target holds L * 784 errors, one without none
     extra = ()
     if loglik:
-        extra = loglik_stats(state.ell.cpu().double().view(L, N, Th), T)   # one copy of L F floats
+        extra = loglik_stats(state.ell.cpu().double().view(L, N, Th), T, *(() if n_obs is None else (n_obs,)))   # one copy of L F floats
     return Prediction(mean, var, mse, std, int(total[0]), mse_t, total, [b - a for a, b in passes], *extra)
 
 
-def predict_marginal(model, X, L, images_per_pass=8192, ts=None):
+def predict_marginal(model, X, L, images_per_pass=8192, ts=None, n_obs=None):
     """``predict(variance=False, loglik=True)`` with the initial state sampled PER DRAW: ``encode_initial_state(X, draws=L)`` gives
     z0 (L,N,order*q) and the log-weights lw (L,N), draw l integrates from z0[l] under function draw l (one rollout launch over L N
     trajectories), and the decoder passes and the fused last kernel are predict's.  -> MarginalPrediction.  ``ts`` (N,T): the
-    observation times of every sequence, shared by its L draws; ``nll_t`` stays indexed by frame, as in predict.  Runs without autograd
+    observation times of every sequence, shared by its L draws; ``nll_t`` stays indexed by frame, as in predict.  ``n_obs`` (N,) int32:
+    the frame counts of ragged sequences, as in predict.  Runs without autograd
     and in eval mode; leaves every module buffer and ``training`` flag as it found them."""
     from . import vae_ops as V
     if X.dim() != 5 or tuple(X.shape[2:]) != (1, 28, 28):
         raise ValueError('predict_marginal: X must be (N,T,1,28,28)')
+    n_obs = _counts(n_obs, X, 'predict_marginal')
     N, T = X.shape[0], X.shape[1]
     L = int(L)
     F = N * T
@@ -252,27 +302,31 @@ def predict_marginal(model, X, L, images_per_pass=8192, ts=None):
         state = V.PredictState(F, X.device, False, loglik=L)
         for l0, l1 in passes:
             c, t8 = dec.decode_frozen_raw(lat[l0:l1], tables)
-            V.dec10_predict(c, t8, dec.decnn[10].weight, dec.decnn[10].bias, X, T, state)
+            if n_obs is None:
+                V.dec10_predict(c, t8, dec.decnn[10].weight, dec.decnn[10].bias, X, T, state)
+            else:
+                V.dec10_predict(c, t8, dec.decnn[10].weight, dec.decnn[10].bias, X, T, state, n_obs=n_obs)
             del c
         se = state.se.double().cpu().view(N, T, 3)
         ell = state.ell.cpu().double().view(L, N, T)
         lw = lw.cpu().double()
     total = merge_states(se.reshape(-1, 3).tolist())
     mse, std = mean_std(total)
-    ll, nll, nlpd, nll_t = loglik_stats(ell, T)
+    ll, nll, nlpd, nll_t = loglik_stats(ell, T, *(() if n_obs is None else (n_obs,)))
     iw_ll, iw_nll, ess = iw_stats(ll, lw)
     return MarginalPrediction(ll, lw, nll, nlpd, iw_ll, iw_nll, ess, nll_t, mse, std, total, [b - a for a, b in passes])
 
 
 def compute_iw_nll(model, loader, L, images_per_pass=8192):
     """(iw_nll, nlpd, mean ess) over a whole loader with L joint draws per batch (predict_marginal): means over all sequences, the
-    batches weighted by their sequence counts.  A loader that yields (X, ts) pairs is evaluated on its time grids."""
+    batches weighted by their sequence counts.  A loader that yields (X, ts) pairs is evaluated on its time grids, one that yields
+    (X, ts, n_obs) triples on its ragged sequences."""
     dev = next(model.parameters()).device
     nseq, iw, nlpd, ess = 0, 0.0, 0.0, 0.0
     for batch in loader:
-        X, ts = _frames_ts(batch)
+        X, ts, n_obs = _frames_ts(batch)
         X = X.to(dev)
-        p = predict_marginal(model, X, L, images_per_pass=images_per_pass, **_grid_kw(ts))
+        p = predict_marginal(model, X, L, images_per_pass=images_per_pass, **_grid_kw(ts, n_obs))
         nseq += X.shape[0]
         iw += p.iw_nll * X.shape[0]
         nlpd += p.nlpd * X.shape[0]
@@ -285,25 +339,25 @@ def compute_iw_nll(model, loader, L, images_per_pass=8192):
 def compute_mse_std(model, loader, L=1, images_per_pass=8192):
     """(mse, std) of the squared reconstruction error over a whole loader with L draws per batch -- ``compute_mse_std`` of the
     evaluation notebook: the batches' (n, mean, M2) triples are merged, so the result is the mean / std over all elements.
-    A loader that yields (X, ts) pairs is evaluated on its time grids."""
+    A loader that yields (X, ts) pairs is evaluated on its time grids, one that yields (X, ts, n_obs) triples on its ragged sequences."""
     dev = next(model.parameters()).device
     states = []
     for batch in loader:
-        X, ts = _frames_ts(batch)
-        states.append(predict(model, X.to(dev), L, images_per_pass=images_per_pass, variance=False, **_grid_kw(ts)).state)
+        X, ts, n_obs = _frames_ts(batch)
+        states.append(predict(model, X.to(dev), L, images_per_pass=images_per_pass, variance=False, **_grid_kw(ts, n_obs)).state)
     return mean_std(merge_states(states))
 
 
 def compute_nll(model, loader, L=1, images_per_pass=8192):
     """(nll, nlpd) of the held-out log-likelihood over a whole loader with L draws per batch: the batches' figures are means over
     their sequences, so they are weighted by the sequence counts -- the mean over all sequences, not over batches.
-    A loader that yields (X, ts) pairs is evaluated on its time grids."""
+    A loader that yields (X, ts) pairs is evaluated on its time grids, one that yields (X, ts, n_obs) triples on its ragged sequences."""
     dev = next(model.parameters()).device
     nseq, nll, nlpd = 0, 0.0, 0.0
     for batch in loader:
-        X, ts = _frames_ts(batch)
+        X, ts, n_obs = _frames_ts(batch)
         X = X.to(dev)
-        p = predict(model, X, L, images_per_pass=images_per_pass, variance=False, loglik=True, **_grid_kw(ts))
+        p = predict(model, X, L, images_per_pass=images_per_pass, variance=False, loglik=True, **_grid_kw(ts, n_obs))
         nseq += X.shape[0]
         nll += p.nll * X.shape[0]
         nlpd += p.nlpd * X.shape[0]
@@ -349,27 +403,33 @@ def make_parser():
 
 
 def _subsampled(args, loader):
-    """The loader's items as (all frames, X, ts): with --subsample_frames K every sequence keeps K frames, drawn per batch from a
-    generator of its own seeded from --seed (so a second pass sees the same subsets), ts = dt * (kept indices); without it X is all
-    frames and ts None."""
+    """The loader's items as (all frames, X, ts, n_obs): with --subsample_frames K every sequence keeps K frames, drawn per batch from
+    a generator of its own seeded from --seed (so a second pass sees the same subsets), ts = dt * (kept indices); with
+    --ragged_frames KMIN every sequence keeps between KMIN and K (or T) frames and is padded (data.utils.ragged_frames), n_obs its
+    count; without either X is all frames and ts, n_obs are None."""
     from .main import _frames, subsample_generator, subsample_lead
-    if not args.subsample_frames:
+    if not args.subsample_frames and not args.ragged_frames:
         for batch in loader:
             X = _frames(batch).to(args.device)
-            yield X, X, None
+            yield X, X, None, None
         return
-    from .data.utils import subsample_frames
+    from .data.utils import ragged_frames, subsample_frames
     gen = subsample_generator(args)
     for batch in loader:
         full = _frames(batch).to(args.device)
+        if args.ragged_frames:
+            X, kept, n_obs = ragged_frames(full, args.ragged_frames, args.subsample_frames or full.shape[1], subsample_lead(args), gen)
+            yield full, X, args.dt * kept.to(torch.float32), n_obs
+            continue
         X, kept = subsample_frames(full, args.subsample_frames, subsample_lead(args), gen)
-        yield full, X, args.dt * kept.to(torch.float32)
+        yield full, X, args.dt * kept.to(torch.float32), None
 
 
 def main(argv=None):
-    from .main import check_subsample
+    from .main import check_ragged, check_subsample
     args = make_parser().parse_args(argv)
     check_subsample(args)
+    check_ragged(args)
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
         raise SystemExit('vae_gp_ode_amd.evaluate is a single-process tool: data-parallel evaluation is not built '
                          '(start it without torchrun, or with one rank)')
@@ -383,14 +443,20 @@ def main(argv=None):
     states, per_step, nseq, first = [], None, 0, None
     nll = nlpd = 0.0
     nll_step = None
-    for full, Xb, tsb in _subsampled(args, testset):
+    have = None                                      # --ragged_frames: sequences that have frame t, the weights of the per-frame means
+    for full, Xb, tsb, nb in _subsampled(args, testset):
         first = full if first is None else first     # the roll-out below: all frames, the uniform grid
-        p = predict(model, Xb, L, variance=False, loglik=True, **_grid_kw(tsb))
+        p = predict(model, Xb, L, variance=False, loglik=True, **_grid_kw(tsb, nb))
         states.append(p.state)
         nll += p.nll * Xb.shape[0]
         nlpd += p.nlpd * Xb.shape[0]
-        nll_step = p.nll_t * Xb.shape[0] if nll_step is None else nll_step + p.nll_t * Xb.shape[0]
-        per_step = p.mse_t * Xb.shape[0] if per_step is None else per_step + p.mse_t * Xb.shape[0]
+        wt = Xb.shape[0]
+        if nb is not None:                           # a frame no sequence of the batch has is nan with weight 0: it adds nothing
+            wt = _observed(nb, Xb.shape[0], Xb.shape[1]).sum(0).to(torch.float64)
+            have = wt if have is None else have + wt
+            p = p._replace(nll_t=torch.nan_to_num(p.nll_t), mse_t=torch.nan_to_num(p.mse_t))
+        nll_step = p.nll_t * wt if nll_step is None else nll_step + p.nll_t * wt
+        per_step = p.mse_t * wt if per_step is None else per_step + p.mse_t * wt
         nseq += Xb.shape[0]
     total = merge_states(states)
     mse, std = mean_std(total)
@@ -398,12 +464,13 @@ def main(argv=None):
     roll = predict(model, first[:3].contiguous(), L, T_custom=args.Troll * T)
     if args.subsample_frames:
         T = args.subsample_frames                    # the frames per sequence behind every figure but the roll-out's
+    per_frame = nseq if have is None else have       # means over the sequences that have the frame (nan where none has it)
     marginal = None
     if args.eval_z0_draws:                           # behind everything else: the figures above see the draws they see without it
         iw = nlpd_m = ess_sum = 0.0
         ess_min = float('inf')
-        for _, Xb, tsb in _subsampled(args, testset):
-            pm = predict_marginal(model, Xb, L, **_grid_kw(tsb))
+        for _, Xb, tsb, nb in _subsampled(args, testset):
+            pm = predict_marginal(model, Xb, L, **_grid_kw(tsb, nb))
             iw += pm.iw_nll * pm.ll.shape[1]
             nlpd_m += pm.nlpd * pm.ll.shape[1]
             ess_sum += pm.ess.sum().item()
@@ -413,11 +480,13 @@ def main(argv=None):
     ms = (time.time() - t0) * 1e3
 
     os.makedirs(args.save, exist_ok=True)
-    out = dict(mse=mse, std=std, mse_t=(per_step / nseq).tolist(), nll=nll / nseq, nlpd=nlpd / nseq, nll_t=(nll_step / nseq).tolist(), L=L, sequences=nseq, T=T, count=int(total[0]),
+    out = dict(mse=mse, std=std, mse_t=(per_step / per_frame).tolist(), nll=nll / nseq, nlpd=nlpd / nseq, nll_t=(nll_step / per_frame).tolist(), L=L, sequences=nseq, T=T, count=int(total[0]),
                rollout_sequences=int(roll.mean.shape[0]), rollout_T=int(roll.mean.shape[1]), rollout_mse=roll.mse, ms=ms,
                checkpoint=os.path.abspath(fname), ranks=1)
     if args.subsample_frames:
         out['subsample_frames'] = args.subsample_frames
+    if args.ragged_frames:
+        out['ragged_frames'] = args.ragged_frames
     if marginal is not None:
         out.update(marginal)
     np.save(os.path.join(args.save, 'rollout_mean.npy'), roll.mean.cpu().numpy())

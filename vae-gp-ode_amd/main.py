@@ -68,6 +68,10 @@ EXT_FLAGS = [
     ('subsample_frames', int, 0, 'K > 0: every sequence of a minibatch keeps K of its T frames, drawn per sequence (the first one always; '
                                  'the first --frames for --ode 2), and is integrated over its own time grid dt * (kept indices); 0: off, '
                                  'the uniform grid.  Drawn per minibatch from a generator of its own, seeded from --seed'),
+    ('ragged_frames', int, 0, 'KMIN > 0: sequences with different NUMBERS of observations -- every sequence of a minibatch keeps '
+                              'between KMIN and K frames (K = --subsample_frames if set, else T), drawn per sequence, and is padded to K: '
+                              'the likelihood sums its observed frames only, the padded ones are integrated and decoded as forecasts; '
+                              '0: off'),
     ('sync_bn', eval, True, 'data parallel: BatchNorm normalises with the statistics of the GLOBAL minibatch (all ranks), as the '
                             'single-process reference does (vae.py:55,58,113,116,119)'),
 ]
@@ -135,6 +139,15 @@ def check_subsample(args):
     if K and (K > args.T or K <= lead):
         raise SystemExit('--subsample_frames %d: must be 0 (off) or more than the %d leading frame(s) the encoders read (--ode %d) and '
                          'at most --T %d' % (K, lead, args.ode, args.T))
+
+
+def check_ragged(args):
+    """--ragged_frames KMIN: 0 (off) or lead < KMIN <= K, K = --subsample_frames if set, else T; refused with a message otherwise"""
+    kmin, lead = args.ragged_frames, subsample_lead(args)
+    kmax = args.subsample_frames or args.T
+    if kmin and (kmin > kmax or kmin <= lead):
+        raise SystemExit('--ragged_frames %d: must be 0 (off) or more than the %d leading frame(s) the encoders read (--ode %d) and '
+                         'at most %s %d' % (kmin, lead, args.ode, '--subsample_frames' if args.subsample_frames else '--T', kmax))
 
 
 def subsample_generator(args):
@@ -215,6 +228,7 @@ def cache_results(logger, args, ep, build_model):
 def main(argv=None):
     args = make_parser().parse_args(argv)
     check_subsample(args)
+    check_ragged(args)
     from .model.core.initialization import initialize_and_fix_kernel_parameters
     from .model.create_model import build_model, compute_loss, compute_test_error, backward
     from .model.misc.torch_utils import seed_everything
@@ -293,15 +307,20 @@ def main(argv=None):
     if args.hip_graph and not capture_ok:
         logger.info('cross-rank BatchNorm over {}: steps are launched eagerly (device noise and side stream stay on)'.format(dist.get_backend()))
 
-    def graphed_step(minibatch, L, ts=None):
-        key = (L, tuple(minibatch.shape), bn_sync.shares if bn_sync is not None else None, None if ts is None else tuple(ts.shape))
+    def graphed_step(minibatch, L, ts=None, n_obs=None):
+        key = (L, tuple(minibatch.shape), bn_sync.shares if bn_sync is not None else None, None if ts is None else tuple(ts.shape),
+               n_obs is not None)
         if key not in graphs:
             buf = torch.empty_like(minibatch)
             tbuf = None if ts is None else torch.empty_like(ts)     # the time grids: a second static input of the captured step
+            nbuf = None if n_obs is None else torch.empty_like(n_obs)   # the frame counts of a ragged minibatch: a third
 
             def step():
                 optimizer.zero_grad()
-                out = compute_loss(model, buf, L) if tbuf is None else compute_loss(model, buf, L, ts=tbuf)
+                if nbuf is not None:
+                    out = compute_loss(model, buf, L, ts=tbuf, n_obs=nbuf)
+                else:
+                    out = compute_loss(model, buf, L) if tbuf is None else compute_loss(model, buf, L, ts=tbuf)
                 backward(out[0])
                 if sync is None:
                     optimizer.step()
@@ -311,34 +330,46 @@ def main(argv=None):
             buf.copy_(minibatch)
             if tbuf is not None:
                 tbuf.copy_(ts)
+            if nbuf is not None:
+                nbuf.copy_(n_obs)
             gs = GraphedStep(step, generators=device_generators(model), warmup=1,
                              grad_params=optimizer.params if sync is not None else None)
-            graphs[key] = (buf, tbuf, gs)
+            graphs[key] = (buf, tbuf, nbuf, gs)
             if sync is not None:                     # the gradients the gather / all-reduce below must see are the warm-up's
                 gs.bind_warm_grads()
             return gs.warm_out                       # the capture warm-up already took this minibatch's (eager) step
-        buf, tbuf, g = graphs[key]
+        buf, tbuf, nbuf, g = graphs[key]
         buf.copy_(minibatch, non_blocking=True)
         if tbuf is not None:
             tbuf.copy_(ts, non_blocking=True)
+        if nbuf is not None:
+            nbuf.copy_(n_obs, non_blocking=True)
         return g()
 
     from . import ops as gp_ops
     solves_mode = 'auto' if args.backward_solves == 'adaptive' else args.backward_solves
     gp_ops.set_backward_solves(solves_mode)
     sub_gen = None
-    if args.subsample_frames:                        # off: no generator exists and no launch below changes
-        from .data.utils import subsample_frames
+    if args.subsample_frames or args.ragged_frames:  # off: no generator exists and no launch below changes
+        from .data.utils import ragged_frames, subsample_frames
         sub_gen = subsample_generator(args)
-        logger.info('Every sequence keeps {} of its frames, drawn per minibatch; time grids per sequence'.format(args.subsample_frames))
+        if args.ragged_frames:
+            logger.info('Every sequence keeps {} to {} of its frames, drawn per minibatch and padded; time grids and frame counts per '
+                        'sequence'.format(args.ragged_frames, args.subsample_frames or args.T))
+        else:
+            logger.info('Every sequence keeps {} of its frames, drawn per minibatch; time grids per sequence'.format(args.subsample_frames))
     logger.info('********** Started Training **********')
     begin = time.time()
     for ep in range(args.Nepoch):
         L = 1 if ep < args.Nepoch // 2 else 5
         for itr, local_batch in enumerate(trainset):
             minibatch = _frames(local_batch).to(args.device)
-            ts = None
-            if sub_gen is not None:                  # the global minibatch's subsets, the same on every rank, ahead of the shards
+            ts = n_obs = None
+            if sub_gen is not None and args.ragged_frames:
+                minibatch, kept, n_obs = ragged_frames(minibatch, args.ragged_frames, args.subsample_frames or minibatch.shape[1],
+                                                       subsample_lead(args), sub_gen)
+                ts = args.dt * kept.to(torch.float32)
+            elif sub_gen is not None:                # the global minibatch's subsets, the same on every rank, ahead of the shards
                 minibatch, kept = subsample_frames(minibatch, args.subsample_frames, subsample_lead(args), sub_gen)
                 ts = args.dt * kept.to(torch.float32)
             if sync is not None and minibatch.shape[0] >= world:     # this rank's shard; its share weights the gradient mean
@@ -346,6 +377,8 @@ def main(argv=None):
                 minibatch = shard_batch(minibatch, rank, world)
                 if ts is not None:
                     ts = shard_batch(ts, rank, world).contiguous()   # the rows follow their sequences
+                if n_obs is not None:
+                    n_obs = shard_batch(n_obs, rank, world).contiguous()   # and so do the frame counts
                 sync.weight = minibatch.shape[0] / n_global
                 if bn_sync is not None:
                     bn_sync.set_shares([hi - lo for lo, hi in (shard_bounds(n_global, r, world) for r in range(world))])
@@ -354,7 +387,9 @@ def main(argv=None):
                 if bn_sync is not None:
                     bn_sync.set_shares(None)
             if args.hip_graph and capture_ok:
-                loss, nlhood, kl_reg, kl_u = graphed_step(minibatch, L, ts)
+                loss, nlhood, kl_reg, kl_u = graphed_step(minibatch, L, ts, n_obs) if n_obs is not None else graphed_step(minibatch, L, ts)
+            elif n_obs is not None:
+                loss, nlhood, kl_reg, kl_u = compute_loss(model, minibatch, L, ts=ts, n_obs=n_obs)
             elif ts is None:
                 loss, nlhood, kl_reg, kl_u = compute_loss(model, minibatch, L)
             else:

@@ -185,10 +185,13 @@ class Decoder(nn.Module):
             raise ValueError('Currently only bernoulli dist implemented')
         return V.bernoulli_loglik(x, z)  # x is broadcast over the L leading copies of z inside the kernel
 
-    def log_prob_rowsum(self, x, z, L=1):
-        """sum over (T,c,h,w) of log_prob, shape (L,N): the reduction create_model.elbo applies, fused."""
+    def log_prob_rowsum(self, x, z, L=1, n_obs=None):
+        """sum over (T,c,h,w) of log_prob, shape (L,N): the reduction create_model.elbo applies, fused.  ``n_obs`` (N,) int32: over
+        the frames t < n_obs[n] of every sequence only (a ragged minibatch, padded to T frames)."""
         N = x.shape[0]
-        return V.bernoulli_loglik_rowsum(x, z, L * N).view(L, N)
+        if n_obs is None:
+            return V.bernoulli_loglik_rowsum(x, z, L * N).view(L, N)
+        return V.bernoulli_loglik_rowsum(x, z, L * N, n_obs).view(L, N)
 
 
 class VAE(nn.Module):

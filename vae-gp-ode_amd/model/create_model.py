@@ -32,11 +32,16 @@ def elbo(model, X, Xrec, s0_mu, s0_logv, v0_mu, v0_logv, L):
     return lhood.mean(), kl_reg.mean(), model.flow.kl()
 
 
-def compute_loss(model, data, L, ts=None):
+def compute_loss(model, data, L, ts=None, n_obs=None):
     """-> (loss, nll, kl_reg, kl_u) (create_model.py:61-73).  Same terms as elbo() above; the per-row pieces go through
     three fused launches (KL rows, likelihood row sums, loss algebra) instead of ~25 elementwise ones.
     ``ts`` (N,T): the observation time of every frame of every sequence (ODEGPVAE.forward); None = the uniform grid, the call as
-    it always was.  Every sequence still has T frames: the loss stage has no frame mask."""
+    it always was.
+    ``n_obs`` (N,) int32 on the device: a ragged minibatch, padded to T frames -- frame t of sequence n is observed iff t < n_obs[n].
+    The likelihood of a sequence sums its observed frames only (nothing is renormalised by the count: the ELBO is a sum over
+    observations), a padded frame gets exactly zero gradient at its logits, and what the padded targets hold is never read into a
+    result.  The padded frames are still integrated and decoded (the forecast at the padding times, whose columns of ``ts`` must
+    keep every row increasing) and enter the decoder's training-mode BatchNorm statistics.  The counts are not read back."""
     from .. import vae_ops as V
     field = model.flow.odefunc.diffeq
     grid = {} if ts is None else {'ts': ts}
@@ -44,11 +49,14 @@ def compute_loss(model, data, L, ts=None):
         # the decoder stops at its logits; sigmoid + likelihood row sums are one pass over them, and the three KL / mean / loss
         # launches one more (gpode_sigmoid_loglik_fwd, gpode_elbo_all_fwd)
         logits, (s0_mu, s0_logv), (v0_mu, v0_logv) = model(data, L, logits=True, **grid)
-        lpart, _ = V.sigmoid_loglik_parts(data, logits, L * data.shape[0])
+        if n_obs is None:
+            lpart, _ = V.sigmoid_loglik_parts(data, logits, L * data.shape[0])
+        else:
+            lpart, _ = V.sigmoid_loglik_parts(data, logits, L * data.shape[0], n_obs)
         return V.elbo_all(lpart, s0_mu, s0_logv, v0_mu, v0_logv, field.Um.optvar, field.us_packed(), field.M, model.num_observations)
     Xrec, (s0_mu, s0_logv), (v0_mu, v0_logv) = model(data, L, **grid)
     kl_rows = model.vae.encoder.kl_rows(s0_mu, s0_logv, v0_mu, v0_logv)               # (N,)
-    lhood_rows = model.vae.decoder.log_prob_rowsum(data, Xrec, L)                     # (L, N)
+    lhood_rows = model.vae.decoder.log_prob_rowsum(data, Xrec, L, n_obs=n_obs)        # (L, N)
     out = V.elbo_terms(lhood_rows, kl_rows, model.flow.kl(), model.num_observations)
     return out[0], out[1], out[2], out[3]
 

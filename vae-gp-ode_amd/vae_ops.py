@@ -603,6 +603,18 @@ class _LogLik(torch.autograd.Function):
         return None, gz
 
 
+def _chk_n_obs(n_obs, X, who):
+    """The frame counts of a ragged minibatch X (N,T,...): (N,) int32 on X's device.  Shape, dtype and device only -- the values are
+    never read back (a captured step stays capturable); the kernels clamp them to [0, T].  -> (n_obs, T, elements per frame)."""
+    if not (torch.is_tensor(n_obs) and n_obs.dtype == torch.int32 and n_obs.device == X.device):
+        raise _lib.GpodeError('%s: n_obs must be an int32 tensor on the device of X' % who)
+    if X.dim() < 2 or tuple(n_obs.shape) != (X.shape[0],):
+        raise _lib.GpodeError('%s: n_obs must be (N,) = (%d,), one frame count per sequence of X (N,T,...); got %s'
+                              % (who, X.shape[0] if X.dim() else 0, tuple(n_obs.shape)))
+    T = int(X.shape[1])
+    return n_obs.contiguous(), T, X.numel() // (X.shape[0] * T)
+
+
 class _LogLikRowSum(torch.autograd.Function):
     @staticmethod
     def forward(ctx, X, z, rows):
@@ -620,6 +632,30 @@ class _LogLikRowSum(torch.autograd.Function):
         gz = _new(z.shape, z)
         _lib.call('gpode_loglik_rowsum_bwd', _ptr(X), _ptr(z), _ptr(g.contiguous()), _ptr(gz), ctx.rows, ctx.inner, X.numel(), _stream())
         return None, gz, None
+
+
+class _LogLikRowSumLen(torch.autograd.Function):
+    """_LogLikRowSum over the observed frames of a ragged minibatch (gpode_loglik_rowsum_fwd_len / _bwd_len)."""
+
+    @staticmethod
+    def forward(ctx, X, z, rows, n_obs):
+        X, z = _chk(X, 'X'), _chk(z, 'z')
+        n_obs, T, frame = _chk_n_obs(n_obs, X, 'bernoulli_loglik_rowsum')
+        inner = z.numel() // rows
+        out = _new((rows,), z)
+        _lib.call('gpode_loglik_rowsum_fwd_len', _ptr(X), _ptr(z), _ptr(out), rows, inner, X.numel(), _ptr(n_obs), T, frame, _stream())
+        ctx.save_for_backward(X, z, n_obs)
+        ctx.dims = (rows, inner, T, frame)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        X, z, n_obs = ctx.saved_tensors
+        rows, inner, T, frame = ctx.dims
+        gz = _new(z.shape, z)
+        _lib.call('gpode_loglik_rowsum_bwd_len', _ptr(X), _ptr(z), _ptr(g.contiguous()), _ptr(gz), rows, inner, X.numel(), _ptr(n_obs), T, frame,
+                  _stream())
+        return None, gz, None, None
 
 
 def _packed_halves(mu, logvar):
@@ -789,11 +825,12 @@ class _ElboAll(torch.autograd.Function):
         if ctx.ll is not None and ctx.needs_input_grad[0]:
             # the logits' gradient in the same launch (every likelihood row receives the same gradient): _SigmoidLogLikParts.backward
             # finds it on the row-gradient tensor it is handed and launches nothing
-            X, z = ctx.ll
+            X, z = ctx.ll[:2]
+            sfx, masked = _ll_len_args(ctx.ll)
             ga = torch.empty_like(z)
-            _lib.call('gpode_elbo_all_bwd_ll', *[_ptr(g) for g in gs], rows, _ptr(hs), _ptr(hv), N, q, M, Um.shape[1], _ptr(Um), _ptr(Us),
+            _lib.call('gpode_elbo_all_bwd_ll' + sfx, *[_ptr(g) for g in gs], rows, _ptr(hs), _ptr(hv), N, q, M, Um.shape[1], _ptr(Um), _ptr(Us),
                       ctypes.c_float(nobs), _ptr(glrow), _ptr(ghs), _ptr(ghv), _ptr(dUm), _ptr(dUs), _ptr(X), _ptr(z), _ptr(ga), z.numel(),
-                      X.numel(), _stream())
+                      X.numel(), *masked, _stream())
         else:
             _lib.call('gpode_elbo_all_bwd', *[_ptr(g) for g in gs], rows, _ptr(hs), _ptr(hv), N, q, M, Um.shape[1], _ptr(Um), _ptr(Us),
                       ctypes.c_float(nobs), _ptr(glrow), _ptr(ghs), _ptr(ghv), _ptr(dUm), _ptr(dUs), _stream())
@@ -807,9 +844,56 @@ class _ElboAll(torch.autograd.Function):
         return glr, ghs, ghv, dUm, dUs, None, None, None, None
 
 
-def sigmoid_loglik_parts(X, logits, rows):
-    """-> (partial row sums (rows, nsplit) of the Bernoulli log-likelihood, z = sigmoid(logits))."""
-    return _SigmoidLogLikParts.apply(X, logits, rows)
+class _SigmoidLogLikPartsLen(torch.autograd.Function):
+    """_SigmoidLogLikParts over the observed frames of a ragged minibatch (gpode_sigmoid_loglik_fwd_len / _bwd_len): z for every
+    element, the partial sums and the logit gradients for the frames t < n_obs[n] only."""
+
+    @staticmethod
+    def forward(ctx, X, a, rows, n_obs):
+        X, a = _chk(X, 'X'), _chk(a, 'logits')
+        n_obs, T, frame = _chk_n_obs(n_obs, X, 'sigmoid_loglik_parts')
+        inner = a.numel() // rows
+        ns = _lib.load().gpode_sigmoid_loglik_splits(rows, inner)
+        z, part = torch.empty_like(a), _new((rows, ns), a)
+        _lib.call('gpode_sigmoid_loglik_fwd_len', _ptr(X), _ptr(a), _ptr(z), _ptr(part), rows, inner, X.numel(), ns, _ptr(n_obs), T, frame,
+                  _stream())
+        ctx.save_for_backward(X, z, n_obs)
+        ctx.dims = (rows, inner, T, frame)
+        ctx.mark_non_differentiable(z)
+        ctx.set_materialize_grads(False)
+        part._gpode_ll = (X, z, n_obs)               # elbo_all(): the fused backward takes its masked form from the third entry
+        return part, z
+
+    @staticmethod
+    def backward(ctx, gpart, _gz):
+        X, z, n_obs = ctx.saved_tensors
+        rows, inner, T, frame = ctx.dims
+        ga = getattr(gpart, '_gpode_ga', None)       # already computed by the ELBO's backward (gpode_elbo_all_bwd_ll_len / _ll_kl_len)
+        if ga is not None and ga.shape == z.shape:
+            return None, ga, None, None
+        grow = gpart[:, 0].contiguous() if gpart.shape[1] > 1 else gpart.contiguous()
+        ga = torch.empty_like(z)
+        _lib.call('gpode_sigmoid_loglik_bwd_len', _ptr(X), _ptr(z), _ptr(grow), _ptr(ga), rows, inner, X.numel(), _ptr(n_obs), T, frame,
+                  _stream())
+        return None, ga, None, None
+
+
+def _ll_len_args(ll):
+    """(entry-point suffix, extra arguments) of the fused backward for the (X, z[, n_obs]) a parts tensor carries"""
+    if len(ll) < 3 or ll[2] is None:
+        return '', ()
+    X, n_obs = ll[0], ll[2]
+    T = int(X.shape[1])
+    return '_len', (_ptr(n_obs), T, X.numel() // (X.shape[0] * T))
+
+
+def sigmoid_loglik_parts(X, logits, rows, n_obs=None):
+    """-> (partial row sums (rows, nsplit) of the Bernoulli log-likelihood, z = sigmoid(logits)).  ``n_obs`` (N,) int32: the frame
+    count of every sequence of a ragged (padded) minibatch X (N,T,...) -- the sums take the frames t < n_obs[n] only and the padded
+    logits get a zero gradient; None: every frame, the launches as they always were."""
+    if n_obs is None:
+        return _SigmoidLogLikParts.apply(X, logits, rows)
+    return _SigmoidLogLikPartsLen.apply(X, logits, rows, n_obs)
 
 
 class _ElboAllKL(torch.autograd.Function):
@@ -834,11 +918,13 @@ class _ElboAllKL(torch.autograd.Function):
         Um, Us = ctx.saved_tensors
         rows, N, M, nobs, lshape, nks, nkv = ctx.dims
         gs = [None if g is None else g.contiguous().float() for g in (g0, g1, g2, g3)]
-        X, z = ctx.ll
+        X, z = ctx.ll[:2]
+        sfx, masked = _ll_len_args(ctx.ll)
         glrow, gkls, gklv = _new((rows,), Um), _new((nks,), Um), (_new((nkv,), Um) if nkv else None)
         dUm, dUs, ga = torch.empty_like(Um), torch.empty_like(Us), torch.empty_like(z)
-        _lib.call('gpode_elbo_all_bwd_ll_kl', *[_ptr(g) for g in gs], rows, N, M, Um.shape[1], _ptr(Um), _ptr(Us), ctypes.c_float(nobs),
-                  _ptr(glrow), _ptr(gkls), nks, _ptr(gklv), nkv, _ptr(dUm), _ptr(dUs), _ptr(X), _ptr(z), _ptr(ga), z.numel(), X.numel(), _stream())
+        _lib.call('gpode_elbo_all_bwd_ll_kl' + sfx, *[_ptr(g) for g in gs], rows, N, M, Um.shape[1], _ptr(Um), _ptr(Us), ctypes.c_float(nobs),
+                  _ptr(glrow), _ptr(gkls), nks, _ptr(gklv), nkv, _ptr(dUm), _ptr(dUs), _ptr(X), _ptr(z), _ptr(ga), z.numel(), X.numel(),
+                  *masked, _stream())
         if (ctx.needs_input_grad[3] and ctx.needs_input_grad[4] and Um.is_leaf and Us.is_leaf and
                 ops.defer_kl_grads((Um, Us), (dUm, dUs))):
             dUm = dUs = None
@@ -982,8 +1068,11 @@ def bernoulli_loglik(X, z):
     return _LogLik.apply(X, z)
 
 
-def bernoulli_loglik_rowsum(X, z, rows):
-    return _LogLikRowSum.apply(X, z, rows)
+def bernoulli_loglik_rowsum(X, z, rows, n_obs=None):
+    """``n_obs`` (N,) int32: sum the frames t < n_obs[n] of a ragged minibatch only (sigmoid_loglik_parts); None: every frame."""
+    if n_obs is None:
+        return _LogLikRowSum.apply(X, z, rows)
+    return _LogLikRowSumLen.apply(X, z, rows, n_obs)
 
 
 # ---- frozen decoder / posterior-predictive evaluation (forward only; evaluate.py) ------------------------------------------------
@@ -1026,12 +1115,17 @@ class PredictState:
         self.se = torch.zeros(F, 3, dtype=torch.float32, device=device)
 
 
-def dec10_predict(c, table, w, b, X, Th, state):
+def dec10_predict(c, table, w, b, X, Th, state, n_obs=None):
     """Fold the draws held in ``c`` -- raw decnn.7 output (Lc * F, 16, 28, 28) laid out (draw, frame) -- into ``state``:
     sigmoid(decnn.10(relu(bn(c)))) is formed in registers and only its statistics against the targets X (N, T_obs, 1, 28, 28) leave
     the kernel (frames t >= T_obs of a sequence have no target and add nothing to the error).  A state with ``ell`` takes
-    gpode_dec10_predict_ll, which also writes the rows of ``ell`` of these draws; a state without it takes gpode_dec10_predict."""
+    gpode_dec10_predict_ll, which also writes the rows of ``ell`` of these draws; a state without it takes gpode_dec10_predict.
+    ``n_obs`` (N,) int32: the frame count of every sequence of a ragged X -- frame t of sequence n has a target iff
+    t < min(T_obs, n_obs[n]) (the *_len entry points); None: the launches as they always were."""
     c, w, table, X = _chk(c.detach(), 'c'), _chk(w.detach(), 'weight'), _chk(table, 'table'), _chk(X, 'X')
+    sfx, masked = '', ()
+    if n_obs is not None:
+        sfx, masked = '_len', (_ptr(_chk_n_obs(n_obs, X, 'dec10_predict')[0]),)
     F = state.F
     N, T_obs = X.shape[0], X.shape[1]
     if tuple(c.shape[1:]) != (16, 28, 28) or tuple(w.shape) != (16, 1, 5, 5) or tuple(table.shape) != (16, 4):
@@ -1043,11 +1137,12 @@ def dec10_predict(c, table, w, b, X, Th, state):
     if ell is not None:
         if ell.dim() != 2 or ell.shape[1] != F or ell.dtype != torch.float32 or not ell.is_contiguous():
             raise _lib.GpodeError('gpode_dec10_predict_ll: ell must be a contiguous float32 (L_total, F) tensor')
-        _lib.call('gpode_dec10_predict_ll', _ptr(c), _ptr(table), _ptr(w), _ptr(None if b is None else _chk(b.detach(), 'bias')), _ptr(X),
-                  Lc, F, int(Th), T_obs, state.done, _ptr(state.mean), _ptr(state.m2), _ptr(state.se), _ptr(ell), ell.shape[0], _stream())
+        _lib.call('gpode_dec10_predict_ll' + sfx, _ptr(c), _ptr(table), _ptr(w), _ptr(None if b is None else _chk(b.detach(), 'bias')), _ptr(X),
+                  Lc, F, int(Th), T_obs, state.done, _ptr(state.mean), _ptr(state.m2), _ptr(state.se), _ptr(ell), ell.shape[0], *masked,
+                  _stream())
         state.done += Lc
         return state
-    _lib.call('gpode_dec10_predict', _ptr(c), _ptr(table), _ptr(w), _ptr(None if b is None else _chk(b.detach(), 'bias')), _ptr(X),
-              Lc, F, int(Th), T_obs, state.done, _ptr(state.mean), _ptr(state.m2), _ptr(state.se), _stream())
+    _lib.call('gpode_dec10_predict' + sfx, _ptr(c), _ptr(table), _ptr(w), _ptr(None if b is None else _chk(b.detach(), 'bias')), _ptr(X),
+              Lc, F, int(Th), T_obs, state.done, _ptr(state.mean), _ptr(state.m2), _ptr(state.se), *masked, _stream())
     state.done += Lc
     return state
