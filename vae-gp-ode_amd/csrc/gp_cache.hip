@@ -425,17 +425,28 @@ __device__ __forceinline__ void tile_load(float (&dst)[NB][NB + 1], const float*
 #pragma unroll
   for (int q = 0; q < 4; ++q) dst[ty + 8 * q][tx] = A[(size_t)(r0 + ty + 8 * q) * np + c0 + tx];
 }
+// acc[q] += sum_p X[ty + NTY q][p] Y[tx][p], every element the sequential p = 0..31 fmaf chain.  Register-blocked: the thread's
+// row of Y is read from LDS once (32 conflict-free reads, lane tx on bank 33 tx + p) and kept for its ROWS rows of X, whose reads
+// are broadcasts (two addresses per wavefront) -- 1 + 1/ROWS LDS reads per FMA instead of 2
+template <int ROWS, int NTY>
+__device__ __forceinline__ void tile_acc(float (&acc)[ROWS], const float (&X)[NB][NB + 1], const float (&Y)[NB][NB + 1], int tx, int ty) {
+  float y[NB];
+#pragma unroll
+  for (int p = 0; p < NB; ++p) y[p] = Y[tx][p];
+#pragma unroll
+  for (int q = 0; q < ROWS; ++q) {
+    const int r = ty + NTY * q;
+#pragma unroll
+    for (int p = 0; p < NB; ++p) acc[q] = fmaf(X[r][p], y[p], acc[q]);
+  }
+}
 // dst = src - X Y^T (32 x 32 tiles in LDS), 256 threads
 __device__ __forceinline__ void tile_sub_xyt(float (&dst)[NB][NB + 1], const float (&src)[NB][NB + 1], const float (&X)[NB][NB + 1],
                                              const float (&Y)[NB][NB + 1], int tx, int ty) {
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  tile_acc<4, 8>(acc, X, Y, tx, ty);
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int r = ty + 8 * q;
-    float acc = 0.f;
-#pragma unroll 8
-    for (int p = 0; p < NB; ++p) acc = fmaf(X[r][p], Y[tx][p], acc);
-    dst[r][tx] = src[r][tx] - acc;
-  }
+  for (int q = 0; q < 4; ++q) dst[ty + 8 * q][tx] = src[ty + 8 * q][tx] - acc[q];
 }
 // one wavefront: factor [Dt ; Pt] (rows of the diagonal tile in lanes 0..31, of the panel tile in lanes 32..63); the panel half goes
 // to Lp, the diagonal half (lower triangle, zeros above) to Ld when given
@@ -541,16 +552,229 @@ __global__ __launch_bounds__(256) void k_chol_rl2(float* __restrict__ Aall, floa
   // ---- stage 4: trailing tile (j >= k + 2) ----
   const float (&Lj0)[NB][NB + 1] = (j == i) ? lPi : lPj;
   const float (&Lj1)[NB][NB + 1] = (j == i) ? lQi : lQj;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  tile_acc<4, 8>(acc, lPi, Lj0, tx, ty);
+  tile_acc<4, 8>(acc, lQi, Lj1, tx, ty);
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const int r = ty + 8 * q;
-    float acc = 0.f;
+    float* dst = A + (size_t)(i * NB + ty + 8 * q) * np + j * NB + tx;
+    *dst = *dst - acc[q];
+  }
+}
+
+// FOUR block columns (k .. k+3) per launch: two consecutive k_chol_rl2 launches (at k and at k + 2) in one workgroup, with the
+// sums in their order, so that every tile of Lmat and Dfac and every trailing tile of A comes out bit-identical:
+//   F0  factor column k                    U1  column k+1:  T -= L_.k L_(k+1)k^T                          (rl2 at k, stages 1, 2)
+//   F1  factor column k+1                  U2  columns k+2, k+3 and the trailing tile:  T -= L_.k L_ck^T + L_.(k+1) L_c(k+1)^T
+//   F2  factor column k+2                  U3  column k+3:  T -= L_.(k+2) L_(k+3)(k+2)^T                  (rl2 at k+2, stages 1, 2)
+//   F3  factor column k+3                  U4  the trailing tile:  T -= L_i(k+2) L_j(k+2)^T + L_i(k+3) L_j(k+3)^T
+// The workgroup of tile (i, j) needs the rows {k .. k+3, i, j} in the four columns; rows that coincide share a SLOT (0..3: rows
+// k .. k+3, 4: row i > k+3, 5: row j > k+3, j != i), and a tile (slot, column) has one place in dynamic LDS, where it is updated
+// and factored in place: 10 tiles of the slots 0..3 (lower triangle), 4 + 4 of the slots 4 and 5, and one more (`extra`) that
+// holds what a workgroup of the columns k .. k+3 publishes (row-major) or else the trailing tile between U2 and U4.  A workgroup of
+// column k + c publishes after F_c and stops.  512 threads: up to five panels are factored side by side, a wavefront each.
+//
+// A source tile is row-major with the [NB][NB + 1] padding (lane r of the factorisation reads row r); its factored panel goes
+// back into the same place TRANSPOSED, Lt[p][r] with row stride NB, which is what the products read: for one p a lane fetches
+// its rows of X as one ds_read_b64 and its four columns of Y as one ds_read_b128 (8 and 16 byte aligned, few distinct addresses
+// per lane group: no bank conflict), 6 LDS cycles for 8 FMAs where the row-major form takes two ds_read_b32 per FMA.
+constexpr int RL4_THREADS = 512, RL4_TILES = 19, RL4_TILE = NB * (NB + 1);
+constexpr size_t RL4_LDS = sizeof(float) * RL4_TILES * RL4_TILE;
+typedef float chol_tile[NB][NB + 1];
+__device__ __forceinline__ int rl4_tile(int s, int c) { return s < 4 ? s * (s + 1) / 2 + c : 10 + 4 * (s - 4) + c; }
+
+// tile_factor with the panel half written back over Pt transposed (and row-major to Lrow when given)
+__device__ __forceinline__ bool tile_factor_t(const chol_tile& Dt, chol_tile& Pt, float (*Ld)[NB + 1], float (*Lrow)[NB + 1], int lane) {
+  const int r = lane & 31;
+  const bool panel = lane >= 32;
+  float row[NB];
+#pragma unroll
+  for (int c = 0; c < NB; ++c) row[c] = panel ? Pt[r][c] : Dt[r][c];
+  const bool bad = chol32_panel_wave(row);
+  if (panel) {
+    float* Pf = &Pt[0][0];
+#pragma unroll
+    for (int c = 0; c < NB; ++c) Pf[c * NB + r] = row[c];
+    if (Lrow) {
+#pragma unroll
+      for (int c = 0; c < NB; ++c) Lrow[r][c] = row[c];
+    }
+  } else if (Ld) {
+#pragma unroll
+    for (int c = 0; c < NB; ++c) Ld[r][c] = c <= r ? row[c] : 0.f;
+  }
+  return bad;
+}
+
+// one wavefront, rows 16 h .. 16 h + 15 of a product: acc += X Y^T from the transposed tiles Xt, Yt; lane (a, b) = (lane >> 3,
+// lane & 7) holds rows 16 h + 2 a, + 1 and columns 4 b .. 4 b + 3.  Every element is the sequential p = 0..31 fmaf chain.
+__device__ __forceinline__ void strip_acc(float (&acc)[2][4], const chol_tile& Xt, const chol_tile& Yt, int h, int lane) {
+  const float2* xp = reinterpret_cast<const float2*>(&Xt[0][0] + 16 * h + 2 * (lane >> 3));
+  const float4* yp = reinterpret_cast<const float4*>(&Yt[0][0] + 4 * (lane & 7));
+#pragma unroll
+  for (int p = 0; p < NB; ++p) {
+    const float2 x = xp[p * (NB / 2)];
+    const float4 y = yp[p * (NB / 4)];
+    acc[0][0] = fmaf(x.x, y.x, acc[0][0]); acc[0][1] = fmaf(x.x, y.y, acc[0][1]);
+    acc[0][2] = fmaf(x.x, y.z, acc[0][2]); acc[0][3] = fmaf(x.x, y.w, acc[0][3]);
+    acc[1][0] = fmaf(x.y, y.x, acc[1][0]); acc[1][1] = fmaf(x.y, y.y, acc[1][1]);
+    acc[1][2] = fmaf(x.y, y.z, acc[1][2]); acc[1][3] = fmaf(x.y, y.w, acc[1][3]);
+  }
+}
+// the same strip of a row-major tile: T -= acc
+__device__ __forceinline__ void strip_sub(chol_tile& T, const float (&acc)[2][4], int h, int lane) {
+  const int r0 = 16 * h + 2 * (lane >> 3), c0 = 4 * (lane & 7);
+#pragma unroll
+  for (int q = 0; q < 2; ++q)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) T[r0 + q][c0 + e] = T[r0 + q][c0 + e] - acc[q][e];
+}
+
+// one wavefront, a whole product: lane (a, b) holds rows 4 a .. 4 a + 3 and columns 4 b .. 4 b + 3, two ds_read_b128 for 16 FMAs
+__device__ __forceinline__ void block_acc(float (&acc)[4][4], const chol_tile& Xt, const chol_tile& Yt, int lane) {
+  const float4* xp = reinterpret_cast<const float4*>(&Xt[0][0] + 4 * (lane >> 3));
+  const float4* yp = reinterpret_cast<const float4*>(&Yt[0][0] + 4 * (lane & 7));
 #pragma unroll 8
-    for (int p = 0; p < NB; ++p) acc = fmaf(lPi[r][p], Lj0[tx][p], acc);
-#pragma unroll 8
-    for (int p = 0; p < NB; ++p) acc = fmaf(lQi[r][p], Lj1[tx][p], acc);
-    float* dst = A + (size_t)(i * NB + r) * np + j * NB + tx;
-    *dst = *dst - acc;
+  for (int p = 0; p < NB; ++p) {
+    const float4 x = xp[p * (NB / 4)];
+    const float4 y = yp[p * (NB / 4)];
+    const float xs[4] = {x.x, x.y, x.z, x.w}, ys[4] = {y.x, y.y, y.z, y.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[q][e] = fmaf(xs[q], ys[e], acc[q][e]);
+  }
+}
+__device__ __forceinline__ void block_sub(chol_tile& T, const float (&acc)[4][4], int lane) {
+  const int r0 = 4 * (lane >> 3), c0 = 4 * (lane & 7);
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) T[r0 + q][c0 + e] = T[r0 + q][c0 + e] - acc[q][e];
+}
+
+__global__ __launch_bounds__(RL4_THREADS) void k_chol_rl4(float* __restrict__ Aall, float* __restrict__ Lall, int np, size_t batch_stride,
+                                                           float* __restrict__ Dfac_all, size_t dfac_stride, int k, int* __restrict__ info,
+                                                           int nblk, int nreal) {
+  extern __shared__ __attribute__((aligned(16))) float rl4_lds[];
+  chol_tile* tiles = reinterpret_cast<chol_tile*>(rl4_lds);
+  chol_tile& extra = tiles[RL4_TILES - 1];
+  float* A = Aall + (size_t)blockIdx.y * batch_stride;
+  float* Lm = Lall + (size_t)blockIdx.y * batch_stride;
+  float* DfacB = Dfac_all + (size_t)blockIdx.y * dfac_stride;
+  const int t = blockIdx.x;
+  int ii = (int)((sqrtf(8.f * (float)t + 1.f) - 1.f) * 0.5f);
+  while ((ii + 1) * (ii + 2) / 2 <= t) ++ii;
+  while (ii * (ii + 1) / 2 > t) --ii;
+  const int i = k + ii, j = k + (t - ii * (ii + 1) / 2);            // tile (i, j), k <= j <= i
+  const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5, wv = tid >> 6, lane = tid & 63;
+  // roles -> slots
+  const int si = i < k + 4 ? i - k : 4;
+  const int sj = j < k + 4 ? j - k : (j == i ? 4 : 5);
+  const int jc = j - k < 3 ? j - k : 3;                // the last column this workgroup factors
+  const unsigned mask = ((2u << jc) - 1u) | (1u << si) | (1u << sj);
+  const bool trailing = j > k + 3;
+  // every load of the workgroup is issued before the first one is waited for (a loop over the tiles it needs would wait per tile):
+  // place tt of the LDS image is tile (slot s, column c) with both known at compile time, the last place the trailing tile
+  {
+    float v[RL4_TILES][2];
+#pragma unroll
+    for (int tt = 0; tt < RL4_TILES; ++tt) {
+      const int s = tt >= 18 ? 6 : tt >= 14 ? 5 : tt >= 10 ? 4 : tt >= 6 ? 3 : tt >= 3 ? 2 : tt >= 1 ? 1 : 0;
+      const int c = s >= 4 ? (tt - 10) & 3 : tt - s * (s + 1) / 2;
+      const bool need = s == 6 ? trailing : ((mask >> s & 1) && c <= jc);
+      const int row = s == 6 ? i : (s < 4 ? k + s : (s == 4 ? i : j));
+      const int col = s == 6 ? j : k + c;
+#pragma unroll
+      for (int q = 0; q < 2; ++q) v[tt][q] = need ? A[(size_t)(row * NB + ty + 16 * q) * np + col * NB + tx] : 0.f;
+    }
+#pragma unroll
+    for (int tt = 0; tt < RL4_TILES; ++tt)
+#pragma unroll
+      for (int q = 0; q < 2; ++q) tiles[tt][ty + 16 * q][tx] = v[tt][q];
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int c = 0; c < 4; ++c) {
+    // ---- F_c: [T(c,c) ; T(s,c)] for every slot s > c of the workgroup, wavefront w the w-th of them ----
+    const bool publisher = si == c && sj == c;         // tile (k+c, k+c)
+    const bool last = j == k + c;                      // this workgroup publishes L_i(k+c) and stops
+    {
+      int ps = -1, cnt = 0;
+      for (int s = c + 1; s < 6; ++s)
+        if (mask >> s & 1) { if (cnt == wv) ps = s; ++cnt; }
+      if (wv == 0 || ps >= 0) {
+        // (no panel: the panel half refactors the diagonal tile in place, unused)
+        const bool bad = tile_factor_t(tiles[rl4_tile(c, c)], tiles[rl4_tile(ps >= 0 ? ps : c, c)], (wv == 0 && publisher) ? &extra[0] : nullptr,
+                                       (last && ps == si) ? &extra[0] : nullptr, lane);
+        if (bad && publisher && wv == 0 && lane == 0) atomicOr(info, 1);
+      }
+    }
+    __syncthreads();
+    if (last) {
+      const int cc = (k + c) * NB;
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int r = ty + 16 * q;
+        if (publisher) {
+          DfacB[(size_t)(k + c) * NB * NB + r * NB + tx] = extra[r][tx];
+          if (r == tx && cc + r < nreal) {
+            atomicMin(reinterpret_cast<unsigned*>(info) + 1, __float_as_uint(extra[r][tx]));
+            atomicMax(reinterpret_cast<unsigned*>(info) + 2, __float_as_uint(extra[r][tx]));
+          }
+        } else Lm[(size_t)(i * NB + r) * np + cc + tx] = extra[r][tx];
+      }
+      return;
+    }
+    // ---- U_(c+1): a unit is 16 rows of a tile, unit u on wavefront u mod 8 ----
+    int u = 0;
+    if (c == 0 || c == 2) {
+      // column c+1 after step c: one product, subtracted from the source
+      for (int s = c + 1; s < 6; ++s) {
+        if (!(mask >> s & 1)) continue;
+        for (int h = 0; h < 2; ++h, ++u) {
+          if ((u & 7) != wv) continue;
+          float acc[2][4] = {};
+          strip_acc(acc, tiles[rl4_tile(s, c)], tiles[rl4_tile(c + 1, c)], h, lane);
+          strip_sub(tiles[rl4_tile(s, c + 1)], acc, h, lane);
+        }
+      }
+    } else if (c == 1) {
+      // what the two-column launch at k subtracts from everything to the right of its pair: the chain over columns k and k+1
+      // (a unit here is a whole tile, 4 x 4 elements per lane: half the LDS cycles of two strips, and there are up to eight of them)
+      for (int d = 2; d <= jc; ++d)
+        for (int s = d; s < 6; ++s) {
+          if (!(mask >> s & 1)) continue;
+          if ((u++ & 7) != wv) continue;
+          float acc[4][4] = {};
+          block_acc(acc, tiles[rl4_tile(s, 0)], tiles[rl4_tile(d, 0)], lane);
+          block_acc(acc, tiles[rl4_tile(s, 1)], tiles[rl4_tile(d, 1)], lane);
+          block_sub(tiles[rl4_tile(s, d)], acc, lane);
+        }
+      if (trailing && (u & 7) == wv) {
+        float acc[4][4] = {};
+        block_acc(acc, tiles[rl4_tile(si, 0)], tiles[rl4_tile(sj, 0)], lane);
+        block_acc(acc, tiles[rl4_tile(si, 1)], tiles[rl4_tile(sj, 1)], lane);
+        block_sub(extra, acc, lane);
+      }
+    } else {
+      // the two-column launch at k+2, stage 4: a second, separate subtraction (only trailing tiles get here)
+      if (wv < 2) {
+        float acc[2][4] = {};
+        strip_acc(acc, tiles[rl4_tile(si, 2)], tiles[rl4_tile(sj, 2)], wv, lane);
+        strip_acc(acc, tiles[rl4_tile(si, 3)], tiles[rl4_tile(sj, 3)], wv, lane);
+        const int r0 = 16 * wv + 2 * (lane >> 3), c0 = 4 * (lane & 7);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          float4 v;
+          v.x = extra[r0 + q][c0] - acc[q][0]; v.y = extra[r0 + q][c0 + 1] - acc[q][1];
+          v.z = extra[r0 + q][c0 + 2] - acc[q][2]; v.w = extra[r0 + q][c0 + 3] - acc[q][3];
+          *reinterpret_cast<float4*>(A + (size_t)(i * NB + r0 + q) * np + j * NB + c0) = v;
+        }
+      }
+      return;
+    }
+    __syncthreads();
   }
 }
 
@@ -1273,7 +1497,7 @@ int cache_sizes(int kernel, int Di, int Do, int M, int S, size_t* pack_floats, s
 }
 
 // Blocked Cholesky of `batch` np x np systems (A is consumed; L goes to Lmat below the diagonal tiles and to Dfac on them).
-static void cholesky_blocked(float* A, float* Lmat, float* Dfac, int np, int nblk, int batch, int* info, hipStream_t st, int nreal) {
+static int cholesky_blocked(float* A, float* Lmat, float* Dfac, int np, int nblk, int batch, int* info, hipStream_t st, int nreal) {
   struct { int np, nblk, batch; } w{np, nblk, batch};
   const size_t bstride = (size_t)np * np, dstride = (size_t)nblk * NB * NB;
   constexpr int PB = ST / NB;                          // 32-blocks per 128-wide panel
@@ -1293,7 +1517,18 @@ static void cholesky_blocked(float* A, float* Lmat, float* Dfac, int np, int nbl
         hipLaunchKernelGGL(k_syrk_mfma, dim3(Tt * (Tt + 1) / 2, w.batch), 256, 0, st, A, Lmat, w.np, bstride, jlim * NB, K * ST);
     }
   } else {
+    // four block columns per launch while four remain (k_chol_rl4), then two, then one: n = 601 (19 columns) is 4 + 1 + 1 dependent
+    // launches.  GPODE_CHOL_COLS=2 (read once) keeps the two-column chain, whose results are the same bit for bit.
+    static const bool cols2 = [] { const char* e = getenv("GPODE_CHOL_COLS"); return e && e[0] == '2'; }();
     int k = 0;
+    if (!cols2 && w.nblk >= 4) {
+      if (set_max_lds((const void*)k_chol_rl4, RL4_LDS)) return 1;
+      for (; k + 3 < w.nblk; k += 4) {
+        const int T = w.nblk - k;
+        hipLaunchKernelGGL(k_chol_rl4, dim3(T * (T + 1) / 2, w.batch), RL4_THREADS, RL4_LDS, st, A, Lmat, w.np, bstride, Dfac, dstride, k, info, w.nblk,
+                           nreal);
+      }
+    }
     for (; k + 1 < w.nblk; k += 2) {                   // two block columns per launch (k_chol_rl2)
       const int T = w.nblk - k;
       hipLaunchKernelGGL(k_chol_rl2, dim3(T * (T + 1) / 2, w.batch), 256, 0, st, A, Lmat, w.np, bstride, Dfac, dstride, k, info, w.nblk, nreal);
@@ -1303,6 +1538,7 @@ static void cholesky_blocked(float* A, float* Lmat, float* Dfac, int np, int nbl
       hipLaunchKernelGGL(k_chol_rl, dim3(T * (T + 1) / 2, w.batch), 256, 0, st, A, Lmat, w.np, bstride, Dfac, dstride, k, info, w.nblk, w.nblk, nreal);
     }
   }
+  return 0;
 }
 
 // nd Monte-Carlo draws in one build (nd = 1: SVGP_Layer.build_cache as the reference calls it).  Noise, pack and the per-draw
@@ -1372,7 +1608,7 @@ int cache_build_fwd(int kernel, int Di, int Do, int M, int S, int nd,
     hipLaunchKernelGGL(k_Kzz_rbf, dim3(cdiv(w.np, 128), w.np, Do), 128, 0, st, Di, Do, M, w.np, Z, ws + w.ell, ws + w.var, up, A, nd);
   else
     hipLaunchKernelGGL(k_Kzz_df, dim3(cdiv(w.np, 128), w.np, 1), 128, 0, st, Do, M, w.np, Z, ws + w.ell, ws + w.var, up, A, nd);
-  cholesky_blocked(A, Lmat, Dfac, w.np, w.nblk, w.batch, info, st, w.n);
+  if (cholesky_blocked(A, Lmat, Dfac, w.np, w.nblk, w.batch, info, st, w.n)) return 1;
   if (check_launch("cholesky")) return 1;
 
   // nu_l = L^-T (u_l - L^-1 u_prior_l), written to ws, to the optional output and into draw l's pack
@@ -1473,7 +1709,7 @@ int compute_nu(int kernel, int Di, int Do, int M, const float* Ku, const float* 
   const size_t bstride = (size_t)w.np * w.np, dstride = (size_t)w.nblk * NB * NB, MD = (size_t)M * Do;
   if (hipMemsetAsync(info, 0, 4 * sizeof(int), st) != hipSuccess) return set_error("gpode_compute_nu: memset failed");
   hipLaunchKernelGGL(k_fill_from_K, dim3(cdiv(w.np, 128), w.np, w.batch), 128, 0, st, kernel, Do, w.n, w.np, Ku, u_prior, A);
-  cholesky_blocked(A, Lmat, Dfac, w.np, w.nblk, w.batch, info, st, w.n);
+  if (cholesky_blocked(A, Lmat, Dfac, w.np, w.nblk, w.batch, info, st, w.n)) return 1;
   if (check_launch("compute_nu: cholesky")) return 1;
   const int u_stride = kernel == 0 ? Do : 1, u_bstride = kernel == 0 ? 1 : 0;
   if (big_factor(w.np)) {
@@ -1663,7 +1899,7 @@ int conditional(int Di, int Do, int M, int N, const float* raw_ell, const float*
   int* info = reinterpret_cast<int*>(ws + c.info);
   const size_t bstride = (size_t)c.np * c.np, dstride = (size_t)c.nblk * NB * NB;
   hipLaunchKernelGGL(k_cond_fill, dim3(cdiv(c.np, 128), c.np, Do), 128, 0, st, Di, Do, M, N, c.np, raw_ell, raw_var, Z, x, ws + c.A, info);
-  cholesky_blocked(ws + c.A, ws + c.Lmat, ws + c.Dfac, c.np, c.nblk, Do, info, st, M);
+  if (cholesky_blocked(ws + c.A, ws + c.Lmat, ws + c.Dfac, c.np, c.nblk, Do, info, st, M)) return 1;
   if (check_launch("conditional: cholesky")) return 1;
   const size_t lds = sizeof(float) * M;
   if (set_max_lds((const void*)k_cond_rows, lds)) return 1;
