@@ -708,7 +708,7 @@ static int dec10_bn_nwg(int B, int& ipb) {
 int dec10_bn_wgrad_scratch_floats() { return kDec10BnMaxWg * dec10::CI * dec10::KK + kDec10BnMaxWg; }
 int dec10_bn_bwd_sums(const float* c, const float* gy, const float* w, const float* gamma, const float* beta, const float* mean,
                       const float* invstd, float* sums, int B, float* scratch, hipStream_t st, float* gw, float* wscratch, float* gbias) {
-  if (!aligned16(gy, c)) return set_error("gpode_dec10_bn_bwd_sums: c / gy must be 16-byte aligned");
+  if (!aligned16(gy, c)) return set_error("gpode_dec10_bn_bwd_sums%s: c / gy must be 16-byte aligned", gw ? "_wgrad" : "");
   if (gw && !wscratch) return set_error("gpode_dec10_bn_bwd_sums_wgrad: scratch for the weight-gradient partials missing");
   int ipb;
   const int nwg = dec10_bn_nwg(B, ipb);
@@ -727,7 +727,7 @@ int dec10_bn_bwd_sums(const float* c, const float* gy, const float* w, const flo
   else rc = launch_dec10_bn<2, 0>(B, st, gy, w, c, gamma, beta, mean, invstd, B, scratch, 0, 0.f, cnp, cnp, 0, np_, np_, np_, np_, np_, np_);
   if (rc) return rc;
   if (sums) hipLaunchKernelGGL(k_dec10_parts_reduce, 1, 512, 0, st, scratch, nwg, sums, 1);
-  return check_launch("dec10_bn_bwd_sums");
+  return check_launch(gw ? "dec10_bn_bwd_sums_wgrad" : "dec10_bn_bwd_sums");
 }
 
 int dec10_bn_bwd_apply(const float* c, const float* gy, const float* w, const float* gamma, const float* beta, const float* mean,
