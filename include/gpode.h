@@ -545,6 +545,34 @@ int gpode_elbo_all_bwd_ll_len(const float* g_loss, const float* g_nll, const flo
                               const float* hv, int N, int q, int M, int Do, const float* Um, const float* Us, float nobs, float* glrow, float* ghs,
                               float* ghv, float* dUm, float* dUs, const float* X, const float* z, float* ga, size_t n_logits, size_t nX,
                               const int* n_obs, int T, size_t frame, void* stream);
+/* Ragged minibatches, compact route: the padded frames are taken out IN FRONT of the decoder, which then decodes the observed frames
+ * only (what the *_len entries above mask out of the likelihood is here never decoded, and never enters a BatchNorm statistic).
+ * The index (vae_ops.frame_index builds it on the host): c[n] = clamp(n_obs[n], 0, T); off[N + 1] (int32, device) the exclusive prefix
+ * sum of c, off[N] = P; src[P] (int32, device), src[j] = n T + t for compact image j = off[n] + t, t < c[n].  The compact batch of L
+ * draws is (L P, ...), ordered (l, n, t): the padded order with the padded frames removed; with full lengths it IS the padded batch.
+ *   gpode_gather_frames_fwd      out[(l P + j), 0..q) = zt[l, src[j] / T, src[j] % T, 0..q) for zt (L,N,T,ld): replaces the position slice
+ *                                + .contiguous() in front of Decoder.forward (odegpvae.py:18-35); ld >= q is the row stride of zt
+ *                                (order * q), so the position slice of a second-order model is folded in.
+ *   gpode_gather_frames_bwd      its adjoint written as a gather: EVERY element of gzt (L,N,T,ld) exactly once -- observed rows, columns
+ *                                < q: the matching element of gout (L P, q); padded rows and columns >= q: zero.  No pre-fill, no atomics.
+ *   gpode_sigmoid_loglik_fwd_pk  gpode_sigmoid_loglik_fwd over compact logits: rows are (draw, sequence), row (l, n) is the c[n] frame
+ *                                contiguous logits at (l P + off[n]) frame, its targets the leading c[n] frames of X + n T frame (padded
+ *                                targets are never addressed).  z is written for the L P frame compact elements; part is (rows, nsplit)
+ *                                with the twin's slices (nsplit from gpode_sigmoid_loglik_splits(rows, T frame)); a slice beyond its
+ *                                row's length, and so every slice of a row with c[n] = 0, is exactly 0.  With c[n] = T for all n, z and
+ *                                part have the bits of gpode_sigmoid_loglik_fwd.  rows = L N with N = nX / (T frame).
+ *   gpode_sigmoid_loglik_bwd_pk  gpode_sigmoid_loglik_bwd over the compact elements: ga[e] from z[e], the target at
+ *                                src[j] frame + e % frame (image e / frame = l P + j) and grow[l N + src[j] / T].
+ * gpode_elbo_all_fwd / _fwd_kl and gpode_elbo_all_bwd serve unchanged (nl_rows = L N).  gpode_last_launch(): "gather_frames_fwd",
+ * "gather_frames_bwd", "sigmoid_loglik_fwd_pk", "sigmoid_loglik_bwd_pk".  Refused, with nothing written: a NULL index or operand,
+ * q > ld, non-positive sizes, P > N T, frame % 4 != 0, nX no whole number of sequences, rows no multiple of N, and what the twins refuse. */
+int gpode_gather_frames_fwd(const float* zt, int ld, int q, const int* src, int L, int N, int T, int P, float* out, void* stream);
+int gpode_gather_frames_bwd(const float* gout, int ld, int q, const int* src, const int* off, int L, int N, int T, int P, float* gzt,
+                            void* stream);
+int gpode_sigmoid_loglik_fwd_pk(const float* X, const float* a, float* z, float* part, size_t rows, const int* off, int T, size_t frame,
+                                size_t nX, int nsplit, void* stream);
+int gpode_sigmoid_loglik_bwd_pk(const float* X, const float* z, const float* grow, float* ga, size_t rows, const int* src, int P, int T,
+                                size_t frame, size_t nX, void* stream);
 /* All device-side noise of a step in one launch (the reference draws on the host with numpy -- kernels.py:13-26,134-137,
  * svpy.py:12-27,94 -- and with torch.randn_like, vae.py:76; `--device_noise` / DeviceNoise draws here instead):
  *   out[0 .. n_normal) ~ N(0,1), out[n_normal .. n_normal + n_uniform) ~ U[0,1): Philox4x32-10 keyed by `seed`, counter = (element

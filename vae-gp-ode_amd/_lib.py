@@ -144,6 +144,11 @@ SIGNATURES.update({
     'gpode_loglik_rowsum_bwd_len': (_i, [_c_float_p] * 4 + [_sz, _sz, _sz, _vp, _i, _sz, _vp]),
     'gpode_elbo_all_bwd_ll_len': (_i, [_c_float_p] * 4 + [_i, _c_float_p, _c_float_p, _i, _i, _i, _i, _c_float_p, _c_float_p, _f] + [_c_float_p] * 8 + [_sz, _sz, _vp, _i, _sz, _vp]),
     'gpode_elbo_all_bwd_ll_kl_len': (_i, [_c_float_p] * 4 + [_i, _i, _i, _i, _c_float_p, _c_float_p, _f, _c_float_p, _c_float_p, _i, _c_float_p, _i] + [_c_float_p] * 5 + [_sz, _sz, _vp, _i, _sz, _vp]),
+    # ragged minibatches, compact route: the frame gather in front of the decoder and the loss stage over compact logits
+    'gpode_gather_frames_fwd': (_i, [_c_float_p, _i, _i, _vp, _i, _i, _i, _i, _c_float_p, _vp]),
+    'gpode_gather_frames_bwd': (_i, [_c_float_p, _i, _i, _vp, _vp, _i, _i, _i, _i, _c_float_p, _vp]),
+    'gpode_sigmoid_loglik_fwd_pk': (_i, [_c_float_p] * 4 + [_sz, _vp, _i, _sz, _sz, _i, _vp]),
+    'gpode_sigmoid_loglik_bwd_pk': (_i, [_c_float_p] * 4 + [_sz, _vp, _i, _i, _sz, _sz, _vp]),
     'gpode_dec10_predict_len': (_i, [_c_float_p] * 5 + [_i] * 5 + [_c_float_p] * 3 + [_vp, _vp]),
     'gpode_dec10_predict_ll_len': (_i, [_c_float_p] * 5 + [_i] * 5 + [_c_float_p] * 4 + [_i, _vp, _vp]),
 })

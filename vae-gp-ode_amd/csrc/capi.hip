@@ -708,6 +708,33 @@ int gpode_sigmoid_loglik_bwd_len(const float* X, const float* z, const float* gr
   if (!rows || !inner || !nX) return gp::set_error("gpode_sigmoid_loglik_bwd_len: empty input");
   return gp::sigmoid_loglik_bwd_len(X, z, grow, ga, rows, inner, nX, n_obs, T, frame, GP_ST);
 }
+int gpode_gather_frames_fwd(const float* zt, int ld, int q, const int* src, int L, int N, int T, int P, float* out, void* stream) {
+  if (!zt || !out) return gp::set_error("gpode_gather_frames_fwd: null pointer");
+  if (!src) return gp::set_error("gpode_gather_frames_fwd: the frame index is NULL");
+  if (q < 1 || q > ld) return gp::set_error("gpode_gather_frames_fwd: 1 <= q <= ld");
+  if (L < 1 || N < 1 || T < 1 || P < 1 || (long long)P > (long long)N * T) return gp::set_error("gpode_gather_frames_fwd: L, N, T >= 1 and 1 <= P <= N * T");
+  return gp::gather_frames_fwd(zt, ld, q, src, L, N, T, P, out, GP_ST);
+}
+int gpode_gather_frames_bwd(const float* gout, int ld, int q, const int* src, const int* off, int L, int N, int T, int P, float* gzt,
+                            void* stream) {
+  if (!gout || !gzt) return gp::set_error("gpode_gather_frames_bwd: null pointer");
+  if (!src || !off) return gp::set_error("gpode_gather_frames_bwd: the frame index is NULL");
+  if (q < 1 || q > ld) return gp::set_error("gpode_gather_frames_bwd: 1 <= q <= ld");
+  if (L < 1 || N < 1 || T < 1 || P < 1 || (long long)P > (long long)N * T) return gp::set_error("gpode_gather_frames_bwd: L, N, T >= 1 and 1 <= P <= N * T");
+  return gp::gather_frames_bwd(gout, ld, q, off, L, N, T, P, gzt, GP_ST);
+}
+int gpode_sigmoid_loglik_fwd_pk(const float* X, const float* a, float* z, float* part, size_t rows, const int* off, int T, size_t frame,
+                                size_t nX, int nsplit, void* stream) {
+  if (!X || !a || !z || !part) return gp::set_error("gpode_sigmoid_loglik_fwd_pk: null pointer");
+  if (!rows || !nX) return gp::set_error("gpode_sigmoid_loglik_fwd_pk: empty input");
+  return gp::sigmoid_loglik_fwd_pk(X, a, z, part, rows, off, T, frame, nX, nsplit, GP_ST);
+}
+int gpode_sigmoid_loglik_bwd_pk(const float* X, const float* z, const float* grow, float* ga, size_t rows, const int* src, int P, int T,
+                                size_t frame, size_t nX, void* stream) {
+  if (!X || !z || !grow || !ga) return gp::set_error("gpode_sigmoid_loglik_bwd_pk: null pointer");
+  if (!rows || !nX) return gp::set_error("gpode_sigmoid_loglik_bwd_pk: empty input");
+  return gp::sigmoid_loglik_bwd_pk(X, z, grow, ga, rows, src, P, T, frame, nX, GP_ST);
+}
 int gpode_elbo_all_fwd(const float* lpart, int nl_rows, int nl_values, const float* hs, const float* hv, int N, int q, int M, int Do,
                        const float* Um, const float* Us, float nobs, float* out, void* stream) {
   if (!lpart || !hs || !Um || !Us || !out) return gp::set_error("gpode_elbo_all_fwd: null pointer");

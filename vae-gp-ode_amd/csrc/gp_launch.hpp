@@ -254,6 +254,14 @@ int elbo_all_bwd_ll_kl_len(const float* g0, const float* g1, const float* g2, co
                            const float* Us, float nobs, float* glrow, float* gkls, int nks, float* gklv, int nkv, float* dUm, float* dUs,
                            const float* X, const float* z, float* ga, size_t n, size_t nX, const int* n_obs, int T, size_t frame,
                            hipStream_t st);
+// ragged minibatches with the padding taken out in front of the decoder: the frame gather and the loss stage over compact logits
+// (off: exclusive prefix sum of the clamped counts, N + 1 entries; src[j] = n T + t of compact image j; P = off[N]); vae_conv.hip
+int gather_frames_fwd(const float* zt, int ld, int q, const int* src, int L, int N, int T, int P, float* out, hipStream_t st);
+int gather_frames_bwd(const float* gout, int ld, int q, const int* off, int L, int N, int T, int P, float* gzt, hipStream_t st);
+int sigmoid_loglik_fwd_pk(const float* X, const float* a, float* z, float* part, size_t rows, const int* off, int T, size_t frame, size_t nX,
+                          int nsplit, hipStream_t st);
+int sigmoid_loglik_bwd_pk(const float* X, const float* z, const float* grow, float* ga, size_t rows, const int* src, int P, int T, size_t frame,
+                          size_t nX, hipStream_t st);
 int dec10_predict_len(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th, int T_obs,
                       int done, float* pred_mean, float* pred_m2, float* se_state, const int* n_obs, hipStream_t st);
 int dec10_predict_ll_len(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th, int T_obs,

@@ -1038,6 +1038,142 @@ int sigmoid_loglik_bwd_len(const float* X, const float* z, const float* grow, fl
   hipLaunchKernelGGL(k_sigmoid_loglik_bwd<true>, ew_grid(n), 256, 0, st, X, z, grow, ga, n, inner, nX, n_obs, T, frame);
   return check_launch("sigmoid_loglik_bwd_len");
 }
+
+// ---- ragged minibatches with the padding taken out in front of the decoder (the *_pk entry points and the frame gather) -----------------
+// c[n] = clamp(n_obs[n], 0, T), off = exclusive prefix sum of c (N + 1 entries, off[N] = P), src[j] = n T + t for compact image j of a
+// draw: the compact batch is (L P, ...), ordered (l, n, t) -- the padded order with the padded frames removed.
+// out[(l P + j), 0..q) = zt[l, src[j], 0..q): rows of 12-64 bytes at a stride of ld floats, one lane per element (launch-bound)
+__global__ void k_gather_frames_fwd(const float* __restrict__ zt, int ld, int q, const int* __restrict__ src, size_t NT, int P,
+                                    float* __restrict__ out, size_t n) {
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = e / q, l = r / P;
+    out[e] = zt[(l * NT + src[r - l * P]) * ld + (e - r * q)];
+  }
+}
+// the adjoint as a gather over gzt (L,N,T,ld): every element is written once -- observed rows, columns < q: the element of gout;
+// padded rows and columns >= q: zero.  No pre-fill, no atomics.
+__global__ void k_gather_frames_bwd(const float* __restrict__ gout, int ld, int q, const int* __restrict__ off, int N, int T, int P,
+                                    float* __restrict__ gzt, size_t n) {
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = e / ld, s = r / T, l = s / N;
+    const int col = (int)(e - r * ld), t = (int)(r - s * T), nn = (int)(s - l * N);
+    const int o0 = off[nn], c = off[nn + 1] - o0;
+    gzt[e] = (col < q && t < c) ? gout[(l * P + o0 + t) * q + col] : 0.f;
+  }
+}
+int gather_frames_fwd(const float* zt, int ld, int q, const int* src, int L, int N, int T, int P, float* out, hipStream_t st) {
+  const size_t n = (size_t)L * P * q;
+  hipLaunchKernelGGL(k_gather_frames_fwd, ew_grid(n), 256, 0, st, zt, ld, q, src, (size_t)N * T, P, out, n);
+  return check_launch("gather_frames_fwd");
+}
+int gather_frames_bwd(const float* gout, int ld, int q, const int* off, int L, int N, int T, int P, float* gzt, hipStream_t st) {
+  const size_t n = (size_t)L * N * T * ld;
+  hipLaunchKernelGGL(k_gather_frames_bwd, ew_grid(n), 256, 0, st, gout, ld, q, off, N, T, P, gzt, n);
+  return check_launch("gather_frames_bwd");
+}
+
+// k_sigmoid_loglik_fwd over compact logits: row (l, n) is the c[n] frame contiguous logits at (l P + off[n]) frame, its targets the
+// leading c[n] frames of X + n T frame -- a padded target is never addressed.  The slices are the twin's (chunk from inner = T frame), a
+// slice beyond its row's length writes exactly 0; element-to-thread assignment and the roundings of a term are those of
+// k_sigmoid_loglik_fwd<true>, so with c[n] = T for all n z and part have the twin's bits.  frame % 4 == 0 (the launcher refuses others):
+// rows, frames and slices start on 16-byte boundaries when the three pointers do (chunk % 4 == 0), else chunk is odd: the scalar path.
+__global__ __launch_bounds__(256) void k_sigmoid_loglik_fwd_pk(const float* __restrict__ X, const float* __restrict__ a, float* __restrict__ z,
+                                                                float* __restrict__ part, const int* __restrict__ off, int N, int T,
+                                                                size_t frame, size_t chunk) {
+  __shared__ float red[4];
+  const size_t row = blockIdx.y, l = row / N, nn = row - l * N;
+  const int o0 = off[nn], c = off[nn + 1] - o0, P = off[N];
+  const size_t len = (size_t)(c < 0 ? 0 : (c > T ? T : c)) * frame;
+  const size_t p0 = (size_t)blockIdx.x * chunk, p1 = p0 + chunk < len ? p0 + chunk : len;
+  const size_t base = (l * P + o0) * frame;
+  const float* __restrict__ ar = a + base;
+  const float* __restrict__ xr = X + nn * T * frame;
+  float* __restrict__ zr = z + base;
+  float acc = 0.f;
+  if ((chunk & 3) == 0) {
+    auto one = [&](float av, float xv) {
+      const float zv = 1.f / (1.f + expf(-av));
+      acc = __fadd_rn(acc, __fmaf_rn(logf(zv), xv, __fmul_rn(logf(1.f - zv), 1.f - xv)));
+      return zv;
+    };
+    for (size_t p = p0 + 4 * threadIdx.x; p < p1; p += 1024) {
+      const float4 av = *reinterpret_cast<const float4*>(ar + p), xv = *reinterpret_cast<const float4*>(xr + p);
+      float4 zv;
+      zv.x = one(av.x, xv.x); zv.y = one(av.y, xv.y); zv.z = one(av.z, xv.z); zv.w = one(av.w, xv.w);
+      *reinterpret_cast<float4*>(zr + p) = zv;
+    }
+  } else {
+    for (size_t p = p0 + threadIdx.x; p < p1; p += 256) {
+      const float xv = xr[p];
+      const float zv = 1.f / (1.f + expf(-ar[p]));
+      acc = __fadd_rn(acc, __fadd_rn(__fmul_rn(logf(zv), xv), __fmul_rn(logf(1.f - zv), 1.f - xv)));
+      zr[p] = zv;
+    }
+  }
+  float in1[1] = {acc}, out1[1];
+  wave_sum_multi<1>(in1, out1);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = out1[0];
+  __syncthreads();
+  if (threadIdx.x == 0) part[row * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+// ga over the compact elements, k_sigmoid_loglik_bwd's expression: element e -> image e / frame = l P + j -> src[j] = n T + t -> its target
+// at src[j] frame + e % frame and the row gradient grow[l N + n].  V4: four elements of one frame per lane (frame % 4 == 0, 16-byte pointers)
+template <bool V4>
+__global__ void k_sigmoid_loglik_bwd_pk(const float* __restrict__ X, const float* __restrict__ z, const float* __restrict__ grow,
+                                        float* __restrict__ ga, const int* __restrict__ src, size_t n, int N, int T, int P, size_t frame) {
+  auto one = [](float xv, float zv, float g) {
+    const float gz = g * (xv / zv - (1.f - xv) / (1.f - zv));
+    return gz * zv * (1.f - zv);
+  };
+  constexpr size_t W = V4 ? 4 : 1;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n / W; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t e = W * i, img = e / frame, l = img / P;
+    const int s = src[img - l * P];
+    const float g = grow[l * N + s / T];
+    const float* __restrict__ xp = X + (size_t)s * frame + (e - img * frame);
+    if constexpr (V4) {
+      const float4 xv = *reinterpret_cast<const float4*>(xp), zv = *reinterpret_cast<const float4*>(z + e);
+      float4 o;
+      o.x = one(xv.x, zv.x, g); o.y = one(xv.y, zv.y, g); o.z = one(xv.z, zv.z, g); o.w = one(xv.w, zv.w, g);
+      *reinterpret_cast<float4*>(ga + e) = o;
+    } else {
+      ga[e] = one(xp[0], z[e], g);
+    }
+  }
+}
+// what the *_pk launchers refuse, with nothing written
+static const char* pk_refusal(size_t rows, const int* index, int T, size_t frame, size_t nX) {
+  if (index == nullptr) return "the frame index is NULL";
+  if (T < 1 || frame < 1 || (frame & 3) != 0) return "T >= 1 and frame a positive multiple of 4";
+  const size_t inner = (size_t)T * frame;
+  if (nX < inner || nX % inner != 0) return "X must hold a whole number of sequences (nX a multiple of T * frame)";
+  if (rows == 0 || rows % (nX / inner) != 0) return "rows must be a multiple of the number of sequences";
+  return nullptr;
+}
+int sigmoid_loglik_fwd_pk(const float* X, const float* a, float* z, float* part, size_t rows, const int* off, int T, size_t frame, size_t nX,
+                          int nsplit, hipStream_t st) {
+  if (nsplit < 1 || rows > 65535) return set_error("gpode_sigmoid_loglik_fwd_pk: nsplit >= 1, rows <= 65535");
+  if (const char* why = pk_refusal(rows, off, T, frame, nX)) return set_error("gpode_sigmoid_loglik_fwd_pk: %s", why);
+  const size_t inner = (size_t)T * frame;
+  size_t chunk = (inner + nsplit - 1) / nsplit;
+  chunk = (chunk + 3) & ~(size_t)3;
+  if (!aligned16(X, a, z)) chunk |= 1;   // scalar path, as the twin takes it
+  hipLaunchKernelGGL(k_sigmoid_loglik_fwd_pk, dim3(nsplit, (unsigned)rows), 256, 0, st, X, a, z, part, off, (int)(nX / inner), T, frame, chunk);
+  return check_launch("sigmoid_loglik_fwd_pk");
+}
+int sigmoid_loglik_bwd_pk(const float* X, const float* z, const float* grow, float* ga, size_t rows, const int* src, int P, int T, size_t frame,
+                          size_t nX, hipStream_t st) {
+  if (const char* why = pk_refusal(rows, src, T, frame, nX)) return set_error("gpode_sigmoid_loglik_bwd_pk: %s", why);
+  const size_t N = nX / ((size_t)T * frame);
+  if (P < 1 || (size_t)P > N * T) return set_error("gpode_sigmoid_loglik_bwd_pk: 1 <= P <= N * T");
+  const size_t n = rows / N * P * frame;
+  if (aligned16(X, z, ga)) {
+    hipLaunchKernelGGL(k_sigmoid_loglik_bwd_pk<true>, ew_grid(n / 4), 256, 0, st, X, z, grow, ga, src, n, (int)N, T, P, frame);
+  } else {
+    hipLaunchKernelGGL(k_sigmoid_loglik_bwd_pk<false>, ew_grid(n), 256, 0, st, X, z, grow, ga, src, n, (int)N, T, P, frame);
+  }
+  return check_launch("sigmoid_loglik_bwd_pk");
+}
 int elbo_all_fwd(const float* lpart, int nl_rows, int nl_values, const float* hs, const float* hv, int N, int q, int M, int Do,
                  const float* Um, const float* Us, float nobs, float* out, hipStream_t st) {
   // out: 4 results + kElboParts floats of scratch

@@ -72,6 +72,9 @@ EXT_FLAGS = [
                               'between KMIN and K frames (K = --subsample_frames if set, else T), drawn per sequence, and is padded to K: '
                               'the likelihood sums its observed frames only, the padded ones are integrated and decoded as forecasts; '
                               '0: off'),
+    ('ragged_compact', eval, False, 'with --ragged_frames: take the padded frames out in front of the decoder -- they are integrated but not '
+                                    'decoded, and enter neither the BatchNorm statistics nor the loss; the frame counts are read back once '
+                                    'per step and the launch sizes follow them, so not with --hip_graph and not on several ranks'),
     ('sync_bn', eval, True, 'data parallel: BatchNorm normalises with the statistics of the GLOBAL minibatch (all ranks), as the '
                             'single-process reference does (vae.py:55,58,113,116,119)'),
 ]
@@ -148,6 +151,20 @@ def check_ragged(args):
     if kmin and (kmin > kmax or kmin <= lead):
         raise SystemExit('--ragged_frames %d: must be 0 (off) or more than the %d leading frame(s) the encoders read (--ode %d) and '
                          'at most %s %d' % (kmin, lead, args.ode, '--subsample_frames' if args.subsample_frames else '--T', kmax))
+
+
+def check_ragged_compact(args):
+    """--ragged_compact True: needs --ragged_frames, eager steps and one rank; refused with a message otherwise, ahead of any device work"""
+    if not args.ragged_compact:
+        return
+    if not args.ragged_frames:
+        raise SystemExit('--ragged_compact True: needs --ragged_frames KMIN (without it no frame is padded and there is nothing to take out)')
+    if args.hip_graph:
+        raise SystemExit('--ragged_compact True: not with --hip_graph True -- the number of observed frames, and with it the launch sizes of '
+                         'the decoder, change from step to step, which a captured step cannot follow')
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        raise SystemExit('--ragged_compact True: not on several ranks (WORLD_SIZE %s) -- cross-rank BatchNorm for compact batches is not '
+                         'built' % os.environ['WORLD_SIZE'])
 
 
 def subsample_generator(args):
@@ -229,6 +246,7 @@ def main(argv=None):
     args = make_parser().parse_args(argv)
     check_subsample(args)
     check_ragged(args)
+    check_ragged_compact(args)
     from .model.core.initialization import initialize_and_fix_kernel_parameters
     from .model.create_model import build_model, compute_loss, compute_test_error, backward
     from .model.misc.torch_utils import seed_everything
@@ -356,6 +374,9 @@ def main(argv=None):
         if args.ragged_frames:
             logger.info('Every sequence keeps {} to {} of its frames, drawn per minibatch and padded; time grids and frame counts per '
                         'sequence'.format(args.ragged_frames, args.subsample_frames or args.T))
+            if args.ragged_compact:
+                logger.info('Padded frames are not decoded: the decoder, its BatchNorm statistics and the loss take the observed frames '
+                            'only (frame counts read back once per step)')
         else:
             logger.info('Every sequence keeps {} of its frames, drawn per minibatch; time grids per sequence'.format(args.subsample_frames))
     logger.info('********** Started Training **********')
@@ -388,6 +409,8 @@ def main(argv=None):
                     bn_sync.set_shares(None)
             if args.hip_graph and capture_ok:
                 loss, nlhood, kl_reg, kl_u = graphed_step(minibatch, L, ts, n_obs) if n_obs is not None else graphed_step(minibatch, L, ts)
+            elif n_obs is not None and args.ragged_compact:
+                loss, nlhood, kl_reg, kl_u = compute_loss(model, minibatch, L, ts=ts, n_obs=n_obs, compact=True)
             elif n_obs is not None:
                 loss, nlhood, kl_reg, kl_u = compute_loss(model, minibatch, L, ts=ts, n_obs=n_obs)
             elif ts is None:

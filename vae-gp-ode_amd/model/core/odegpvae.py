@@ -19,6 +19,14 @@ class ODEGPVAE(nn.Module):
         lat = ztL if self.order == 1 else ztL[..., :ztL.shape[-1] // 2]
         return (self.vae.decoder(lat, logits=True) if logits else self.vae.decoder(lat)).view([L, N, T, nc, d, d])
 
+    def decode_observed(self, ztL, index, logits=False):
+        """ztL (L,N,T,order*q) -> the decodings of the OBSERVED frames only, (L P, nc, d, d) ordered (l, n, t): the latent states (the
+        positions for order 2) of the frames ``index`` lists (vae_ops.frame_index) are gathered in one launch and the decoder runs on
+        L P images -- a padded frame is not decoded and enters no BatchNorm statistic."""
+        from ... import vae_ops
+        lat = vae_ops.gather_frames(ztL, index, ztL.shape[-1] // self.order)
+        return self.vae.decoder(lat, logits=True) if logits else self.vae.decoder(lat)
+
     def sample_trajectories(self, z0, T, L=1, ts=None):
         """L independent function draws, each shared by the whole minibatch (odegpvae.py:37-45).  z0 (L,N,D): draw l starts from
         its own sample z0[l] of the initial states (encode_initial_state(X, draws=L)).
@@ -82,13 +90,19 @@ class ODEGPVAE(nn.Module):
         mu_v, logv_v = vel(torch.squeeze(X[:, 0:self.v_steps]))
         return torch.concat([z0, vel.sample(mu=mu_v, logvar=logv_v)], dim=1), (mu_s, logv_s), (mu_v, logv_v)
 
-    def forward(self, X, L=1, T_custom=None, logits=False, ts=None):
+    def forward(self, X, L=1, T_custom=None, logits=False, ts=None, obs_index=None):
         """X (N,T,nc,d,d) -> (Xrec (L,N,T',nc,d,d), (mu_s, logv_s), (mu_v, logv_v)); T' = T_custom or T (odegpvae.py:48-70).
         ``ts`` (N,T'): the time at which frame t of sequence n was observed -- the latent state is integrated to those times and
         decoded there; None = the uniform grid dt * arange(T').  The encoders read the leading frames as they stand: for a
-        second-order model the first ``v_steps`` frames are taken to be consecutive."""
+        second-order model the first ``v_steps`` frames are taken to be consecutive.
+        ``obs_index`` (vae_ops.frame_index of a ragged minibatch): the states are integrated over the whole padded grid as ever, but
+        only the observed frames are decoded (decode_observed) -- in place of Xrec stands the compact (L P, nc, d, d) tensor; None:
+        the calls as they always were."""
         N, T, nc, d, _ = X.shape
         horizon = T_custom if T_custom else T
+        if obs_index is not None and (obs_index.N, obs_index.T) != (N, horizon):
+            raise ValueError('forward: obs_index lists the frames of (N,T\') = (%d,%d), the minibatch is (%d,%d)'
+                             % (obs_index.N, obs_index.T, N, horizon))
         if ts is not None and (ts.dim() != 2 or tuple(ts.shape) != (N, horizon)):
             raise ValueError('forward: ts must be (N,T\') = (%d,%d), one row of observation times per sequence; got %s'
                              % (N, horizon, tuple(ts.shape)))
@@ -103,4 +117,6 @@ class ODEGPVAE(nn.Module):
             field.prebuild_cache(None if L == 1 else L)   # overlap mode only: the cache of the draw(s) builds next to the encoder
         z0, code_s, code_v = self.encode_initial_state(X)
         ztL = self.sample_trajectories(z0, horizon, L, ts=ts)
+        if obs_index is not None:
+            return self.decode_observed(ztL, obs_index, logits).view([L * obs_index.P, nc, d, d]), code_s, code_v
         return self.build_decoding(ztL, (L, N, horizon, nc, d, d), logits), code_s, code_v

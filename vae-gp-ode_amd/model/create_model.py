@@ -32,7 +32,27 @@ def elbo(model, X, Xrec, s0_mu, s0_logv, v0_mu, v0_logv, L):
     return lhood.mean(), kl_reg.mean(), model.flow.kl()
 
 
-def compute_loss(model, data, L, ts=None, n_obs=None):
+def _compact_loss(model, data, L, grid, n_obs, counts):
+    """compute_loss(compact=True): decode and score the observed frames only"""
+    from .. import vae_ops as V
+    if n_obs is None:
+        raise ValueError('compute_loss: compact=True needs n_obs, the frame count of every sequence of the padded minibatch')
+    field = model.flow.odefunc.diffeq
+    if not _FUSED_LOSS:
+        raise ValueError('compute_loss: compact=True has one loss route, from the logits; it is not available under GPODE_UNFUSED_LOSS=1')
+    if not hasattr(field, 'us_packed') or model.vae.decoder.distribution != 'bernoulli':
+        raise ValueError('compute_loss: compact=True needs the Bernoulli decoder and the fused loss stage (a %s decoder is not covered)'
+                         % model.vae.decoder.distribution)
+    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        raise ValueError('compute_loss: compact=True on several ranks is not built: the cross-rank BatchNorm (parallel.count_all) takes a '
+                         "rank's image count to be proportional to its share of the sequences, which taking the padding out breaks")
+    index = V.frame_index(n_obs, data.shape[1], counts=counts)
+    logits, (s0_mu, s0_logv), (v0_mu, v0_logv) = model(data, L, logits=True, obs_index=index, **grid)
+    lpart, _ = V.sigmoid_loglik_parts(data, logits, L * data.shape[0], index=index)
+    return V.elbo_all(lpart, s0_mu, s0_logv, v0_mu, v0_logv, field.Um.optvar, field.us_packed(), field.M, model.num_observations)
+
+
+def compute_loss(model, data, L, ts=None, n_obs=None, compact=False, counts=None):
     """-> (loss, nll, kl_reg, kl_u) (create_model.py:61-73).  Same terms as elbo() above; the per-row pieces go through
     three fused launches (KL rows, likelihood row sums, loss algebra) instead of ~25 elementwise ones.
     ``ts`` (N,T): the observation time of every frame of every sequence (ODEGPVAE.forward); None = the uniform grid, the call as
@@ -41,10 +61,19 @@ def compute_loss(model, data, L, ts=None, n_obs=None):
     The likelihood of a sequence sums its observed frames only (nothing is renormalised by the count: the ELBO is a sum over
     observations), a padded frame gets exactly zero gradient at its logits, and what the padded targets hold is never read into a
     result.  The padded frames are still integrated and decoded (the forecast at the padding times, whose columns of ``ts`` must
-    keep every row increasing) and enter the decoder's training-mode BatchNorm statistics.  The counts are not read back."""
+    keep every row increasing) and enter the decoder's training-mode BatchNorm statistics.  The counts are not read back.
+    ``compact=True`` (needs ``n_obs``): the padded frames are taken out in front of the decoder (vae_ops.frame_index, gather_frames).
+    The states are integrated over the whole padded grid as before, the decoder runs on the L P observed frames only, so its
+    BatchNorm batch and running statistics are over observed frames, and the loss stage reads compact logits
+    (gpode_sigmoid_loglik_fwd_pk, gpode_elbo_all_fwd; backward: gpode_elbo_all_bwd and gpode_sigmoid_loglik_bwd_pk).  What the padded
+    columns of ``ts`` and the padded target frames hold then reaches no result.  The index needs the counts on the host: ``counts`` (a
+    host sequence) if the caller has them, else ``n_obs`` is read back once per call (one synchronisation).  One loss route, from the
+    logits: refused under GPODE_UNFUSED_LOSS=1, for a non-Bernoulli decoder, and with several ranks."""
     from .. import vae_ops as V
-    field = model.flow.odefunc.diffeq
     grid = {} if ts is None else {'ts': ts}
+    if compact:
+        return _compact_loss(model, data, L, grid, n_obs, counts)
+    field = model.flow.odefunc.diffeq
     if _FUSED_LOSS and hasattr(field, 'us_packed') and model.vae.decoder.distribution == 'bernoulli':
         # the decoder stops at its logits; sigmoid + likelihood row sums are one pass over them, and the three KL / mean / loss
         # launches one more (gpode_sigmoid_loglik_fwd, gpode_elbo_all_fwd)

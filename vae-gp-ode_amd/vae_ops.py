@@ -887,10 +887,126 @@ def _ll_len_args(ll):
     return '_len', (_ptr(n_obs), T, X.numel() // (X.shape[0] * T))
 
 
-def sigmoid_loglik_parts(X, logits, rows, n_obs=None):
+# ---- ragged minibatches, compact route: the padded frames are taken out in front of the decoder (include/gpode.h) ------------------------
+class FrameIndex:
+    """The observed frames of a ragged minibatch (N sequences padded to T frames), see frame_index()."""
+    __slots__ = ('off', 'src', 'P', 'N', 'T', 'counts')
+
+    def __init__(self, off, src, P, N, T, counts):
+        self.off, self.src, self.P, self.N, self.T, self.counts = off, src, P, N, T, counts
+
+
+def frame_index(n_obs, T, counts=None):
+    """-> FrameIndex of a ragged minibatch: c[n] = clamp(n_obs[n], 0, T); ``off`` (N+1,) int32 on the device, the exclusive prefix sum
+    of c with off[N] = P; ``src`` (P,) int32 on the device, src[j] = n T + t for compact image j = off[n] + t; ``P``, ``N``, ``T`` and the
+    host ``counts`` c.  The compact batch of L draws is (L P, ...), ordered (l, n, t).
+    The index needs the counts on the HOST: the decoder's launch sizes depend on P.  ``counts`` (a host sequence of N integers): nothing
+    is read back.  Otherwise ``n_obs`` (N,) int32 on the device is read back once -- 4 N bytes and ONE SYNCHRONISATION per step, which a
+    caller that has the counts on the host anyway avoids by passing them.  The index itself goes to the device in one copy.
+    Refused under stream capture (the read-back and the copy cannot be captured, and a captured step would have P baked in) and when
+    no frame of the minibatch is observed."""
+    T = int(T)
+    on_device = torch.is_tensor(n_obs) and n_obs.is_cuda
+    if (on_device or (n_obs is None and torch.cuda.is_available())) and torch.cuda.is_current_stream_capturing():
+        raise _lib.GpodeError('frame_index: the frame index cannot be built under stream capture (its size P sets the launch sizes of the '
+                              'decoder); build it ahead of the capture, or run the step eagerly')
+    if counts is None:
+        if not (torch.is_tensor(n_obs) and n_obs.dim() == 1):
+            raise _lib.GpodeError('frame_index: n_obs must be an (N,) integer tensor, or pass counts=')
+        counts = n_obs.detach().cpu().tolist()       # the read-back: 4 N bytes, one synchronisation
+    c = torch.as_tensor([int(k) for k in counts], dtype=torch.int64).reshape(-1).clamp_(0, T)
+    N = c.numel()
+    if torch.is_tensor(n_obs) and tuple(n_obs.shape) != (N,):
+        raise _lib.GpodeError('frame_index: %d counts for n_obs of shape %s' % (N, tuple(n_obs.shape)))
+    off = torch.zeros(N + 1, dtype=torch.int64)
+    torch.cumsum(c, 0, out=off[1:])
+    P = int(off[N])
+    if P == 0:
+        raise _lib.GpodeError('frame_index: no observed frame in the minibatch (every count is <= 0)')
+    seq = torch.repeat_interleave(torch.arange(N), c)
+    src = seq * T + (torch.arange(P) - off[:-1][seq])
+    device = n_obs.device if torch.is_tensor(n_obs) else torch.device('cuda' if torch.cuda.is_available() else 'cpu')
+    both = torch.cat((off, src)).to(torch.int32).to(device)
+    return FrameIndex(both[:N + 1], both[N + 1:], P, N, T, c.tolist())
+
+
+class _GatherFrames(torch.autograd.Function):
+    """ztL (L,N,T,ld) -> the first q columns of the observed rows, (L P, q) ordered (l, n, t) (gpode_gather_frames_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, zt, index, q):
+        zt = _chk(zt, 'ztL')
+        if zt.dim() != 4 or tuple(zt.shape[1:3]) != (index.N, index.T):
+            raise _lib.GpodeError('gather_frames: ztL must be (L,N,T,ld) = (L,%d,%d,ld), got %s' % (index.N, index.T, tuple(zt.shape)))
+        L, N, T, ld = zt.shape
+        out = _new((L * index.P, q), zt)
+        _lib.call('gpode_gather_frames_fwd', _ptr(zt), ld, q, _ptr(index.src), L, N, T, index.P, _ptr(out), _stream())
+        ctx.index, ctx.dims = index, (L, N, T, ld, q)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        index, (L, N, T, ld, q) = ctx.index, ctx.dims
+        gzt = _new((L, N, T, ld), gout)
+        _lib.call('gpode_gather_frames_bwd', _ptr(gout.contiguous()), ld, q, _ptr(index.src), _ptr(index.off), L, N, T, index.P, _ptr(gzt),
+                  _stream())
+        return gzt, None, None
+
+
+def gather_frames(ztL, index, q):
+    """The latent states of the observed frames only: ztL (L,N,T,order*q) -> (L P, q), the first ``q`` columns (the positions of a
+    second-order model) of the rows ``index`` (frame_index) lists, ordered (l, n, t).  The backward writes every element of the
+    gradient of ztL: zero on padded rows and on the columns >= q."""
+    return _GatherFrames.apply(ztL, index, int(q))
+
+
+class _SigmoidLogLikPartsPk(torch.autograd.Function):
+    """_SigmoidLogLikParts over COMPACT logits (L P, ...): the observed frames only, in the order of ``index`` (gpode_sigmoid_loglik_fwd_pk
+    / _bwd_pk).  Rows are (draw, sequence) as ever; the padded target frames of X are never addressed."""
+
+    @staticmethod
+    def forward(ctx, X, a, rows, index):
+        X, a = _chk(X, 'X'), _chk(a, 'logits')
+        N, T, P = index.N, index.T, index.P
+        if X.dim() < 2 or tuple(X.shape[:2]) != (N, T) or rows % N != 0:
+            raise _lib.GpodeError('sigmoid_loglik_parts: X must be (N,T,...) = (%d,%d,...) and rows a multiple of N; got %s, rows %d'
+                                  % (N, T, tuple(X.shape), rows))
+        frame, L = X.numel() // (N * T), rows // N
+        if a.numel() != L * P * frame:
+            raise _lib.GpodeError('sigmoid_loglik_parts: %d compact logits expected (L P frame = %d x %d x %d), got %d'
+                                  % (L * P * frame, L, P, frame, a.numel()))
+        ns = _lib.load().gpode_sigmoid_loglik_splits(rows, T * frame)
+        z, part = torch.empty_like(a), _new((rows, ns), a)
+        _lib.call('gpode_sigmoid_loglik_fwd_pk', _ptr(X), _ptr(a), _ptr(z), _ptr(part), rows, _ptr(index.off), T, frame, X.numel(), ns,
+                  _stream())
+        ctx.save_for_backward(X, z)
+        ctx.index, ctx.dims = index, (rows, frame)
+        ctx.mark_non_differentiable(z)
+        ctx.set_materialize_grads(False)
+        return part, z                               # no _gpode_ll: elbo_all() then runs gpode_elbo_all_bwd, and the logits' gradient is
+                                                     # one launch of its own below
+
+    @staticmethod
+    def backward(ctx, gpart, _gz):
+        X, z = ctx.saved_tensors
+        index, (rows, frame) = ctx.index, ctx.dims
+        grow = gpart[:, 0].contiguous() if gpart.shape[1] > 1 else gpart.contiguous()
+        ga = torch.empty_like(z)
+        _lib.call('gpode_sigmoid_loglik_bwd_pk', _ptr(X), _ptr(z), _ptr(grow), _ptr(ga), rows, _ptr(index.src), index.P, index.T, frame,
+                  X.numel(), _stream())
+        return None, ga, None, None
+
+
+def sigmoid_loglik_parts(X, logits, rows, n_obs=None, *, index=None):
     """-> (partial row sums (rows, nsplit) of the Bernoulli log-likelihood, z = sigmoid(logits)).  ``n_obs`` (N,) int32: the frame
     count of every sequence of a ragged (padded) minibatch X (N,T,...) -- the sums take the frames t < n_obs[n] only and the padded
-    logits get a zero gradient; None: every frame, the launches as they always were."""
+    logits get a zero gradient; None: every frame, the launches as they always were.
+    ``index`` (frame_index; not together with ``n_obs``): ``logits`` are COMPACT, (L P, ...) for the observed frames only, ordered
+    (l, n, t) -- z and the logit gradients are compact as well, rows stay (draw, sequence)."""
+    if index is not None:
+        if n_obs is not None:
+            raise _lib.GpodeError('sigmoid_loglik_parts: n_obs (padded logits, masked) and index (compact logits) exclude each other')
+        return _SigmoidLogLikPartsPk.apply(X, logits, rows, index)
     if n_obs is None:
         return _SigmoidLogLikParts.apply(X, logits, rows)
     return _SigmoidLogLikPartsLen.apply(X, logits, rows, n_obs)
