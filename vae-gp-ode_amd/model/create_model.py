@@ -32,8 +32,8 @@ def elbo(model, X, Xrec, s0_mu, s0_logv, v0_mu, v0_logv, L):
     return lhood.mean(), kl_reg.mean(), model.flow.kl()
 
 
-def _compact_loss(model, data, L, grid, n_obs, counts):
-    """compute_loss(compact=True): decode and score the observed frames only"""
+def _compact_index(model, data, n_obs, counts):
+    """compute_loss(compact=True): its refusals, then the index of the observed frames (vae_ops.frame_index)"""
     from .. import vae_ops as V
     if n_obs is None:
         raise ValueError('compute_loss: compact=True needs n_obs, the frame count of every sequence of the padded minibatch')
@@ -46,10 +46,7 @@ def _compact_loss(model, data, L, grid, n_obs, counts):
     if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
         raise ValueError('compute_loss: compact=True on several ranks is not built: the cross-rank BatchNorm (parallel.count_all) takes a '
                          "rank's image count to be proportional to its share of the sequences, which taking the padding out breaks")
-    index = V.frame_index(n_obs, data.shape[1], counts=counts)
-    logits, (s0_mu, s0_logv), (v0_mu, v0_logv) = model(data, L, logits=True, obs_index=index, **grid)
-    lpart, _ = V.sigmoid_loglik_parts(data, logits, L * data.shape[0], index=index)
-    return V.elbo_all(lpart, s0_mu, s0_logv, v0_mu, v0_logv, field.Um.optvar, field.us_packed(), field.M, model.num_observations)
+    return V.frame_index(n_obs, data.shape[1], counts=counts)
 
 
 def compute_loss(model, data, L, ts=None, n_obs=None, compact=False, counts=None):
@@ -71,17 +68,16 @@ def compute_loss(model, data, L, ts=None, n_obs=None, compact=False, counts=None
     logits: refused under GPODE_UNFUSED_LOSS=1, for a non-Bernoulli decoder, and with several ranks."""
     from .. import vae_ops as V
     grid = {} if ts is None else {'ts': ts}
-    if compact:
-        return _compact_loss(model, data, L, grid, n_obs, counts)
+    index = None
+    if compact:                                      # the index stands for the counts from here on
+        index, n_obs = _compact_index(model, data, n_obs, counts), None
+        grid['obs_index'] = index
     field = model.flow.odefunc.diffeq
-    if _FUSED_LOSS and hasattr(field, 'us_packed') and model.vae.decoder.distribution == 'bernoulli':
+    if compact or (_FUSED_LOSS and hasattr(field, 'us_packed') and model.vae.decoder.distribution == 'bernoulli'):
         # the decoder stops at its logits; sigmoid + likelihood row sums are one pass over them, and the three KL / mean / loss
         # launches one more (gpode_sigmoid_loglik_fwd, gpode_elbo_all_fwd)
         logits, (s0_mu, s0_logv), (v0_mu, v0_logv) = model(data, L, logits=True, **grid)
-        if n_obs is None:
-            lpart, _ = V.sigmoid_loglik_parts(data, logits, L * data.shape[0])
-        else:
-            lpart, _ = V.sigmoid_loglik_parts(data, logits, L * data.shape[0], n_obs)
+        lpart, _ = V.sigmoid_loglik_parts(data, logits, L * data.shape[0], n_obs, index=index)
         return V.elbo_all(lpart, s0_mu, s0_logv, v0_mu, v0_logv, field.Um.optvar, field.us_packed(), field.M, model.num_observations)
     Xrec, (s0_mu, s0_logv), (v0_mu, v0_logv) = model(data, L, **grid)
     kl_rows = model.vae.encoder.kl_rows(s0_mu, s0_logv, v0_mu, v0_logv)               # (N,)

@@ -9,8 +9,40 @@ from . import _lib, ops
 from .ops import _chk, _ptr, _stream
 
 
+# ---- what rides on tensors and modules --------------------------------------------------------------------------------------------
+# Six attributes carry a by-product from the function that has it to the one that would otherwise launch for it.  None is a
+# contract with callers; each has one writer and one reader.
+#   _gpode_chansum  on an input gradient: its per-channel sums.  Set by every BatchNorm backward (_BatchNormTrain, _BatchNormTrainPair,
+#                   _BnReluConvT); taken by the convolution backward that receives the gradient (_fused_chansum) as its bias
+#                   gradient.  The taker DELETES it: the sums go on to autograd, which clones a gradient that has a second owner -- a
+#                   read, and none may happen before the deferred reductions have run (set_deferred_reductions).
+#   _gpode_bnstats  on a convolution output: (module, mean, invstd, table) of the BatchNorm behind it.  Set by _convT_fwd_stats;
+#                   read (not deleted: the fallback of bn_relu_conv_transpose2d looks too) by the _BnReluConvT that consumes the
+#                   output for that very module.  Lives as long as the activation.
+#   _gpode_ll       on the partial sums of sigmoid_loglik_parts: (X, z, route).  Set by _SigmoidLogLikParts.forward; read by
+#                   elbo_all(), which decides there whether its backward also produces the logit gradients.  Lives with the sums.
+#   _gpode_ga       on the row gradient the ELBO backward returns: the logit gradients it produced in the same launch.  Set in
+#                   _elbo_all_bwd; read by _SigmoidLogLikParts.backward, which then launches nothing.  Dies with the row gradient at
+#                   the end of that backward; nobody else may keep the row gradient.
+#   _gpode_klpart   on the encoder's packed (mu | logvar) rows: the KL partial sums of _ReparamKL.  Set by reparam(); read by
+#                   elbo_all().  Replaced by the next reparam() on the same rows; lives with them.
+#   _gpode_slot     on an nn.BatchNorm2d: its slot (0..63) in the library's statistics hand-over.  Set once by _stats_slot; never
+#                   deleted.
+# A new by-product follows _fused_chansum: hand the tensor over with no second owner before the deferred reductions have run.
+
+
 def _new(shape, like):
     return torch.empty(shape, dtype=torch.float32, device=like.device)
+
+
+def _bchw(x):
+    """(images, channels, elements per channel image) of x (B,C,...)"""
+    return x.shape[0], x.shape[1], x[0, 0].numel()
+
+
+def _convT_out(Hi, Wi, K, stride, pad, out_pad):
+    """output size of a transposed convolution"""
+    return (Hi - 1) * stride - 2 * pad + K + out_pad, (Wi - 1) * stride - 2 * pad + K + out_pad
 
 
 def _scratch(n, like):
@@ -77,14 +109,19 @@ def set_bn_sync(group):
     _bn_sync = group
 
 
-def _bn_global_stats(x, gamma, beta, running_mean, running_var, nbt, momentum, eps, scratch):
-    """Forward half of the cross-rank BatchNorm: local moments -> all-gather -> rank-ordered combination.
-    Returns (mean, invstd, table[C][4])."""
-    B, C = x.shape[0], x.shape[1]
-    HW = x[0, 0].numel()
+# The cross-rank BatchNorm in its halves: what a rank computes before the all-gather and what it does with the gathered rows.
+# _bn_global_stats / _bn_global_bwd put one gather between them; _BatchNormTrainPair puts ONE between the halves of two layers.
+def _bn_moments(x):
+    """the local moments of x, (2C + 1,): what the ranks exchange in the forward pass"""
+    B, C, HW = _bchw(x)
     mom = _new((2 * C + 1,), x)
-    _lib.call('gpode_bn_moments', _ptr(x), _ptr(mom), B, C, HW, _ptr(scratch), _stream())
-    gathered = _bn_sync.gather(mom)
+    _lib.call('gpode_bn_moments', _ptr(x), _ptr(mom), B, C, HW, _ptr(_bn_scratch(B, C, x)), _stream())
+    return mom
+
+
+def _bn_finalize(gathered, x, gamma, beta, running_mean, running_var, nbt, momentum, eps):
+    """rank-ordered combination of the gathered moments.  Returns (mean, invstd, table[C][4])."""
+    C = x.shape[1]
     mean, invstd, table = _new((C,), x), _new((C,), x), _new((C, 4), x)
     _lib.call('gpode_bn_finalize', _ptr(gathered), _bn_sync.world, _ptr(_chk(gamma, 'gamma')), _ptr(_chk(beta, 'beta')), _ptr(mean),
               _ptr(invstd), _ptr(running_mean), _ptr(running_var), _ptr(nbt), ctypes.c_float(momentum), ctypes.c_float(eps), _ptr(table), C,
@@ -92,20 +129,52 @@ def _bn_global_stats(x, gamma, beta, running_mean, running_var, nbt, momentum, e
     return mean, invstd, table
 
 
-def _bn_global_bwd(sync, x, gy, gamma, beta, mean, invstd, relu):
-    """Backward half: local sums -> all-gather -> gx with the global centring terms.  Returns (gx, ggamma, gbeta, chansum)."""
-    B, C = x.shape[0], x.shape[1]
-    HW = x[0, 0].numel()
-    scratch = _bn_scratch(B, C, x)
-    sums = _new((2 * C,), x)
-    gy = gy.contiguous()
+def _bn_apply(x, table, relu):
+    B, C, HW = _bchw(x)
+    y = _new(x.shape, x)
+    _lib.call('gpode_bn_apply', _ptr(x), _ptr(table), _ptr(y), B, C, HW, int(relu), _stream())
+    return y
+
+
+def _bn_global_stats(x, gamma, beta, running_mean, running_var, nbt, momentum, eps):
+    """Forward half of the cross-rank BatchNorm: local moments -> all-gather -> rank-ordered combination."""
+    return _bn_finalize(_bn_sync.gather(_bn_moments(x)), x, gamma, beta, running_mean, running_var, nbt, momentum, eps)
+
+
+def _bn_bwd_sums(x, gy, gamma, beta, mean, invstd, relu):
+    """the local sums of the backward pass, (2C,): what the ranks exchange.  Returns (sums, gy as the kernels read it, scratch)."""
+    B, C, HW = _bchw(x)
+    scratch, sums, gy = _bn_scratch(B, C, x), _new((2 * C,), x), gy.contiguous()
     _lib.call('gpode_bn_bwd_sums', _ptr(x), _ptr(gy), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd), _ptr(sums), B, C, HW, int(relu),
               _ptr(scratch), _stream())
-    gathered = sync.gather(sums)
+    return sums, gy, scratch
+
+
+def _bn_bwd_apply(sync, gathered, scratch, x, gy, gamma, beta, mean, invstd, relu):
+    """gx with the global centring terms from the gathered sums.  Returns (gx, ggamma, gbeta, chansum)."""
+    B, C, HW = _bchw(x)
     gx, gg, gb, cs = _new(x.shape, x), _new((C,), x), _new((C,), x), _new((C,), x)
     _bwd_call('gpode_bn_bwd_apply', _ptr(x), _ptr(gy), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd), _ptr(gathered),
               _ptr(sync.weights(x.device)), sync.world, ctypes.c_float(sync.count_all(B * HW)), _ptr(gx), _ptr(gg), _ptr(gb), _ptr(cs),
               B, C, HW, int(relu), _ptr(scratch), _stream(), keep=(scratch,))
+    return gx, gg, gb, cs
+
+
+def _bn_global_bwd(sync, x, gy, gamma, beta, mean, invstd, relu):
+    """Backward half: local sums -> all-gather -> gx with the global centring terms."""
+    sums, gy, scratch = _bn_bwd_sums(x, gy, gamma, beta, mean, invstd, relu)
+    return _bn_bwd_apply(sync, sync.gather(sums), scratch, x, gy, gamma, beta, mean, invstd, relu)
+
+
+def _bn_bwd(sync, x, gy, gamma, beta, mean, invstd, relu):
+    """BatchNorm (+ ReLU) backward on the statistics of this process (``sync`` None) or of all ranks: (gx, ggamma, gbeta, chansum)."""
+    if sync is not None:
+        return _bn_global_bwd(sync, x, gy, gamma, beta, mean, invstd, relu)
+    B, C, HW = _bchw(x)
+    gx, gg, gb, cs = _new(x.shape, x), _new((C,), x), _new((C,), x), _new((C,), x)
+    bs = _bn_scratch(B, C, x)
+    _bwd_call('gpode_bn_bwd', _ptr(x), _ptr(gy.contiguous()), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd), _ptr(gx), _ptr(gg),
+              _ptr(gb), _ptr(cs), B, C, HW, relu, _ptr(bs), _stream(), keep=(bs,))
     return gx, gg, gb, cs
 
 
@@ -130,53 +199,30 @@ class _BatchNormTrainPair(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x1, g1, b1, rm1, rv1, nbt1, x2, g2, b2, rm2, rv2, nbt2, momentum, eps, relu):
-        sync = _bn_sync
-        xs, moms = (_chk(x1, 'x1'), _chk(x2, 'x2')), []
-        for x in xs:
-            B, C, HW = x.shape[0], x.shape[1], x[0, 0].numel()
-            mom = _new((2 * C + 1,), x)
-            _lib.call('gpode_bn_moments', _ptr(x), _ptr(mom), B, C, HW, _ptr(_bn_scratch(B, C, x)), _stream())
-            moms.append(mom)
-        gathered = sync.gather_many(moms)
+        xs = (_chk(x1, 'x1'), _chk(x2, 'x2'))
+        gathered = _bn_sync.gather_many([_bn_moments(x) for x in xs])
         ys, saved = [], []
         for x, gam, bet, rm, rv, nbt, got in zip(xs, (g1, g2), (b1, b2), (rm1, rm2), (rv1, rv2), (nbt1, nbt2), gathered):
-            B, C, HW = x.shape[0], x.shape[1], x[0, 0].numel()
-            mean, invstd, table, y = _new((C,), x), _new((C,), x), _new((C, 4), x), _new(x.shape, x)
-            _lib.call('gpode_bn_finalize', _ptr(got), sync.world, _ptr(_chk(gam, 'gamma')), _ptr(_chk(bet, 'beta')), _ptr(mean), _ptr(invstd),
-                      _ptr(rm), _ptr(rv), _ptr(nbt), ctypes.c_float(momentum), ctypes.c_float(eps), _ptr(table), C, _stream())
-            _lib.call('gpode_bn_apply', _ptr(x), _ptr(table), _ptr(y), B, C, HW, int(relu), _stream())
-            ys.append(y)
+            mean, invstd, table = _bn_finalize(got, x, gam, bet, rm, rv, nbt, momentum, eps)
+            ys.append(_bn_apply(x, table, relu))
             saved += [x, gam, bet, mean, invstd]
         ctx.save_for_backward(*saved)
-        ctx.sync, ctx.relu = sync, int(relu)
+        ctx.sync, ctx.relu = _bn_sync, int(relu)
         return ys[0], ys[1]
 
     @staticmethod
     def backward(ctx, gy1, gy2):
         sv, sync = ctx.saved_tensors, ctx.sync
-        packs, sums, scr = [], [], []
-        for i, gy in enumerate((gy1, gy2)):
-            x, gam, bet, mean, invstd = sv[5 * i:5 * i + 5]
-            B, C, HW = x.shape[0], x.shape[1], x[0, 0].numel()
-            gy = gy.contiguous()
-            scratch, s = _bn_scratch(B, C, x), _new((2 * C,), x)
-            _lib.call('gpode_bn_bwd_sums', _ptr(x), _ptr(gy), _ptr(gam), _ptr(bet), _ptr(mean), _ptr(invstd), _ptr(s), B, C, HW, ctx.relu,
-                      _ptr(scratch), _stream())
-            packs.append((x, gy, gam, bet, mean, invstd))
-            sums.append(s)
-            scr.append(scratch)
-        gathered = sync.gather_many(sums)
+        # per layer (x, gy, gamma, beta, mean, invstd, relu), as the halves take them; both sums, one gather, both applies
+        layers = [(x, gy, *rest, ctx.relu) for (x, *rest), gy in zip((sv[:5], sv[5:]), (gy1, gy2))]
+        sums = [_bn_bwd_sums(*layer) for layer in layers]
+        gathered = sync.gather_many([s for s, _, _ in sums])
         out = []
-        for (x, gy, gam, bet, mean, invstd), got, scratch in zip(packs, gathered, scr):
-            B, C, HW = x.shape[0], x.shape[1], x[0, 0].numel()
-            gx, gg, gb, cs = _new(x.shape, x), _new((C,), x), _new((C,), x), _new((C,), x)
-            _bwd_call('gpode_bn_bwd_apply', _ptr(x), _ptr(gy), _ptr(gam), _ptr(bet), _ptr(mean), _ptr(invstd), _ptr(got),
-                      _ptr(sync.weights(x.device)), sync.world, ctypes.c_float(sync.count_all(B * HW)), _ptr(gx), _ptr(gg), _ptr(gb), _ptr(cs),
-                      B, C, HW, ctx.relu, _ptr(scratch), _stream(), keep=(scratch,))
+        for (x, _, *rest), (_, gy, scratch), got in zip(layers, sums, gathered):
+            gx, gg, gb, cs = _bn_bwd_apply(sync, got, scratch, x, gy, *rest)
             gx._gpode_chansum = cs
-            out.append((gx, gg, gb))
-        (gx1, gg1, gb1), (gx2, gg2, gb2) = out
-        return gx1, gg1, gb1, None, None, None, gx2, gg2, gb2, None, None, None, None, None, None
+            out += [gx, gg, gb, None, None, None]
+        return (*out, None, None, None)
 
 
 def batch_norm_train_pair(x1, bn1, x2, bn2, relu):
@@ -333,7 +379,7 @@ class _ConvT2d(torch.autograd.Function):
         x, w = _chk(x, 'x'), _chk(w, 'weight')
         B, Cin, Hi, Wi = x.shape
         _, Cout, K, _ = w.shape
-        Ht, Wt = (Hi - 1) * stride - 2 * pad + K + out_pad, (Wi - 1) * stride - 2 * pad + K + out_pad
+        Ht, Wt = _convT_out(Hi, Wi, K, stride, pad, out_pad)
         y = _new((B, Cout, Ht, Wt), x)
         # conv geometry: "input" (B,Ci=Cout,H=Ht,W=Wt), "output" (B,Co=Cin,Ho=Hi,Wo=Wi)
         if _can_fuse_stats(stats_for, x, Cin, Cout, K, stride, pad, Hi):
@@ -378,12 +424,12 @@ class _BnReluConvT(torch.autograd.Function):
         c, w = _chk(c, 'c'), _chk(w, 'weight')
         B, Cin, Hi, Wi = c.shape
         _, Cout, K, _ = w.shape
-        Ht, Wt = (Hi - 1) * stride - 2 * pad + K + out_pad, (Wi - 1) * stride - 2 * pad + K + out_pad
+        Ht, Wt = _convT_out(Hi, Wi, K, stride, pad, out_pad)
         ctx.sync = _bn_sync
         if pre is not None and pre[0] is bn and bn is not None and _bn_sync is None:
             _, mean, invstd, table = pre
         elif _bn_sync is not None:
-            mean, invstd, table = _bn_global_stats(c, gamma, beta, running_mean, running_var, nbt, momentum, eps, _bn_scratch(B, Cin, c))
+            mean, invstd, table = _bn_global_stats(c, gamma, beta, running_mean, running_var, nbt, momentum, eps)
         else:
             mean, invstd, table = _new((Cin,), c), _new((Cin,), c), _new((Cin, 4), c)
             _lib.call('gpode_bn_stats', _ptr(c), _ptr(_chk(gamma, 'gamma')), _ptr(_chk(beta, 'beta')), _ptr(mean), _ptr(invstd),
@@ -406,44 +452,30 @@ class _BnReluConvT(torch.autograd.Function):
         gy = gy.contiguous()
         gw = gb = None
         last_stage = _dec10_fused and (Cout, Cin, K, S, P, Hi, Wi, Ht, Wt) == (1, 16, 5, 1, 2, 28, 28, 28, 28)
+        # the last stage's weight gradient rides in its BatchNorm sums pass below, and a bias gradient nobody has summed yet with it
         gw_rides = last_stage and ctx.needs_input_grad[8] and c.data_ptr() % 16 == 0
         if ctx.needs_input_grad[8]:
             gw = _new(w.shape, c)
-            if not gw_rides:                         # (the last stage's weight gradient rides in its BatchNorm sums pass below)
+            if not gw_rides:
                 ws = _wgrad_scratch(B, Cout, Cin, K, c)
                 _bwd_call('gpode_conv2d_bwd_weight_bn', _ptr(gy), _ptr(c), _ptr(table), _ptr(gw), _ptr(None),
                           _ptr(ws), B, Cout, Ht, Wt, Cin, K, S, P, Hi, Wi, _stream(), keep=(ws,))
-            if has_b:
-                gb = _fused_chansum(gy, Cout)
-                if gb is None:
-                    gb = _new((Cout,), c)
-                    if not gw_rides:                 # (with the weight gradient, the bias gradient rides in the sums pass too)
-                        bs = _bn_scratch(B, Cout, c)
-                        _bwd_call('gpode_chan_sum', _ptr(gy), _ptr(gb), B, Cout, Ht * Wt, _ptr(bs), _stream(), keep=(bs,))
-                        gb_rides = None
-                    else:
-                        gb_rides = gb
-                else:
-                    gb_rides = None
-            else:
-                gb_rides = None
-        else:
-            gb_rides = None
+            gb = _fused_chansum(gy, Cout) if has_b else None
+        to_sum = has_b and gw is not None and gb is None
+        if to_sum:
+            gb = _new((Cout,), c)
+            if not gw_rides:
+                bs = _bn_scratch(B, Cout, c)
+                _bwd_call('gpode_chan_sum', _ptr(gy), _ptr(gb), B, Cout, Ht * Wt, _ptr(bs), _stream(), keep=(bs,))
+        gb_rides = gb if (to_sum and gw_rides) else None
         if last_stage:
             # the decoder's last stage: the gradient w.r.t. the normalised activation is recomputed inside both BatchNorm passes
             gc, gg, gbeta, cs = _dec10_bn_bwd(ctx.sync, c, gy, w, gamma, beta, mean, invstd, gw=gw if gw_rides else None, gbias=gb_rides)
-            gc._gpode_chansum = cs
-            return gc, gg, gbeta, None, None, None, None, None, gw, gb, None, None, None, None, None
-        # gradient w.r.t. the (never materialised) normalised activation, then through the BatchNorm to c
-        ga = _new(c.shape, c)
-        _lib.call('gpode_conv2d_fwd', _ptr(gy), _ptr(w), _ptr(None), _ptr(ga), B, Cout, Ht, Wt, Cin, K, S, P, Hi, Wi, _stream())
-        if ctx.sync is not None:
-            gc, gg, gbeta, cs = _bn_global_bwd(ctx.sync, c, ga, gamma, beta, mean, invstd, 1)
         else:
-            gc, gg, gbeta, cs = _new(c.shape, c), _new((Cin,), c), _new((Cin,), c), _new((Cin,), c)
-            bs = _bn_scratch(B, Cin, c)
-            _bwd_call('gpode_bn_bwd', _ptr(c), _ptr(ga), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd), _ptr(gc), _ptr(gg), _ptr(gbeta),
-                      _ptr(cs), B, Cin, Hi * Wi, 1, _ptr(bs), _stream(), keep=(bs,))
+            # gradient w.r.t. the (never materialised) normalised activation, then through the BatchNorm to c
+            ga = _new(c.shape, c)
+            _lib.call('gpode_conv2d_fwd', _ptr(gy), _ptr(w), _ptr(None), _ptr(ga), B, Cout, Ht, Wt, Cin, K, S, P, Hi, Wi, _stream())
+            gc, gg, gbeta, cs = _bn_bwd(ctx.sync, c, ga, gamma, beta, mean, invstd, 1)
         gc._gpode_chansum = cs
         return gc, gg, gbeta, None, None, None, None, None, gw, gb, None, None, None, None, None
 
@@ -452,17 +484,15 @@ class _BatchNormTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps, relu, nbt=None):
         x = _chk(x, 'x')
-        B, C = x.shape[0], x.shape[1]
-        HW = x[0, 0].numel()
-        y = _new(x.shape, x)
-        mean, invstd = _new((C,), x), _new((C,), x)
+        B, C, HW = _bchw(x)
         if nbt is not None and not (nbt.is_cuda and nbt.dtype == torch.int64):
             raise _lib.GpodeError('num_batches_tracked must be an int64 CUDA/HIP scalar')
         ctx.sync = _bn_sync
         if _bn_sync is not None:
-            mean, invstd, table = _bn_global_stats(x, gamma, beta, running_mean, running_var, nbt, momentum, eps, _bn_scratch(B, C, x))
-            _lib.call('gpode_bn_apply', _ptr(x), _ptr(table), _ptr(y), B, C, HW, int(relu), _stream())
+            mean, invstd, table = _bn_global_stats(x, gamma, beta, running_mean, running_var, nbt, momentum, eps)
+            y = _bn_apply(x, table, relu)
         else:
+            y, mean, invstd = _new(x.shape, x), _new((C,), x), _new((C,), x)
             _lib.call('gpode_bn_fwd', _ptr(x), _ptr(_chk(gamma, 'gamma')), _ptr(_chk(beta, 'beta')), _ptr(y), _ptr(mean), _ptr(invstd),
                       _ptr(running_mean), _ptr(running_var), _ptr(nbt), ctypes.c_float(momentum), ctypes.c_float(eps), B, C, HW, int(relu),
                       _ptr(_bn_scratch(B, C, x)), _stream())
@@ -473,15 +503,7 @@ class _BatchNormTrain(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, gamma, beta, mean, invstd = ctx.saved_tensors
-        B, C = x.shape[0], x.shape[1]
-        HW = x[0, 0].numel()
-        if ctx.sync is not None:
-            gx, gg, gb, cs = _bn_global_bwd(ctx.sync, x, gy, gamma, beta, mean, invstd, ctx.relu)
-        else:
-            gx, gg, gb, cs = _new(x.shape, x), _new((C,), x), _new((C,), x), _new((C,), x)
-            bs = _bn_scratch(B, C, x)
-            _bwd_call('gpode_bn_bwd', _ptr(x), _ptr(gy.contiguous()), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd), _ptr(gx), _ptr(gg),
-                      _ptr(gb), _ptr(cs), B, C, HW, ctx.relu, _ptr(bs), _stream(), keep=(bs,))
+        gx, gg, gb, cs = _bn_bwd(ctx.sync, x, gy, gamma, beta, mean, invstd, ctx.relu)
         # the channel sums of gx ride along with it: the convolution that produced x needs exactly these as its bias gradient
         gx._gpode_chansum = cs
         return gx, gg, gb, None, None, None, None, None, None
@@ -493,8 +515,7 @@ class _BatchNormEval(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, eps, relu):
         x = _chk(x, 'x')
-        B, C = x.shape[0], x.shape[1]
-        HW = x[0, 0].numel()
+        B, C, HW = _bchw(x)
         y = _new(x.shape, x)
         _lib.call('gpode_bn_eval', _ptr(x), _ptr(None), _ptr(_chk(gamma, 'gamma')), _ptr(_chk(beta, 'beta')), _ptr(running_mean),
                   _ptr(running_var), ctypes.c_float(eps), _ptr(y), B, C, HW, int(relu), _stream())
@@ -507,8 +528,7 @@ class _BatchNormEval(torch.autograd.Function):
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             raise _lib.GpodeError('eval-mode BatchNorm is built for frozen layers (main.py:160-161 sets requires_grad=False)')
         x, gamma, beta, rm, rv = ctx.saved_tensors
-        B, C = x.shape[0], x.shape[1]
-        HW = x[0, 0].numel()
+        B, C, HW = _bchw(x)
         gx = _new(x.shape, x)
         _lib.call('gpode_bn_eval', _ptr(x), _ptr(gy.contiguous()), _ptr(gamma), _ptr(beta), _ptr(rm), _ptr(rv), ctypes.c_float(ctx.eps),
                   _ptr(gx), B, C, HW, ctx.relu, _stream())
@@ -615,46 +635,64 @@ def _chk_n_obs(n_obs, X, who):
     return n_obs.contiguous(), T, X.numel() // (X.shape[0] * T)
 
 
+# ---- which frames of X (N,T,...) the loss stage scores: a route object per call -----------------------------------------------------
+# The library has one templated kernel per operation and an entry point per route (include/gpode.h: gpode_sigmoid_loglik_fwd, _fwd_len,
+# _fwd_pk, ...); a route says which, and with which arguments, so that every wrapper below is written once.  A route has
+#   suffix        of the entry points ('', '_len', '_pk');
+#   fused         whether the ELBO backward has a form that also produces the logit gradients on this route (elbo_all);
+#   bind(X, elements, rows, who)   its argument checks, run by the Function once X has passed _chk; -> the row length the partial sums
+#                 are split for (gpode_sigmoid_loglik_splits);
+#   fwd_dims / bwd_dims(X, rows, inner)   the header's arguments behind the four tensor pointers, up to and including nX;
+#   tail          the header's arguments in front of the stream (also of the fused ELBO backward);
+#   tensors       what a Function saves for its backward besides (X, z).
+# Every frame: _EVERY.  Padded logits masked by the frame counts: _Masked(n_obs).  Compact logits: a FrameIndex (below).
+class _EveryFrame:
+    suffix, fused, tail, tensors = '', True, (), ()
+
+    def bind(self, X, elements, rows, who):
+        return elements // rows
+
+    def fwd_dims(self, X, rows, inner):
+        return rows, inner, X.numel()
+
+    bwd_dims = fwd_dims
+
+
+_EVERY = _EveryFrame()
+
+
+class _Masked(_EveryFrame):
+    """the frames t < n_obs[n] of every sequence; the launches cover the padded frames too"""
+    suffix = '_len'
+
+    def __init__(self, n_obs):
+        self.n_obs = n_obs
+
+    def bind(self, X, elements, rows, who):
+        n_obs, T, frame = _chk_n_obs(self.n_obs, X, who)
+        self.tensors, self.tail = (n_obs,), (_ptr(n_obs), T, frame)
+        return elements // rows
+
+
 class _LogLikRowSum(torch.autograd.Function):
+    """row sums of the Bernoulli log-likelihood of X under z, over the frames of ``route`` (gpode_loglik_rowsum_fwd[_len] / _bwd[_len])"""
+
     @staticmethod
-    def forward(ctx, X, z, rows):
+    def forward(ctx, X, z, rows, route):
         X, z = _chk(X, 'X'), _chk(z, 'z')
-        inner = z.numel() // rows
+        inner = route.bind(X, z.numel(), rows, 'bernoulli_loglik_rowsum')
         out = _new((rows,), z)
-        _lib.call('gpode_loglik_rowsum_fwd', _ptr(X), _ptr(z), _ptr(out), rows, inner, X.numel(), _stream())
-        ctx.save_for_backward(X, z)
-        ctx.rows, ctx.inner = rows, inner
+        _lib.call('gpode_loglik_rowsum_fwd' + route.suffix, _ptr(X), _ptr(z), _ptr(out), *route.fwd_dims(X, rows, inner), *route.tail, _stream())
+        ctx.save_for_backward(X, z, *route.tensors)
+        ctx.rows, ctx.inner, ctx.route = rows, inner, route
         return out
 
     @staticmethod
     def backward(ctx, g):
-        X, z = ctx.saved_tensors
-        gz = _new(z.shape, z)
-        _lib.call('gpode_loglik_rowsum_bwd', _ptr(X), _ptr(z), _ptr(g.contiguous()), _ptr(gz), ctx.rows, ctx.inner, X.numel(), _stream())
-        return None, gz, None
-
-
-class _LogLikRowSumLen(torch.autograd.Function):
-    """_LogLikRowSum over the observed frames of a ragged minibatch (gpode_loglik_rowsum_fwd_len / _bwd_len)."""
-
-    @staticmethod
-    def forward(ctx, X, z, rows, n_obs):
-        X, z = _chk(X, 'X'), _chk(z, 'z')
-        n_obs, T, frame = _chk_n_obs(n_obs, X, 'bernoulli_loglik_rowsum')
-        inner = z.numel() // rows
-        out = _new((rows,), z)
-        _lib.call('gpode_loglik_rowsum_fwd_len', _ptr(X), _ptr(z), _ptr(out), rows, inner, X.numel(), _ptr(n_obs), T, frame, _stream())
-        ctx.save_for_backward(X, z, n_obs)
-        ctx.dims = (rows, inner, T, frame)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        X, z, n_obs = ctx.saved_tensors
-        rows, inner, T, frame = ctx.dims
-        gz = _new(z.shape, z)
-        _lib.call('gpode_loglik_rowsum_bwd_len', _ptr(X), _ptr(z), _ptr(g.contiguous()), _ptr(gz), rows, inner, X.numel(), _ptr(n_obs), T, frame,
-                  _stream())
+        X, z = ctx.saved_tensors[:2]
+        route, gz = ctx.route, _new(z.shape, z)
+        _lib.call('gpode_loglik_rowsum_bwd' + route.suffix, _ptr(X), _ptr(z), _ptr(g.contiguous()), _ptr(gz),
+                  *route.bwd_dims(X, ctx.rows, ctx.inner), *route.tail, _stream())
         return None, gz, None, None
 
 
@@ -766,33 +804,38 @@ class _Elbo(torch.autograd.Function):
 
 class _SigmoidLogLikParts(torch.autograd.Function):
     """Decoder logits -> partial row sums of the Bernoulli log-likelihood of X under sigmoid(logits) (gpode_sigmoid_loglik_fwd):
-    the decoder's nn.Sigmoid (vae.py:84) and the summed log_prob (vae.py:136-153, create_model.py:49) in one pass over the logits."""
+    the decoder's nn.Sigmoid (vae.py:84) and the summed log_prob (vae.py:136-153, create_model.py:49) in one pass over the logits.
+    ``route``: every frame; the observed frames of a ragged minibatch, z for every element but sums and logit gradients for the frames
+    t < n_obs[n] only (_fwd_len / _bwd_len); or COMPACT logits (L P, ...) in the order of a FrameIndex, rows (draw, sequence) as ever
+    and the padded target frames of X never addressed (_fwd_pk / _bwd_pk)."""
 
     @staticmethod
-    def forward(ctx, X, a, rows):
+    def forward(ctx, X, a, rows, route):
         X, a = _chk(X, 'X'), _chk(a, 'logits')
-        inner = a.numel() // rows
+        inner = route.bind(X, a.numel(), rows, 'sigmoid_loglik_parts')
         ns = _lib.load().gpode_sigmoid_loglik_splits(rows, inner)
         z, part = torch.empty_like(a), _new((rows, ns), a)
-        _lib.call('gpode_sigmoid_loglik_fwd', _ptr(X), _ptr(a), _ptr(z), _ptr(part), rows, inner, X.numel(), ns, _stream())
-        ctx.save_for_backward(X, z)
-        ctx.rows, ctx.inner = rows, inner
+        _lib.call('gpode_sigmoid_loglik_fwd' + route.suffix, _ptr(X), _ptr(a), _ptr(z), _ptr(part), *route.fwd_dims(X, rows, inner), ns,
+                  *route.tail, _stream())
+        ctx.save_for_backward(X, z, *route.tensors)
+        ctx.rows, ctx.inner, ctx.route = rows, inner, route
         ctx.mark_non_differentiable(z)
         ctx.set_materialize_grads(False)             # no zero-filled stand-in for the gradient of z (a fill of rows x inner floats per step)
-        part._gpode_ll = (X, z)                      # for elbo_all(): its backward can then produce the logit gradients in the same launch
+        part._gpode_ll = (X, z, route)               # for elbo_all(): its backward can then produce the logit gradients in the same launch
         return part, z
 
     @staticmethod
     def backward(ctx, gpart, _gz):
-        X, z = ctx.saved_tensors
-        ga = getattr(gpart, '_gpode_ga', None)       # already computed by _ElboAll.backward (gpode_elbo_all_bwd_ll)
+        X, z = ctx.saved_tensors[:2]
+        ga = getattr(gpart, '_gpode_ga', None)       # already computed by the ELBO's backward (gpode_elbo_all_bwd_ll*)
         if ga is not None and ga.shape == z.shape:
-            return None, ga, None
+            return None, ga, None, None
         # the ELBO hands every slice of a row the row's gradient: column 0 is the row gradient
         grow = gpart[:, 0].contiguous() if gpart.shape[1] > 1 else gpart.contiguous()
         ga = torch.empty_like(z)
-        _lib.call('gpode_sigmoid_loglik_bwd', _ptr(X), _ptr(z), _ptr(grow), _ptr(ga), ctx.rows, ctx.inner, X.numel(), _stream())
-        return None, ga, None
+        _lib.call('gpode_sigmoid_loglik_bwd' + ctx.route.suffix, _ptr(X), _ptr(z), _ptr(grow), _ptr(ga),
+                  *ctx.route.bwd_dims(X, ctx.rows, ctx.inner), *ctx.route.tail, _stream())
+        return None, ga, None, None
 
 
 class _ElboAll(torch.autograd.Function):
@@ -801,7 +844,7 @@ class _ElboAll(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, lpart, hs, hv, Um, Us, rows, M, nobs, ll=None):
-        ctx.ll = ll if (ll is not None and ll[1].numel() % ll[0].numel() == 0) else None
+        ctx.ll = ll
         lpart, hs, Um, Us = _chk(lpart, 'lpart'), _chk(hs, 'hs'), _chk(Um, 'Um'), _chk(Us, 'Us_sqrt.optvar')
         hv = _chk(hv, 'hv') if hv is not None else None
         N, q = hs.shape[0], hs.shape[1] // 2
@@ -817,83 +860,70 @@ class _ElboAll(torch.autograd.Function):
     def backward(ctx, g0, g1, g2, g3):
         hs, hv, Um, Us = ctx.saved_tensors
         rows, N, q, M, nobs, lshape = ctx.dims
-        gs = [None if g is None else g.contiguous().float() for g in (g0, g1, g2, g3)]
-        glrow = _new((rows,), hs)
         ghs, ghv = torch.empty_like(hs), (torch.empty_like(hv) if hv is not None else None)
-        dUm, dUs = torch.empty_like(Um), torch.empty_like(Us)
-        ga = None
-        if ctx.ll is not None and ctx.needs_input_grad[0]:
-            # the logits' gradient in the same launch (every likelihood row receives the same gradient): _SigmoidLogLikParts.backward
-            # finds it on the row-gradient tensor it is handed and launches nothing
-            X, z = ctx.ll[:2]
-            sfx, masked = _ll_len_args(ctx.ll)
-            ga = torch.empty_like(z)
-            _lib.call('gpode_elbo_all_bwd_ll' + sfx, *[_ptr(g) for g in gs], rows, _ptr(hs), _ptr(hv), N, q, M, Um.shape[1], _ptr(Um), _ptr(Us),
-                      ctypes.c_float(nobs), _ptr(glrow), _ptr(ghs), _ptr(ghv), _ptr(dUm), _ptr(dUs), _ptr(X), _ptr(z), _ptr(ga), z.numel(),
-                      X.numel(), *masked, _stream())
-        else:
-            _lib.call('gpode_elbo_all_bwd', *[_ptr(g) for g in gs], rows, _ptr(hs), _ptr(hv), N, q, M, Um.shape[1], _ptr(Um), _ptr(Us),
-                      ctypes.c_float(nobs), _ptr(glrow), _ptr(ghs), _ptr(ghv), _ptr(dUm), _ptr(dUs), _stream())
-        if (ctx.needs_input_grad[3] and ctx.needs_input_grad[4] and Um.is_leaf and Us.is_leaf and
-                ops.defer_kl_grads((Um, Us), (dUm, dUs))):
-            dUm = dUs = None                         # overlap mode: the flow's deferred backward adds its share to them in place
-        # every slice of a likelihood row carries the row's gradient (a broadcast view: nothing is copied)
-        glr = glrow.view(rows, 1).expand(lshape)
-        if ga is not None:
-            glr._gpode_ga = ga
+        ll = ctx.ll if ctx.needs_input_grad[0] else None
+        glr, dUm, dUs = _elbo_all_bwd(
+            ctx, (g0, g1, g2, g3), 'gpode_elbo_all_bwd' if ll is None else 'gpode_elbo_all_bwd_ll', ll, Um, Us, rows, lshape,
+            lambda glrow, dUm, dUs: (rows, _ptr(hs), _ptr(hv), N, q, M, Um.shape[1], _ptr(Um), _ptr(Us), ctypes.c_float(nobs), _ptr(glrow),
+                                     _ptr(ghs), _ptr(ghv), _ptr(dUm), _ptr(dUs)))
         return glr, ghs, ghv, dUm, dUs, None, None, None, None
 
 
-class _SigmoidLogLikPartsLen(torch.autograd.Function):
-    """_SigmoidLogLikParts over the observed frames of a ragged minibatch (gpode_sigmoid_loglik_fwd_len / _bwd_len): z for every
-    element, the partial sums and the logit gradients for the frames t < n_obs[n] only."""
-
-    @staticmethod
-    def forward(ctx, X, a, rows, n_obs):
-        X, a = _chk(X, 'X'), _chk(a, 'logits')
-        n_obs, T, frame = _chk_n_obs(n_obs, X, 'sigmoid_loglik_parts')
-        inner = a.numel() // rows
-        ns = _lib.load().gpode_sigmoid_loglik_splits(rows, inner)
-        z, part = torch.empty_like(a), _new((rows, ns), a)
-        _lib.call('gpode_sigmoid_loglik_fwd_len', _ptr(X), _ptr(a), _ptr(z), _ptr(part), rows, inner, X.numel(), ns, _ptr(n_obs), T, frame,
-                  _stream())
-        ctx.save_for_backward(X, z, n_obs)
-        ctx.dims = (rows, inner, T, frame)
-        ctx.mark_non_differentiable(z)
-        ctx.set_materialize_grads(False)
-        part._gpode_ll = (X, z, n_obs)               # elbo_all(): the fused backward takes its masked form from the third entry
-        return part, z
-
-    @staticmethod
-    def backward(ctx, gpart, _gz):
-        X, z, n_obs = ctx.saved_tensors
-        rows, inner, T, frame = ctx.dims
-        ga = getattr(gpart, '_gpode_ga', None)       # already computed by the ELBO's backward (gpode_elbo_all_bwd_ll_len / _ll_kl_len)
-        if ga is not None and ga.shape == z.shape:
-            return None, ga, None, None
-        grow = gpart[:, 0].contiguous() if gpart.shape[1] > 1 else gpart.contiguous()
+def _elbo_all_bwd(ctx, seeds, name, ll, Um, Us, rows, lshape, args):
+    """What the backward of both ELBO forms does: gradient seeds -> ONE launch -> in overlap mode the gradients of (Um, Us) go to the
+    flow's deferred backward -> the row gradient as a broadcast view.  ``name``: the entry point, without the route's suffix;
+    ``args(glrow, dUm, dUs)``: its arguments between the seeds and the logit block.  ``ll`` = (X, z, route) of sigmoid_loglik_parts: the
+    logits' gradient comes out of the same launch (every likelihood row receives the same gradient) and rides on the row gradient,
+    where _SigmoidLogLikParts.backward finds it and launches nothing.  -> (row gradient, dUm, dUs)"""
+    gs = [None if g is None else g.contiguous().float() for g in seeds]
+    glrow, dUm, dUs = _new((rows,), Um), torch.empty_like(Um), torch.empty_like(Us)
+    ga, logit_block = None, ()
+    if ll is not None:
+        X, z, route = ll
         ga = torch.empty_like(z)
-        _lib.call('gpode_sigmoid_loglik_bwd_len', _ptr(X), _ptr(z), _ptr(grow), _ptr(ga), rows, inner, X.numel(), _ptr(n_obs), T, frame,
-                  _stream())
-        return None, ga, None, None
-
-
-def _ll_len_args(ll):
-    """(entry-point suffix, extra arguments) of the fused backward for the (X, z[, n_obs]) a parts tensor carries"""
-    if len(ll) < 3 or ll[2] is None:
-        return '', ()
-    X, n_obs = ll[0], ll[2]
-    T = int(X.shape[1])
-    return '_len', (_ptr(n_obs), T, X.numel() // (X.shape[0] * T))
+        name, logit_block = name + route.suffix, (_ptr(X), _ptr(z), _ptr(ga), z.numel(), X.numel(), *route.tail)
+    _lib.call(name, *[_ptr(g) for g in gs], *args(glrow, dUm, dUs), *logit_block, _stream())
+    if (ctx.needs_input_grad[3] and ctx.needs_input_grad[4] and Um.is_leaf and Us.is_leaf and
+            ops.defer_kl_grads((Um, Us), (dUm, dUs))):
+        dUm = dUs = None                             # overlap mode: the flow's deferred backward adds its share to them in place
+    # every slice of a likelihood row carries the row's gradient (a broadcast view: nothing is copied)
+    glr = glrow.view(rows, 1).expand(lshape)
+    if ga is not None:
+        glr._gpode_ga = ga
+    return glr, dUm, dUs
 
 
 # ---- ragged minibatches, compact route: the padded frames are taken out in front of the decoder (include/gpode.h) ------------------------
 class FrameIndex:
-    """The observed frames of a ragged minibatch (N sequences padded to T frames), see frame_index()."""
+    """The observed frames of a ragged minibatch (N sequences padded to T frames), see frame_index().  Also the loss stage's route
+    over COMPACT logits (see _EveryFrame): the `_pk` entry points take ``off, T, frame`` (forward) or ``src, P, T, frame`` (backward)
+    in front of nX, and there is no fused ELBO backward for them -- elbo_all() runs gpode_elbo_all_bwd, and the logits' gradient is one
+    launch of its own."""
     __slots__ = ('off', 'src', 'P', 'N', 'T', 'counts')
+    suffix, fused, tail, tensors = '_pk', False, (), ()
 
     def __init__(self, off, src, P, N, T, counts):
         self.off, self.src, self.P, self.N, self.T, self.counts = off, src, P, N, T, counts
+
+    def _frame(self, X):
+        return X.numel() // (self.N * self.T)
+
+    def bind(self, X, elements, rows, who):
+        N, T, P = self.N, self.T, self.P
+        if X.dim() < 2 or tuple(X.shape[:2]) != (N, T) or rows % N != 0:
+            raise _lib.GpodeError('%s: X must be (N,T,...) = (%d,%d,...) and rows a multiple of N; got %s, rows %d'
+                                  % (who, N, T, tuple(X.shape), rows))
+        frame, L = self._frame(X), rows // N
+        if elements != L * P * frame:
+            raise _lib.GpodeError('%s: %d compact logits expected (L P frame = %d x %d x %d), got %d'
+                                  % (who, L * P * frame, L, P, frame, elements))
+        return T * frame
+
+    def fwd_dims(self, X, rows, inner):
+        return rows, _ptr(self.off), self.T, self._frame(X), X.numel()
+
+    def bwd_dims(self, X, rows, inner):
+        return rows, _ptr(self.src), self.P, self.T, self._frame(X), X.numel()
 
 
 def frame_index(n_obs, T, counts=None):
@@ -960,61 +990,20 @@ def gather_frames(ztL, index, q):
     return _GatherFrames.apply(ztL, index, int(q))
 
 
-class _SigmoidLogLikPartsPk(torch.autograd.Function):
-    """_SigmoidLogLikParts over COMPACT logits (L P, ...): the observed frames only, in the order of ``index`` (gpode_sigmoid_loglik_fwd_pk
-    / _bwd_pk).  Rows are (draw, sequence) as ever; the padded target frames of X are never addressed."""
-
-    @staticmethod
-    def forward(ctx, X, a, rows, index):
-        X, a = _chk(X, 'X'), _chk(a, 'logits')
-        N, T, P = index.N, index.T, index.P
-        if X.dim() < 2 or tuple(X.shape[:2]) != (N, T) or rows % N != 0:
-            raise _lib.GpodeError('sigmoid_loglik_parts: X must be (N,T,...) = (%d,%d,...) and rows a multiple of N; got %s, rows %d'
-                                  % (N, T, tuple(X.shape), rows))
-        frame, L = X.numel() // (N * T), rows // N
-        if a.numel() != L * P * frame:
-            raise _lib.GpodeError('sigmoid_loglik_parts: %d compact logits expected (L P frame = %d x %d x %d), got %d'
-                                  % (L * P * frame, L, P, frame, a.numel()))
-        ns = _lib.load().gpode_sigmoid_loglik_splits(rows, T * frame)
-        z, part = torch.empty_like(a), _new((rows, ns), a)
-        _lib.call('gpode_sigmoid_loglik_fwd_pk', _ptr(X), _ptr(a), _ptr(z), _ptr(part), rows, _ptr(index.off), T, frame, X.numel(), ns,
-                  _stream())
-        ctx.save_for_backward(X, z)
-        ctx.index, ctx.dims = index, (rows, frame)
-        ctx.mark_non_differentiable(z)
-        ctx.set_materialize_grads(False)
-        return part, z                               # no _gpode_ll: elbo_all() then runs gpode_elbo_all_bwd, and the logits' gradient is
-                                                     # one launch of its own below
-
-    @staticmethod
-    def backward(ctx, gpart, _gz):
-        X, z = ctx.saved_tensors
-        index, (rows, frame) = ctx.index, ctx.dims
-        grow = gpart[:, 0].contiguous() if gpart.shape[1] > 1 else gpart.contiguous()
-        ga = torch.empty_like(z)
-        _lib.call('gpode_sigmoid_loglik_bwd_pk', _ptr(X), _ptr(z), _ptr(grow), _ptr(ga), rows, _ptr(index.src), index.P, index.T, frame,
-                  X.numel(), _stream())
-        return None, ga, None, None
-
-
 def sigmoid_loglik_parts(X, logits, rows, n_obs=None, *, index=None):
     """-> (partial row sums (rows, nsplit) of the Bernoulli log-likelihood, z = sigmoid(logits)).  ``n_obs`` (N,) int32: the frame
     count of every sequence of a ragged (padded) minibatch X (N,T,...) -- the sums take the frames t < n_obs[n] only and the padded
     logits get a zero gradient; None: every frame, the launches as they always were.
     ``index`` (frame_index; not together with ``n_obs``): ``logits`` are COMPACT, (L P, ...) for the observed frames only, ordered
     (l, n, t) -- z and the logit gradients are compact as well, rows stay (draw, sequence)."""
-    if index is not None:
-        if n_obs is not None:
-            raise _lib.GpodeError('sigmoid_loglik_parts: n_obs (padded logits, masked) and index (compact logits) exclude each other')
-        return _SigmoidLogLikPartsPk.apply(X, logits, rows, index)
-    if n_obs is None:
-        return _SigmoidLogLikParts.apply(X, logits, rows)
-    return _SigmoidLogLikPartsLen.apply(X, logits, rows, n_obs)
+    if index is not None and n_obs is not None:
+        raise _lib.GpodeError('sigmoid_loglik_parts: n_obs (padded logits, masked) and index (compact logits) exclude each other')
+    return _SigmoidLogLikParts.apply(X, logits, rows, index if index is not None else _Masked(n_obs) if n_obs is not None else _EVERY)
 
 
 class _ElboAllKL(torch.autograd.Function):
     """_ElboAll on the KL partial sums of _ReparamKL instead of the packed (mu | logvar) rows (gpode_elbo_all_fwd_kl /
-    gpode_elbo_all_bwd_ll_kl); its backward also produces the logits' gradient (ll = (X, z) of sigmoid_loglik_parts)."""
+    gpode_elbo_all_bwd_ll_kl); its backward also produces the logits' gradient (ll = (X, z, route) of sigmoid_loglik_parts)."""
 
     @staticmethod
     def forward(ctx, lpart, kls, klv, Um, Us, rows, N, M, nobs, ll):
@@ -1033,35 +1022,31 @@ class _ElboAllKL(torch.autograd.Function):
     def backward(ctx, g0, g1, g2, g3):
         Um, Us = ctx.saved_tensors
         rows, N, M, nobs, lshape, nks, nkv = ctx.dims
-        gs = [None if g is None else g.contiguous().float() for g in (g0, g1, g2, g3)]
-        X, z = ctx.ll[:2]
-        sfx, masked = _ll_len_args(ctx.ll)
-        glrow, gkls, gklv = _new((rows,), Um), _new((nks,), Um), (_new((nkv,), Um) if nkv else None)
-        dUm, dUs, ga = torch.empty_like(Um), torch.empty_like(Us), torch.empty_like(z)
-        _lib.call('gpode_elbo_all_bwd_ll_kl' + sfx, *[_ptr(g) for g in gs], rows, N, M, Um.shape[1], _ptr(Um), _ptr(Us), ctypes.c_float(nobs),
-                  _ptr(glrow), _ptr(gkls), nks, _ptr(gklv), nkv, _ptr(dUm), _ptr(dUs), _ptr(X), _ptr(z), _ptr(ga), z.numel(), X.numel(),
-                  *masked, _stream())
-        if (ctx.needs_input_grad[3] and ctx.needs_input_grad[4] and Um.is_leaf and Us.is_leaf and
-                ops.defer_kl_grads((Um, Us), (dUm, dUs))):
-            dUm = dUs = None
-        glr = glrow.view(rows, 1).expand(lshape)
-        glr._gpode_ga = ga
+        gkls, gklv = _new((nks,), Um), (_new((nkv,), Um) if nkv else None)
+        glr, dUm, dUs = _elbo_all_bwd(
+            ctx, (g0, g1, g2, g3), 'gpode_elbo_all_bwd_ll_kl', ctx.ll, Um, Us, rows, lshape,
+            lambda glrow, dUm, dUs: (rows, N, M, Um.shape[1], _ptr(Um), _ptr(Us), ctypes.c_float(nobs), _ptr(glrow), _ptr(gkls), nks,
+                                     _ptr(gklv), nkv, _ptr(dUm), _ptr(dUs)))
         return glr, gkls, gklv, dUm, dUs, None, None, None, None, None
 
 
 def elbo_all(lpart, mu_s, logvar_s, mu_v, logvar_v, Um, Us_packed, M, nobs):
     """-> (loss, nll, kl_reg, kl_u), see _ElboAll."""
+    # (X, z, route) when the backward can produce the logits' gradient in its own launch: the parts come from sigmoid_loglik_parts
+    # on a route that has the fused form, and X covers the logits a whole number of times (the draws)
     ll = getattr(lpart, '_gpode_ll', None)
+    if ll is not None and not (ll[2].fused and ll[1].numel() % ll[0].numel() == 0):
+        ll = None
     hs0 = _packed_halves(mu_s, logvar_s)
     kls = getattr(hs0, '_gpode_klpart', None) if hs0 is not None else None
     klv = None
     if mu_v is not None:
         hv0 = _packed_halves(mu_v, logvar_v)
         klv = getattr(hv0, '_gpode_klpart', None) if hv0 is not None else None
-    if (ll is not None and ll[1].numel() % ll[0].numel() == 0 and kls is not None and (mu_v is None or klv is not None)):
+    if ll is not None and kls is not None and (mu_v is None or klv is not None):
         return _ElboAllKL.apply(lpart, kls, klv, Um, Us_packed, lpart.shape[0], mu_s.shape[0], M, float(nobs), ll)
     hv = _pack(mu_v, logvar_v) if mu_v is not None else None
-    return _ElboAll.apply(lpart, _pack(mu_s, logvar_s), hv, Um, Us_packed, lpart.shape[0], M, float(nobs), getattr(lpart, '_gpode_ll', None))
+    return _ElboAll.apply(lpart, _pack(mu_s, logvar_s), hv, Um, Us_packed, lpart.shape[0], M, float(nobs), ll)
 
 
 def _pack(mu, logvar):
@@ -1186,9 +1171,7 @@ def bernoulli_loglik(X, z):
 
 def bernoulli_loglik_rowsum(X, z, rows, n_obs=None):
     """``n_obs`` (N,) int32: sum the frames t < n_obs[n] of a ragged minibatch only (sigmoid_loglik_parts); None: every frame."""
-    if n_obs is None:
-        return _LogLikRowSum.apply(X, z, rows)
-    return _LogLikRowSumLen.apply(X, z, rows, n_obs)
+    return _LogLikRowSum.apply(X, z, rows, _Masked(n_obs) if n_obs is not None else _EVERY)
 
 
 # ---- frozen decoder / posterior-predictive evaluation (forward only; evaluate.py) ------------------------------------------------
@@ -1211,7 +1194,7 @@ def table_conv_transpose2d(c, table, w, b, stride, pad, out_pad=0):
     _, Cout, K, _ = w.shape
     if tuple(table.shape) != (Cin, 4):
         raise _lib.GpodeError('table_conv_transpose2d: table must be (%d, 4)' % Cin)
-    Ht, Wt = (Hi - 1) * stride - 2 * pad + K + out_pad, (Wi - 1) * stride - 2 * pad + K + out_pad
+    Ht, Wt = _convT_out(Hi, Wi, K, stride, pad, out_pad)
     y = _new((B, Cout, Ht, Wt), c)
     _lib.call('gpode_conv2d_bwd_data_bn', _ptr(c), _ptr(table), _ptr(w), _ptr(None if b is None else _chk(b.detach(), 'bias')), _ptr(y),
               B, Cout, Ht, Wt, Cin, K, stride, pad, Hi, Wi, _stream())
@@ -1239,9 +1222,9 @@ def dec10_predict(c, table, w, b, X, Th, state, n_obs=None):
     ``n_obs`` (N,) int32: the frame count of every sequence of a ragged X -- frame t of sequence n has a target iff
     t < min(T_obs, n_obs[n]) (the *_len entry points); None: the launches as they always were."""
     c, w, table, X = _chk(c.detach(), 'c'), _chk(w.detach(), 'weight'), _chk(table, 'table'), _chk(X, 'X')
-    sfx, masked = '', ()
+    name, extra = 'gpode_dec10_predict', ()
     if n_obs is not None:
-        sfx, masked = '_len', (_ptr(_chk_n_obs(n_obs, X, 'dec10_predict')[0]),)
+        n_obs = _chk_n_obs(n_obs, X, 'dec10_predict')[0]
     F = state.F
     N, T_obs = X.shape[0], X.shape[1]
     if tuple(c.shape[1:]) != (16, 28, 28) or tuple(w.shape) != (16, 1, 5, 5) or tuple(table.shape) != (16, 4):
@@ -1253,12 +1236,10 @@ def dec10_predict(c, table, w, b, X, Th, state, n_obs=None):
     if ell is not None:
         if ell.dim() != 2 or ell.shape[1] != F or ell.dtype != torch.float32 or not ell.is_contiguous():
             raise _lib.GpodeError('gpode_dec10_predict_ll: ell must be a contiguous float32 (L_total, F) tensor')
-        _lib.call('gpode_dec10_predict_ll' + sfx, _ptr(c), _ptr(table), _ptr(w), _ptr(None if b is None else _chk(b.detach(), 'bias')), _ptr(X),
-                  Lc, F, int(Th), T_obs, state.done, _ptr(state.mean), _ptr(state.m2), _ptr(state.se), _ptr(ell), ell.shape[0], *masked,
-                  _stream())
-        state.done += Lc
-        return state
-    _lib.call('gpode_dec10_predict' + sfx, _ptr(c), _ptr(table), _ptr(w), _ptr(None if b is None else _chk(b.detach(), 'bias')), _ptr(X),
-              Lc, F, int(Th), T_obs, state.done, _ptr(state.mean), _ptr(state.m2), _ptr(state.se), *masked, _stream())
+        name, extra = name + '_ll', (_ptr(ell), ell.shape[0])
+    if n_obs is not None:
+        name, extra = name + '_len', extra + (_ptr(n_obs),)
+    _lib.call(name, _ptr(c), _ptr(table), _ptr(w), _ptr(None if b is None else _chk(b.detach(), 'bias')), _ptr(X),
+              Lc, F, int(Th), T_obs, state.done, _ptr(state.mean), _ptr(state.m2), _ptr(state.se), *extra, _stream())
     state.done += Lc
     return state
