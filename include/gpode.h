@@ -67,7 +67,7 @@ int gpode_rhs_fwd(int kernel, int Di, int Do, int M, int S, const float* pack,
                   const float* x, int N, float* f, int mode, void* stream);
 
 /* Flow.forward (flow.py:68-86) given a built cache: z0 (N,D), ts (T) -> zt (N,T,D),
- * D = Di = order*Do.  One fixed-grid step per output interval.
+ * D = Di = order*Do.  One fixed-grid step per output interval (the `_ns` entry points below take several).
  * xstage (nullable): (N, T-1, NS, D) receives the input of every RHS evaluation (NS = 1 euler, 4 rk4);
  * pass it when gradients are needed -- gpode_rollout_bwd walks it backwards. */
 int gpode_rollout_fwd(int kernel, int order, int method, int Di, int Do, int M, int S,
@@ -223,6 +223,37 @@ int gpode_rollout_bwd_nt(int kernel, int order, int method, int Di, int Do, int 
 int gpode_rollout_bwd_pgrad_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                                const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
                                float* gz0, float* astage, float* slab, int nchunk, float* gpack, int ts_per_traj, void* stream);
+/* The fixed-grid rollout and its reverse sweeps with SUB-STEPS between the output times (the reference's --ts_dense_scale,
+ * torchdiffeq's options=dict(step_size=...)): the arguments of the `_nt` twin plus `substeps`, directly in front of `stream`.
+ *   gpode_rollout_fwd_ns  gpode_rollout_fwd_nt      gpode_rollout_bwd_ns  gpode_rollout_bwd_nt
+ *   gpode_rollout_bwd_pgrad_ns  gpode_rollout_bwd_pgrad_nt
+ * Every output interval [ts[t], ts[t+1]] of every trajectory is integrated in `substeps` equal steps of h = (ts[t+1] - ts[t]) /
+ * substeps (one fp32 division per interval; the right-hand side is autonomous, so only h matters).  Outputs stay at ts: zt, gzt and
+ * gz0 keep the twin's layout, and nothing between the output times is written to zt.  The record grows by the sub-step axis,
+ *   xstage ([L,] N, T-1, substeps, NS, D)     astage ([L,] N, T-1, substeps, NS, Do)
+ * contiguous -- the same bytes as ([L,] N, (T-1)*substeps, NS, .) -- so gpode_param_grad_n runs over all its rows unchanged, and
+ * gpode_rollout_bwd_pgrad_chunks (which does not depend on the count) sizes the slab of the fused form as before.  The reverse
+ * sweep walks intervals and sub-steps backwards; gzt[t] enters when the walk reaches the start of interval t.
+ *   substeps = 1        the same launch, the same tag, the same bits as the twin
+ *   substeps 1 ... 64   accepted; any other value is refused before anything is launched (gpode_last_error() names the entry
+ *                       point) and nothing is written
+ * method = GPODE_METHOD_DOPRI5 is refused as in the twins.  The route, and with it the tag gpode_last_launch() returns, does not
+ * depend on substeps. */
+/* For tests.  The rollout kernels exist in two instantiations: the one-step one, which the twins and substeps = 1 launch (the code they
+ * always ran), and the sub-step one, which every other count launches.  on = 1 sends one-step launches through the sub-step
+ * instantiation as well, so that a test can hold that instantiation to itself on a refined grid (two separately compiled kernels
+ * need not round alike); on = 0 is the state the library starts in.  Any other value is refused.  Process-wide, not thread-safe. */
+int gpode_test_substep_kernels(int on);
+int gpode_rollout_fwd_ns(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                         const float* pack, const float* z0, const float* ts, int N, int T,
+                         float* zt, float* xstage, int z0_per_draw, int ts_per_traj, int substeps, void* stream);
+int gpode_rollout_bwd_ns(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                         const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
+                         float* gz0, float* astage, int ts_per_traj, int substeps, void* stream);
+int gpode_rollout_bwd_pgrad_ns(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                               const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
+                               float* gz0, float* astage, float* slab, int nchunk, float* gpack, int ts_per_traj, int substeps,
+                               void* stream);
 /* gpode_rollout_bwd_n and gpode_param_grad_n in ONE pass: the reverse sweep visits every (stage input, adjoint) row anyway, so the
  * rows' parameter-gradient terms are accumulated on the way and come out as gpack (ndraws, pack_floats) -- what the two calls
  * produce together, with one launch and one pass over the rows less.  slab: ndraws * nchunk * pack_floats floats of scratch with

@@ -59,6 +59,10 @@ SIGNATURES = {
     'gpode_rollout_dense_fwd_nt': (_i, [_i] * 8 + [_vp] * 3 + [_i, _i, _f, _f, _i] + [_vp] * 6 + [_i, _i, _vp]),
     'gpode_rollout_bwd_nt': (_i, [_i] * 8 + [_vp] * 4 + [_i, _i, _vp, _vp, _i, _vp]),
     'gpode_rollout_bwd_pgrad_nt': (_i, [_i] * 8 + [_vp] * 4 + [_i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
+    'gpode_test_substep_kernels': (_i, [_i]),
+    'gpode_rollout_fwd_ns': (_i, [_i] * 8 + [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
+    'gpode_rollout_bwd_ns': (_i, [_i] * 8 + [_vp] * 4 + [_i, _i, _vp, _vp, _i, _i, _vp]),
+    'gpode_rollout_bwd_pgrad_ns': (_i, [_i] * 8 + [_vp] * 4 + [_i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     'gpode_rollout_bwd_pgrad_chunks': (_i, [_i] * 8),
     'gpode_rollout_bwd_pgrad_n': (_i, [_i] * 8 + [_vp] * 4 + [_i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     'gpode_param_grad_n': (_i, [_i] * 6 + [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp]),

@@ -11,6 +11,10 @@ const char** last_launch_slot() {
   static thread_local const char* tag = "";
   return &tag;
 }
+bool* force_substep_kernels() {
+  static bool on = false;                            // gpode_test_substep_kernels
+  return &on;
+}
 }  // namespace gp
 
 extern "C" {
@@ -93,17 +97,23 @@ static int ts_flag_refused(const char* who, int ts_per_traj) {
   if (ts_per_traj == 0 || ts_per_traj == 1) return 0;
   return gp::set_error("%s: ts_per_traj=%d (0 one (T,) grid shared, 1 one row of (N,T) per trajectory)", who, ts_per_traj);
 }
-static gp::Draws with_ts(gp::Draws d, int ts_per_traj, int T) {
+// substeps of the `_ns` entry points: equal solver steps per output interval, 1 (the twin's launch) ... gp::kMaxSubsteps
+static int substeps_refused(const char* who, int substeps) {
+  if (substeps >= 1 && substeps <= gp::kMaxSubsteps) return 0;
+  return gp::set_error("%s: substeps=%d (1 ... %d steps per output interval)", who, substeps, gp::kMaxSubsteps);
+}
+static gp::Draws with_ts(gp::Draws d, int ts_per_traj, int T, int substeps = 1) {
   d.ts = ts_per_traj ? (size_t)T : 0;
+  d.sub = substeps;
   return d;
 }
 
 // `who`: the entry point's name in the messages; z0_per_draw: 0 = z0 (N,D) shared by the draws, 1 = (ndraws,N,D)
 static int rollout_fwd_any(const char* who, int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                            const float* pack, const float* z0, const float* ts, int N, int T,
-                           float* zt, float* xstage, int z0_per_draw, void* stream, int ts_per_traj = 0) {
+                           float* zt, float* xstage, int z0_per_draw, void* stream, int ts_per_traj = 0, int substeps = 1) {
   if (z0_per_draw != 0 && z0_per_draw != 1) return gp::set_error("%s: z0_per_draw=%d (0 shared, 1 one (N,D) slab per draw)", who, z0_per_draw);
-  if (ts_flag_refused(who, ts_per_traj)) return 1;
+  if (ts_flag_refused(who, ts_per_traj) || substeps_refused(who, substeps)) return 1;
   if (N < 0 || T < 1 || ndraws < 1 || ndraws > 65535) return gp::set_error("%s: N=%d T=%d draws=%d", who, N, T, ndraws);
   if (N == 0) return 0;
   if (!pack || !z0 || !ts || !zt) return gp::set_error("%s: null pointer", who);
@@ -111,7 +121,7 @@ static int rollout_fwd_any(const char* who, int kernel, int order, int method, i
   if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
   return gp::rollout_fwd(kernel, order, method, Di, Do, M, S, pack, z0, ts, N, T, zt, xstage, (hipStream_t)stream,
                          with_ts(draws_of(ndraws, pf, z0_per_draw ? (size_t)N * Di : 0, (size_t)N * T * Di, 0,
-                                          (size_t)N * (T - 1) * stage_count(method) * Di), ts_per_traj, T));
+                                          (size_t)N * (T - 1) * substeps * stage_count(method) * Di), ts_per_traj, T, substeps));
 }
 int gpode_rollout_fwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                         const float* pack, const float* z0, const float* ts, int N, int T,
@@ -130,24 +140,47 @@ int gpode_rollout_fwd_nt(int kernel, int order, int method, int Di, int Do, int 
   return rollout_fwd_any("gpode_rollout_fwd_nt", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, zt, xstage, z0_per_draw,
                          stream, ts_per_traj);
 }
+int gpode_test_substep_kernels(int on) {
+  if (on != 0 && on != 1) return gp::set_error("gpode_test_substep_kernels: on=%d (0 or 1)", on);
+  *gp::force_substep_kernels() = on != 0;
+  return 0;
+}
+int gpode_rollout_fwd_ns(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                         const float* pack, const float* z0, const float* ts, int N, int T,
+                         float* zt, float* xstage, int z0_per_draw, int ts_per_traj, int substeps, void* stream) {
+  return rollout_fwd_any("gpode_rollout_fwd_ns", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, zt, xstage, z0_per_draw,
+                         stream, ts_per_traj, substeps);
+}
 int gpode_rollout_fwd(int kernel, int order, int method, int Di, int Do, int M, int S,
                       const float* pack, const float* z0, const float* ts, int N, int T,
                       float* zt, float* xstage, void* stream) {
   return gpode_rollout_fwd_n(kernel, order, method, Di, Do, M, S, 1, pack, z0, ts, N, T, zt, xstage, stream);
 }
 
+static int rollout_bwd_any(const char* who, int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                           const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
+                           float* gz0, float* astage, int ts_per_traj, int substeps, void* stream) {
+  if (ts_flag_refused(who, ts_per_traj) || substeps_refused(who, substeps)) return 1;
+  if (N < 0 || T < 1 || ndraws < 1 || ndraws > 65535) return gp::set_error("%s: N=%d T=%d draws=%d", who, N, T, ndraws);
+  if (N == 0) return 0;
+  if (!pack || !gzt || !ts || !gz0 || (T > 1 && (!xstage || !astage))) return gp::set_error("%s: null pointer", who);
+  size_t pf = 0;
+  if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
+  const size_t rows = (size_t)N * (T - 1) * substeps * stage_count(method);
+  return gp::rollout_bwd(kernel, order, method, Di, Do, M, S, pack, xstage, gzt, ts, N, T, gz0, astage, (hipStream_t)stream,
+                         with_ts(draws_of(ndraws, pf, rows * Di, (size_t)N * Di, (size_t)N * T * Di, rows * Do), ts_per_traj, T, substeps));
+}
 int gpode_rollout_bwd_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                          const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
                          float* gz0, float* astage, int ts_per_traj, void* stream) {
-  if (ts_flag_refused("gpode_rollout_bwd", ts_per_traj)) return 1;
-  if (N < 0 || T < 1 || ndraws < 1 || ndraws > 65535) return gp::set_error("gpode_rollout_bwd: N=%d T=%d draws=%d", N, T, ndraws);
-  if (N == 0) return 0;
-  if (!pack || !gzt || !ts || !gz0 || (T > 1 && (!xstage || !astage))) return gp::set_error("gpode_rollout_bwd: null pointer");
-  size_t pf = 0;
-  if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
-  const size_t rows = (size_t)N * (T - 1) * stage_count(method);
-  return gp::rollout_bwd(kernel, order, method, Di, Do, M, S, pack, xstage, gzt, ts, N, T, gz0, astage, (hipStream_t)stream,
-                         with_ts(draws_of(ndraws, pf, rows * Di, (size_t)N * Di, (size_t)N * T * Di, rows * Do), ts_per_traj, T));
+  return rollout_bwd_any("gpode_rollout_bwd", kernel, order, method, Di, Do, M, S, ndraws, pack, xstage, gzt, ts, N, T, gz0, astage,
+                         ts_per_traj, 1, stream);
+}
+int gpode_rollout_bwd_ns(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                         const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
+                         float* gz0, float* astage, int ts_per_traj, int substeps, void* stream) {
+  return rollout_bwd_any("gpode_rollout_bwd_ns", kernel, order, method, Di, Do, M, S, ndraws, pack, xstage, gzt, ts, N, T, gz0, astage,
+                         ts_per_traj, substeps, stream);
 }
 int gpode_rollout_bwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                         const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
@@ -157,18 +190,33 @@ int gpode_rollout_bwd_n(int kernel, int order, int method, int Di, int Do, int M
 int gpode_rollout_bwd_pgrad_chunks(int kernel, int order, int method, int Di, int Do, int M, int S, int N) {
   return gp::rollout_bwd_pgrad_chunks(kernel, order, method, Di, Do, M, S, N);
 }
+static int rollout_bwd_pgrad_any(const char* who, int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                                 const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
+                                 float* gz0, float* astage, float* slab, int nchunk, float* gpack, int ts_per_traj, int substeps,
+                                 void* stream) {
+  if (ts_flag_refused(who, ts_per_traj) || substeps_refused(who, substeps)) return 1;
+  if (N < 1 || T < 2 || ndraws < 1 || ndraws > 65535) return gp::set_error("%s: N=%d T=%d draws=%d", who, N, T, ndraws);
+  if (!pack || !gzt || !ts || !gz0 || !xstage || !astage || !slab || !gpack) return gp::set_error("%s: null pointer", who);
+  size_t pf = 0;
+  if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
+  const size_t rows = (size_t)N * (T - 1) * substeps * stage_count(method);
+  return gp::rollout_bwd_pgrad(kernel, order, method, Di, Do, M, S, pack, xstage, gzt, ts, N, T, gz0, astage, slab, nchunk, gpack,
+                               (hipStream_t)stream,
+                               with_ts(draws_of(ndraws, pf, rows * Di, (size_t)N * Di, (size_t)N * T * Di, rows * Do), ts_per_traj, T,
+                                       substeps));
+}
 int gpode_rollout_bwd_pgrad_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                                const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
                                float* gz0, float* astage, float* slab, int nchunk, float* gpack, int ts_per_traj, void* stream) {
-  if (ts_flag_refused("gpode_rollout_bwd_pgrad", ts_per_traj)) return 1;
-  if (N < 1 || T < 2 || ndraws < 1 || ndraws > 65535) return gp::set_error("gpode_rollout_bwd_pgrad: N=%d T=%d draws=%d", N, T, ndraws);
-  if (!pack || !gzt || !ts || !gz0 || !xstage || !astage || !slab || !gpack) return gp::set_error("gpode_rollout_bwd_pgrad: null pointer");
-  size_t pf = 0;
-  if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
-  const size_t rows = (size_t)N * (T - 1) * stage_count(method);
-  return gp::rollout_bwd_pgrad(kernel, order, method, Di, Do, M, S, pack, xstage, gzt, ts, N, T, gz0, astage, slab, nchunk, gpack,
-                               (hipStream_t)stream,
-                               with_ts(draws_of(ndraws, pf, rows * Di, (size_t)N * Di, (size_t)N * T * Di, rows * Do), ts_per_traj, T));
+  return rollout_bwd_pgrad_any("gpode_rollout_bwd_pgrad", kernel, order, method, Di, Do, M, S, ndraws, pack, xstage, gzt, ts, N, T, gz0,
+                               astage, slab, nchunk, gpack, ts_per_traj, 1, stream);
+}
+int gpode_rollout_bwd_pgrad_ns(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                               const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
+                               float* gz0, float* astage, float* slab, int nchunk, float* gpack, int ts_per_traj, int substeps,
+                               void* stream) {
+  return rollout_bwd_pgrad_any("gpode_rollout_bwd_pgrad_ns", kernel, order, method, Di, Do, M, S, ndraws, pack, xstage, gzt, ts, N, T, gz0,
+                               astage, slab, nchunk, gpack, ts_per_traj, substeps, stream);
 }
 int gpode_rollout_bwd_pgrad_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                               const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,

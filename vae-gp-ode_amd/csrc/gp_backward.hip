@@ -42,7 +42,9 @@ template <class EV> struct GradsOf<EV, true> { using type = typename EV::Grads; 
 // PG (register-resident team evaluators only): the parameter-gradient sums of the rows this workgroup walks are accumulated in
 // the same pass (EV::vjp_grad) and written to slab[blockIdx.x] in pack layout -- what param_grad_{rbf,df}_kernel computes from the
 // stored (x, a) rows in a launch of its own, the first node of the backward pass's side branch.
-template <class EV, int DI, int DO, int ORDER, int METHOD, bool PG = false>
+// SUB (gp_rollout.hpp): false = one step per output interval, the kernel as it always was; true = dw.sub steps per interval, walked
+// last first; the record is (N, T-1, sub, NS, .) and gzt[t] enters when the walk reaches the start of interval t either way.
+template <class EV, int DI, int DO, int ORDER, int METHOD, bool PG = false, bool SUB = false>
 __global__ __launch_bounds__(64 * EV::kTeam) void rollout_bwd_team_kernel(const float* __restrict__ pack, int M, int S,
                                                                 const float* __restrict__ xstage, const float* __restrict__ gzt,
                                                                 const float* __restrict__ ts, int N, int T,
@@ -59,72 +61,75 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rollout_bwd_team_kernel(const 
   GR G;
   if constexpr (PG) G.zero();
   const float third = (float)(1.0 / 3.0);
+  const int sub = sub_count<SUB>(dw.sub);
   for (int n = blockIdx.x; n < N; n += gridDim.x) {
     const float* gz = gzt + (size_t)n * T * DI;
-    const float* xs = xstage + (size_t)n * (T - 1) * NS * DI;
-    float* as = astage + (size_t)n * (T - 1) * NS * DO;
+    const float* xs = xstage + (size_t)n * (T - 1) * sub * NS * DI;
+    float* as = astage + (size_t)n * (T - 1) * sub * NS * DO;
     float lam[DI];
 #pragma unroll
     for (int i = 0; i < DI; ++i) lam[i] = gz[(size_t)(T - 1) * DI + i];
     const float* tn = ts_row(ts, n, dw.ts);          // this trajectory's grid (dw.ts = 0: the shared one)
     for (int t = T - 2; t >= 0; --t) {
-      const float dt = tn[t + 1] - tn[t];
-      const float* xt = xs + (size_t)t * NS * DI;
-      float* at = as + (size_t)t * NS * DO;
-      float x[DI], g[DI], af[DO];
-      if (METHOD == 0) {
-        float a1[DI];
+      const float dt = sub_step<SUB>(tn[t], tn[t + 1], sub);
+      for (int r = (t + 1) * sub - 1; r >= t * sub; --r) {   // the interval's steps, last first: row block r of the record
+        const float* xt = xs + (size_t)r * NS * DI;
+        float* at = as + (size_t)r * NS * DO;
+        float x[DI], g[DI], af[DO];
+        if (METHOD == 0) {
+          float a1[DI];
 #pragma unroll
-        for (int i = 0; i < DI; ++i) { a1[i] = dt * lam[i]; x[i] = xt[i]; }
-        ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a1, g, af, &G);
-        if (wave == 0) store_vec<DO>(at, af, lane);
+          for (int i = 0; i < DI; ++i) { a1[i] = dt * lam[i]; x[i] = xt[i]; }
+          ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a1, g, af, &G);
+          if (wave == 0) store_vec<DO>(at, af, lane);
 #pragma unroll
-        for (int i = 0; i < DI; ++i) lam[i] += g[i];
-      } else if (METHOD == 2) {
-        // midpoint: y1 = y + dt k2, k2 = f(x2), x2 = y + dt/2 k1, k1 = f(y)
-        float a1[DI], a2[DI], ay[DI];
+          for (int i = 0; i < DI; ++i) lam[i] += g[i];
+        } else if (METHOD == 2) {
+          // midpoint: y1 = y + dt k2, k2 = f(x2), x2 = y + dt/2 k1, k1 = f(y)
+          float a1[DI], a2[DI], ay[DI];
 #pragma unroll
-        for (int i = 0; i < DI; ++i) { a2[i] = dt * lam[i]; x[i] = xt[DI + i]; }
-        ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a2, g, af, &G);
-        if (wave == 0) store_vec<DO>(at + DO, af, lane);
+          for (int i = 0; i < DI; ++i) { a2[i] = dt * lam[i]; x[i] = xt[DI + i]; }
+          ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a2, g, af, &G);
+          if (wave == 0) store_vec<DO>(at + DO, af, lane);
 #pragma unroll
-        for (int i = 0; i < DI; ++i) { ay[i] = lam[i] + g[i]; a1[i] = 0.5f * dt * g[i]; x[i] = xt[i]; }
-        ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a1, g, af, &G);
-        if (wave == 0) store_vec<DO>(at, af, lane);
+          for (int i = 0; i < DI; ++i) { ay[i] = lam[i] + g[i]; a1[i] = 0.5f * dt * g[i]; x[i] = xt[i]; }
+          ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a1, g, af, &G);
+          if (wave == 0) store_vec<DO>(at, af, lane);
 #pragma unroll
-        for (int i = 0; i < DI; ++i) lam[i] = ay[i] + g[i];
-      } else {
-        // y1 = y + (k1 + 3(k2+k3) + k4) dt/8 ;  x2 = y + dt k1/3 ; x3 = y + dt(k2 - k1/3) ; x4 = y + dt(k1 - k2 + k3)
-        float a1[DI], a2[DI], a3[DI], a4[DI], ay[DI];
+          for (int i = 0; i < DI; ++i) lam[i] = ay[i] + g[i];
+        } else {
+          // y1 = y + (k1 + 3(k2+k3) + k4) dt/8 ;  x2 = y + dt k1/3 ; x3 = y + dt(k2 - k1/3) ; x4 = y + dt(k1 - k2 + k3)
+          float a1[DI], a2[DI], a3[DI], a4[DI], ay[DI];
 #pragma unroll
-        for (int i = 0; i < DI; ++i) {
-          const float l8 = lam[i] * dt * 0.125f;
-          a1[i] = l8; a4[i] = l8; a2[i] = 3.f * l8; a3[i] = 3.f * l8; ay[i] = lam[i];
+          for (int i = 0; i < DI; ++i) {
+            const float l8 = lam[i] * dt * 0.125f;
+            a1[i] = l8; a4[i] = l8; a2[i] = 3.f * l8; a3[i] = 3.f * l8; ay[i] = lam[i];
+          }
+#pragma unroll
+          for (int i = 0; i < DI; ++i) x[i] = xt[3 * DI + i];
+          ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a4, g, af, &G);
+          if (wave == 0) store_vec<DO>(at + 3 * DO, af, lane);
+#pragma unroll
+          for (int i = 0; i < DI; ++i) { ay[i] += g[i]; a1[i] += dt * g[i]; a2[i] -= dt * g[i]; a3[i] += dt * g[i]; }
+#pragma unroll
+          for (int i = 0; i < DI; ++i) x[i] = xt[2 * DI + i];
+          ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a3, g, af, &G);
+          if (wave == 0) store_vec<DO>(at + 2 * DO, af, lane);
+#pragma unroll
+          for (int i = 0; i < DI; ++i) { ay[i] += g[i]; a2[i] += dt * g[i]; a1[i] -= dt * third * g[i]; }
+#pragma unroll
+          for (int i = 0; i < DI; ++i) x[i] = xt[1 * DI + i];
+          ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a2, g, af, &G);
+          if (wave == 0) store_vec<DO>(at + 1 * DO, af, lane);
+#pragma unroll
+          for (int i = 0; i < DI; ++i) { ay[i] += g[i]; a1[i] += dt * third * g[i]; }
+#pragma unroll
+          for (int i = 0; i < DI; ++i) x[i] = xt[i];
+          ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a1, g, af, &G);
+          if (wave == 0) store_vec<DO>(at, af, lane);
+#pragma unroll
+          for (int i = 0; i < DI; ++i) lam[i] = ay[i] + g[i];
         }
-#pragma unroll
-        for (int i = 0; i < DI; ++i) x[i] = xt[3 * DI + i];
-        ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a4, g, af, &G);
-        if (wave == 0) store_vec<DO>(at + 3 * DO, af, lane);
-#pragma unroll
-        for (int i = 0; i < DI; ++i) { ay[i] += g[i]; a1[i] += dt * g[i]; a2[i] -= dt * g[i]; a3[i] += dt * g[i]; }
-#pragma unroll
-        for (int i = 0; i < DI; ++i) x[i] = xt[2 * DI + i];
-        ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a3, g, af, &G);
-        if (wave == 0) store_vec<DO>(at + 2 * DO, af, lane);
-#pragma unroll
-        for (int i = 0; i < DI; ++i) { ay[i] += g[i]; a2[i] += dt * g[i]; a1[i] -= dt * third * g[i]; }
-#pragma unroll
-        for (int i = 0; i < DI; ++i) x[i] = xt[1 * DI + i];
-        ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a2, g, af, &G);
-        if (wave == 0) store_vec<DO>(at + 1 * DO, af, lane);
-#pragma unroll
-        for (int i = 0; i < DI; ++i) { ay[i] += g[i]; a1[i] += dt * third * g[i]; }
-#pragma unroll
-        for (int i = 0; i < DI; ++i) x[i] = xt[i];
-        ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a1, g, af, &G);
-        if (wave == 0) store_vec<DO>(at, af, lane);
-#pragma unroll
-        for (int i = 0; i < DI; ++i) lam[i] = ay[i] + g[i];
       }
 #pragma unroll
       for (int i = 0; i < DI; ++i) lam[i] += gz[(size_t)t * DI + i];
@@ -655,10 +660,12 @@ int rollout_bwd(int kernel, int order, int method, int Di, int Do, int M, int S,
         constexpr int ORDER = decltype(o)::value, METHOD = decltype(m)::value;
         return reverse_route<KERNEL, DI, DO>(N, M, S, [&](auto ev, const LaunchGeom& g) {
           using EV = typename decltype(ev)::type;
-          if (launch_route(rollout_bwd_team_kernel<EV, DI, DO, ORDER, METHOD>, g, dw.nd, st, pack, M, S, xstage, gzt, ts, N, T, gz0, astage, dw,
-                           (float*)nullptr, (size_t)0))
-            return 1;
-          return check_launch(tags[KERNEL][g.route]);
+          return dispatch_substeps(dw.sub, [&](auto sb) {
+            if (launch_route(rollout_bwd_team_kernel<EV, DI, DO, ORDER, METHOD, false, decltype(sb)::value>, g, dw.nd, st, pack, M, S, xstage, gzt,
+                             ts, N, T, gz0, astage, dw, (float*)nullptr, (size_t)0))
+              return 1;
+            return check_launch(tags[KERNEL][g.route]);
+          });
         });
       });
     });
@@ -696,10 +703,14 @@ int rollout_bwd_pgrad(int kernel, int order, int method, int Di, int Do, int M, 
   if (cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
   const int done = pgrad_width(kernel, Do, [&](auto d) {
     constexpr int D = decltype(d)::value;
-    if (method == 0) hipLaunchKernelGGL((rollout_bwd_team_kernel<RbfTeamEval<D, D, 1>, D, D, 1, 0, true>), dim3(grid, dw.nd), 256, 0, st,
-                                        pack, M, S, xstage, gzt, ts, N, T, gz0, astage, dw, slab, pf);
-    else hipLaunchKernelGGL((rollout_bwd_team_kernel<RbfTeamEval<D, D, 1>, D, D, 1, 1, true>), dim3(grid, dw.nd), 256, 0, st,
-                            pack, M, S, xstage, gzt, ts, N, T, gz0, astage, dw, slab, pf);
+    dispatch_substeps(dw.sub, [&](auto sb) {
+      constexpr bool SUB = decltype(sb)::value;
+      if (method == 0) hipLaunchKernelGGL((rollout_bwd_team_kernel<RbfTeamEval<D, D, 1>, D, D, 1, 0, true, SUB>), dim3(grid, dw.nd), 256, 0, st,
+                                          pack, M, S, xstage, gzt, ts, N, T, gz0, astage, dw, slab, pf);
+      else hipLaunchKernelGGL((rollout_bwd_team_kernel<RbfTeamEval<D, D, 1>, D, D, 1, 1, true, SUB>), dim3(grid, dw.nd), 256, 0, st,
+                              pack, M, S, xstage, gzt, ts, N, T, gz0, astage, dw, slab, pf);
+      return 0;
+    });
     return 1;
   });
   if (!done) return set_error("gpode_rollout_bwd_pgrad: width %d not built", Do);

@@ -44,9 +44,10 @@ __global__ __launch_bounds__(256) void rhs_kernel(const float* __restrict__ pack
 }
 
 
-// z0 (N,DI), ts (T) or (N,T) [dw.ts = T] -> zt (N,T,DI).  One wave per trajectory, persistent over the T-1 steps.
+// z0 (N,DI), ts (T) or (N,T) [dw.ts = T] -> zt (N,T,DI).  One wave per trajectory, persistent over the T-1 output intervals, each
+// taken in one step (SUB = false: the kernel as it always was) or in dw.sub equal steps (xstage: (N, T-1, sub, NS, DI), the stage inputs of every step).
 // Stage algebra follows torchdiffeq's fixed-grid solvers at flow.py:76-85 (3/8-rule rk4).
-template <class EV, int DI, int DO, int ORDER, int METHOD, bool USE_LDS>
+template <class EV, int DI, int DO, int ORDER, int METHOD, bool USE_LDS, bool SUB>
 __global__ __launch_bounds__(256) void rollout_kernel(const float* __restrict__ pack, int M, int S, size_t lds_f4,
                                const float* __restrict__ z0, const float* __restrict__ ts, int N, int T,
                                float* __restrict__ zt, float* __restrict__ xstage, Draws dw) {
@@ -60,46 +61,49 @@ __global__ __launch_bounds__(256) void rollout_kernel(const float* __restrict__ 
   EV ev;
   ev.init(pack, M, S, lane);
   const float third = (float)(1.0 / 3.0);
+  const int sub = sub_count<SUB>(dw.sub);
   for (int n = blockIdx.x * wpb + wave; n < N; n += gridDim.x * wpb) {
     float y[DI];
 #pragma unroll
     for (int i = 0; i < DI; ++i) y[i] = z0[(size_t)n * DI + i];
     float* out = zt + (size_t)n * T * DI;
-    float* xs_out = xstage ? xstage + (size_t)n * (T - 1) * NS * DI : nullptr;
+    float* xs_out = xstage ? xstage + (size_t)n * (T - 1) * sub * NS * DI : nullptr;
     store_state<DI>(out, y, lane);
     const float* tn = ts_row(ts, n, dw.ts);
     for (int t = 0; t + 1 < T; ++t) {
-      const float dt = tn[t + 1] - tn[t];
-      float k1[DI];
-      if (xs_out) store_state<DI>(xs_out + (size_t)(t * NS) * DI, y, lane);
-      ode_rhs<EV, DI, DO, ORDER>(ev, y, k1);
-      if (METHOD == 0) {
+      const float dt = sub_step<SUB>(tn[t], tn[t + 1], sub);
+      for (int r = t * sub; r < (t + 1) * sub; ++r) {   // r: the step's row block of the record, (T-1, sub, NS, DI)
+        float k1[DI];
+        if (xs_out) store_state<DI>(xs_out + (size_t)(r * NS) * DI, y, lane);
+        ode_rhs<EV, DI, DO, ORDER>(ev, y, k1);
+        if (METHOD == 0) {
 #pragma unroll
-        for (int i = 0; i < DI; ++i) y[i] = y[i] + dt * k1[i];
-      } else if (METHOD == 2) {                      // midpoint: y1 = y + dt f(y + dt/2 f(y))
-        float k2[DI], xs[DI];
+          for (int i = 0; i < DI; ++i) y[i] = y[i] + dt * k1[i];
+        } else if (METHOD == 2) {                      // midpoint: y1 = y + dt f(y + dt/2 f(y))
+          float k2[DI], xs[DI];
 #pragma unroll
-        for (int i = 0; i < DI; ++i) xs[i] = y[i] + 0.5f * dt * k1[i];
-        if (xs_out) store_state<DI>(xs_out + (size_t)(t * NS + 1) * DI, xs, lane);
-        ode_rhs<EV, DI, DO, ORDER>(ev, xs, k2);
+          for (int i = 0; i < DI; ++i) xs[i] = y[i] + 0.5f * dt * k1[i];
+          if (xs_out) store_state<DI>(xs_out + (size_t)(r * NS + 1) * DI, xs, lane);
+          ode_rhs<EV, DI, DO, ORDER>(ev, xs, k2);
 #pragma unroll
-        for (int i = 0; i < DI; ++i) y[i] = y[i] + dt * k2[i];
-      } else {
-        float k2[DI], k3[DI], k4[DI], xs[DI];
+          for (int i = 0; i < DI; ++i) y[i] = y[i] + dt * k2[i];
+        } else {
+          float k2[DI], k3[DI], k4[DI], xs[DI];
 #pragma unroll
-        for (int i = 0; i < DI; ++i) xs[i] = y[i] + dt * k1[i] * third;
-        if (xs_out) store_state<DI>(xs_out + (size_t)(t * NS + 1) * DI, xs, lane);
-        ode_rhs<EV, DI, DO, ORDER>(ev, xs, k2);
+          for (int i = 0; i < DI; ++i) xs[i] = y[i] + dt * k1[i] * third;
+          if (xs_out) store_state<DI>(xs_out + (size_t)(r * NS + 1) * DI, xs, lane);
+          ode_rhs<EV, DI, DO, ORDER>(ev, xs, k2);
 #pragma unroll
-        for (int i = 0; i < DI; ++i) xs[i] = y[i] + dt * (k2[i] - k1[i] * third);
-        if (xs_out) store_state<DI>(xs_out + (size_t)(t * NS + 2) * DI, xs, lane);
-        ode_rhs<EV, DI, DO, ORDER>(ev, xs, k3);
+          for (int i = 0; i < DI; ++i) xs[i] = y[i] + dt * (k2[i] - k1[i] * third);
+          if (xs_out) store_state<DI>(xs_out + (size_t)(r * NS + 2) * DI, xs, lane);
+          ode_rhs<EV, DI, DO, ORDER>(ev, xs, k3);
 #pragma unroll
-        for (int i = 0; i < DI; ++i) xs[i] = y[i] + dt * (k1[i] - k2[i] + k3[i]);
-        if (xs_out) store_state<DI>(xs_out + (size_t)(t * NS + 3) * DI, xs, lane);
-        ode_rhs<EV, DI, DO, ORDER>(ev, xs, k4);
+          for (int i = 0; i < DI; ++i) xs[i] = y[i] + dt * (k1[i] - k2[i] + k3[i]);
+          if (xs_out) store_state<DI>(xs_out + (size_t)(r * NS + 3) * DI, xs, lane);
+          ode_rhs<EV, DI, DO, ORDER>(ev, xs, k4);
 #pragma unroll
-        for (int i = 0; i < DI; ++i) y[i] = y[i] + (k1[i] + 3.f * (k2[i] + k3[i]) + k4[i]) * dt * 0.125f;
+          for (int i = 0; i < DI; ++i) y[i] = y[i] + (k1[i] + 3.f * (k2[i] + k3[i]) + k4[i]) * dt * 0.125f;
+        }
       }
       store_state<DI>(out + (size_t)(t + 1) * DI, y, lane);
     }
@@ -131,7 +135,7 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rhs_team_kernel(const float* _
 }
 
 
-template <class EV, int DI, int DO, int ORDER, int METHOD>
+template <class EV, int DI, int DO, int ORDER, int METHOD, bool SUB>
 __global__ __launch_bounds__(64 * EV::kTeam) void rollout_team_kernel(const float* __restrict__ pack, int M, int S,
                                                             const float* __restrict__ z0, const float* __restrict__ ts,
                                                             int N, int T, float* __restrict__ zt, float* __restrict__ xstage, Draws dw) {
@@ -145,46 +149,49 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rollout_team_kernel(const floa
   EV ev;
   ev.init(pack, M, S, slots, wave, lane);
   const float third = (float)(1.0 / 3.0);
+  const int sub = sub_count<SUB>(dw.sub);
   for (int n = blockIdx.x; n < N; n += gridDim.x) {
     float y[DI];
 #pragma unroll
     for (int i = 0; i < DI; ++i) y[i] = z0[(size_t)n * DI + i];
     float* out = zt + (size_t)n * T * DI;
-    float* xs_out = (xstage && wave == 0) ? xstage + (size_t)n * (T - 1) * NS * DI : nullptr;
+    float* xs_out = (xstage && wave == 0) ? xstage + (size_t)n * (T - 1) * sub * NS * DI : nullptr;
     if (wave == 0) store_state<DI>(out, y, lane);
     const float* tn = ts_row(ts, n, dw.ts);
     for (int t = 0; t + 1 < T; ++t) {
-      const float dt = tn[t + 1] - tn[t];
-      float k1[DI];
-      if (xs_out) store_state<DI>(xs_out + (size_t)(t * NS) * DI, y, lane);
-      ode_rhs_mut<EV, DI, DO, ORDER>(ev, y, k1);
-      if (METHOD == 0) {
+      const float dt = sub_step<SUB>(tn[t], tn[t + 1], sub);
+      for (int r = t * sub; r < (t + 1) * sub; ++r) {   // r: the step's row block of the record, (T-1, sub, NS, DI)
+        float k1[DI];
+        if (xs_out) store_state<DI>(xs_out + (size_t)(r * NS) * DI, y, lane);
+        ode_rhs_mut<EV, DI, DO, ORDER>(ev, y, k1);
+        if (METHOD == 0) {
 #pragma unroll
-        for (int i = 0; i < DI; ++i) y[i] = y[i] + dt * k1[i];
-      } else if (METHOD == 2) {                      // midpoint
-        float k2[DI], xs[DI];
+          for (int i = 0; i < DI; ++i) y[i] = y[i] + dt * k1[i];
+        } else if (METHOD == 2) {                      // midpoint
+          float k2[DI], xs[DI];
 #pragma unroll
-        for (int i = 0; i < DI; ++i) xs[i] = y[i] + 0.5f * dt * k1[i];
-        if (xs_out) store_state<DI>(xs_out + (size_t)(t * NS + 1) * DI, xs, lane);
-        ode_rhs_mut<EV, DI, DO, ORDER>(ev, xs, k2);
+          for (int i = 0; i < DI; ++i) xs[i] = y[i] + 0.5f * dt * k1[i];
+          if (xs_out) store_state<DI>(xs_out + (size_t)(r * NS + 1) * DI, xs, lane);
+          ode_rhs_mut<EV, DI, DO, ORDER>(ev, xs, k2);
 #pragma unroll
-        for (int i = 0; i < DI; ++i) y[i] = y[i] + dt * k2[i];
-      } else {
-        float k2[DI], k3[DI], k4[DI], xs[DI];
+          for (int i = 0; i < DI; ++i) y[i] = y[i] + dt * k2[i];
+        } else {
+          float k2[DI], k3[DI], k4[DI], xs[DI];
 #pragma unroll
-        for (int i = 0; i < DI; ++i) xs[i] = y[i] + dt * k1[i] * third;
-        if (xs_out) store_state<DI>(xs_out + (size_t)(t * NS + 1) * DI, xs, lane);
-        ode_rhs_mut<EV, DI, DO, ORDER>(ev, xs, k2);
+          for (int i = 0; i < DI; ++i) xs[i] = y[i] + dt * k1[i] * third;
+          if (xs_out) store_state<DI>(xs_out + (size_t)(r * NS + 1) * DI, xs, lane);
+          ode_rhs_mut<EV, DI, DO, ORDER>(ev, xs, k2);
 #pragma unroll
-        for (int i = 0; i < DI; ++i) xs[i] = y[i] + dt * (k2[i] - k1[i] * third);
-        if (xs_out) store_state<DI>(xs_out + (size_t)(t * NS + 2) * DI, xs, lane);
-        ode_rhs_mut<EV, DI, DO, ORDER>(ev, xs, k3);
+          for (int i = 0; i < DI; ++i) xs[i] = y[i] + dt * (k2[i] - k1[i] * third);
+          if (xs_out) store_state<DI>(xs_out + (size_t)(r * NS + 2) * DI, xs, lane);
+          ode_rhs_mut<EV, DI, DO, ORDER>(ev, xs, k3);
 #pragma unroll
-        for (int i = 0; i < DI; ++i) xs[i] = y[i] + dt * (k1[i] - k2[i] + k3[i]);
-        if (xs_out) store_state<DI>(xs_out + (size_t)(t * NS + 3) * DI, xs, lane);
-        ode_rhs_mut<EV, DI, DO, ORDER>(ev, xs, k4);
+          for (int i = 0; i < DI; ++i) xs[i] = y[i] + dt * (k1[i] - k2[i] + k3[i]);
+          if (xs_out) store_state<DI>(xs_out + (size_t)(r * NS + 3) * DI, xs, lane);
+          ode_rhs_mut<EV, DI, DO, ORDER>(ev, xs, k4);
 #pragma unroll
-        for (int i = 0; i < DI; ++i) y[i] = y[i] + (k1[i] + 3.f * (k2[i] + k3[i]) + k4[i]) * dt * 0.125f;
+          for (int i = 0; i < DI; ++i) y[i] = y[i] + (k1[i] + 3.f * (k2[i] + k3[i]) + k4[i]) * dt * 0.125f;
+        }
       }
       if (wave == 0) store_state<DI>(out + (size_t)(t + 1) * DI, y, lane);
     }
@@ -228,14 +235,17 @@ int rollout_fwd(int kernel, int order, int method, int Di, int Do, int M, int S,
         return forward_route<KERNEL, DI, DO>(N, M, S, [&](auto ev, auto map, const LaunchGeom& g) {
           using EV = typename decltype(ev)::type;
           constexpr int MAP = decltype(map)::value;
-          if constexpr (MAP == kTeam) {
-            if (launch_route(rollout_team_kernel<EV, DI, DO, ORDER, METHOD>, g, dw.nd, st, pack, M, S, z0, ts, N, T, zt, xstage, dw)) return 1;
-          } else {
-            if (launch_route(rollout_kernel<EV, DI, DO, ORDER, METHOD, MAP == kWaveLds>, g, dw.nd, st, pack, M, S, g.lds_f4, z0, ts, N, T, zt,
-                             xstage, dw))
-              return 1;
-          }
-          return check_launch(tags[KERNEL][g.route]);
+          return dispatch_substeps(dw.sub, [&](auto sb) {
+            constexpr bool SUB = decltype(sb)::value;
+            if constexpr (MAP == kTeam) {
+              if (launch_route(rollout_team_kernel<EV, DI, DO, ORDER, METHOD, SUB>, g, dw.nd, st, pack, M, S, z0, ts, N, T, zt, xstage, dw)) return 1;
+            } else {
+              if (launch_route(rollout_kernel<EV, DI, DO, ORDER, METHOD, MAP == kWaveLds, SUB>, g, dw.nd, st, pack, M, S, g.lds_f4, z0, ts, N, T,
+                               zt, xstage, dw))
+                return 1;
+            }
+            return check_launch(tags[KERNEL][g.route]);
+          });
         });
       });
     });

@@ -72,10 +72,14 @@ inline int num_cus() {
 // handed to the prior-only rhs, the initial states z0 of a rollout).  Which operand each stride belongs to is listed per entry point.
 // ts: floats between the time grids of consecutive TRAJECTORIES (not draws: a grid belongs to the sequence), 0 = one (T,) grid shared
 // by all of them, T = one row of a dense (N,T) block each.  Read by the fixed-grid rollout and its reverse sweep only.
+// sub: equal solver steps per output interval [ts[t], ts[t+1]] (1 ... kMaxSubsteps), read by the same two; the record of an interval
+// is then `sub` row blocks (T-1, sub, NS, D), and nothing between the output times reaches zt.
+static const int kMaxSubsteps = 64;
 struct Draws {
   int nd = 1;
   size_t pack = 0, in = 0, out = 0, in2 = 0, out2 = 0;
   size_t ts = 0;
+  int sub = 1;
 };
 
 // entry points implemented across the .hip files

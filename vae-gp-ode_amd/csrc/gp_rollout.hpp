@@ -160,6 +160,19 @@ __device__ __forceinline__ const float* ts_row(const float* __restrict__ ts, int
   return ts + (size_t)__builtin_amdgcn_readfirstlane(n) * stride;
 }
 
+// Sub-steps: two instantiations of each rollout kernel.  SUB = false is the kernel as it always was -- one step per output interval,
+// the count a compile-time 1, so that the loop over the steps of an interval folds away and the launches with one step run the code
+// they always ran; SUB = true reads the count from Draws::sub (measured: a run-time count in ONE instantiation cost every one-step
+// launch 3 us at configs[0] and 6 us at configs[1]).  dispatch_substeps chooses on the host.
+template <bool SUB> __device__ __forceinline__ int sub_count(int sub) { return SUB ? sub : 1; }
+// The solver step inside the output interval [t0, t1] cut into `sub` equal steps: ONE fp32 division per interval, so that any sub gives
+// the refined grid's own differences wherever those are exact in fp32 (a product with a rounded 1/sub would not).  Wave-uniform like
+// its operands: read through the first lane the quotient stays a scalar.
+template <bool SUB> __device__ __forceinline__ float sub_step(float t0, float t1, int sub) {
+  if constexpr (!SUB) return t1 - t0;
+  else return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((t1 - t0) / (float)sub)));
+}
+
 template <int DI> __device__ __forceinline__ void store_state(float* __restrict__ dst, const float (&y)[DI], int lane) {
   if (lane < DI) {
     float v = y[0];
@@ -325,6 +338,14 @@ template <int DI, int DO, class F> static int dispatch_order(const char* who, in
   if constexpr (DI == DO) { if (order == 1) return f(int_c<1>{}); }
   if constexpr (DI == 2 * DO) { if (order == 2) return f(int_c<2>{}); }
   return set_error("%s: order=%d needs Di == order*Do (Di=%d Do=%d)", who, order, DI, DO);
+}
+
+// One step per output interval (the kernels as they always were) or Draws::sub of them: f(std::bool_constant<SUB>).
+// force_substep_kernels (capi.hip, gpode_test_substep_kernels): a door for tests, shut unless a test opens it, that sends a count of 1
+// through the SUB = true instantiation as well -- the way to hold that instantiation to itself on a refined grid.
+bool* force_substep_kernels();
+template <class F> static int dispatch_substeps(int sub, F&& f) {
+  return sub == 1 && !*force_substep_kernels() ? f(std::false_type{}) : f(std::true_type{});
 }
 
 // The fixed-grid solver, 0 euler, 1 rk4, 2 midpoint (the caller has refused every other value): f(int_c<METHOD>).

@@ -426,10 +426,11 @@ def _subsampled(args, loader):
 
 
 def main(argv=None):
-    from .main import check_ragged, check_subsample
+    from .main import check_dense_scale, check_ragged, check_subsample
     args = make_parser().parse_args(argv)
     check_subsample(args)
     check_ragged(args)
+    check_dense_scale(args)
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
         raise SystemExit('vae_gp_ode_amd.evaluate is a single-process tool: data-parallel evaluation is not built '
                          '(start it without torchrun, or with one rank)')

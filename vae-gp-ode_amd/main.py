@@ -45,7 +45,8 @@ FLAGS = [
     ('q_diag', eval, False, 'Diagonal posterior approximation for inducing variables'),
     ('ode', int, 1, 'order of ODE'), ('D_in', int, 6, 'ODE f(x) input dimensionality'), ('D_out', int, 6, 'ODE f(x) output dimensionality'),
     ('solver', str, 'euler', 'ODE solver for numerical integration'),
-    ('ts_dense_scale', int, 2, 'Factor for making a dense integration time grid'),
+    ('ts_dense_scale', int, 2, 'Factor for making a dense integration time grid (useful for explicit solvers): euler, midpoint and '
+                               'rk4 take max(scale - 1, 1) equal steps inside every output interval; at most 65'),
     ('use_adjoint', eval, False, 'Use adjoint method for gradient computation'), ('dt', float, 0.1, 'numerical solver dt'),
     ('Nepoch', int, 5000, 'Number of gradient steps for model training'), ('lr', float, 0.001, 'Learning rate for model training'),
     ('eval_sample_size', int, 128, 'Number of posterior samples to evaluate the model predictive performance'),
@@ -153,6 +154,13 @@ def check_ragged(args):
                          'at most %s %d' % (kmin, lead, args.ode, '--subsample_frames' if args.subsample_frames else '--T', kmax))
 
 
+def check_dense_scale(args):
+    """--ts_dense_scale: the solver steps per output interval it stands for (1 up to 2); refused with a message above 65, ahead of any
+    device work"""
+    from .model.core.flow import substeps_of_dense_scale
+    return substeps_of_dense_scale(args.ts_dense_scale)
+
+
 def check_ragged_compact(args):
     """--ragged_compact True: needs --ragged_frames, eager steps and one rank; refused with a message otherwise, ahead of any device work"""
     if not args.ragged_compact:
@@ -247,6 +255,7 @@ def main(argv=None):
     check_subsample(args)
     check_ragged(args)
     check_ragged_compact(args)
+    check_dense_scale(args)
     from .model.core.initialization import initialize_and_fix_kernel_parameters
     from .model.create_model import build_model, compute_loss, compute_test_error, backward
     from .model.misc.torch_utils import seed_everything
@@ -283,6 +292,9 @@ def main(argv=None):
         model.vae.decoder.eval()
         logger.info('***** Loaded pretrained VAE from {} ********'.format(args.vae_path))
     logger.info('********** Model Built {} ODE **********'.format(args.ode))
+    if model.flow.substeps > 1:
+        logger.info('--ts_dense_scale {}: {} {} steps inside every output interval{}'.format(
+            args.ts_dense_scale, model.flow.substeps, args.solver, ' (ignored by dopri5)' if args.solver == 'dopri5' else ''))
     if args.continue_training:
         fname = os.path.join(os.path.abspath(os.getcwd()), args.model_path, 'odegpvae_mnist.pth')
         model.load_state_dict(torch.load(fname, map_location=args.device))

@@ -7,7 +7,10 @@ team of four) integrates one trajectory over the whole grid.  Solvers: the fixed
 (csrc/gp_adaptive.hip: Dormand-Prince 5(4), one step-size controller per trajectory, steps landing
 on ``ts`` -- it agrees with torchdiffeq's to the tolerances, not step by step; with
 ``dense_output`` the steps are free of ``ts`` and the outputs are interpolated, as torchdiffeq
-does).  The rest of the
+does).  The fixed-grid solvers take ``substeps`` equal steps inside every interval of ``ts``
+(1 by default; the reference's --ts_dense_scale, torchdiffeq's options=dict(step_size=...)), so
+that where the observations are does not set the step size; nothing between the output times is
+stored or returned.  The rest of the
 reference's --solver list (bdf, adams, explicit_adams, fixed_adams) is refused: ops.REFUSED_SOLVERS.
 """
 import os
@@ -88,8 +91,23 @@ def dense_output_default():
     return os.environ.get('GPODE_DOPRI5_DENSE', '0').strip() not in ('', '0')
 
 
+def substeps_of_dense_scale(ts_dense_scale):
+    """--ts_dense_scale -> solver steps per output interval, with the reference's meaning: compute_ts_dense (torch_utils.py) places
+    linspace(t1, t2, scale)[:-1] in every interval -- scale - 1 steps -- and leaves the grid alone for scale <= 2."""
+    sub = max(int(ts_dense_scale) - 1, 1)
+    if sub > ops.MAX_SUBSTEPS:
+        raise SystemExit('--ts_dense_scale %d asks for %d solver steps per output interval; at most %d (--ts_dense_scale %d) are built'
+                         % (ts_dense_scale, sub, ops.MAX_SUBSTEPS, ops.MAX_SUBSTEPS + 1))
+    return sub
+
+
 class Flow(nn.Module):
-    def __init__(self, diffeq, order=2, solver='dopri5', atol=1e-6, rtol=1e-6, use_adjoint=False, max_steps=None, dense_output=None):
+    def __init__(self, diffeq, order=2, solver='dopri5', atol=1e-6, rtol=1e-6, use_adjoint=False, max_steps=None, dense_output=None,
+                 substeps=1):
+        """``substeps`` (an int in 1 ... ops.MAX_SUBSTEPS): read by 'euler', 'midpoint' and 'rk4' only, and ignored by 'dopri5', as
+        ``atol`` / ``rtol`` / ``max_steps`` / ``dense_output`` are ignored by the others.  Every interval [ts[t], ts[t+1]] of every
+        trajectory is integrated in ``substeps`` equal steps; the outputs stay at ``ts``.  Time grids per sequence, z0 per draw and
+        several draws work with it unchanged; 1 is the launch it always was."""
         super().__init__()
         self.odefunc = ODEfunc(diffeq, order)
         self.solver = solver
@@ -101,6 +119,7 @@ class Flow(nn.Module):
         # dopri5: steps cut at ts[-1] only, interior outputs interpolated.  None = the environment decides (GPODE_DOPRI5_DENSE,
         # unset or 0: off), so that everything built through build_model can be switched without a flag; ignored by fixed grids
         self.dense_output = dense_output_default() if dense_output is None else bool(dense_output)
+        self.substeps = substeps
         self._last_counts = None
 
     def forward(self, z0, ts, draws=None):
@@ -120,8 +139,8 @@ class Flow(nn.Module):
         if self.solver == 'dopri5':
             return ops.flow(gp, z0, ts, self.odefunc.order, self.solver, draws,
                             (self.rtol, self.atol, self.max_steps, self._take_counts, bool(self.dense_output)))
-        zt = ops.flow(gp, z0, ts, self.odefunc.order, self.solver, draws)
-        self.odefunc._set_evals(EVALS_PER_STEP[self.solver] * (ts.shape[-1] - 1))
+        zt = ops.flow(gp, z0, ts, self.odefunc.order, self.solver, draws, substeps=self.substeps)
+        self.odefunc._set_evals(EVALS_PER_STEP[self.solver] * (ts.shape[-1] - 1) * self.substeps)
         return zt
 
     def _take_counts(self, counts):

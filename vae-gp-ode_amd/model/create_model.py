@@ -4,7 +4,7 @@ import os
 import torch
 from torch.distributions import kl_divergence as kl
 
-from .core.flow import Flow
+from .core.flow import Flow, substeps_of_dense_scale
 from .core.odegpvae import ODEGPVAE
 from .core.svpy import SVGP_Layer
 from .core.vae import VAE
@@ -15,11 +15,14 @@ _FUSED_LOSS = os.environ.get('GPODE_UNFUSED_LOSS', '0') != '1'
 
 def build_model(args):
     """GP vector field -> Flow -> VAE -> ODEGPVAE from the argument namespace of main.py (create_model.py:16-33 reads the
-    same fields).  The construction order fixes the order of the numpy draws that initialise the GP parameters."""
+    same fields).  The construction order fixes the order of the numpy draws that initialise the GP parameters.
+    ``ts_dense_scale`` (optional, 2 when absent): scale - 1 solver steps per output interval for the fixed-grid solvers; a value the
+    kernels are not built for exits here, ahead of any device work."""
     a = args
+    substeps = substeps_of_dense_scale(getattr(a, 'ts_dense_scale', 2))
     field = SVGP_Layer(a.D_in, a.D_out, a.num_inducing, a.num_features, q_diag=a.q_diag, dimwise=a.dimwise, device=a.device,
                        kernel=a.kernel)
-    return ODEGPVAE(flow=Flow(field, order=a.ode, solver=a.solver, use_adjoint=a.use_adjoint),
+    return ODEGPVAE(flow=Flow(field, order=a.ode, solver=a.solver, use_adjoint=a.use_adjoint, substeps=substeps),
                     vae=VAE(frames=a.frames, n_filt=a.n_filt, latent_dim=a.latent_dim, device=a.device, order=a.ode),
                     num_observations=a.Ndata, steps=a.frames, order=a.ode, dt=a.dt)
 

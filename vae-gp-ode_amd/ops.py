@@ -357,6 +357,31 @@ def _rollout_args(cache, z0, ts, order):
     return z0, ts, zpd, tpt, N, D
 
 
+MAX_SUBSTEPS = 64
+
+
+def _substeps(substeps, method):
+    """The fixed-grid solvers' steps per output interval: an int in 1 ... MAX_SUBSTEPS (checked here, ahead of any library call); dopri5
+    chooses its own steps and takes 1 only."""
+    if isinstance(substeps, bool) or not isinstance(substeps, int) or not 1 <= substeps <= MAX_SUBSTEPS:
+        raise _lib.GpodeError('substeps must be an int in 1 ... %d, got %r' % (MAX_SUBSTEPS, substeps))
+    if substeps != 1 and method == 'dopri5':
+        raise _lib.GpodeError('substeps=%d: dopri5 chooses its own steps (sub-steps belong to euler, midpoint and rk4)' % substeps)
+    return substeps
+
+
+def _sub_axis(sub):
+    """the sub-step axis of a record: absent at one step per interval, where the record keeps the shape it always had"""
+    return () if sub == 1 else (sub,)
+
+
+def _sub_record(xstage, head, sub, NS, D):
+    """xstage of a reverse sweep with sub-steps must be the whole record head + (sub, NS, D): the sweep indexes it by that layout"""
+    if sub != 1 and tuple(xstage.shape) != head + (sub, NS, D):
+        raise _lib.GpodeError('xstage: expected %s for substeps=%d, got %s' % (head + (sub, NS, D), sub, tuple(xstage.shape)))
+    return xstage
+
+
 def _gzt_lead(cache, gzt):
     """gzt ([L,] N,T,D) of rollout_bwd and rollout_adaptive_bwd, contiguous, and the leading draw axis of the cache it must carry"""
     gzt = _chk(gzt, 'gzt')
@@ -430,16 +455,19 @@ def rollout_adaptive_bwd(cache, xstage, hstep, iend, gzt, order, theta=None):
     return gz0, ast
 
 
-def rollout(cache, z0, ts, order, method, save_stages=False, rtol=1e-6, atol=1e-6, max_steps=None, dense=False):
+def rollout(cache, z0, ts, order, method, save_stages=False, rtol=1e-6, atol=1e-6, max_steps=None, dense=False, substeps=1):
     """Flow.forward (flow.py:68-86) for a built cache: z0 (N,D), ts (T,) -> zt (N,T,D); a cache of L draws integrates all L * N
     trajectories in ONE launch -> zt (L,N,T,D) (the stack of odegpvae.py:41-44).  z0 (L,N,D) with L = the draws of the cache: draw l
     starts from z0[l] (gpode_rollout_fwd_nz) -- joint samples of the initial state and the function.
     ts (N,T): trajectory n of every draw is integrated over its own grid ts[n] (gpode_rollout_fwd_nt).
     save_stages=True also returns the inputs of all RHS evaluations ([L,] N,T-1,NS,D) for the reverse sweep.
+    substeps = s > 1 (euler, midpoint, rk4; gpode_rollout_fwd_ns): every output interval is integrated in s equal steps; zt stays
+    at ts and the record becomes ([L,] N,T-1,s,NS,D).
     method 'dopri5' (the only one that reads rtol / atol / max_steps / dense) is rollout_adaptive(): with save_stages the second value
     is its record (xstage, hstep, iend, counts), which rollout_bwd takes in place of xstage; in dense-output mode the record is
     (xstage, hstep, istep, counts, theta)."""
     check_solver(method)
+    sub = _substeps(substeps, method)
     if method == 'dopri5':
         out = rollout_adaptive(cache, z0, ts, order, rtol, atol, max_steps, save_stages, dense=dense)
         return (out[0], (out[2], out[3], out[4], out[1]) + tuple(out[5:])) if save_stages else out[0]
@@ -447,10 +475,13 @@ def rollout(cache, z0, ts, order, method, save_stages=False, rtol=1e-6, atol=1e-
     T = ts.shape[-1]
     lead = cache.lead
     zt = torch.empty(lead + (N, T, D), dtype=torch.float32, device=z0.device)
-    xs = torch.empty(lead + (N, max(T - 1, 0), NSTAGE[method], D), dtype=torch.float32, device=z0.device) if save_stages else None
+    xs = torch.empty(lead + (N, max(T - 1, 0)) + _sub_axis(sub) + (NSTAGE[method], D), dtype=torch.float32,
+                     device=z0.device) if save_stages else None
     head = (KERNEL_ID[cache.kernel], order, METHOD_ID[method], cache.Di, cache.Do, cache.M, cache.S, cache.nd, _ptr(cache.pack), _ptr(z0),
             _ptr(ts), N, T, _ptr(zt), _ptr(xs))
-    if tpt:
+    if sub != 1:
+        _lib.call('gpode_rollout_fwd_ns', *head, zpd, tpt, sub, _stream())
+    elif tpt:
         _lib.call('gpode_rollout_fwd_nt', *head, zpd, tpt, _stream())
     elif zpd:
         _lib.call('gpode_rollout_fwd_nz', *head, zpd, _stream())
@@ -459,19 +490,24 @@ def rollout(cache, z0, ts, order, method, save_stages=False, rtol=1e-6, atol=1e-
     return (zt, xs) if save_stages else zt
 
 
-def rollout_bwd(cache, xstage, gzt, ts, order, method):
+def rollout_bwd(cache, xstage, gzt, ts, order, method, substeps=1):
     """Reverse sweep: gzt ([L,] N,T,D) -> gz0 ([L,] N,D), astage ([L,] N,T-1,NS,Do) (dopri5: xstage is rollout's record, astage
-    ([L,] N,K,6,Do), or ([L,] N,K,7,Do) for a dense-output record).  ts (T,) or (N,T) as in rollout (gpode_rollout_bwd_nt)."""
+    ([L,] N,K,6,Do), or ([L,] N,K,7,Do) for a dense-output record).  ts (T,) or (N,T) as in rollout (gpode_rollout_bwd_nt).
+    substeps = s > 1 as in rollout (gpode_rollout_bwd_ns): xstage ([L,] N,T-1,s,NS,D) -> astage ([L,] N,T-1,s,NS,Do)."""
+    sub = _substeps(substeps, method)
     if method == 'dopri5':
         return rollout_adaptive_bwd(cache, xstage[0], xstage[1], xstage[2], gzt, order, theta=xstage[4] if len(xstage) > 4 else None)
     (gzt, lead), xstage, ts = _gzt_lead(cache, gzt), _chk(xstage, 'xstage'), _chk(ts, 'ts')
     N, T, D = gzt.shape[-3:]
     tpt = _ts_per_traj(ts, N, T, rows='gzt %s' % (tuple(gzt.shape),))
     gz0 = torch.empty(lead + (N, D), dtype=torch.float32, device=gzt.device)
-    ast = torch.empty(lead + (N, T - 1, NSTAGE[method], cache.Do), dtype=torch.float32, device=gzt.device)
+    xstage = _sub_record(xstage, lead + (N, T - 1), sub, NSTAGE[method], D)
+    ast = torch.empty(lead + (N, T - 1) + _sub_axis(sub) + (NSTAGE[method], cache.Do), dtype=torch.float32, device=gzt.device)
     head = (KERNEL_ID[cache.kernel], order, METHOD_ID[method], cache.Di, cache.Do, cache.M, cache.S, cache.nd, _ptr(cache.pack),
             _ptr(xstage), _ptr(gzt), _ptr(ts), N, T, _ptr(gz0), _ptr(ast))
-    if tpt:
+    if sub != 1:
+        _lib.call('gpode_rollout_bwd_ns', *head, tpt, sub, _stream())
+    elif tpt:
         _lib.call('gpode_rollout_bwd_nt', *head, tpt, _stream())
     else:
         _lib.call('gpode_rollout_bwd_n', *head, _stream())
@@ -493,21 +529,25 @@ def pgrad_chunks(cache, N, order, method, force=False):
                                                       cache.S, int(N))
 
 
-def rollout_bwd_pgrad(cache, xstage, gzt, ts, order, method, nchunk, keep=None):
-    """rollout_bwd() and param_grad() in one pass over the rows (gpode_rollout_bwd_pgrad_n; ts (N,T): gpode_rollout_bwd_pgrad_nt):
-    -> gz0, astage, gpack ([L,] pack_floats)."""
+def rollout_bwd_pgrad(cache, xstage, gzt, ts, order, method, nchunk, keep=None, substeps=1):
+    """rollout_bwd() and param_grad() in one pass over the rows (gpode_rollout_bwd_pgrad_n; ts (N,T): gpode_rollout_bwd_pgrad_nt;
+    substeps > 1: gpode_rollout_bwd_pgrad_ns): -> gz0, astage, gpack ([L,] pack_floats)."""
+    sub = _substeps(substeps, method)
     gzt = _chk(gzt, 'gzt'); xstage = _chk(xstage, 'xstage'); ts = _chk(ts, 'ts')
     lead = cache.lead
     N, T, D = gzt.shape[-3:]
     tpt = _ts_per_traj(ts, N, T, rows='gzt %s' % (tuple(gzt.shape),))
     pf = cache.pack.shape[-1]
     gz0 = torch.empty(lead + (N, D), dtype=torch.float32, device=gzt.device)
-    ast = torch.empty(lead + (N, T - 1, NSTAGE[method], cache.Do), dtype=torch.float32, device=gzt.device)
+    xstage = _sub_record(xstage, lead + (N, T - 1), sub, NSTAGE[method], D)
+    ast = torch.empty(lead + (N, T - 1) + _sub_axis(sub) + (NSTAGE[method], cache.Do), dtype=torch.float32, device=gzt.device)
     slab = torch.empty(cache.nd * nchunk * pf, dtype=torch.float32, device=gzt.device)
     gpack = torch.empty(lead + (pf,), dtype=torch.float32, device=gzt.device)
     head = (KERNEL_ID[cache.kernel], order, METHOD_ID[method], cache.Di, cache.Do, cache.M, cache.S, cache.nd, _ptr(cache.pack),
             _ptr(xstage), _ptr(gzt), _ptr(ts), N, T, _ptr(gz0), _ptr(ast), _ptr(slab), nchunk, _ptr(gpack))
-    if tpt:
+    if sub != 1:
+        _lib.call('gpode_rollout_bwd_pgrad_ns', *head, tpt, sub, _stream())
+    elif tpt:
         _lib.call('gpode_rollout_bwd_pgrad_nt', *head, tpt, _stream())
     else:
         _lib.call('gpode_rollout_bwd_pgrad_n', *head, _stream())
@@ -713,10 +753,12 @@ class _Flow(torch.autograd.Function):
     is (xstage, hstep, istep, theta) with 7 rows per step, saved behind the landing mode's tensors.
     z0 (L,N,D) with ``draws`` = L: every draw starts from its own slab (the `_nz` entry points); the gradient of z0 is then the
     reverse sweep's gz0 (L,N,D) as it stands, where a shared z0 takes its sum over the draws.
-    ts (N,T): a time grid per trajectory, shared by the draws (the `_nt` entry points); ts carries no gradient either way."""
+    ts (N,T): a time grid per trajectory, shared by the draws (the `_nt` entry points); ts carries no gradient either way.
+    ``substeps`` = s > 1 (euler, midpoint, rk4): s equal solver steps per output interval (the `_ns` entry points); zt stays at ts,
+    the saved record is ([L,] N,T-1,s,NS,D) and the parameter sums run over all its rows."""
 
     @staticmethod
-    def forward(ctx, z0, ts, raw_ell, raw_var, Z, Um, Us, gp, order, method, draws=None, adaptive=None):
+    def forward(ctx, z0, ts, raw_ell, raw_var, Z, Um, Us, gp, order, method, draws=None, adaptive=None, substeps=1):
         cache = gp.take_prebuilt_cache() if hasattr(gp, 'take_prebuilt_cache') else None
         if cache is None:
             cache = gp.build_cache() if draws is None else gp.build_cache(draws=draws)
@@ -739,10 +781,10 @@ class _Flow(torch.autograd.Function):
             if sink is not None:
                 sink(counts)
         elif need:
-            zt, xs = rollout(cache, z0, ts, order, method, save_stages=True)
+            zt, xs = rollout(cache, z0, ts, order, method, save_stages=True, substeps=substeps)
         else:
-            zt, xs = rollout(cache, z0, ts, order, method), None
-        ctx.cache, ctx.order, ctx.method, ctx.z0_per_draw = cache, order, method, z0.dim() == 3
+            zt, xs = rollout(cache, z0, ts, order, method, substeps=substeps), None
+        ctx.cache, ctx.order, ctx.method, ctx.z0_per_draw, ctx.substeps = cache, order, method, z0.dim() == 3, substeps
         ctx.save_for_backward(ts, xs, raw_ell.detach(), raw_var.detach(), Z.detach(), hs, ie, th)
         return zt
 
@@ -757,15 +799,15 @@ class _Flow(torch.autograd.Function):
         nch = pgrad_chunks(c, gzt.shape[-3], ctx.order, ctx.method) if want_p else 0
         gpack_f = None
         if nch:
-            gz0, ast, gpack_f = rollout_bwd_pgrad(c, xs, gzt.contiguous(), ts, ctx.order, ctx.method, nch)
+            gz0, ast, gpack_f = rollout_bwd_pgrad(c, xs, gzt.contiguous(), ts, ctx.order, ctx.method, nch, substeps=ctx.substeps)
         elif ctx.method == 'dopri5':
             gz0, ast = rollout_adaptive_bwd(c, xs, hs, ie, gzt.contiguous(), ctx.order, theta=th)
         else:
-            gz0, ast = rollout_bwd(c, xs, gzt.contiguous(), ts, ctx.order, ctx.method)
+            gz0, ast = rollout_bwd(c, xs, gzt.contiguous(), ts, ctx.order, ctx.method, substeps=ctx.substeps)
         if c.stacked and not ctx.z0_per_draw:
             gz0 = gz0.sum(0)                         # every draw starts from the same z0 (odegpvae.py:42)
         if not want_p:
-            return (gz0,) + (None,) * 11
+            return (gz0,) + (None,) * 12
         leaves = all(p.is_leaf and p.requires_grad for p in ctx.params) and all(ctx.needs_input_grad[2:7])
         if _overlap['on'] and leaves:
             # parameter gradients on the side stream, next to the encoder's backward; join_side_stream() adds them
@@ -784,33 +826,35 @@ class _Flow(torch.autograd.Function):
             # otherwise hand the block to the encoder-backward kernels the main stream launches meanwhile
             _overlap['pending'].append((ctx.params, [gg.view_as(p) for gg, p in zip(grads, ctx.params)],
                                         (g, gpack, xs, ast, c, scratch, raw_ell, raw_var, Z, ctx.prepared, hs, ie, th)))
-            return (gz0,) + (None,) * 11
+            return (gz0,) + (None,) * 12
         if ctx.prepared is not None:
             torch.cuda.current_stream().wait_stream(side_stream())
         gpack = gpack_f if gpack_f is not None else param_grad(c, xs.reshape(lead + (-1, c.Di)), ast.reshape(lead + (-1, c.Do)))
         g = cache_build_bwd(c, raw_ell, raw_var, Z, gpack, prepared=ctx.prepared)
-        return (gz0, None, g['raw_ell'], g['raw_var'], g['Z'], g['Um'], g['Us'], None, None, None, None, None)
+        return (gz0, None, g['raw_ell'], g['raw_var'], g['Z'], g['Um'], g['Us'], None, None, None, None, None, None)
 
 
-def flow(gp, z0, ts, order, method, draws=None, adaptive=None):
+def flow(gp, z0, ts, order, method, draws=None, adaptive=None, substeps=1):
     """One function draw -> zt (N,T,D); ``draws`` = L -> the L draws of odegpvae.py:41-44 in one pass, zt (L,N,T,D).
     ``adaptive`` = (rtol, atol, max_steps, sink[, dense]) for method 'dopri5' (see _Flow).
     ts (T,), or (N,T): one grid per trajectory (row n for trajectory n of every draw).
     z0 (L,N,D): draw l starts from z0[l].  With ``draws`` = L on a layer that batches its draws this is still one pass; otherwise
     (``draws`` None, or a zero-padded width, whose draws are built one by one) it is L single-draw flows, stacked -- the sink of an
-    adaptive solve then sees the counts of the last one, as after the reference's loop."""
+    adaptive solve then sees the counts of the last one, as after the reference's loop.
+    ``substeps`` = s (euler, midpoint, rk4; an int in 1 ... 64): s equal solver steps per interval of ts, outputs at ts only."""
     check_solver(method)
+    substeps = _substeps(substeps, method)
     if z0.dim() == 3:
         if draws is not None and draws != z0.shape[0]:
             raise _lib.GpodeError('z0 holds initial states for %d draws, the flow was asked for %d' % (z0.shape[0], draws))
         if draws is None or not getattr(gp, 'batched_draws_supported', lambda: True)():
-            return torch.stack([flow(gp, z0[l], ts, order, method, None, adaptive) for l in range(z0.shape[0])], 0)
+            return torch.stack([flow(gp, z0[l], ts, order, method, None, adaptive, substeps) for l in range(z0.shape[0])], 0)
     k = gp.kern
     raw_ell, raw_var = k.raw_dimwise() if hasattr(k, 'raw_dimwise') else (k.unconstrained_lengthscales, k.unconstrained_variance)
     params = (raw_ell, raw_var, gp.inducing_loc.optvar, gp.Um.optvar, gp.us_packed() if hasattr(gp, 'us_packed') else gp.Us_sqrt.optvar)
     pad = getattr(gp, 'width_pad', None)
     if pad is None:
-        return _Flow.apply(z0, ts, *params, gp, order, method, draws, adaptive)
+        return _Flow.apply(z0, ts, *params, gp, order, method, draws, adaptive, substeps)
     # a width outside the compiled list: the compiled kernels on zero-padded operands (see WidthPad); autograd carries the
     # gradients back through the scatter / slice
     if adaptive is not None:
@@ -818,7 +862,7 @@ def flow(gp, z0, ts, order, method, draws=None, adaptive=None):
         # tolerances scaled by sqrt(D / D_padded) give the ratio over the D real components
         w = (len(pad.in_index) / float(pad.Dip)) ** 0.5
         adaptive = (adaptive[0] * w, adaptive[1] * w) + tuple(adaptive[2:])
-    zt = _Flow.apply(pad.state(z0), ts, *pad.params(*params), gp, order, method, draws, adaptive)
+    zt = _Flow.apply(pad.state(z0), ts, *pad.params(*params), gp, order, method, draws, adaptive, substeps)
     return pad.unstate(zt)
 
 
