@@ -322,6 +322,25 @@ int gpode_conditional(int Di, int Do, int M, int N, const float* raw_ell, const 
                       const float* Um, const float* Us, int us_rank1, const float* x, int full_cov, float* mean,
                       float* var, float* ws, void* stream);
 
+/* Posterior moments of the divergence-free layer, q(f(x)) = N(m(x), Sigma(x)) at the rows of x (N,D).  No reference line computes
+ * it (svpy.py:176-210 assumes the RBF layout); this entry DEFINES it, from the sampling path (sample_inducing svpy.py:88-101,
+ * compute_nu / f_update kernels.py:376-393).  With n = M D, rows and columns ordered (point, output) as kern.K orders them:
+ *   L = chol(K(Z) + jitter I) (lower triangle read),  A = L^-1 K(Z,x) (n, N D),  a_j = column j = (query, b) of A viewed as (M,D),
+ *   t_j[:, d] = Us_d^T a_j[:, d],   mean[query, b] = sum_{m,d} a_j[m,d] Um[m,d],
+ *   cov[j, j'] = K(x,x)[j, j'] + sum_d t_j[:, d] . t_j'[:, d] - a_j . a_j'.
+ * With per-entry lengthscales the DF matrix is not symmetric: K(Z,x) enters (as in f_update), not K(x,Z)^T, and K(x,x) is kern.K(x)
+ * as it stands.  raw_ell (D,D), raw_var (D), Z (M,D), Um (M,D), Us_packed (D, M(M+1)/2) as in gpode_cache_build_fwd (q_diag: the
+ * softplus'd scale on the packed diagonal, the q(u) that sample_inducing draws from).  mean (N,D).  cov_mode 0: var (N,D) marginal
+ * variances; 1: var (N,D,D), the covariance of the D outputs at each query; 2: var (N D, N D), the full covariance in the layout
+ * of kern.K(x).  D = 2 .. 16, M D <= 8192, (M + N) D <= 65408 (chunk the queries; every call refactors K(Z)).
+ * ws: gpode_conditional_df_ws floats of scratch (at most 3 np^2 for np >= 64, np = the system rows (M + N) D rounded up to 32, to
+ * 128 from 1024); every float the call reads it has written.  Its first word is the factorisation status (gpode_cache_info), as for
+ * gpode_conditional.  gpode_last_launch(): "conditional_df: chain32" or "conditional_df: panel". */
+int gpode_conditional_df_ws(int D, int M, int N, size_t* ws_floats);
+int gpode_conditional_df(int D, int M, int N, const float* raw_ell, const float* raw_var, const float* Z, const float* Um,
+                         const float* Us_packed, const float* x, int cov_mode, float* mean, float* var, float* ws,
+                         void* stream);
+
 /* SVGP_Layer.kl (svpy.py:144-175, q_diag=False): Um (M,Do), Us_packed (Do, M(M+1)/2) -> kl (1 float).
  * _bwd: g = d loss / d kl (1 float, device) -> dUm (M,Do), dUs (Do, M(M+1)/2). */
 int gpode_svgp_kl_fwd(int M, int Do, const float* Um, const float* Us_packed, float* kl, void* stream);

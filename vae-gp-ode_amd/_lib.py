@@ -33,6 +33,9 @@ SIGNATURES = {
     'gpode_kernel_matrix': (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
     'gpode_conditional_ws': (_i, [_i, _i, _i, _i, _sz_p]),
     'gpode_conditional': (_i, [_i, _i, _i, _i] + [_vp] * 5 + [_i, _vp, _i] + [_vp] * 3 + [_vp]),
+    # posterior moments of the divergence-free layer: defined by this entry (include/gpode.h), no reference line computes it
+    'gpode_conditional_df_ws': (_i, [_i, _i, _i, _sz_p]),
+    'gpode_conditional_df': (_i, [_i, _i, _i] + [_vp] * 6 + [_i] + [_vp] * 3 + [_vp]),
     'gpode_svgp_kl_fwd': (_i, [_i, _i, _vp, _vp, _vp, _vp]),
     'gpode_svgp_kl_bwd': (_i, [_i, _i] + [_vp] * 5 + [_vp]),
     'gpode_rhs_fwd': (_i, [_i] * 5 + [_vp, _vp, _i, _vp, _i, _vp]),

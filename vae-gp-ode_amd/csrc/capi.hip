@@ -405,6 +405,17 @@ int gpode_conditional(int Di, int Do, int M, int N, const float* raw_ell, const 
   return gp::conditional(Di, Do, M, N, raw_ell, raw_var, Z, Um, Us, us_rank1, x, full_cov, mean, var, ws, (hipStream_t)stream);
 }
 
+int gpode_conditional_df_ws(int D, int M, int N, size_t* ws_floats) {
+  if (!ws_floats) return gp::set_error("gpode_conditional_df_ws: null pointer");
+  return gp::conditional_df_ws(D, M, N, ws_floats);
+}
+
+int gpode_conditional_df(int D, int M, int N, const float* raw_ell, const float* raw_var, const float* Z, const float* Um,
+                         const float* Us_packed, const float* x, int cov_mode, float* mean, float* var, float* ws, void* stream) {
+  if (!raw_ell || !raw_var || !Z || !Um || !Us_packed || !x || !mean || !var || !ws) return gp::set_error("gpode_conditional_df: null pointer");
+  return gp::conditional_df(D, M, N, raw_ell, raw_var, Z, Um, Us_packed, x, cov_mode, mean, var, ws, (hipStream_t)stream);
+}
+
 int gpode_svgp_kl_fwd(int M, int Do, const float* Um, const float* Us_packed, float* kl, void* stream) {
   if (!Um || !Us_packed || !kl) return gp::set_error("gpode_svgp_kl_fwd: null pointer");
   return gp::svgp_kl_fwd(M, Do, Um, Us_packed, kl, (hipStream_t)stream);

@@ -1910,4 +1910,168 @@ int conditional(int Di, int Do, int M, int N, const float* raw_ell, const float*
   return check_launch(big_factor(c.np) ? "conditional: panel" : "conditional: chain32");
 }
 
+// ---------------------------------------------------------------------------------------------
+// Posterior moments of the divergence-free layer: q(f(x)) = N(m(x), Sigma(x)) with the whitened q(u) = N(Um, S_d) that
+// sample_inducing draws from (svpy.py:88-101) pushed through compute_nu / f_update (kernels.py:376-393).  No reference line
+// computes it (svpy.py:176-210 assumes the RBF (D,M,M) layout); the definition, with n = M D and j = (query, output):
+//   L = chol(K(Z) + jitter I)  (lower triangle read),   A = L^-1 K(Z,x)  (n, N D),   a_j = column j of A viewed as (M,D),
+//   t_j[:, d] = Us_d^T a_j[:, d],   mean[j] = a_j . Um,   cov[j, j'] = K(x,x)[j, j'] + t_j . t_j' - a_j . a_j'.
+// With dimwise hyper-parameters the DF matrix is not symmetric (ell by (a,b), var by b): it is K(Z,x) that enters, as in f_update,
+// not K(x,Z)^T, and K(x,x) is taken as kern.K(x) gives it.  The machinery is build_conditional's: the N D rows K(Z,x)^T are
+// appended to K(Z) (huge diagonal), and after the Cholesky rows n.. of the factor hold A^T.
+// ---------------------------------------------------------------------------------------------
+struct CondDfLayout { size_t info, A, Lmat, Dfac, a, t, total; int n, nq, np, nblk; };
+static CondDfLayout cond_df_layout(int D, int M, int N) {
+  CondDfLayout c;
+  c.n = M * D;
+  c.nq = N * D;
+  c.nblk = cdiv(c.n + c.nq, NB);
+  if (c.nblk >= 32) c.nblk = (c.nblk + 3) / 4 * 4;
+  c.np = c.nblk * NB;
+  size_t o = 0;
+  auto take = [&](size_t nfl) { size_t at = o; o += (nfl + 3) / 4 * 4; return at; };
+  c.info = take(4);
+  c.A = take((size_t)c.np * c.np);
+  c.Lmat = take((size_t)c.np * c.np);
+  c.Dfac = take((size_t)c.nblk * NB * NB);
+  c.a = take((size_t)c.nq * c.n);
+  c.t = take((size_t)c.nq * c.n);
+  c.total = o;
+  return c;
+}
+
+// entry (a, b) of the D x D block of the DF kernel between a row point p and a column point q (kernels.py:289-303; the formula of
+// k_Kzz_df on the raw parameters): delta = q - p, ell indexed by (a, b), var by b
+__device__ __forceinline__ float df_k(int D, const float* __restrict__ raw_ell, const float* __restrict__ raw_var,
+                                      const float* __restrict__ p, int a, const float* __restrict__ q, int b) {
+  float r2 = 0.f;
+  for (int i = 0; i < D; ++i) { const float t = q[i] - p[i]; r2 = fmaf(t, t, r2); }
+  const float l = softplus_lower(raw_ell[a * D + b]);
+  const float il2 = 1.f / (l * l);
+  const float da = q[a] - p[a], db = q[b] - p[b];
+  const float term = da * db * il2 + ((a == b) ? ((float)(D - 1) - r2 * il2) : 0.f);
+  return softplus_lower(raw_var[b]) * expf(-0.5f * r2 * il2) * term * il2;
+}
+
+// rows 0..n-1: K(Z) + jitter I (lower triangle read);  row n + (q,b), column (m,a): K(Z,x)[(m,a),(q,b)], 1e30 on its diagonal;
+// identity padding behind.  Clears the status words (pivot minimum: +inf).
+__global__ void k_cond_df_fill(int D, int n, int nq, int np, const float* __restrict__ raw_ell, const float* __restrict__ raw_var,
+                               const float* __restrict__ Z, const float* __restrict__ x, float* __restrict__ A, int* __restrict__ info) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  const int r = blockIdx.y;
+  if (blockIdx.x == 0 && r == 0 && threadIdx.x < 4) info[threadIdx.x] = threadIdx.x == 1 ? 0x7f800000 : 0;
+  if (c >= np) return;
+  float v;
+  if (r < n) {
+    v = c < n ? df_k(D, raw_ell, raw_var, Z + (size_t)(r / D) * D, r % D, Z + (size_t)(c / D) * D, c % D) + (r == c ? kJitter : 0.f) : 0.f;
+  } else if (r < n + nq) {
+    const int j = r - n;
+    v = c < n ? df_k(D, raw_ell, raw_var, Z + (size_t)(c / D) * D, c % D, x + (size_t)(j / D) * D, j % D) : (c == r ? 1e30f : 0.f);
+  } else {
+    v = (r == c) ? 1.f : 0.f;
+  }
+  A[(size_t)r * np + c] = v;
+}
+
+// grid N D (one workgroup per appended row j = (q, b)), block 256, dynamic LDS n floats: a_j out of the factor, t_j, the mean and
+// (var_diag) the marginal variance K_jj + |t_j|^2 - |a_j|^2.  a_j and t_j are kept, both (M,D) row-major, for the covariances.
+__global__ __launch_bounds__(256) void k_cond_df_rows(int D, int M, int np, const float* __restrict__ Lm, const float* __restrict__ Dfac,
+                                                       const float* __restrict__ raw_ell, const float* __restrict__ raw_var,
+                                                       const float* __restrict__ x, const float* __restrict__ Um,
+                                                       const float* __restrict__ Us, float* __restrict__ Aws, float* __restrict__ Tws,
+                                                       float* __restrict__ mean, float* __restrict__ var_diag) {
+  extern __shared__ float sa[];
+  __shared__ float red[4][3];
+  const int j = blockIdx.x, tid = threadIdx.x, n = M * D;
+  float* arow = Aws + (size_t)j * n;
+  float* trow = Tws + (size_t)j * n;
+  float acc[3] = {0.f, 0.f, 0.f};                                   // a . Um,  |t|^2,  |a|^2
+  for (int i = tid; i < n; i += 256) {
+    const float v = factor_elem(Lm, Dfac, np, n + j, i);
+    sa[i] = v;
+    arow[i] = v;
+    acc[0] = fmaf(v, Um[i], acc[0]);
+    acc[2] = fmaf(v, v, acc[2]);
+  }
+  __syncthreads();
+  const size_t P = (size_t)M * (M + 1) / 2;
+  for (int i = tid; i < n; i += 256) {
+    const int d = i / M, k = i % M;                                 // neighbouring threads: neighbouring columns k of Us_d
+    const float* Ud = Us + (size_t)d * P;                           // packed lower triangle, row-major (transforms.py:67-69)
+    float t = 0.f;
+    for (int m = k; m < M; ++m) t = fmaf(Ud[(size_t)m * (m + 1) / 2 + k], sa[m * D + d], t);   // (Us_d^T a[:, d])_k
+    trow[k * D + d] = t;
+    acc[1] = fmaf(t, t, acc[1]);
+  }
+  float out[3];
+  wave_sum_multi<3>(acc, out);
+  if ((tid & 63) == 0) { red[tid >> 6][0] = out[0]; red[tid >> 6][1] = out[1]; red[tid >> 6][2] = out[2]; }
+  __syncthreads();
+  if (tid == 0) {
+    const float m0 = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+    const float t2 = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+    const float a2 = (red[0][2] + red[1][2]) + (red[2][2] + red[3][2]);
+    mean[j] = m0;
+    if (var_diag) {
+      const float* xq = x + (size_t)(j / D) * D;
+      var_diag[j] = df_k(D, raw_ell, raw_var, xq, j % D, xq, j % D) + (t2 - a2);   // K_jj = var_b (D - 1) / ell_bb^2
+    }
+  }
+}
+
+// one wavefront per pair of appended rows (j, j'): cov = K(x,x)[j, j'] + t_j . t_j' - a_j . a_j'.
+//   point (per_point): the D x D block of every query, cov (N,D,D);  full: every pair, cov (N D, N D) in the layout of kern.K(x)
+__global__ __launch_bounds__(256) void k_cond_df_cov(int D, int n, int nq, int per_point, const float* __restrict__ raw_ell,
+                                                      const float* __restrict__ raw_var, const float* __restrict__ x,
+                                                      const float* __restrict__ Aws, const float* __restrict__ Tws, float* __restrict__ cov) {
+  const int lane = threadIdx.x & 63;
+  const size_t pair = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const size_t npairs = per_point ? (size_t)nq * D : (size_t)nq * nq;
+  if (pair >= npairs) return;                                        // wave-uniform
+  int j1, j2;
+  if (per_point) { j1 = (int)(pair / D); j2 = (j1 / D) * D + (int)(pair % D); }
+  else { j1 = (int)(pair / nq); j2 = (int)(pair % nq); }
+  const float* a1 = Aws + (size_t)j1 * n;
+  const float* a2 = Aws + (size_t)j2 * n;
+  const float* t1 = Tws + (size_t)j1 * n;
+  const float* t2 = Tws + (size_t)j2 * n;
+  float acc = 0.f;
+  for (int i = lane; i < n; i += 64) acc += t1[i] * t2[i] - a1[i] * a2[i];
+  const float in1[1] = {acc};
+  float out1[1];
+  wave_sum_multi<1>(in1, out1);
+  if (lane == 0) cov[pair] = df_k(D, raw_ell, raw_var, x + (size_t)(j1 / D) * D, j1 % D, x + (size_t)(j2 / D) * D, j2 % D) + out1[0];
+}
+
+int conditional_df_ws(int D, int M, int N, size_t* ws_floats) {
+  if (D < 2 || D > 16) return set_error("gpode_conditional_df: the divergence-free kernel is built for D = 2 .. 16, got D=%d", D);
+  if (M <= 0 || N <= 0) return set_error("gpode_conditional_df: M=%d N=%d", M, N);
+  if ((long long)M * D > 8192) return set_error("gpode_conditional_df: M D = %lld inducing values, at most 8192", (long long)M * D);
+  if (((long long)M + N) * D > 65536 - 4 * NB)
+    return set_error("gpode_conditional_df: (M + N) D = %lld system rows, at most %d per call (chunk the queries)", ((long long)M + N) * D,
+                     65536 - 4 * NB);
+  *ws_floats = cond_df_layout(D, M, N).total;
+  return 0;
+}
+
+int conditional_df(int D, int M, int N, const float* raw_ell, const float* raw_var, const float* Z, const float* Um,
+                   const float* Us_packed, const float* x, int cov_mode, float* mean, float* var, float* ws, hipStream_t st) {
+  size_t need = 0;
+  if (conditional_df_ws(D, M, N, &need)) return 1;
+  if (cov_mode < 0 || cov_mode > 2) return set_error("gpode_conditional_df: cov_mode=%d (0 marginals, 1 per point, 2 full)", cov_mode);
+  const CondDfLayout c = cond_df_layout(D, M, N);
+  int* info = reinterpret_cast<int*>(ws + c.info);
+  hipLaunchKernelGGL(k_cond_df_fill, dim3(cdiv(c.np, 128), c.np), 128, 0, st, D, c.n, c.nq, c.np, raw_ell, raw_var, Z, x, ws + c.A, info);
+  if (cholesky_blocked(ws + c.A, ws + c.Lmat, ws + c.Dfac, c.np, c.nblk, 1, info, st, c.n)) return 1;
+  if (check_launch("conditional_df: cholesky")) return 1;
+  hipLaunchKernelGGL(k_cond_df_rows, c.nq, 256, sizeof(float) * c.n, st, D, M, c.np, ws + c.Lmat, ws + c.Dfac, raw_ell, raw_var, x, Um,
+                     Us_packed, ws + c.a, ws + c.t, mean, cov_mode == 0 ? var : nullptr);
+  if (cov_mode != 0) {
+    const size_t npairs = cov_mode == 1 ? (size_t)c.nq * D : (size_t)c.nq * c.nq;
+    hipLaunchKernelGGL(k_cond_df_cov, (unsigned)((npairs + 3) / 4), 256, 0, st, D, c.n, c.nq, cov_mode == 1 ? 1 : 0, raw_ell, raw_var, x,
+                       ws + c.a, ws + c.t, var);
+  }
+  return check_launch(big_factor(c.np) ? "conditional_df: panel" : "conditional_df: chain32");
+}
+
 }  // namespace gp

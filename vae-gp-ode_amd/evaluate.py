@@ -32,9 +32,13 @@ take its observed frames only (``predict(..., n_obs=)``), ``mse_t`` / ``nll_t`` 
 ``count`` is L 784 times the number of observed frames.  ``--subsample_frames K``: every test
 sequence keeps K of its frames (drawn per sequence, reproducibly from ``--seed``) and is evaluated on its own time grid
 (``predict(..., ts=)``); the long roll-out stays on the uniform grid.  ``--eval_z0_draws True`` adds a second pass over the test split
-with a z0 sample per draw and reports ``iw_nll``, ``nlpd_marginal``, ``ess_mean``, ``ess_min``; every other figure is unchanged.  Single process: data-parallel
+with a z0 sample per draw and reports ``iw_nll``, ``nlpd_marginal``, ``ess_mean``, ``ess_min``; every other figure is unchanged.
+``--eval_field True`` then evaluates the posterior of the vector field itself (``field_posterior``: mean and marginal variances of
+q(f(z)), either kernel) at the encoder means of the initial states of the test split, writes ``field_z.npy``, ``field_mean.npy``,
+``field_var.npy`` and adds ``field_points``, ``field_var_mean``, ``field_var_max``; without it nothing changes.  Single process: data-parallel
 evaluation is not built.  No plots.
 """
+import argparse
 import json
 import math
 import os
@@ -366,6 +370,25 @@ def compute_nll(model, loader, L=1, images_per_pass=8192):
     return nll / nseq, nlpd / nseq
 
 
+def initial_state_means(model, X):
+    """The encoder means of the initial states of the sequences X (N,T,1,28,28), (N, order*q): for order 2 the position and the
+    velocity means concatenated, the layout of the state the flow integrates.  No sample is drawn.  Eval mode, no autograd."""
+    with torch.no_grad(), _EvalMode(model):
+        X = X.contiguous().float()
+        mu_s, _ = model.vae.encoder(X[:, 0])
+        if model.order == 1:
+            return mu_s
+        mu_v, _ = model.vae.encoder_v(X[:, 0:model.v_steps].squeeze(2))
+        return torch.cat([mu_s, mu_v], dim=1)
+
+
+def field_posterior(model, z, cov='diag'):
+    """(mean, var) of the learnt vector field q(f(z)) at the latent states z (N, order*q): ``SVGP_Layer.posterior`` of the model's
+    GP layer, for either kernel -- where the field is confident and what its mean is, away from the decoded frames.  ``cov`` as
+    there ('diag': marginal variances (N,D_out))."""
+    return model.flow.odefunc.diffeq.posterior(z, cov=cov)
+
+
 def build_from_checkpoint(args):
     """(model, test loader, checkpoint file) for a parsed command line, the way ``vae_gp_ode_amd.main`` sets a run up: seed, data,
     model, kernel initialisation, then the checkpoint ``--model_path`` (the .pth file, or the results directory that holds
@@ -399,7 +422,17 @@ def make_parser():
     p.add_argument('--eval_z0_draws', type=eval, default=False,
                    help='also report the importance-weighted marginal likelihood: a second pass over the test split in which every one of '
                         'the --eval_sample_size draws samples its own initial state (iw_nll, nlpd_marginal, ess_mean, ess_min)')
+    # absent from the namespace unless given (read with eval_field(args)): a command line without it parses to what it always did
+    p.add_argument('--eval_field', type=eval, default=argparse.SUPPRESS,
+                   help='also evaluate the posterior of the vector field at the encoder means of the initial states of the test split: '
+                        'field_z.npy, field_mean.npy, field_var.npy (marginal variances) and field_points, field_var_mean, field_var_max '
+                        '(default: False)')
     return p
+
+
+def eval_field(args):
+    """--eval_field of a parsed command line; False when the switch was not given"""
+    return bool(getattr(args, 'eval_field', False))
 
 
 def _subsampled(args, loader):
@@ -477,6 +510,11 @@ def main(argv=None):
             ess_sum += pm.ess.sum().item()
             ess_min = min(ess_min, pm.ess.min().item())
         marginal = dict(iw_nll=iw / nseq, nlpd_marginal=nlpd_m / nseq, ess_mean=ess_sum / nseq, ess_min=ess_min)
+    field = None
+    if eval_field(args):                             # behind everything else, and draws nothing: the figures above are unchanged
+        fz = torch.cat([initial_state_means(model, Xb) for _, Xb, _, _ in _subsampled(args, testset)])
+        fm, fv = field_posterior(model, fz)
+        field = (fz.cpu().numpy(), fm.cpu().numpy(), fv.cpu().numpy())
     torch.cuda.synchronize()
     ms = (time.time() - t0) * 1e3
 
@@ -490,6 +528,10 @@ def main(argv=None):
         out['ragged_frames'] = args.ragged_frames
     if marginal is not None:
         out.update(marginal)
+    if field is not None:
+        out.update(field_points=int(field[0].shape[0]), field_var_mean=float(field[2].mean()), field_var_max=float(field[2].max()))
+        for name, arr in zip(('field_z.npy', 'field_mean.npy', 'field_var.npy'), field):
+            np.save(os.path.join(args.save, name), arr)
     np.save(os.path.join(args.save, 'rollout_mean.npy'), roll.mean.cpu().numpy())
     np.save(os.path.join(args.save, 'rollout_var.npy'), roll.var.cpu().numpy())
     with open(os.path.join(args.save, 'eval.json'), 'w') as f:

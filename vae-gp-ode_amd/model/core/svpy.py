@@ -205,6 +205,46 @@ class SVGP_Layer(torch.nn.Module):
                                    Us.detach(), x.detach().to(self.inducing_loc.optvar.device, torch.float32), full_cov,
                                    us_rank1=self.q_diag)
 
+    def posterior(self, x, cov='diag', max_rows=None):
+        """Moments of q(f(x)) at the rows of x (N,D_in) under the q(u) that ``sample_inducing`` draws from, for either kernel:
+        (mean (N,D_out), var).  ``cov`` = 'diag': the marginal variances (N,D_out); 'point': the covariance of the outputs at each
+        query (N,D_out,D_out); 'full': the covariance between the queries.  Computed without autograd.
+        DF: ``ops.conditional_df`` (its definition: include/gpode.h).  The outputs are correlated, so 'point' is a full block, and
+        'full' is (N D, N D) in the layout of ``kern.K(x)``; the queries are chunked to ``max_rows`` system rows
+        (ops.CONDITIONAL_DF_MAX_ROWS), each chunk refactoring K(Z), and 'full' needs them in one chunk.
+        RBF: ``ops.conditional`` on ``us_packed()``.  The outputs are independent: 'point' is the diagonal embedding of the
+        marginals and 'full' the reference's (N,N,D_out).  q_diag=False is the launch, and the bits, of ``build_conditional``.
+        q_diag=True departs from it: ``build_conditional`` follows the reference's rank-one S_d = s_d s_d^T (svpy.py:194-195), this
+        method uses the diagonal S_d = diag(s_d^2) -- the covariance of the u that ``sample_inducing`` actually returns
+        (svpy.py:95-96).  The means agree; the variances do not.  A width that is not compiled is evaluated zero-padded, as
+        ``forward`` does."""
+        if cov not in ops.COV_MODES:
+            raise ValueError("posterior: cov must be 'diag', 'point' or 'full', got %r" % (cov,))
+        raw_ell, raw_var = self.kern.raw_dimwise()
+        with torch.no_grad():
+            dev = self.inducing_loc.optvar.device
+            x = x.detach().to(dev, torch.float32)
+            params = (raw_ell.detach(), raw_var.detach(), self.inducing_loc.optvar.detach(), self.Um.optvar.detach(), self.us_packed().detach())
+            if self.kernel_n == 'DF':
+                return ops.conditional_df(*params, x, cov=cov, max_rows=max_rows)
+            pad = self.width_pad
+            if pad is not None:
+                params, x = tuple(t.contiguous() for t in pad.params(*params)), pad.state(x).contiguous()
+            mean, var = ops.conditional(*params, x, cov == 'full', us_rank1=False)
+            if pad is not None:
+                mean, var = mean[:, :self.D_out].contiguous(), var[..., :self.D_out].contiguous()
+            return mean, (torch.diag_embed(var) if cov == 'point' else var)
+
+    def mean_noise(self):
+        """The draw under which the sampled function IS the posterior mean: ``eps_u`` = 0 (u = Um) and ``rff_w`` = 0 (no prior
+        function), so ``build_cache(noise=mean_noise())`` followed by ``forward(x)`` gives m(x) = K(Z,x)^T L^-T Um, and a Flow
+        under it integrates the mean field deterministically.  The frequency noise multiplies the zero weights; it is set to
+        ones (phases zero), since the DF features divide by the norm of the frequencies."""
+        dev = self.inducing_loc.optvar.device
+        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
+        return dict(eps_u=z(self.M, self.D_out), rff_w=z(self.S if self.kernel_n == 'RBF' else 2 * self.S, self.D_out),
+                    rff_eps=torch.ones(self.D_in, self.S, self.D_out, dtype=torch.float32, device=dev), rff_u=z(1, self.S, self.D_out))
+
     def kl(self):
         """KL(q(u) || N(0,I)) in whitened form (svpy.py:144-175)."""
         return ops.svgp_kl(self.Um.optvar, self.us_packed(), self.M)

@@ -740,6 +740,68 @@ def conditional(raw_ell, raw_var, Z, Um, Us, x, full_cov=False, us_rank1=False):
     return mean, var
 
 
+COV_MODES = {'diag': 0, 'point': 1, 'full': 2}
+# Most rows of one augmented system of conditional_df (inducing values M D + the queries' N D of a launch).  The workspace is
+# 3 np^2 floats (np = the rows rounded up to whole tiles), so 4096 rows bound it at 192 MiB; the cost of a chunk grows with rows^3
+# while every chunk refactors K(Z), so chunks should be several times M D rows.  N = 256 queries at M = 100, D = 6 are 2136 rows.
+CONDITIONAL_DF_MAX_ROWS = 4096
+
+
+def conditional_df_chunks(D, M, N, cov='diag', max_rows=None):
+    """Query ranges [(first, end), ...] of the launches of conditional_df: every launch factors one system of M D + (end - first) D
+    rows, at most ``max_rows`` (CONDITIONAL_DF_MAX_ROWS when None).  All chunks but the last hold (max_rows - M D) // D queries.
+    The full covariance couples every pair of queries, so it exists for one chunk only: more raises, naming the limit.  Pure
+    host arithmetic -- nothing is launched."""
+    if cov not in COV_MODES:
+        raise _lib.GpodeError("conditional_df: cov must be 'diag', 'point' or 'full', got %r" % (cov,))
+    max_rows = CONDITIONAL_DF_MAX_ROWS if max_rows is None else int(max_rows)
+    if D < 1 or M < 1 or N < 1:
+        raise _lib.GpodeError('conditional_df: D=%d M=%d N=%d' % (D, M, N))
+    per = (max_rows - M * D) // D
+    if per < 1:
+        raise _lib.GpodeError('conditional_df: max_rows=%d leaves no room for a query behind the M D = %d inducing rows (a query '
+                              'takes D = %d)' % (max_rows, M * D, D))
+    if cov == 'full' and N > per:
+        raise _lib.GpodeError("conditional_df: cov='full' needs all %d queries in one system of %d rows; max_rows=%d allows %d queries "
+                              "(raise max_rows, or ask for 'point' / 'diag')" % (N, (M + N) * D, max_rows, per))
+    return [(s, min(N, s + per)) for s in range(0, N, per)]
+
+
+def conditional_df(raw_ell, raw_var, Z, Um, Us_packed, x, cov='diag', max_rows=None):
+    """Posterior moments q(f(x)) = N(mean, cov) of the divergence-free layer (gpode_conditional_df; the definition is in
+    include/gpode.h): mean (N,D) and, by ``cov``, 'diag' the marginal variances (N,D), 'point' the covariance of the D outputs at
+    each query (N,D,D), 'full' the covariance of all N D values (N D, N D) in the layout of kern.K(x).  Forward only.
+    The queries are cut into chunks (conditional_df_chunks) so that a launch factors at most ``max_rows`` system rows --
+    CONDITIONAL_DF_MAX_ROWS = 4096 by default, a workspace of at most 3 * 4096^2 floats whatever N -- and every chunk refactors
+    K(Z).  'full' over more than one chunk raises before any launch.  A failed factorisation (K(Z) + jitter I not positive
+    definite) raises; reading its status word synchronises the stream once per chunk."""
+    if raw_ell.dim() != 2 or raw_ell.shape[0] != raw_ell.shape[1]:
+        raise _lib.GpodeError('conditional_df: the divergence-free kernel needs D_in == D_out, raw_ell is %s' % (tuple(raw_ell.shape),))
+    D = raw_ell.shape[0]
+    if x.dim() != 2 or x.shape[1] != D:
+        raise _lib.GpodeError('conditional_df: x must be (N,%d), one query per row; got %s' % (D, tuple(x.shape)))
+    if cov not in COV_MODES:
+        raise _lib.GpodeError("conditional_df: cov must be 'diag', 'point' or 'full', got %r" % (cov,))
+    M, N = Z.shape[0], x.shape[0]
+    raw_ell = _chk(raw_ell, 'raw_ell', (D, D)); raw_var = _chk(raw_var, 'raw_var', (D,))
+    Z = _chk(Z, 'Z', (M, D)); Um = _chk(Um, 'Um', (M, D)); x = _chk(x, 'x', (N, D))
+    Us_packed = _chk(Us_packed, 'Us_packed', (D, M * (M + 1) // 2))
+    chunks = conditional_df_chunks(D, M, N, cov, max_rows)
+    wf = ctypes.c_size_t(0)
+    _lib.call('gpode_conditional_df_ws', D, M, chunks[0][1] - chunks[0][0], ctypes.byref(wf))   # the first chunk is the largest
+    new = lambda *s: torch.empty(s, dtype=torch.float32, device=x.device)
+    ws, mean = new(wf.value), new(N, D)
+    var = new(N, D) if cov == 'diag' else new(N, D, D) if cov == 'point' else new(N * D, N * D)
+    info = ctypes.c_int(0)
+    for s, e in chunks:
+        _lib.call('gpode_conditional_df', D, M, e - s, _ptr(raw_ell), _ptr(raw_var), _ptr(Z), _ptr(Um), _ptr(Us_packed), _ptr(x[s:e]),
+                  COV_MODES[cov], _ptr(mean[s:e]), _ptr(var[s:e] if cov != 'full' else var), _ptr(ws), _stream())
+        _lib.call('gpode_cache_info', _ptr(ws), ctypes.byref(info), _stream())
+        if info.value & 1:
+            raise _lib.GpodeError('linalg.cholesky: K_uu + jitter*I is not positive-definite')
+    return mean, var
+
+
 class _Flow(torch.autograd.Function):
     """GP function draw(s) + fixed-grid integration (flow.py:68-86), differentiable w.r.t. z0 and the five GP parameter tensors.
     ``draws`` None: one draw, zt (N,T,D).  ``draws`` = L: the L draws of ODEGPVAE.sample_trajectories (odegpvae.py:37-45) in one
