@@ -237,6 +237,44 @@ def test_the_calls_reach_the_entry_points_they_should(monkeypatch):
         assert tuple(ast.shape) == (L, N, T - 1, 3, 1, D) and tuple(gpack.shape) == (L, 64)
 
 
+def test_the_dopri5_record_has_names_and_stays_a_tuple(monkeypatch):
+    """rollout(..., 'dopri5', save_stages=True): the record's fields by name are its positions (xstage, hstep, iend / istep, counts, and in
+    dense-output mode theta; a landing record stays four long, its theta None) and are the tensors handed to the entry point;
+    rollout_bwd takes a plain tuple in that order as before"""
+    from vae_gp_ode_amd import _lib, ops
+    calls = []
+    monkeypatch.setattr(_lib, 'call', lambda name, *a: calls.append((name, a)))
+    monkeypatch.setattr(ops, '_chk', lambda t, name, shape=None: t.contiguous())
+    monkeypatch.setattr(ops, '_stream', lambda: None)
+    monkeypatch.setattr(ops, '_ptr', lambda t: t)                            # the tensors themselves stand in for their addresses
+    monkeypatch.setattr(ops, '_check_increasing', lambda ts: None)           # asks the device whether a capture is under way
+    N, T, D, L, K = 5, 4, 6, 2, 12
+    c = ops.GPCache()
+    c.kernel, c.Di, c.Do, c.M, c.S, c.nd, c.stacked, c.pack = 'RBF', D, D, 8, 16, L, True, torch.zeros(L, 64)
+    z0, ts, gzt = torch.zeros(N, D), torch.arange(T).float(), torch.zeros(L, N, T, D)
+    for dense, fwd, bwd in ((False, 'gpode_rollout_adaptive_fwd_n', 'gpode_rollout_adaptive_bwd_n'),
+                            (True, 'gpode_rollout_dense_fwd_n', 'gpode_rollout_dense_bwd_n')):
+        del calls[:]
+        zt, rec = ops.rollout(c, z0, ts, 1, 'dopri5', save_stages=True, dense=dense)
+        names = ('xstage', 'hstep', 'index', 'counts') + (('theta',) if dense else ())
+        assert isinstance(rec, tuple) and len(rec) == len(names) and rec._fields == names
+        assert all(getattr(rec, n) is rec[i] for i, n in enumerate(names))
+        assert tuple(rec.xstage.shape) == (L, N, K, 7 if dense else 6, D) and tuple(rec.hstep.shape) == (L, N, K)
+        assert tuple(rec.index.shape) == (L, N, T - 1) and rec.index.dtype == torch.int32 and tuple(rec.counts.shape) == (L, N, 4)
+        assert (tuple(rec.theta.shape) == (L, N, T - 1)) if dense else rec.theta is None
+        (name, a), = calls
+        tail = (rec.xstage, rec.hstep, rec.index) + ((rec.theta,) if dense else ()) + (rec.counts, None)
+        assert name == fwd and a[16] is zt and len(a) == 17 + len(tail) and all(x is y for x, y in zip(a[17:], tail))
+        # the reverse sweep: the record itself, a plain tuple in its order and one without the counts behind the index go to the same call
+        for r in [rec, tuple(rec)] + ([] if dense else [tuple(rec)[:3]]):
+            del calls[:]
+            gz0, ast = ops.rollout_bwd(c, r, gzt, ts, 1, 'dopri5')
+            (name, a), = calls
+            want = (rec.xstage, rec.hstep, rec.index) + ((rec.theta,) if dense else ()) + (gzt, N, T, K, gz0, ast, None)
+            assert name == bwd and len(a) == 9 + len(want) and all(x is y for x, y in zip(a[9:], want))
+            assert tuple(ast.shape) == (L, N, K, 7 if dense else 6, D)
+
+
 def test_library_refuses_a_count_outside_the_range_by_name():
     """the entry points themselves (no GPU needed: refused before anything is launched), with gpode_last_error() naming the entry point"""
     from vae_gp_ode_amd import _lib

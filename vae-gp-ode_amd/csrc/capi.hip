@@ -85,71 +85,117 @@ int gpode_rhs_fwd(int kernel, int Di, int Do, int M, int S, const float* pack,
   return gp::rhs_fwd(kernel, Di, Do, M, S, pack, x, N, f, mode, (hipStream_t)stream);
 }
 
-static gp::Draws draws_of(int nd, size_t pack, size_t in, size_t out, size_t in2, size_t out2) {
-  gp::Draws d;
-  d.nd = nd; d.pack = pack; d.in = in; d.out = out; d.in2 = in2; d.out2 = out2;
-  return d;
-}
-static int stage_count(int method) { return method == 0 ? 1 : (method == 1 ? 4 : 2); }
-
 // ts_per_traj of the `_nt` entry points: 0 = ts (T,) shared by the trajectories, 1 = (N,T), row n for trajectory n of every draw
 static int ts_flag_refused(const char* who, int ts_per_traj) {
   if (ts_per_traj == 0 || ts_per_traj == 1) return 0;
   return gp::set_error("%s: ts_per_traj=%d (0 one (T,) grid shared, 1 one row of (N,T) per trajectory)", who, ts_per_traj);
+}
+// z0_per_draw of the `_nz` entry points: 0 = z0 (N,D) shared by the draws, 1 = (ndraws,N,D)
+static int z0_flag_refused(const char* who, int z0_per_draw) {
+  if (z0_per_draw == 0 || z0_per_draw == 1) return 0;
+  return gp::set_error("%s: z0_per_draw=%d (0 shared, 1 one (N,D) slab per draw)", who, z0_per_draw);
 }
 // substeps of the `_ns` entry points: equal solver steps per output interval, 1 (the twin's launch) ... gp::kMaxSubsteps
 static int substeps_refused(const char* who, int substeps) {
   if (substeps >= 1 && substeps <= gp::kMaxSubsteps) return 0;
   return gp::set_error("%s: substeps=%d (1 ... %d steps per output interval)", who, substeps, gp::kMaxSubsteps);
 }
-static gp::Draws with_ts(gp::Draws d, int ts_per_traj, int T, int substeps = 1) {
-  d.ts = ts_per_traj ? (size_t)T : 0;
-  d.sub = substeps;
-  return d;
-}
+static bool draws_ok(int ndraws) { return ndraws >= 1 && ndraws <= 65535; }   // the draws ride on gridDim.y
 
-// `who`: the entry point's name in the messages; z0_per_draw: 0 = z0 (N,D) shared by the draws, 1 = (ndraws,N,D)
+// The four checked operations under the gpode_rollout_* exports, which only name themselves (`who`, the entry point the error texts
+// start with) and the flags their prototype lacks.  Each checks the arguments and fills the launcher's struct by member name; the
+// strides and the record layout are the launcher's (gp_launch.hpp).
 static int rollout_fwd_any(const char* who, int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                            const float* pack, const float* z0, const float* ts, int N, int T,
-                           float* zt, float* xstage, int z0_per_draw, void* stream, int ts_per_traj = 0, int substeps = 1) {
-  if (z0_per_draw != 0 && z0_per_draw != 1) return gp::set_error("%s: z0_per_draw=%d (0 shared, 1 one (N,D) slab per draw)", who, z0_per_draw);
-  if (ts_flag_refused(who, ts_per_traj) || substeps_refused(who, substeps)) return 1;
-  if (N < 0 || T < 1 || ndraws < 1 || ndraws > 65535) return gp::set_error("%s: N=%d T=%d draws=%d", who, N, T, ndraws);
+                           float* zt, float* xstage, int z0_per_draw, int ts_per_traj, int substeps, void* stream) {
+  if (z0_flag_refused(who, z0_per_draw) || ts_flag_refused(who, ts_per_traj) || substeps_refused(who, substeps)) return 1;
+  if (N < 0 || T < 1 || !draws_ok(ndraws)) return gp::set_error("%s: N=%d T=%d draws=%d", who, N, T, ndraws);
   if (N == 0) return 0;
   if (!pack || !z0 || !ts || !zt) return gp::set_error("%s: null pointer", who);
-  size_t pf = 0;
-  if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
-  return gp::rollout_fwd(kernel, order, method, Di, Do, M, S, pack, z0, ts, N, T, zt, xstage, (hipStream_t)stream,
-                         with_ts(draws_of(ndraws, pf, z0_per_draw ? (size_t)N * Di : 0, (size_t)N * T * Di, 0,
-                                          (size_t)N * (T - 1) * substeps * stage_count(method) * Di), ts_per_traj, T, substeps));
+  const gp::RolloutFwdArgs a{.M = M, .S = S, .pack = pack, .z0 = z0, .ts = ts, .N = N, .T = T, .zt = zt, .xstage = xstage,
+                             .z0_per_draw = z0_per_draw != 0, .ts_per_traj = ts_per_traj != 0, .substeps = substeps};
+  return gp::rollout_fwd(kernel, order, method, Di, Do, a, ndraws, (hipStream_t)stream);
 }
-int gpode_rollout_fwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
-                        const float* pack, const float* z0, const float* ts, int N, int T,
-                        float* zt, float* xstage, void* stream) {
-  return rollout_fwd_any("gpode_rollout_fwd", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, zt, xstage, 0, stream);
+// slab / nchunk / gpack: the fused sweep with parameter sums (`pgrad`, which needs a step to sum over); null / 0 for the plain one
+static int rollout_bwd_any(const char* who, bool pgrad, int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                           const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
+                           float* gz0, float* astage, float* slab, int nchunk, float* gpack, int ts_per_traj, int substeps,
+                           void* stream) {
+  if (ts_flag_refused(who, ts_per_traj) || substeps_refused(who, substeps)) return 1;
+  if (N < (pgrad ? 1 : 0) || T < (pgrad ? 2 : 1) || !draws_ok(ndraws)) return gp::set_error("%s: N=%d T=%d draws=%d", who, N, T, ndraws);
+  if (N == 0) return 0;
+  if (!pack || !gzt || !ts || !gz0 || (T > 1 && (!xstage || !astage)) || (pgrad && (!slab || !gpack)))
+    return gp::set_error("%s: null pointer", who);
+  const gp::RolloutBwdArgs a{.M = M, .S = S, .pack = pack, .xstage = xstage, .gzt = gzt, .ts = ts, .N = N, .T = T, .gz0 = gz0,
+                             .astage = astage, .ts_per_traj = ts_per_traj != 0, .substeps = substeps, .slab = slab, .nchunk = nchunk,
+                             .gpack = gpack};
+  return pgrad ? gp::rollout_bwd_pgrad(kernel, order, method, Di, Do, a, ndraws, (hipStream_t)stream)
+               : gp::rollout_bwd(kernel, order, method, Di, Do, a, ndraws, (hipStream_t)stream);
 }
-int gpode_rollout_fwd_nz(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
-                         const float* pack, const float* z0, const float* ts, int N, int T,
-                         float* zt, float* xstage, int z0_per_draw, void* stream) {
-  return rollout_fwd_any("gpode_rollout_fwd_nz", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, zt, xstage, z0_per_draw,
-                         stream);
+// dopri5, landing (index = iend, theta unused) or dense (index = istep)
+static int adaptive_fwd_any(const char* who, bool dense, int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                            const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
+                            float* zt, float* xstage, float* hstep, int* index, float* theta, int* counts, int z0_per_draw,
+                            int ts_per_traj, void* stream) {
+  if (ts_flag_refused(who, ts_per_traj) || z0_flag_refused(who, z0_per_draw)) return 1;
+  if (method != GPODE_METHOD_DOPRI5) return gp::set_error("%s: method %d (3 dopri5)", who, method);
+  if (N < 0 || T < 1 || K < 0 || !draws_ok(ndraws)) return gp::set_error("%s: N=%d T=%d K=%d draws=%d", who, N, T, K, ndraws);
+  if (!(rtol >= 0.f) || !(atol >= 0.f) || !(rtol + atol > 0.f) || !(rtol + atol < 1e30f))
+    return gp::set_error("%s: rtol=%g atol=%g (both >= 0, not both 0)", who, rtol, atol);
+  if (N == 0) return 0;
+  if (!pack || !z0 || !ts || !zt || !counts) return gp::set_error("%s: null pointer", who);
+  if (xstage && T > 1 && (!index || (dense && !theta) || (K > 0 && !hstep)))
+    return gp::set_error(dense ? "%s: xstage without hstep / istep / theta" : "%s: xstage without hstep / iend", who);
+  const gp::AdaptFwdArgs a{.M = M, .S = S, .pack = pack, .z0 = z0, .ts = ts, .N = N, .T = T, .K = K, .rtol = rtol, .atol = atol,
+                           .zt = zt, .xstage = xstage, .hstep = hstep, .index = index, .theta = theta, .counts = counts,
+                           .z0_per_draw = z0_per_draw != 0, .ts_per_traj = ts_per_traj != 0};
+  return gp::rollout_adaptive_fwd(kernel, order, Di, Do, a, dense, ndraws, (hipStream_t)stream);
 }
-int gpode_rollout_fwd_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
-                         const float* pack, const float* z0, const float* ts, int N, int T,
-                         float* zt, float* xstage, int z0_per_draw, int ts_per_traj, void* stream) {
-  return rollout_fwd_any("gpode_rollout_fwd_nt", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, zt, xstage, z0_per_draw,
-                         stream, ts_per_traj);
+static int adaptive_bwd_any(const char* who, bool dense, int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                            const float* pack, const float* xstage, const float* hstep, const int* index, const float* theta,
+                            const float* gzt, int N, int T, int K, float* gz0, float* astage, void* stream) {
+  if (method != GPODE_METHOD_DOPRI5) return gp::set_error("%s: method %d (3 dopri5)", who, method);
+  if (N < 0 || T < 1 || K < 0 || !draws_ok(ndraws)) return gp::set_error("%s: N=%d T=%d K=%d draws=%d", who, N, T, K, ndraws);
+  if (N == 0) return 0;
+  if (!pack || !gzt || !gz0 || (T > 1 && (!index || (dense && !theta))) || (T > 1 && K > 0 && (!xstage || !hstep || !astage)))
+    return gp::set_error("%s: null pointer", who);
+  const gp::AdaptBwdArgs a{.M = M, .S = S, .pack = pack, .xstage = xstage, .hstep = hstep, .index = index, .theta = theta, .gzt = gzt,
+                           .N = N, .T = T, .K = K, .gz0 = gz0, .astage = astage};
+  return gp::rollout_adaptive_bwd(kernel, order, Di, Do, a, dense, ndraws, (hipStream_t)stream);
 }
+
 int gpode_test_substep_kernels(int on) {
   if (on != 0 && on != 1) return gp::set_error("gpode_test_substep_kernels: on=%d (0 or 1)", on);
   *gp::force_substep_kernels() = on != 0;
   return 0;
 }
+int gpode_rollout_bwd_pgrad_chunks(int kernel, int order, int method, int Di, int Do, int M, int S, int N) {
+  return gp::rollout_bwd_pgrad_chunks(kernel, order, method, Di, Do, M, S, N);
+}
+
+// The exports: thin forwards.  An entry point without a flag passes the value its twin with the flag takes for "as before".
+int gpode_rollout_fwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                        const float* pack, const float* z0, const float* ts, int N, int T,
+                        float* zt, float* xstage, void* stream) {
+  return rollout_fwd_any("gpode_rollout_fwd", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, zt, xstage, 0, 0, 1, stream);
+}
+int gpode_rollout_fwd_nz(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                         const float* pack, const float* z0, const float* ts, int N, int T,
+                         float* zt, float* xstage, int z0_per_draw, void* stream) {
+  return rollout_fwd_any("gpode_rollout_fwd_nz", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, zt, xstage, z0_per_draw,
+                         0, 1, stream);
+}
+int gpode_rollout_fwd_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
+                         const float* pack, const float* z0, const float* ts, int N, int T,
+                         float* zt, float* xstage, int z0_per_draw, int ts_per_traj, void* stream) {
+  return rollout_fwd_any("gpode_rollout_fwd_nt", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, zt, xstage, z0_per_draw,
+                         ts_per_traj, 1, stream);
+}
 int gpode_rollout_fwd_ns(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                          const float* pack, const float* z0, const float* ts, int N, int T,
                          float* zt, float* xstage, int z0_per_draw, int ts_per_traj, int substeps, void* stream) {
   return rollout_fwd_any("gpode_rollout_fwd_ns", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, zt, xstage, z0_per_draw,
-                         stream, ts_per_traj, substeps);
+                         ts_per_traj, substeps, stream);
 }
 int gpode_rollout_fwd(int kernel, int order, int method, int Di, int Do, int M, int S,
                       const float* pack, const float* z0, const float* ts, int N, int T,
@@ -157,66 +203,40 @@ int gpode_rollout_fwd(int kernel, int order, int method, int Di, int Do, int M, 
   return gpode_rollout_fwd_n(kernel, order, method, Di, Do, M, S, 1, pack, z0, ts, N, T, zt, xstage, stream);
 }
 
-static int rollout_bwd_any(const char* who, int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
-                           const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
-                           float* gz0, float* astage, int ts_per_traj, int substeps, void* stream) {
-  if (ts_flag_refused(who, ts_per_traj) || substeps_refused(who, substeps)) return 1;
-  if (N < 0 || T < 1 || ndraws < 1 || ndraws > 65535) return gp::set_error("%s: N=%d T=%d draws=%d", who, N, T, ndraws);
-  if (N == 0) return 0;
-  if (!pack || !gzt || !ts || !gz0 || (T > 1 && (!xstage || !astage))) return gp::set_error("%s: null pointer", who);
-  size_t pf = 0;
-  if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
-  const size_t rows = (size_t)N * (T - 1) * substeps * stage_count(method);
-  return gp::rollout_bwd(kernel, order, method, Di, Do, M, S, pack, xstage, gzt, ts, N, T, gz0, astage, (hipStream_t)stream,
-                         with_ts(draws_of(ndraws, pf, rows * Di, (size_t)N * Di, (size_t)N * T * Di, rows * Do), ts_per_traj, T, substeps));
-}
 int gpode_rollout_bwd_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                          const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
                          float* gz0, float* astage, int ts_per_traj, void* stream) {
-  return rollout_bwd_any("gpode_rollout_bwd", kernel, order, method, Di, Do, M, S, ndraws, pack, xstage, gzt, ts, N, T, gz0, astage,
-                         ts_per_traj, 1, stream);
+  return rollout_bwd_any("gpode_rollout_bwd", false, kernel, order, method, Di, Do, M, S, ndraws, pack, xstage, gzt, ts, N, T, gz0, astage,
+                         nullptr, 0, nullptr, ts_per_traj, 1, stream);
 }
 int gpode_rollout_bwd_ns(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                          const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
                          float* gz0, float* astage, int ts_per_traj, int substeps, void* stream) {
-  return rollout_bwd_any("gpode_rollout_bwd_ns", kernel, order, method, Di, Do, M, S, ndraws, pack, xstage, gzt, ts, N, T, gz0, astage,
-                         ts_per_traj, substeps, stream);
+  return rollout_bwd_any("gpode_rollout_bwd_ns", false, kernel, order, method, Di, Do, M, S, ndraws, pack, xstage, gzt, ts, N, T, gz0, astage,
+                         nullptr, 0, nullptr, ts_per_traj, substeps, stream);
 }
 int gpode_rollout_bwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                         const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
                         float* gz0, float* astage, void* stream) {
   return gpode_rollout_bwd_nt(kernel, order, method, Di, Do, M, S, ndraws, pack, xstage, gzt, ts, N, T, gz0, astage, 0, stream);
 }
-int gpode_rollout_bwd_pgrad_chunks(int kernel, int order, int method, int Di, int Do, int M, int S, int N) {
-  return gp::rollout_bwd_pgrad_chunks(kernel, order, method, Di, Do, M, S, N);
-}
-static int rollout_bwd_pgrad_any(const char* who, int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
-                                 const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
-                                 float* gz0, float* astage, float* slab, int nchunk, float* gpack, int ts_per_traj, int substeps,
-                                 void* stream) {
-  if (ts_flag_refused(who, ts_per_traj) || substeps_refused(who, substeps)) return 1;
-  if (N < 1 || T < 2 || ndraws < 1 || ndraws > 65535) return gp::set_error("%s: N=%d T=%d draws=%d", who, N, T, ndraws);
-  if (!pack || !gzt || !ts || !gz0 || !xstage || !astage || !slab || !gpack) return gp::set_error("%s: null pointer", who);
-  size_t pf = 0;
-  if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
-  const size_t rows = (size_t)N * (T - 1) * substeps * stage_count(method);
-  return gp::rollout_bwd_pgrad(kernel, order, method, Di, Do, M, S, pack, xstage, gzt, ts, N, T, gz0, astage, slab, nchunk, gpack,
-                               (hipStream_t)stream,
-                               with_ts(draws_of(ndraws, pf, rows * Di, (size_t)N * Di, (size_t)N * T * Di, rows * Do), ts_per_traj, T,
-                                       substeps));
+int gpode_rollout_bwd(int kernel, int order, int method, int Di, int Do, int M, int S,
+                      const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
+                      float* gz0, float* astage, void* stream) {
+  return gpode_rollout_bwd_n(kernel, order, method, Di, Do, M, S, 1, pack, xstage, gzt, ts, N, T, gz0, astage, stream);
 }
 int gpode_rollout_bwd_pgrad_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                                const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
                                float* gz0, float* astage, float* slab, int nchunk, float* gpack, int ts_per_traj, void* stream) {
-  return rollout_bwd_pgrad_any("gpode_rollout_bwd_pgrad", kernel, order, method, Di, Do, M, S, ndraws, pack, xstage, gzt, ts, N, T, gz0,
-                               astage, slab, nchunk, gpack, ts_per_traj, 1, stream);
+  return rollout_bwd_any("gpode_rollout_bwd_pgrad", true, kernel, order, method, Di, Do, M, S, ndraws, pack, xstage, gzt, ts, N, T, gz0,
+                         astage, slab, nchunk, gpack, ts_per_traj, 1, stream);
 }
 int gpode_rollout_bwd_pgrad_ns(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                                const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
                                float* gz0, float* astage, float* slab, int nchunk, float* gpack, int ts_per_traj, int substeps,
                                void* stream) {
-  return rollout_bwd_pgrad_any("gpode_rollout_bwd_pgrad_ns", kernel, order, method, Di, Do, M, S, ndraws, pack, xstage, gzt, ts, N, T, gz0,
-                               astage, slab, nchunk, gpack, ts_per_traj, substeps, stream);
+  return rollout_bwd_any("gpode_rollout_bwd_pgrad_ns", true, kernel, order, method, Di, Do, M, S, ndraws, pack, xstage, gzt, ts, N, T, gz0,
+                         astage, slab, nchunk, gpack, ts_per_traj, substeps, stream);
 }
 int gpode_rollout_bwd_pgrad_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                               const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
@@ -224,120 +244,57 @@ int gpode_rollout_bwd_pgrad_n(int kernel, int order, int method, int Di, int Do,
   return gpode_rollout_bwd_pgrad_nt(kernel, order, method, Di, Do, M, S, ndraws, pack, xstage, gzt, ts, N, T, gz0, astage, slab, nchunk,
                                     gpack, 0, stream);
 }
-int gpode_rollout_bwd(int kernel, int order, int method, int Di, int Do, int M, int S,
-                      const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
-                      float* gz0, float* astage, void* stream) {
-  return gpode_rollout_bwd_n(kernel, order, method, Di, Do, M, S, 1, pack, xstage, gzt, ts, N, T, gz0, astage, stream);
-}
 
-// The argument checks of the dopri5 entry points, landing and dense alike.  who: the entry point the error names.
-// -> 1 refused (the error is set), -1 nothing to integrate (N = 0), 0 go on.
-static int adaptive_fwd_args(const char* who, int method, int ndraws, const float* pack, const float* z0, const float* ts, int N, int T,
-                             float rtol, float atol, int K, const float* zt, const int* counts, int z0_per_draw) {
-  if (z0_per_draw != 0 && z0_per_draw != 1) return gp::set_error("%s: z0_per_draw=%d (0 shared, 1 one (N,D) slab per draw)", who, z0_per_draw);
-  if (method != GPODE_METHOD_DOPRI5) return gp::set_error("%s: method %d (3 dopri5)", who, method);
-  if (N < 0 || T < 1 || K < 0 || ndraws < 1 || ndraws > 65535)
-    return gp::set_error("%s: N=%d T=%d K=%d draws=%d", who, N, T, K, ndraws);
-  if (!(rtol >= 0.f) || !(atol >= 0.f) || !(rtol + atol > 0.f) || !(rtol + atol < 1e30f))
-    return gp::set_error("%s: rtol=%g atol=%g (both >= 0, not both 0)", who, rtol, atol);
-  if (N == 0) return -1;
-  if (!pack || !z0 || !ts || !zt || !counts) return gp::set_error("%s: null pointer", who);
-  return 0;
-}
-// index: the mode's index of the record is there (iend; istep and theta)
-static int adaptive_bwd_args(const char* who, int method, int ndraws, const float* pack, const float* xstage, const float* hstep, bool index,
-                             const float* gzt, int N, int T, int K, const float* gz0, const float* astage) {
-  if (method != GPODE_METHOD_DOPRI5) return gp::set_error("%s: method %d (3 dopri5)", who, method);
-  if (N < 0 || T < 1 || K < 0 || ndraws < 1 || ndraws > 65535) return gp::set_error("%s: N=%d T=%d K=%d draws=%d", who, N, T, K, ndraws);
-  if (N == 0) return -1;
-  if (!pack || !gzt || !gz0 || (T > 1 && !index) || (T > 1 && K > 0 && (!xstage || !hstep || !astage))) return gp::set_error("%s: null pointer", who);
-  return 0;
-}
-
-static int rollout_adaptive_fwd_any(const char* who, int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
-                                    const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
-                                    float* zt, float* xstage, float* hstep, int* iend, int* counts, int z0_per_draw, void* stream,
-                                    int ts_per_traj = 0) {
-  if (ts_flag_refused(who, ts_per_traj)) return 1;
-  if (const int rc = adaptive_fwd_args(who, method, ndraws, pack, z0, ts, N, T, rtol, atol, K, zt, counts, z0_per_draw)) return rc > 0;
-  if (xstage && T > 1 && (!iend || (K > 0 && !hstep))) return gp::set_error("%s: xstage without hstep / iend", who);
-  size_t pf = 0;
-  if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
-  return gp::rollout_adaptive_fwd(kernel, order, Di, Do, M, S, ndraws, pack, pf, z0, ts, N, T, rtol, atol, K, zt, xstage, hstep, iend,
-                                  counts, (hipStream_t)stream, z0_per_draw ? (size_t)N * Di : 0, ts_per_traj ? (size_t)T : 0);
-}
 int gpode_rollout_adaptive_fwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                                  const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
                                  float* zt, float* xstage, float* hstep, int* iend, int* counts, void* stream) {
-  return rollout_adaptive_fwd_any("gpode_rollout_adaptive_fwd", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol, atol,
-                                  K, zt, xstage, hstep, iend, counts, 0, stream);
+  return adaptive_fwd_any("gpode_rollout_adaptive_fwd", false, kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol, atol,
+                          K, zt, xstage, hstep, iend, nullptr, counts, 0, 0, stream);
 }
 int gpode_rollout_adaptive_fwd_nz(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                                   const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
                                   float* zt, float* xstage, float* hstep, int* iend, int* counts, int z0_per_draw, void* stream) {
-  return rollout_adaptive_fwd_any("gpode_rollout_adaptive_fwd_nz", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol,
-                                  atol, K, zt, xstage, hstep, iend, counts, z0_per_draw, stream);
+  return adaptive_fwd_any("gpode_rollout_adaptive_fwd_nz", false, kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol,
+                          atol, K, zt, xstage, hstep, iend, nullptr, counts, z0_per_draw, 0, stream);
 }
 int gpode_rollout_adaptive_fwd_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                                   const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
                                   float* zt, float* xstage, float* hstep, int* iend, int* counts, int z0_per_draw, int ts_per_traj,
                                   void* stream) {
-  return rollout_adaptive_fwd_any("gpode_rollout_adaptive_fwd_nt", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol,
-                                  atol, K, zt, xstage, hstep, iend, counts, z0_per_draw, stream, ts_per_traj);
+  return adaptive_fwd_any("gpode_rollout_adaptive_fwd_nt", false, kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol,
+                          atol, K, zt, xstage, hstep, iend, nullptr, counts, z0_per_draw, ts_per_traj, stream);
 }
 int gpode_rollout_adaptive_bwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                                  const float* pack, const float* xstage, const float* hstep, const int* iend, const float* gzt,
                                  int N, int T, int K, float* gz0, float* astage, void* stream) {
-  if (const int rc = adaptive_bwd_args("gpode_rollout_adaptive_bwd", method, ndraws, pack, xstage, hstep, iend != nullptr, gzt, N, T, K, gz0, astage))
-    return rc > 0;
-  size_t pf = 0;
-  if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
-  return gp::rollout_adaptive_bwd(kernel, order, Di, Do, M, S, ndraws, pack, pf, xstage, hstep, iend, gzt, N, T, K, gz0, astage,
-                                  (hipStream_t)stream);
-}
-
-static int rollout_dense_fwd_any(const char* who, int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
-                                 const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
-                                 float* zt, float* xstage, float* hstep, int* istep, float* theta, int* counts, int z0_per_draw,
-                                 void* stream, int ts_per_traj = 0) {
-  if (ts_flag_refused(who, ts_per_traj)) return 1;
-  if (const int rc = adaptive_fwd_args(who, method, ndraws, pack, z0, ts, N, T, rtol, atol, K, zt, counts, z0_per_draw)) return rc > 0;
-  if (xstage && T > 1 && (!istep || !theta || (K > 0 && !hstep)))
-    return gp::set_error("%s: xstage without hstep / istep / theta", who);
-  size_t pf = 0;
-  if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
-  return gp::rollout_dense_fwd(kernel, order, Di, Do, M, S, ndraws, pack, pf, z0, ts, N, T, rtol, atol, K, zt, xstage, hstep, istep, theta,
-                               counts, (hipStream_t)stream, z0_per_draw ? (size_t)N * Di : 0, ts_per_traj ? (size_t)T : 0);
+  return adaptive_bwd_any("gpode_rollout_adaptive_bwd", false, kernel, order, method, Di, Do, M, S, ndraws, pack, xstage, hstep, iend,
+                          nullptr, gzt, N, T, K, gz0, astage, stream);
 }
 int gpode_rollout_dense_fwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                               const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
                               float* zt, float* xstage, float* hstep, int* istep, float* theta, int* counts, void* stream) {
-  return rollout_dense_fwd_any("gpode_rollout_dense_fwd", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol, atol, K, zt,
-                               xstage, hstep, istep, theta, counts, 0, stream);
+  return adaptive_fwd_any("gpode_rollout_dense_fwd", true, kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol, atol, K, zt,
+                          xstage, hstep, istep, theta, counts, 0, 0, stream);
 }
 int gpode_rollout_dense_fwd_nz(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                                const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
                                float* zt, float* xstage, float* hstep, int* istep, float* theta, int* counts, int z0_per_draw,
                                void* stream) {
-  return rollout_dense_fwd_any("gpode_rollout_dense_fwd_nz", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol, atol, K,
-                               zt, xstage, hstep, istep, theta, counts, z0_per_draw, stream);
+  return adaptive_fwd_any("gpode_rollout_dense_fwd_nz", true, kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol, atol, K,
+                          zt, xstage, hstep, istep, theta, counts, z0_per_draw, 0, stream);
 }
 int gpode_rollout_dense_fwd_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                                const float* pack, const float* z0, const float* ts, int N, int T, float rtol, float atol, int K,
                                float* zt, float* xstage, float* hstep, int* istep, float* theta, int* counts, int z0_per_draw,
                                int ts_per_traj, void* stream) {
-  return rollout_dense_fwd_any("gpode_rollout_dense_fwd_nt", kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol, atol, K,
-                               zt, xstage, hstep, istep, theta, counts, z0_per_draw, stream, ts_per_traj);
+  return adaptive_fwd_any("gpode_rollout_dense_fwd_nt", true, kernel, order, method, Di, Do, M, S, ndraws, pack, z0, ts, N, T, rtol, atol, K,
+                          zt, xstage, hstep, istep, theta, counts, z0_per_draw, ts_per_traj, stream);
 }
 int gpode_rollout_dense_bwd_n(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                               const float* pack, const float* xstage, const float* hstep, const int* istep, const float* theta,
                               const float* gzt, int N, int T, int K, float* gz0, float* astage, void* stream) {
-  if (const int rc = adaptive_bwd_args("gpode_rollout_dense_bwd", method, ndraws, pack, xstage, hstep, istep && theta, gzt, N, T, K, gz0, astage))
-    return rc > 0;
-  size_t pf = 0;
-  if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
-  return gp::rollout_dense_bwd(kernel, order, Di, Do, M, S, ndraws, pack, pf, xstage, hstep, istep, theta, gzt, N, T, K, gz0, astage,
-                               (hipStream_t)stream);
+  return adaptive_bwd_any("gpode_rollout_dense_bwd", true, kernel, order, method, Di, Do, M, S, ndraws, pack, xstage, hstep, istep, theta,
+                          gzt, N, T, K, gz0, astage, stream);
 }
 
 int gpode_rhs_vjp(int kernel, int Di, int Do, int M, int S, const float* pack,
@@ -353,8 +310,9 @@ int gpode_param_grad_n(int kernel, int Di, int Do, int M, int S, int ndraws, con
   if (ndraws < 1 || ndraws > 65535) return gp::set_error("gpode_param_grad: %d draws", ndraws);
   size_t pf = 0;
   if (gp::cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
-  return gp::param_grad(kernel, Di, Do, M, S, pack, x, a, R, slab, nchunk, gpack, accumulate, 0, (hipStream_t)stream,
-                        draws_of(ndraws, pf, (size_t)R * Di, pf, (size_t)R * Do, 0));
+  gp::Draws d;
+  d.nd = ndraws; d.pack = pf; d.in = (size_t)R * Di; d.in2 = (size_t)R * Do; d.out = pf;
+  return gp::param_grad(kernel, Di, Do, M, S, pack, x, a, R, slab, nchunk, gpack, accumulate, 0, (hipStream_t)stream, d);
 }
 int gpode_param_grad(int kernel, int Di, int Do, int M, int S, const float* pack,
                      const float* x, const float* a, int R, float* slab, int nchunk, float* gpack, int accumulate,

@@ -74,7 +74,8 @@ struct AdaptBwd {
   const float* xstage; const float* hstep; const int* iend; const float* gzt; int N, T, K;
   float* gz0; float* astage;
 };
-// What the kernels take.  z0_stride: floats between the draws' initial states, 0 = one (N,D) block shared by all draws; it is the
+// What the kernels take, filled from AdaptFwdArgs / AdaptBwdArgs (gp_launch.hpp) by adapt_fwd_arg and rollout_adaptive_bwd below.
+// z0_stride: floats between the draws' initial states, 0 = one (N,D) block shared by all draws; it is the
 // member after the mode's own pointers, so every other argument stays where it was.  ts_stride follows it: floats between the
 // trajectories' time grids, 0 = the one (T,) grid all of them share, T = row n of a dense (N,T) block for trajectory n of every draw.
 // The dense mode's kernels take one pointer more.
@@ -130,7 +131,7 @@ __device__ __forceinline__ void dopri5_trajectory(EV& ev, const AdaptFwd& a, con
   int* irec = rec ? iend + (size_t)n * (T - 1) : nullptr;
   float* trec = DENSE && rec ? theta + (size_t)n * (T - 1) : nullptr;
   if (wr) store_state<DI>(out, y, lane);
-  ode_rhs_mut<EV, DI, DO, ORDER>(ev, y, kv);
+  ode_rhs<EV, DI, DO, ORDER>(ev, y, kv);
   put_row<DI>(kst, kv);
   int nacc = 0, nrej = 0, status = 0, nfe = 1, t = 0;
   float h = 0.f, tn = 0.f;                           // tn (dense): time reached, as an offset from ts[0]
@@ -170,7 +171,7 @@ __device__ __forceinline__ void dopri5_trajectory(EV& ev, const AdaptFwd& a, con
 #pragma unroll
         for (int d = 0; d < DI; ++d) xs[d] = fmaf(hs, acc[d], y[d]);
         if (rec && s < NR) store_state<DI>(xrec + (size_t)(nacc * NR + s) * DI, xs, lane);
-        ode_rhs_mut<EV, DI, DO, ORDER>(ev, xs, kv);
+        ode_rhs<EV, DI, DO, ORDER>(ev, xs, kv);
         put_row<DI>(kst + s * KP, kv);
       }
       nfe += 6;
@@ -514,18 +515,20 @@ static int adaptive_fwd(int kernel, int order, int Di, int Do, const AdaptFwdArg
   });
 }
 
-int rollout_adaptive_fwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
-                         const float* z0, const float* ts, int N, int T, float rtol, float atol, int K, float* zt, float* xstage,
-                         float* hstep, int* iend, int* counts, hipStream_t st, size_t z0_stride, size_t ts_stride) {
-  const AdaptFwdLand a{{pack, pack_stride, M, S, z0, ts, N, T, K, rtol, atol, zt, xstage, hstep, iend, counts}, z0_stride, ts_stride};
-  return adaptive_fwd<false>(kernel, order, Di, Do, a, nd, st);
+// What the kernels take, from the entry point's arguments: the draws' packs pack_floats apart, z0 a slab per draw or shared.
+template <bool DENSE> static AdaptFwdArg<DENSE> adapt_fwd_arg(const AdaptFwdArgs& a, int Di, size_t pack_floats) {
+  const AdaptFwd base{a.pack, pack_floats, a.M, a.S, a.z0, a.ts, a.N, a.T, a.K, a.rtol, a.atol, a.zt, a.xstage, a.hstep, a.index, a.counts};
+  const size_t z0_stride = a.z0_per_draw ? (size_t)a.N * Di : 0, ts_stride = a.ts_per_traj ? (size_t)a.T : 0;
+  if constexpr (DENSE) return {base, a.theta, z0_stride, ts_stride};
+  else return {base, z0_stride, ts_stride};
 }
 
-int rollout_dense_fwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
-                      const float* z0, const float* ts, int N, int T, float rtol, float atol, int K, float* zt, float* xstage,
-                      float* hstep, int* istep, float* theta, int* counts, hipStream_t st, size_t z0_stride, size_t ts_stride) {
-  const AdaptFwdDense a{{pack, pack_stride, M, S, z0, ts, N, T, K, rtol, atol, zt, xstage, hstep, istep, counts}, theta, z0_stride, ts_stride};
-  return adaptive_fwd<true>(kernel, order, Di, Do, a, nd, st);
+int rollout_adaptive_fwd(int kernel, int order, int Di, int Do, const AdaptFwdArgs& a, bool dense, int nd, hipStream_t st) {
+  size_t pf = 0;
+  if (cache_sizes(kernel, Di, Do, a.M, a.S, &pf, nullptr)) return 1;
+  // landing first, as the two have always been instantiated: the order decides the numbering of the object's local labels
+  if (!dense) return adaptive_fwd<false>(kernel, order, Di, Do, adapt_fwd_arg<false>(a, Di, pf), nd, st);
+  return adaptive_fwd<true>(kernel, order, Di, Do, adapt_fwd_arg<true>(a, Di, pf), nd, st);
 }
 
 // the reverse kernel of a mode
@@ -553,18 +556,12 @@ static int adaptive_bwd(int kernel, int order, int Di, int Do, const AdaptBwdArg
   });
 }
 
-int rollout_adaptive_bwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
-                         const float* xstage, const float* hstep, const int* iend, const float* gzt, int N, int T, int K,
-                         float* gz0, float* astage, hipStream_t st) {
-  const AdaptBwd a{pack, pack_stride, M, S, xstage, hstep, iend, gzt, N, T, K, gz0, astage};
-  return adaptive_bwd<false>(kernel, order, Di, Do, a, nd, st);
-}
-
-int rollout_dense_bwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
-                      const float* xstage, const float* hstep, const int* istep, const float* theta, const float* gzt, int N, int T,
-                      int K, float* gz0, float* astage, hipStream_t st) {
-  const AdaptBwdDense a{{pack, pack_stride, M, S, xstage, hstep, istep, gzt, N, T, K, gz0, astage}, theta};
-  return adaptive_bwd<true>(kernel, order, Di, Do, a, nd, st);
+int rollout_adaptive_bwd(int kernel, int order, int Di, int Do, const AdaptBwdArgs& a, bool dense, int nd, hipStream_t st) {
+  size_t pf = 0;
+  if (cache_sizes(kernel, Di, Do, a.M, a.S, &pf, nullptr)) return 1;
+  const AdaptBwd base{a.pack, pf, a.M, a.S, a.xstage, a.hstep, a.index, a.gzt, a.N, a.T, a.K, a.gz0, a.astage};
+  if (!dense) return adaptive_bwd<false>(kernel, order, Di, Do, base, nd, st);
+  return adaptive_bwd<true>(kernel, order, Di, Do, AdaptBwdDense{base, a.theta}, nd, st);
 }
 
 }  // namespace gp

@@ -18,15 +18,6 @@
 
 namespace gp {
 
-template <int DI> __device__ __forceinline__ void store_vec(float* __restrict__ dst, const float (&y)[DI], int lane) {
-  if (lane < DI) {
-    float v = y[0];
-#pragma unroll
-    for (int i = 1; i < DI; ++i) v = (lane == i) ? y[i] : v;
-    dst[lane] = v;
-  }
-}
-
 template <int DI, int DO, int NJ>
 __device__ __forceinline__ void store_grads_rbf(const typename RbfTeamEval<DI, DO, NJ>::Grads& G, float* __restrict__ out, int M, int S,
                                                 int wave, int lane, float (*sInd)[64][4 * RbfLayout<DI, DO>::RQ2],
@@ -50,7 +41,7 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rollout_bwd_team_kernel(const 
                                                                 const float* __restrict__ ts, int N, int T,
                                                                 float* __restrict__ gz0, float* __restrict__ astage, Draws dw,
                                                                 float* __restrict__ slab = nullptr, size_t pack_floats = 0) {
-  constexpr int NS = METHOD == 0 ? 1 : (METHOD == 1 ? 4 : 2);
+  constexpr int NS = stages_of(METHOD);
   __shared__ float slots[2 * EV::kTeam * TeamCombine::DP];
   // blockIdx.y = Monte-Carlo draw
   pack += blockIdx.y * dw.pack; xstage += blockIdx.y * dw.in; gzt += blockIdx.y * dw.in2; gz0 += blockIdx.y * dw.out; astage += blockIdx.y * dw.out2;
@@ -81,7 +72,7 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rollout_bwd_team_kernel(const 
 #pragma unroll
           for (int i = 0; i < DI; ++i) { a1[i] = dt * lam[i]; x[i] = xt[i]; }
           ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a1, g, af, &G);
-          if (wave == 0) store_vec<DO>(at, af, lane);
+          if (wave == 0) store_state<DO>(at, af, lane);
 #pragma unroll
           for (int i = 0; i < DI; ++i) lam[i] += g[i];
         } else if (METHOD == 2) {
@@ -90,11 +81,11 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rollout_bwd_team_kernel(const 
 #pragma unroll
           for (int i = 0; i < DI; ++i) { a2[i] = dt * lam[i]; x[i] = xt[DI + i]; }
           ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a2, g, af, &G);
-          if (wave == 0) store_vec<DO>(at + DO, af, lane);
+          if (wave == 0) store_state<DO>(at + DO, af, lane);
 #pragma unroll
           for (int i = 0; i < DI; ++i) { ay[i] = lam[i] + g[i]; a1[i] = 0.5f * dt * g[i]; x[i] = xt[i]; }
           ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a1, g, af, &G);
-          if (wave == 0) store_vec<DO>(at, af, lane);
+          if (wave == 0) store_state<DO>(at, af, lane);
 #pragma unroll
           for (int i = 0; i < DI; ++i) lam[i] = ay[i] + g[i];
         } else {
@@ -108,25 +99,25 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rollout_bwd_team_kernel(const 
 #pragma unroll
           for (int i = 0; i < DI; ++i) x[i] = xt[3 * DI + i];
           ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a4, g, af, &G);
-          if (wave == 0) store_vec<DO>(at + 3 * DO, af, lane);
+          if (wave == 0) store_state<DO>(at + 3 * DO, af, lane);
 #pragma unroll
           for (int i = 0; i < DI; ++i) { ay[i] += g[i]; a1[i] += dt * g[i]; a2[i] -= dt * g[i]; a3[i] += dt * g[i]; }
 #pragma unroll
           for (int i = 0; i < DI; ++i) x[i] = xt[2 * DI + i];
           ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a3, g, af, &G);
-          if (wave == 0) store_vec<DO>(at + 2 * DO, af, lane);
+          if (wave == 0) store_state<DO>(at + 2 * DO, af, lane);
 #pragma unroll
           for (int i = 0; i < DI; ++i) { ay[i] += g[i]; a2[i] += dt * g[i]; a1[i] -= dt * third * g[i]; }
 #pragma unroll
           for (int i = 0; i < DI; ++i) x[i] = xt[1 * DI + i];
           ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a2, g, af, &G);
-          if (wave == 0) store_vec<DO>(at + 1 * DO, af, lane);
+          if (wave == 0) store_state<DO>(at + 1 * DO, af, lane);
 #pragma unroll
           for (int i = 0; i < DI; ++i) { ay[i] += g[i]; a1[i] += dt * third * g[i]; }
 #pragma unroll
           for (int i = 0; i < DI; ++i) x[i] = xt[i];
           ode_vjp<EV, DI, DO, ORDER, GR>(ev, x, a1, g, af, &G);
-          if (wave == 0) store_vec<DO>(at, af, lane);
+          if (wave == 0) store_state<DO>(at, af, lane);
 #pragma unroll
           for (int i = 0; i < DI; ++i) lam[i] = ay[i] + g[i];
         }
@@ -134,7 +125,7 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rollout_bwd_team_kernel(const 
 #pragma unroll
       for (int i = 0; i < DI; ++i) lam[i] += gz[(size_t)t * DI + i];
     }
-    if (wave == 0) store_vec<DI>(gz0 + (size_t)n * DI, lam, lane);
+    if (wave == 0) store_state<DI>(gz0 + (size_t)n * DI, lam, lane);
   }
   if constexpr (PG) {
     float* out = slab + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * pack_floats;
@@ -170,7 +161,7 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rhs_vjp_team_kernel(const floa
 #pragma unroll
     for (int i = 0; i < DO; ++i) av[i] = a[(size_t)n * DO + i];
     ev.vjp(xv, av, g, prior_only != 0);
-    if (wave == 0) store_vec<DI>(gx + (size_t)n * DI, g, lane);
+    if (wave == 0) store_state<DI>(gx + (size_t)n * DI, g, lane);
   }
 }
 
@@ -646,23 +637,36 @@ __global__ __launch_bounds__(1024) void reduce_slab_kernel(const float* __restri
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
+// What rollout_bwd_team_kernel reads of Draws: in = xstage, in2 = gzt, out = gz0, out2 = astage -- the record's rows in Di and in Do.
+static Draws rollout_bwd_draws(int method, int Di, int Do, const RolloutBwdArgs& a, int nd, size_t pack_floats) {
+  const size_t rows = record_rows(a.N, a.T, a.substeps, method);
+  Draws d;
+  d.nd = nd; d.pack = pack_floats;
+  d.in = rows * Di; d.in2 = (size_t)a.N * a.T * Di;
+  d.out = (size_t)a.N * Di; d.out2 = rows * Do;
+  d.ts = a.ts_per_traj ? (size_t)a.T : 0; d.sub = a.substeps;
+  return d;
+}
+
 // The register-resident or the streamed team, and the grid: reverse_route (gp_rollout.hpp).
-int rollout_bwd(int kernel, int order, int method, int Di, int Do, int M, int S, const float* pack, const float* xstage,
-                const float* gzt, const float* ts, int N, int T, float* gz0, float* astage, hipStream_t st, Draws dw) {
+int rollout_bwd(int kernel, int order, int method, int Di, int Do, const RolloutBwdArgs& a, int nd, hipStream_t st) {
   static const char* const who = "gpode_rollout_bwd";
   static const char* const tags[2][2] = {{"rollout_bwd_rbf", "rollout_bwd_rbf_stream"}, {"rollout_bwd_df", "rollout_bwd_df_stream"}};
+  size_t pf = 0;
+  if (cache_sizes(kernel, Di, Do, a.M, a.S, &pf, nullptr)) return 1;
   if (method < 0 || method > 2) return set_error("gpode_rollout_bwd: method %d (0 euler, 1 rk4, 2 midpoint; 3 dopri5: gpode_rollout_adaptive_bwd_n)", method);
   if (kernel != 0 && order != 1) return set_error("gpode_rollout_bwd: DF kernel is first-order only");
+  const Draws dw = rollout_bwd_draws(method, Di, Do, a, nd, pf);
   return dispatch_dims(who, kernel, Di, Do, [&](auto k, auto di, auto dO) {
     constexpr int KERNEL = decltype(k)::value, DI = decltype(di)::value, DO = decltype(dO)::value;
     return dispatch_order<DI, DO>(who, order, [&](auto o) {
       return dispatch_method(method, [&](auto m) {
         constexpr int ORDER = decltype(o)::value, METHOD = decltype(m)::value;
-        return reverse_route<KERNEL, DI, DO>(N, M, S, [&](auto ev, const LaunchGeom& g) {
+        return reverse_route<KERNEL, DI, DO>(a.N, a.M, a.S, [&](auto ev, const LaunchGeom& g) {
           using EV = typename decltype(ev)::type;
           return dispatch_substeps(dw.sub, [&](auto sb) {
-            if (launch_route(rollout_bwd_team_kernel<EV, DI, DO, ORDER, METHOD, false, decltype(sb)::value>, g, dw.nd, st, pack, M, S, xstage, gzt,
-                             ts, N, T, gz0, astage, dw, (float*)nullptr, (size_t)0))
+            if (launch_route(rollout_bwd_team_kernel<EV, DI, DO, ORDER, METHOD, false, decltype(sb)::value>, g, nd, st, a.pack, a.M, a.S, a.xstage,
+                             a.gzt, a.ts, a.N, a.T, a.gz0, a.astage, dw, (float*)nullptr, (size_t)0))
               return 1;
             return check_launch(tags[KERNEL][g.route]);
           });
@@ -692,31 +696,31 @@ int rollout_bwd_pgrad_chunks(int kernel, int order, int method, int Di, int Do, 
   if (order != 1 || Di != Do || (method != 0 && method != 1) || N < 1) return 0;
   return pgrad_width(kernel, Do, [&](auto d) { return rbf_team_ok<decltype(d)::value, decltype(d)::value>(M, S) ? team_grid(N) : 0; });
 }
-int rollout_bwd_pgrad(int kernel, int order, int method, int Di, int Do, int M, int S, const float* pack, const float* xstage,
-                      const float* gzt, const float* ts, int N, int T, float* gz0, float* astage, float* slab, int nchunk,
-                      float* gpack, hipStream_t st, Draws dw) {
-  const int grid = rollout_bwd_pgrad_chunks(kernel, order, method, Di, Do, M, S, N);
-  if (grid == 0) return set_error("gpode_rollout_bwd_pgrad: no fused form for kernel=%d order=%d method=%d Di=%d Do=%d M=%d S=%d", kernel, order,
-                                  method, Di, Do, M, S);
-  if (nchunk != grid) return set_error("gpode_rollout_bwd_pgrad: slab for %d chunks, the launch has %d", nchunk, grid);
+int rollout_bwd_pgrad(int kernel, int order, int method, int Di, int Do, const RolloutBwdArgs& a, int nd, hipStream_t st) {
   size_t pf = 0;
-  if (cache_sizes(kernel, Di, Do, M, S, &pf, nullptr)) return 1;
+  if (cache_sizes(kernel, Di, Do, a.M, a.S, &pf, nullptr)) return 1;
+  const int grid = rollout_bwd_pgrad_chunks(kernel, order, method, Di, Do, a.M, a.S, a.N);
+  if (grid == 0) return set_error("gpode_rollout_bwd_pgrad: no fused form for kernel=%d order=%d method=%d Di=%d Do=%d M=%d S=%d", kernel, order,
+                                  method, Di, Do, a.M, a.S);
+  if (a.nchunk != grid) return set_error("gpode_rollout_bwd_pgrad: slab for %d chunks, the launch has %d", a.nchunk, grid);
+  const Draws dw = rollout_bwd_draws(method, Di, Do, a, nd, pf);
+  const LaunchGeom g{kRouteTeam, grid, 256, 0};      // one chunk slab per workgroup of the register-resident team
   const int done = pgrad_width(kernel, Do, [&](auto d) {
     constexpr int D = decltype(d)::value;
-    dispatch_substeps(dw.sub, [&](auto sb) {
-      constexpr bool SUB = decltype(sb)::value;
-      if (method == 0) hipLaunchKernelGGL((rollout_bwd_team_kernel<RbfTeamEval<D, D, 1>, D, D, 1, 0, true, SUB>), dim3(grid, dw.nd), 256, 0, st,
-                                          pack, M, S, xstage, gzt, ts, N, T, gz0, astage, dw, slab, pf);
-      else hipLaunchKernelGGL((rollout_bwd_team_kernel<RbfTeamEval<D, D, 1>, D, D, 1, 1, true, SUB>), dim3(grid, dw.nd), 256, 0, st,
-                              pack, M, S, xstage, gzt, ts, N, T, gz0, astage, dw, slab, pf);
-      return 0;
-    });
+    const auto sweep = [&](auto m) {                 // Euler and the 3/8 rule only (rollout_bwd_pgrad_chunks): no midpoint instantiation
+      return dispatch_substeps(dw.sub, [&](auto sb) {
+        return launch_route(rollout_bwd_team_kernel<RbfTeamEval<D, D, 1>, D, D, 1, decltype(m)::value, true, decltype(sb)::value>, g, nd, st,
+                            a.pack, a.M, a.S, a.xstage, a.gzt, a.ts, a.N, a.T, a.gz0, a.astage, dw, a.slab, pf);
+      });
+    };
+    if (method == 0) sweep(int_c<0>{});
+    else sweep(int_c<1>{});
     return 1;
   });
   if (!done) return set_error("gpode_rollout_bwd_pgrad: width %d not built", Do);
   if (check_launch("rollout_bwd_pgrad")) return 1;
-  // the chunk slabs -> the pack-layout gradient of every draw (dw.out2 is astage's draw stride; gpack is dense per draw)
-  hipLaunchKernelGGL(reduce_slab_kernel, dim3((unsigned)((pf + 63) / 64), dw.nd), 1024, 0, st, slab, grid, pf, gpack, 0, pf, grid);
+  // the chunk slabs -> the pack-layout gradient of every draw (gpack is dense per draw)
+  hipLaunchKernelGGL(reduce_slab_kernel, dim3((unsigned)((pf + 63) / 64), nd), 1024, 0, st, a.slab, grid, pf, a.gpack, 0, pf, grid);
   return check_launch("reduce_slab");
 }
 

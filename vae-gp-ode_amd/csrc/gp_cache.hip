@@ -1583,7 +1583,8 @@ int cache_build_fwd(int kernel, int Di, int Do, int M, int S, int nd,
   // u_prior = f_prior(Z): the rhs kernel in prior-only mode on the M inducing locations, every draw with its own pack (straight
   // into the caller's buffer when one is given: no copy node on the critical path of the step)
   float* up = u_prior ? u_prior : ws + w.u_prior;
-  if (rhs_fwd(kernel, Di, Do, M, S, pack, Z, M, up, 1, st, Draws{nd, pf, 0, MD})) return 1;
+  Draws du; du.nd = nd; du.pack = pf; du.in = 0; du.out = MD;       // Z shared by the draws, u_prior (M, Do) per draw
+  if (rhs_fwd(kernel, Di, Do, M, S, pack, Z, M, up, 1, st, du)) return 1;
 
   float* A = ws + w.A;
   float* Lmat = ws + w.Lmat;

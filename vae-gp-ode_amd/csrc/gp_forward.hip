@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void rollout_kernel(const float* __restrict__ 
                                const float* __restrict__ z0, const float* __restrict__ ts, int N, int T,
                                float* __restrict__ zt, float* __restrict__ xstage, Draws dw) {
   static_assert(DI == ORDER * DO, "state dim = order * D_out");
-  constexpr int NS = METHOD == 0 ? 1 : (METHOD == 1 ? 4 : 2);
+  constexpr int NS = stages_of(METHOD);
   pack += blockIdx.y * dw.pack; z0 += blockIdx.y * dw.in; zt += blockIdx.y * dw.out;    // blockIdx.y = Monte-Carlo draw
   if (xstage) xstage += blockIdx.y * dw.out2;
   if (USE_LDS) stage_pack_lds(pack, lds_f4);
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rollout_team_kernel(const floa
                                                             const float* __restrict__ z0, const float* __restrict__ ts,
                                                             int N, int T, float* __restrict__ zt, float* __restrict__ xstage, Draws dw) {
   static_assert(DI == ORDER * DO, "state dim = order * D_out");
-  constexpr int NS = METHOD == 0 ? 1 : (METHOD == 1 ? 4 : 2);
+  constexpr int NS = stages_of(METHOD);
   __shared__ float slots[2 * EV::kTeam * TeamCombine::DP];
   // blockIdx.y = Monte-Carlo draw: its own pack (function draw), the shared initial states, its own trajectories
   pack += blockIdx.y * dw.pack; z0 += blockIdx.y * dw.in; zt += blockIdx.y * dw.out;
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rollout_team_kernel(const floa
       for (int r = t * sub; r < (t + 1) * sub; ++r) {   // r: the step's row block of the record, (T-1, sub, NS, DI)
         float k1[DI];
         if (xs_out) store_state<DI>(xs_out + (size_t)(r * NS) * DI, y, lane);
-        ode_rhs_mut<EV, DI, DO, ORDER>(ev, y, k1);
+        ode_rhs<EV, DI, DO, ORDER>(ev, y, k1);
         if (METHOD == 0) {
 #pragma unroll
           for (int i = 0; i < DI; ++i) y[i] = y[i] + dt * k1[i];
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rollout_team_kernel(const floa
 #pragma unroll
           for (int i = 0; i < DI; ++i) xs[i] = y[i] + 0.5f * dt * k1[i];
           if (xs_out) store_state<DI>(xs_out + (size_t)(r * NS + 1) * DI, xs, lane);
-          ode_rhs_mut<EV, DI, DO, ORDER>(ev, xs, k2);
+          ode_rhs<EV, DI, DO, ORDER>(ev, xs, k2);
 #pragma unroll
           for (int i = 0; i < DI; ++i) y[i] = y[i] + dt * k2[i];
         } else {
@@ -180,15 +180,15 @@ __global__ __launch_bounds__(64 * EV::kTeam) void rollout_team_kernel(const floa
 #pragma unroll
           for (int i = 0; i < DI; ++i) xs[i] = y[i] + dt * k1[i] * third;
           if (xs_out) store_state<DI>(xs_out + (size_t)(r * NS + 1) * DI, xs, lane);
-          ode_rhs_mut<EV, DI, DO, ORDER>(ev, xs, k2);
+          ode_rhs<EV, DI, DO, ORDER>(ev, xs, k2);
 #pragma unroll
           for (int i = 0; i < DI; ++i) xs[i] = y[i] + dt * (k2[i] - k1[i] * third);
           if (xs_out) store_state<DI>(xs_out + (size_t)(r * NS + 2) * DI, xs, lane);
-          ode_rhs_mut<EV, DI, DO, ORDER>(ev, xs, k3);
+          ode_rhs<EV, DI, DO, ORDER>(ev, xs, k3);
 #pragma unroll
           for (int i = 0; i < DI; ++i) xs[i] = y[i] + dt * (k1[i] - k2[i] + k3[i]);
           if (xs_out) store_state<DI>(xs_out + (size_t)(r * NS + 3) * DI, xs, lane);
-          ode_rhs_mut<EV, DI, DO, ORDER>(ev, xs, k4);
+          ode_rhs<EV, DI, DO, ORDER>(ev, xs, k4);
 #pragma unroll
           for (int i = 0; i < DI; ++i) y[i] = y[i] + (k1[i] + 3.f * (k2[i] + k3[i]) + k4[i]) * dt * 0.125f;
         }
@@ -219,29 +219,42 @@ int rhs_fwd(int kernel, int Di, int Do, int M, int S, const float* pack, const f
   });
 }
 
-int rollout_fwd(int kernel, int order, int method, int Di, int Do, int M, int S, const float* pack,
-                const float* z0, const float* ts, int N, int T, float* zt, float* xstage, hipStream_t st, Draws dw) {
+// What rollout_kernel / rollout_team_kernel read of Draws: in = z0 (0: shared by the draws), out = zt, out2 = xstage.
+static Draws rollout_fwd_draws(int method, int Di, const RolloutFwdArgs& a, int nd, size_t pack_floats) {
+  Draws d;
+  d.nd = nd; d.pack = pack_floats;
+  d.in = a.z0_per_draw ? (size_t)a.N * Di : 0;
+  d.out = (size_t)a.N * a.T * Di; d.out2 = record_rows(a.N, a.T, a.substeps, method) * Di;
+  d.ts = a.ts_per_traj ? (size_t)a.T : 0; d.sub = a.substeps;
+  return d;
+}
+
+int rollout_fwd(int kernel, int order, int method, int Di, int Do, const RolloutFwdArgs& a, int nd, hipStream_t st) {
   static const char* const who = "gpode_rollout_fwd";
   static const char* const tags[2][kRoutes] = {
       {"rollout_rbf_team", "rollout_rbf_team_stream", "rollout_rbf_reg42", "rollout_rbf_reg11", "rollout_rbf_stream"},
       {"rollout_df_team", "rollout_df_team_stream", "rollout_df_lds", "rollout_df_stream"}};
+  size_t pf = 0;
+  if (cache_sizes(kernel, Di, Do, a.M, a.S, &pf, nullptr)) return 1;
   if (method < 0 || method > 2) return set_error("gpode_rollout_fwd: method %d (0 euler, 1 rk4, 2 midpoint; 3 dopri5: gpode_rollout_adaptive_fwd_n)", method);
   if (kernel != 0 && order != 1) return set_error("gpode_rollout_fwd: DF kernel is first-order only (kernels.py:259-262)");
+  const Draws dw = rollout_fwd_draws(method, Di, a, nd, pf);
   return dispatch_dims(who, kernel, Di, Do, [&](auto k, auto di, auto dO) {
     constexpr int KERNEL = decltype(k)::value, DI = decltype(di)::value, DO = decltype(dO)::value;
     return dispatch_order<DI, DO>(who, order, [&](auto o) {
       return dispatch_method(method, [&](auto m) {
         constexpr int ORDER = decltype(o)::value, METHOD = decltype(m)::value;
-        return forward_route<KERNEL, DI, DO>(N, M, S, [&](auto ev, auto map, const LaunchGeom& g) {
+        return forward_route<KERNEL, DI, DO>(a.N, a.M, a.S, [&](auto ev, auto map, const LaunchGeom& g) {
           using EV = typename decltype(ev)::type;
           constexpr int MAP = decltype(map)::value;
           return dispatch_substeps(dw.sub, [&](auto sb) {
             constexpr bool SUB = decltype(sb)::value;
             if constexpr (MAP == kTeam) {
-              if (launch_route(rollout_team_kernel<EV, DI, DO, ORDER, METHOD, SUB>, g, dw.nd, st, pack, M, S, z0, ts, N, T, zt, xstage, dw)) return 1;
+              if (launch_route(rollout_team_kernel<EV, DI, DO, ORDER, METHOD, SUB>, g, nd, st, a.pack, a.M, a.S, a.z0, a.ts, a.N, a.T, a.zt, a.xstage, dw))
+                return 1;
             } else {
-              if (launch_route(rollout_kernel<EV, DI, DO, ORDER, METHOD, MAP == kWaveLds, SUB>, g, dw.nd, st, pack, M, S, g.lds_f4, z0, ts, N, T,
-                               zt, xstage, dw))
+              if (launch_route(rollout_kernel<EV, DI, DO, ORDER, METHOD, MAP == kWaveLds, SUB>, g, nd, st, a.pack, a.M, a.S, g.lds_f4, a.z0, a.ts,
+                               a.N, a.T, a.zt, a.xstage, dw))
                 return 1;
             }
             return check_launch(tags[KERNEL][g.route]);

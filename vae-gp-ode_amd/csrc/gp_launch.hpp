@@ -69,7 +69,8 @@ inline int num_cus() {
 
 // Monte-Carlo draws batched into ONE launch (the reference loops `for l in range(L)` over whole flow calls, odegpvae.py:41-43):
 // blockIdx.y = draw.  Strides in floats of the operands that differ per draw -- 0 = shared by all draws (the inducing locations
-// handed to the prior-only rhs, the initial states z0 of a rollout).  Which operand each stride belongs to is listed per entry point.
+// handed to the prior-only rhs, the initial states z0 of a rollout).  Which operand each stride belongs to: the row operations'
+// declarations below, rollout_fwd_draws (gp_forward.hip), rollout_bwd_draws (gp_backward.hip).
 // ts: floats between the time grids of consecutive TRAJECTORIES (not draws: a grid belongs to the sequence), 0 = one (T,) grid shared
 // by all of them, T = one row of a dense (N,T) block each.  Read by the fixed-grid rollout and its reverse sweep only.
 // sub: equal solver steps per output interval [ts[t], ts[t+1]] (1 ... kMaxSubsteps), read by the same two; the record of an interval
@@ -82,37 +83,44 @@ struct Draws {
   int sub = 1;
 };
 
+// One argument struct per rollout operation: capi.hip checks the arguments and fills it by member name, the launcher next to the
+// kernel turns it into what the kernel takes (the strides between draws, the record's row count: rollout_fwd_draws, rollout_bwd_draws, adapt_fwd_arg).
+// Operands are dense, [L,] the draw axis: z0 ([L,] N,Di) (z0_per_draw: one slab per draw, else shared), ts (T,) or (N,T)
+// (ts_per_traj), zt / gzt (L,N,T,Di), gz0 (L,N,Di); the fixed-grid record xstage (L,N,T-1,substeps,NS,Di), astage the same in Do.
+struct RolloutFwdArgs {
+  int M, S; const float* pack; const float* z0; const float* ts; int N, T;
+  float* zt; float* xstage; bool z0_per_draw, ts_per_traj; int substeps;
+};
+// slab (L, nchunk, pack_floats), gpack (L, pack_floats): the fused sweep's parameter sums (rollout_bwd_pgrad); null / 0 for the plain one
+struct RolloutBwdArgs {
+  int M, S; const float* pack; const float* xstage; const float* gzt; const float* ts; int N, T;
+  float* gz0; float* astage; bool ts_per_traj; int substeps; float* slab; int nchunk; float* gpack;
+};
+// dopri5, landing and dense alike: the record is xstage (L,N,K,6|7,Di), hstep (L,N,K), index (L,N,T-1) (landing: iend, dense: istep)
+// and, dense only, theta (L,N,T-1); counts (L,N,4)
+struct AdaptFwdArgs {
+  int M, S; const float* pack; const float* z0; const float* ts; int N, T, K; float rtol, atol;
+  float* zt; float* xstage; float* hstep; int* index; float* theta; int* counts; bool z0_per_draw, ts_per_traj;
+};
+struct AdaptBwdArgs {
+  int M, S; const float* pack; const float* xstage; const float* hstep; const int* index; const float* theta; const float* gzt;
+  int N, T, K; float* gz0; float* astage;
+};
+
 // entry points implemented across the .hip files
 int dims_supported(int kernel, int Di, int Do);
-//   rhs_fwd:     in = x, out = f                       rollout_fwd: in = z0, out = zt, out2 = xstage
-//   rollout_bwd: in = xstage, in2 = gzt, out = gz0, out2 = astage
-//   rhs_vjp:     in = x, in2 = a, out = gx             param_grad:  in = xr, in2 = ar, out = gpack (slab: nchunk * pack_floats per draw)
+// the row operations take their Draws as it is:
+//   rhs_fwd: in = x, out = f      rhs_vjp: in = x, in2 = a, out = gx      param_grad: in = xr, in2 = ar, out = gpack
 int rhs_fwd(int kernel, int Di, int Do, int M, int S, const float* pack, const float* x, int N, float* f, int mode, hipStream_t st,
             Draws dw = Draws{});
-int rollout_fwd(int kernel, int order, int method, int Di, int Do, int M, int S, const float* pack,
-                const float* z0, const float* ts, int N, int T, float* zt, float* xstage, hipStream_t st, Draws dw = Draws{});
-int rollout_bwd(int kernel, int order, int method, int Di, int Do, int M, int S, const float* pack, const float* xstage,
-                const float* gzt, const float* ts, int N, int T, float* gz0, float* astage, hipStream_t st, Draws dw = Draws{});
+int rollout_fwd(int kernel, int order, int method, int Di, int Do, const RolloutFwdArgs& a, int nd, hipStream_t st);
+int rollout_bwd(int kernel, int order, int method, int Di, int Do, const RolloutBwdArgs& a, int nd, hipStream_t st);
 int rollout_bwd_pgrad_chunks(int kernel, int order, int method, int Di, int Do, int M, int S, int N);
-int rollout_bwd_pgrad(int kernel, int order, int method, int Di, int Do, int M, int S, const float* pack, const float* xstage,
-                      const float* gzt, const float* ts, int N, int T, float* gz0, float* astage, float* slab, int nchunk,
-                      float* gpack, hipStream_t st, Draws dw = Draws{});
-// adaptive Dormand-Prince rollout and its reverse sweep (gp_adaptive.hip); every per-draw operand is dense, `pack_stride` apart;
-// z0_stride: floats between the draws' initial states, 0 = shared by all draws; ts_stride: floats between the trajectories' time
-// grids, 0 = one (T,) grid shared by all trajectories
-int rollout_adaptive_fwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
-                         const float* z0, const float* ts, int N, int T, float rtol, float atol, int K, float* zt, float* xstage,
-                         float* hstep, int* iend, int* counts, hipStream_t st, size_t z0_stride = 0, size_t ts_stride = 0);
-int rollout_adaptive_bwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
-                         const float* xstage, const float* hstep, const int* iend, const float* gzt, int N, int T, int K,
-                         float* gz0, float* astage, hipStream_t st);
-// the same in dense-output mode: steps cut at ts[T-1] only, interior outputs interpolated (record: 7 rows per step, istep, theta)
-int rollout_dense_fwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
-                      const float* z0, const float* ts, int N, int T, float rtol, float atol, int K, float* zt, float* xstage,
-                      float* hstep, int* istep, float* theta, int* counts, hipStream_t st, size_t z0_stride = 0, size_t ts_stride = 0);
-int rollout_dense_bwd(int kernel, int order, int Di, int Do, int M, int S, int nd, const float* pack, size_t pack_stride,
-                      const float* xstage, const float* hstep, const int* istep, const float* theta, const float* gzt, int N, int T,
-                      int K, float* gz0, float* astage, hipStream_t st);
+int rollout_bwd_pgrad(int kernel, int order, int method, int Di, int Do, const RolloutBwdArgs& a, int nd, hipStream_t st);
+// adaptive Dormand-Prince rollout and its reverse sweep (gp_adaptive.hip).  dense: steps cut at ts[T-1] only, interior outputs
+// interpolated (record: 7 rows per step, istep, theta)
+int rollout_adaptive_fwd(int kernel, int order, int Di, int Do, const AdaptFwdArgs& a, bool dense, int nd, hipStream_t st);
+int rollout_adaptive_bwd(int kernel, int order, int Di, int Do, const AdaptBwdArgs& a, bool dense, int nd, hipStream_t st);
 int rhs_vjp(int kernel, int Di, int Do, int M, int S, const float* pack, const float* x, const float* a, int R, float* gx,
             int prior_only, hipStream_t st, Draws dw = Draws{});
 int param_grad(int kernel, int Di, int Do, int M, int S, const float* pack, const float* xr, const float* ar, int R,

@@ -139,20 +139,6 @@ __device__ __forceinline__ void stage_pack_lds(const float* pack, size_t n_f4) {
   __syncthreads();
 }
 
-// ODE right-hand side on the state (flow.py:27-45): order 1: f(y); order 2: [v ; f(s,v)].
-template <class EV, int DI, int DO, int ORDER>
-__device__ __forceinline__ void ode_rhs(const EV& ev, const float (&y)[DI], float (&dy)[DI]) {
-  float fv[DO];
-  ev.template eval<0>(y, fv);
-  if (ORDER == 1) {
-#pragma unroll
-    for (int i = 0; i < DO; ++i) dy[i] = fv[i];
-  } else {
-#pragma unroll
-    for (int i = 0; i < DO; ++i) { dy[i] = y[DO + i]; dy[DO + i] = fv[i]; }
-  }
-}
-
 // The time grid of trajectory n: ts + n * stride (stride 0: the one grid every trajectory shares).  n is the same in every lane of a
 // wavefront but lives in a vector register where it derives from threadIdx; read through the first lane it is a scalar, so the row
 // pointer is one and the grid's entries stay scalar loads -- the step size multiplies the stage algebra as a scalar either way.
@@ -173,6 +159,11 @@ template <bool SUB> __device__ __forceinline__ float sub_step(float t0, float t1
   else return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((t1 - t0) / (float)sub)));
 }
 
+// Recorded stage inputs per step of a fixed-grid solver (0 euler, 1 rk4, 2 midpoint) -- the kernels' NS -- and the rows of a draw's
+// record (N, T-1, sub, NS, .): the ONE place that spells the layout on the host.
+constexpr int stages_of(int method) { return method == 0 ? 1 : (method == 1 ? 4 : 2); }
+inline size_t record_rows(int N, int T, int sub, int method) { return (size_t)N * (T - 1) * sub * stages_of(method); }
+
 template <int DI> __device__ __forceinline__ void store_state(float* __restrict__ dst, const float (&y)[DI], int lane) {
   if (lane < DI) {
     float v = y[0];
@@ -182,8 +173,9 @@ template <int DI> __device__ __forceinline__ void store_state(float* __restrict_
   }
 }
 
+// ODE right-hand side on the state (flow.py:27-45): order 1: f(y); order 2: [v ; f(s,v)].
 template <class EV, int DI, int DO, int ORDER>
-__device__ __forceinline__ void ode_rhs_mut(EV& ev, const float (&y)[DI], float (&dy)[DI]) {
+__device__ __forceinline__ void ode_rhs(EV& ev, const float (&y)[DI], float (&dy)[DI]) {
   float fv[DO];
   ev.template eval<0>(y, fv);
   if (ORDER == 1) {

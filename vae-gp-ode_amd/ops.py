@@ -5,6 +5,7 @@ libgpode_hip.so and returns torch tensors.  Nothing here computes on the CPU.
 """
 import ctypes
 import os
+import typing
 
 import torch
 
@@ -391,17 +392,41 @@ def _gzt_lead(cache, gzt):
     return gzt, lead
 
 
-def rollout_adaptive(cache, z0, ts, order, rtol=1e-6, atol=1e-6, max_steps=None, save_stages=False, dense=False):
-    """Adaptive Dormand-Prince 5(4) rollout (gpode_rollout_adaptive_fwd_n): one step-size controller per trajectory, steps landing
-    on ts.  ``max_steps`` = accepted steps a trajectory may take (default 4 (T-1)).  -> zt ([L,] N,T,D), counts ([L,] N,4) int32
-    = (accepted, rejected, status, evaluations of f); with save_stages also the record of the accepted steps: xstage
-    ([L,] N,K,6,D), hstep ([L,] N,K), iend ([L,] N,T-1) int32.  A trajectory with status != 0 is NaN from the output it missed.
-    ``dense`` (gpode_rollout_dense_fwd_n): steps are cut at ts[-1] only and the interior outputs are interpolated (4th-order
-    continuous extension, no evaluation of f); the record is then xstage ([L,] N,K,7,D), hstep, istep ([L,] N,T-1) int32 = 1-based
-    number of the accepted step that holds output t+1, theta ([L,] N,T-1) = the output's position inside that step, in (0, 1].
-    z0 (L,N,D) with L = cache.nd gives every draw its own initial states (gpode_rollout_adaptive_fwd_nz / _dense_fwd_nz).
-    ts (N,T) gives every trajectory its own output times (gpode_rollout_adaptive_fwd_nt / _dense_fwd_nt); a row that is not
-    strictly increasing is refused here, or -- under capture -- stops that trajectory alone with status 3."""
+def _head(cache, order, method):
+    """the nine values every rollout entry point starts with"""
+    return (KERNEL_ID[cache.kernel], order, METHOD_ID[method], cache.Di, cache.Do, cache.M, cache.S, cache.nd, _ptr(cache.pack))
+
+
+def _entry(base, zpd, tpt, sub=1):
+    """The twin of entry point ``base`` that the flags ask for, and the flag arguments it takes in front of the stream: `_ns` for
+    sub-steps, else `_nt` for a grid per trajectory, else `_nz` for initial states per draw, else `_n`.  zpd None: an operation
+    without that flag (the reverse sweeps, which have no `_nz`)."""
+    z = () if zpd is None else (zpd,)
+    if sub != 1:
+        return base + '_ns', z + (tpt, sub)
+    if tpt:
+        return base + '_nt', z + (tpt,)
+    if zpd:
+        return base + '_nz', z
+    return base + '_n', ()
+
+
+# What a dopri5 rollout keeps for its reverse sweep, in the order rollout() has always returned it: the stage inputs of the accepted
+# steps, their sizes, the index of the outputs into them (iend; dense: istep), the solve's counts and -- in dense-output mode only, a
+# landing record stays four entries long and its theta reads None -- the outputs' positions inside their steps.
+_RECORD = [(name, typing.Optional[torch.Tensor]) for name in ('xstage', 'hstep', 'index', 'counts')]
+Dopri5Record = typing.NamedTuple('Dopri5Record', _RECORD)
+Dopri5Record.theta = None
+Dopri5DenseRecord = typing.NamedTuple('Dopri5DenseRecord', _RECORD + [('theta', torch.Tensor)])
+
+
+def _dopri5_record(xstage, hstep, index, counts=None, theta=None):
+    """the record of either mode, also from a plain tuple in its order (rollout_bwd)"""
+    return Dopri5Record(xstage, hstep, index, counts) if theta is None else Dopri5DenseRecord(xstage, hstep, index, counts, theta)
+
+
+def _dopri5(cache, z0, ts, order, rtol, atol, max_steps, save_stages, dense):
+    """rollout_adaptive() -> zt, its record (counts alone unless save_stages)"""
     z0, ts, zpd, tpt, N, D = _rollout_args(cache, z0, ts, order)
     T = ts.shape[-1]
     K = 4 * max(T - 1, 0) if max_steps is None else int(max_steps)
@@ -417,17 +442,27 @@ def rollout_adaptive(cache, z0, ts, order, rtol=1e-6, atol=1e-6, max_steps=None,
         hs = torch.empty(lead + (N, K), dtype=torch.float32, device=dev)
         ie = torch.empty(lead + (N, max(T - 1, 0)), dtype=torch.int32, device=dev)
         th = torch.empty(lead + (N, max(T - 1, 0)), dtype=torch.float32, device=dev) if dense else None
-    head = (KERNEL_ID[cache.kernel], order, METHOD_ID['dopri5'], cache.Di, cache.Do, cache.M, cache.S, cache.nd, _ptr(cache.pack),
-            _ptr(z0), _ptr(ts), N, T, float(rtol), float(atol), K, _ptr(zt), _ptr(xs), _ptr(hs), _ptr(ie))
-    head += (_ptr(th), _ptr(counts)) if dense else (_ptr(counts),)
-    name = 'gpode_rollout_dense_fwd' if dense else 'gpode_rollout_adaptive_fwd'
-    if tpt:
-        _lib.call(name + '_nt', *head, zpd, tpt, _stream())
-    elif zpd:
-        _lib.call(name + '_nz', *head, zpd, _stream())
-    else:
-        _lib.call(name + '_n', *head, _stream())
-    return ((zt, counts, xs, hs, ie) + ((th,) if dense else ())) if save_stages else (zt, counts)
+    name, flags = _entry('gpode_rollout_dense_fwd' if dense else 'gpode_rollout_adaptive_fwd', zpd, tpt)
+    _lib.call(name, *_head(cache, order, 'dopri5'), _ptr(z0), _ptr(ts), N, T, float(rtol), float(atol), K, _ptr(zt), _ptr(xs), _ptr(hs),
+              _ptr(ie), *((_ptr(th),) if dense else ()), _ptr(counts), *flags, _stream())
+    return zt, _dopri5_record(xs, hs, ie, counts, th)
+
+
+def rollout_adaptive(cache, z0, ts, order, rtol=1e-6, atol=1e-6, max_steps=None, save_stages=False, dense=False):
+    """Adaptive Dormand-Prince 5(4) rollout (gpode_rollout_adaptive_fwd_n): one step-size controller per trajectory, steps landing
+    on ts.  ``max_steps`` = accepted steps a trajectory may take (default 4 (T-1)).  -> zt ([L,] N,T,D), counts ([L,] N,4) int32
+    = (accepted, rejected, status, evaluations of f); with save_stages also the record of the accepted steps: xstage
+    ([L,] N,K,6,D), hstep ([L,] N,K), iend ([L,] N,T-1) int32.  A trajectory with status != 0 is NaN from the output it missed.
+    ``dense`` (gpode_rollout_dense_fwd_n): steps are cut at ts[-1] only and the interior outputs are interpolated (4th-order
+    continuous extension, no evaluation of f); the record is then xstage ([L,] N,K,7,D), hstep, istep ([L,] N,T-1) int32 = 1-based
+    number of the accepted step that holds output t+1, theta ([L,] N,T-1) = the output's position inside that step, in (0, 1].
+    z0 (L,N,D) with L = cache.nd gives every draw its own initial states (gpode_rollout_adaptive_fwd_nz / _dense_fwd_nz).
+    ts (N,T) gives every trajectory its own output times (gpode_rollout_adaptive_fwd_nt / _dense_fwd_nt); a row that is not
+    strictly increasing is refused here, or -- under capture -- stops that trajectory alone with status 3."""
+    zt, r = _dopri5(cache, z0, ts, order, rtol, atol, max_steps, save_stages, dense)
+    if not save_stages:
+        return zt, r.counts
+    return (zt, r.counts, r.xstage, r.hstep, r.index) + ((r.theta,) if dense else ())
 
 
 def rollout_adaptive_bwd(cache, xstage, hstep, iend, gzt, order, theta=None):
@@ -437,21 +472,17 @@ def rollout_adaptive_bwd(cache, xstage, hstep, iend, gzt, order, theta=None):
     gzt, lead = _gzt_lead(cache, gzt)
     N, T, D = gzt.shape[-3:]
     K = hstep.shape[-1]
-    NS = NSTAGE['dopri5'] if theta is None else NSTAGE_DENSE
+    dense = theta is not None
+    NS = NSTAGE_DENSE if dense else NSTAGE['dopri5']
     xstage = _chk(xstage, 'xstage', lead + (N, K, NS, D)); hstep = _chk(hstep, 'hstep', lead + (N, K))
     if iend.dtype != torch.int32 or tuple(iend.shape) != lead + (N, max(T - 1, 0)) or not iend.is_contiguous():
         raise _lib.GpodeError('iend: expected contiguous int32 %s, got %s %s' % (lead + (N, T - 1), iend.dtype, tuple(iend.shape)))
     gz0 = torch.empty(lead + (N, D), dtype=torch.float32, device=gzt.device)
     ast = torch.empty(lead + (N, K, NS, cache.Do), dtype=torch.float32, device=gzt.device)
-    if theta is not None:
+    if dense:
         theta = _chk(theta, 'theta', lead + (N, max(T - 1, 0)))
-        _lib.call('gpode_rollout_dense_bwd_n', KERNEL_ID[cache.kernel], order, METHOD_ID['dopri5'], cache.Di, cache.Do, cache.M,
-                  cache.S, cache.nd, _ptr(cache.pack), _ptr(xstage), _ptr(hstep), _ptr(iend), _ptr(theta), _ptr(gzt), N, T, K, _ptr(gz0),
-                  _ptr(ast), _stream())
-        return gz0, ast
-    _lib.call('gpode_rollout_adaptive_bwd_n', KERNEL_ID[cache.kernel], order, METHOD_ID['dopri5'], cache.Di, cache.Do, cache.M,
-              cache.S, cache.nd, _ptr(cache.pack), _ptr(xstage), _ptr(hstep), _ptr(iend), _ptr(gzt), N, T, K, _ptr(gz0), _ptr(ast),
-              _stream())
+    _lib.call('gpode_rollout_dense_bwd_n' if dense else 'gpode_rollout_adaptive_bwd_n', *_head(cache, order, 'dopri5'), _ptr(xstage),
+              _ptr(hstep), _ptr(iend), *((_ptr(theta),) if dense else ()), _ptr(gzt), N, T, K, _ptr(gz0), _ptr(ast), _stream())
     return gz0, ast
 
 
@@ -464,54 +495,56 @@ def rollout(cache, z0, ts, order, method, save_stages=False, rtol=1e-6, atol=1e-
     substeps = s > 1 (euler, midpoint, rk4; gpode_rollout_fwd_ns): every output interval is integrated in s equal steps; zt stays
     at ts and the record becomes ([L,] N,T-1,s,NS,D).
     method 'dopri5' (the only one that reads rtol / atol / max_steps / dense) is rollout_adaptive(): with save_stages the second value
-    is its record (xstage, hstep, iend, counts), which rollout_bwd takes in place of xstage; in dense-output mode the record is
-    (xstage, hstep, istep, counts, theta)."""
+    is its record, a Dopri5Record (xstage, hstep, iend, counts), which rollout_bwd takes in place of xstage; in dense-output mode
+    a Dopri5DenseRecord (xstage, hstep, istep, counts, theta)."""
     check_solver(method)
     sub = _substeps(substeps, method)
     if method == 'dopri5':
-        out = rollout_adaptive(cache, z0, ts, order, rtol, atol, max_steps, save_stages, dense=dense)
-        return (out[0], (out[2], out[3], out[4], out[1]) + tuple(out[5:])) if save_stages else out[0]
+        zt, rec = _dopri5(cache, z0, ts, order, rtol, atol, max_steps, save_stages, dense)
+        return (zt, rec) if save_stages else zt
     z0, ts, zpd, tpt, N, D = _rollout_args(cache, z0, ts, order)
     T = ts.shape[-1]
     lead = cache.lead
     zt = torch.empty(lead + (N, T, D), dtype=torch.float32, device=z0.device)
     xs = torch.empty(lead + (N, max(T - 1, 0)) + _sub_axis(sub) + (NSTAGE[method], D), dtype=torch.float32,
                      device=z0.device) if save_stages else None
-    head = (KERNEL_ID[cache.kernel], order, METHOD_ID[method], cache.Di, cache.Do, cache.M, cache.S, cache.nd, _ptr(cache.pack), _ptr(z0),
-            _ptr(ts), N, T, _ptr(zt), _ptr(xs))
-    if sub != 1:
-        _lib.call('gpode_rollout_fwd_ns', *head, zpd, tpt, sub, _stream())
-    elif tpt:
-        _lib.call('gpode_rollout_fwd_nt', *head, zpd, tpt, _stream())
-    elif zpd:
-        _lib.call('gpode_rollout_fwd_nz', *head, zpd, _stream())
-    else:
-        _lib.call('gpode_rollout_fwd_n', *head, _stream())
+    name, flags = _entry('gpode_rollout_fwd', zpd, tpt, sub)
+    _lib.call(name, *_head(cache, order, method), _ptr(z0), _ptr(ts), N, T, _ptr(zt), _ptr(xs), *flags, _stream())
     return (zt, xs) if save_stages else zt
 
 
-def rollout_bwd(cache, xstage, gzt, ts, order, method, substeps=1):
-    """Reverse sweep: gzt ([L,] N,T,D) -> gz0 ([L,] N,D), astage ([L,] N,T-1,NS,Do) (dopri5: xstage is rollout's record, astage
-    ([L,] N,K,6,Do), or ([L,] N,K,7,Do) for a dense-output record).  ts (T,) or (N,T) as in rollout (gpode_rollout_bwd_nt).
-    substeps = s > 1 as in rollout (gpode_rollout_bwd_ns): xstage ([L,] N,T-1,s,NS,D) -> astage ([L,] N,T-1,s,NS,Do)."""
+def _rollout_bwd(cache, xstage, gzt, ts, order, method, substeps, nchunk=None, keep=None):
+    """rollout_bwd, and with ``nchunk`` rollout_bwd_pgrad: the same checks and allocations, the fused form's slab and pack gradient more"""
     sub = _substeps(substeps, method)
-    if method == 'dopri5':
-        return rollout_adaptive_bwd(cache, xstage[0], xstage[1], xstage[2], gzt, order, theta=xstage[4] if len(xstage) > 4 else None)
     (gzt, lead), xstage, ts = _gzt_lead(cache, gzt), _chk(xstage, 'xstage'), _chk(ts, 'ts')
     N, T, D = gzt.shape[-3:]
     tpt = _ts_per_traj(ts, N, T, rows='gzt %s' % (tuple(gzt.shape),))
     gz0 = torch.empty(lead + (N, D), dtype=torch.float32, device=gzt.device)
     xstage = _sub_record(xstage, lead + (N, T - 1), sub, NSTAGE[method], D)
     ast = torch.empty(lead + (N, T - 1) + _sub_axis(sub) + (NSTAGE[method], cache.Do), dtype=torch.float32, device=gzt.device)
-    head = (KERNEL_ID[cache.kernel], order, METHOD_ID[method], cache.Di, cache.Do, cache.M, cache.S, cache.nd, _ptr(cache.pack),
-            _ptr(xstage), _ptr(gzt), _ptr(ts), N, T, _ptr(gz0), _ptr(ast))
-    if sub != 1:
-        _lib.call('gpode_rollout_bwd_ns', *head, tpt, sub, _stream())
-    elif tpt:
-        _lib.call('gpode_rollout_bwd_nt', *head, tpt, _stream())
-    else:
-        _lib.call('gpode_rollout_bwd_n', *head, _stream())
-    return gz0, ast
+    out, more = (gz0, ast), ()
+    if nchunk is not None:
+        pf = cache.pack.shape[-1]
+        slab = torch.empty(cache.nd * nchunk * pf, dtype=torch.float32, device=gzt.device)
+        gpack = torch.empty(lead + (pf,), dtype=torch.float32, device=gzt.device)
+        out, more = (gz0, ast, gpack), (_ptr(slab), nchunk, _ptr(gpack))
+        if keep is not None:
+            keep.append(slab)
+    name, flags = _entry('gpode_rollout_bwd' if nchunk is None else 'gpode_rollout_bwd_pgrad', None, tpt, sub)
+    _lib.call(name, *_head(cache, order, method), _ptr(xstage), _ptr(gzt), _ptr(ts), N, T, _ptr(gz0), _ptr(ast), *more, *flags, _stream())
+    return out
+
+
+def rollout_bwd(cache, xstage, gzt, ts, order, method, substeps=1):
+    """Reverse sweep: gzt ([L,] N,T,D) -> gz0 ([L,] N,D), astage ([L,] N,T-1,NS,Do) (dopri5: xstage is rollout's record, or a plain
+    tuple in its order; astage ([L,] N,K,6,Do), or ([L,] N,K,7,Do) for a dense-output record).  ts (T,) or (N,T) as in rollout
+    (gpode_rollout_bwd_nt).
+    substeps = s > 1 as in rollout (gpode_rollout_bwd_ns): xstage ([L,] N,T-1,s,NS,D) -> astage ([L,] N,T-1,s,NS,Do)."""
+    if method == 'dopri5':
+        _substeps(substeps, method)
+        rec = _dopri5_record(*xstage)
+        return rollout_adaptive_bwd(cache, rec.xstage, rec.hstep, rec.index, gzt, order, theta=rec.theta)
+    return _rollout_bwd(cache, xstage, gzt, ts, order, method, substeps)
 
 
 # The fused form is OFF by default (GPODE_FUSED_PGRAD=1 switches it on): measured at configs[0] it LENGTHENS the step, 0.737 -> 0.757 ms
@@ -532,28 +565,7 @@ def pgrad_chunks(cache, N, order, method, force=False):
 def rollout_bwd_pgrad(cache, xstage, gzt, ts, order, method, nchunk, keep=None, substeps=1):
     """rollout_bwd() and param_grad() in one pass over the rows (gpode_rollout_bwd_pgrad_n; ts (N,T): gpode_rollout_bwd_pgrad_nt;
     substeps > 1: gpode_rollout_bwd_pgrad_ns): -> gz0, astage, gpack ([L,] pack_floats)."""
-    sub = _substeps(substeps, method)
-    gzt = _chk(gzt, 'gzt'); xstage = _chk(xstage, 'xstage'); ts = _chk(ts, 'ts')
-    lead = cache.lead
-    N, T, D = gzt.shape[-3:]
-    tpt = _ts_per_traj(ts, N, T, rows='gzt %s' % (tuple(gzt.shape),))
-    pf = cache.pack.shape[-1]
-    gz0 = torch.empty(lead + (N, D), dtype=torch.float32, device=gzt.device)
-    xstage = _sub_record(xstage, lead + (N, T - 1), sub, NSTAGE[method], D)
-    ast = torch.empty(lead + (N, T - 1) + _sub_axis(sub) + (NSTAGE[method], cache.Do), dtype=torch.float32, device=gzt.device)
-    slab = torch.empty(cache.nd * nchunk * pf, dtype=torch.float32, device=gzt.device)
-    gpack = torch.empty(lead + (pf,), dtype=torch.float32, device=gzt.device)
-    head = (KERNEL_ID[cache.kernel], order, METHOD_ID[method], cache.Di, cache.Do, cache.M, cache.S, cache.nd, _ptr(cache.pack),
-            _ptr(xstage), _ptr(gzt), _ptr(ts), N, T, _ptr(gz0), _ptr(ast), _ptr(slab), nchunk, _ptr(gpack))
-    if sub != 1:
-        _lib.call('gpode_rollout_bwd_pgrad_ns', *head, tpt, sub, _stream())
-    elif tpt:
-        _lib.call('gpode_rollout_bwd_pgrad_nt', *head, tpt, _stream())
-    else:
-        _lib.call('gpode_rollout_bwd_pgrad_n', *head, _stream())
-    if keep is not None:
-        keep.append(slab)
-    return gz0, ast, gpack
+    return _rollout_bwd(cache, xstage, gzt, ts, order, method, substeps, nchunk, keep)
 
 
 def rhs_vjp(cache, x, a):
@@ -838,10 +850,10 @@ class _Flow(torch.autograd.Function):
         hs = ie = th = None
         if method == 'dopri5':
             rtol, atol, max_steps, sink, dense = (tuple(adaptive) + (False,))[:5] if adaptive is not None else (1e-6, 1e-6, None, None, False)
-            zt, counts, xs, hs, ie, th = (rollout_adaptive(cache, z0, ts, order, rtol, atol, max_steps, save_stages=need, dense=bool(dense))
-                                          + (None,) * 4)[:6]
+            zt, rec = _dopri5(cache, z0, ts, order, rtol, atol, max_steps, need, bool(dense))
+            xs, hs, ie, th = rec.xstage, rec.hstep, rec.index, rec.theta
             if sink is not None:
-                sink(counts)
+                sink(rec.counts)
         elif need:
             zt, xs = rollout(cache, z0, ts, order, method, save_stages=True, substeps=substeps)
         else:
@@ -849,6 +861,12 @@ class _Flow(torch.autograd.Function):
         ctx.cache, ctx.order, ctx.method, ctx.z0_per_draw, ctx.substeps = cache, order, method, z0.dim() == 3, substeps
         ctx.save_for_backward(ts, xs, raw_ell.detach(), raw_var.detach(), Z.detach(), hs, ie, th)
         return zt
+
+    @staticmethod
+    def _grads(gz0, g=None):
+        """backward's return, one entry per input of forward: z0, ts, the five GP parameter tensors, then the six that are not tensors"""
+        gp = (None,) * 5 if g is None else (g['raw_ell'], g['raw_var'], g['Z'], g['Um'], g['Us'])
+        return (gz0, None) + gp + (None,) * 6
 
     @staticmethod
     def backward(ctx, gzt):
@@ -869,7 +887,7 @@ class _Flow(torch.autograd.Function):
         if c.stacked and not ctx.z0_per_draw:
             gz0 = gz0.sum(0)                         # every draw starts from the same z0 (odegpvae.py:42)
         if not want_p:
-            return (gz0,) + (None,) * 12
+            return _Flow._grads(gz0)
         leaves = all(p.is_leaf and p.requires_grad for p in ctx.params) and all(ctx.needs_input_grad[2:7])
         if _overlap['on'] and leaves:
             # parameter gradients on the side stream, next to the encoder's backward; join_side_stream() adds them
@@ -888,12 +906,12 @@ class _Flow(torch.autograd.Function):
             # otherwise hand the block to the encoder-backward kernels the main stream launches meanwhile
             _overlap['pending'].append((ctx.params, [gg.view_as(p) for gg, p in zip(grads, ctx.params)],
                                         (g, gpack, xs, ast, c, scratch, raw_ell, raw_var, Z, ctx.prepared, hs, ie, th)))
-            return (gz0,) + (None,) * 12
+            return _Flow._grads(gz0)
         if ctx.prepared is not None:
             torch.cuda.current_stream().wait_stream(side_stream())
         gpack = gpack_f if gpack_f is not None else param_grad(c, xs.reshape(lead + (-1, c.Di)), ast.reshape(lead + (-1, c.Do)))
         g = cache_build_bwd(c, raw_ell, raw_var, Z, gpack, prepared=ctx.prepared)
-        return (gz0, None, g['raw_ell'], g['raw_var'], g['Z'], g['Um'], g['Us'], None, None, None, None, None, None)
+        return _Flow._grads(gz0, g)
 
 
 def flow(gp, z0, ts, order, method, draws=None, adaptive=None, substeps=1):
