@@ -664,6 +664,42 @@ int gpode_reparam_fwd(const float* mu, const float* logvar, int ld, const float*
  * every run. */
 int gpode_reparam_draws_fwd(const float* mu, const float* logvar, int ld, const float* eps, float* z, int ldz, float* lw,
                             int accumulate, int L, int N, int q, void* stream);
+/* The adjoint of gpode_reparam_draws_fwd (training on the importance-weighted bound below): gz (K,N,.) with row stride ldgz >= q -- one
+ * half of an order-2 state gradient is read in place -- and glw (K,N); either may be NULL, meaning zero.  With sigma = exp(logvar / 2)
+ * and z = mu + sigma eps:
+ *   gmu[n,i]     = sum_k ( gz - glw z )
+ *   glogvar[n,i] = sum_k ( gz sigma eps / 2 + glw (1/2 - z sigma eps / 2) )
+ * written with row stride ldg.  One lane per (n,i) sums k = 0 .. K-1 in that order: no atomics, the same bits every run.
+ * gpode_last_launch(): "reparam_draws_bwd".  Refused, with nothing written: a NULL mu, logvar, eps, gmu or glogvar, K outside 1..64,
+ * N < 1, q < 1, a stride below q. */
+int gpode_reparam_draws_bwd(const float* gz, int ldgz, const float* glw, const float* mu, const float* logvar, int ld, const float* eps,
+                            float* gmu, float* glogvar, int ldg, int K, int N, int q, void* stream);
+/* The importance-weighted bound over K initial-state draws per sequence, shared by the L function draws.  lpart (rows,
+ * nsplit) are the partial sums of gpode_sigmoid_loglik_fwd[_len] over rows = L K N likelihood rows ordered (l,k,n) (X is broadcast by
+ * row % N), lw (K,N) the log-weights of gpode_reparam_draws_fwd; Um, Us packed, M, Do, nobs as in gpode_elbo_all_fwd.  With
+ * a[l,k,n] = sum_s lpart[(l,k,n)][s] + lw[k,n] and iw[l,n] = logsumexp_k a[l,k,n] - log K:
+ *   gpode_elbo_iw_fwd     out[0..4] = {loss = -(nobs mean_{l,n} iw - kl_u), -mean iw, -mean_{k,n} lw (the Monte-Carlo KL(q(z0) || p)),
+ *                         kl_u, mean_{l,n} ess}, ess = (sum_k w)^2 / sum_k w^2 with w = exp(a - max_k a); out: 5 + 256 floats, the tail is
+ *                         scratch for the sum over a big Us.  One wavefront reduces a group (l,n), one lane per draw; the maximum over k is
+ *                         subtracted before any exp.  gpode_last_launch(): "elbo_iw_fwd" [" (Us in parts)"].
+ *   gpode_elbo_iw_bwd     seeds of the five outputs (device scalars, NULL = 0) -> grow[rows] = softmax_k(a)[l,k,n] (-g_loss nobs - g_nll)
+ *                         / (L N), glw (K,N) = sum_l of the same - g_kl / (K N), dUm, dUs as gpode_elbo_all_bwd.  The ess output is a
+ *                         diagnostic: g_ess is accepted and carries NO gradient.  A weight that underflows is exactly 0.  "elbo_iw_bwd".
+ *   gpode_elbo_iw_bwd_ll  gpode_elbo_iw_bwd and gpode_sigmoid_loglik_bwd in one launch (every-frame route only): also
+ *                         ga[e] = grow[row] (x/z - (1-x)/(1-z)) z (1-z) for the n_logits logits (whole rows; X of nX values broadcast);
+ *                         every output has the bits of the two separate launches.  "elbo_iw_loglik_bwd".
+ * Ragged minibatches run gpode_elbo_iw_bwd followed by gpode_sigmoid_loglik_bwd_len, which reads a gradient per row.  Fixed summation
+ * orders, no atomics.  Refused, with nothing written: a NULL operand other than a seed, K outside 1..64, L, N, M or Do < 1, nsplit < 1,
+ * rows != L K N, rows > 65535 (the grid of gpode_sigmoid_loglik_fwd), logits that are no whole rows or that X does not tile. */
+int gpode_elbo_iw_fwd(const float* lpart, int rows, int nsplit, const float* lw, int L, int K, int N, int M, int Do, const float* Um,
+                      const float* Us, float nobs, float* out, void* stream);
+int gpode_elbo_iw_bwd(const float* g_loss, const float* g_nll, const float* g_kl, const float* g_klu, const float* g_ess, const float* lpart,
+                      int rows, int nsplit, const float* lw, int L, int K, int N, int M, int Do, const float* Um, const float* Us, float nobs,
+                      float* grow, float* glw, float* dUm, float* dUs, void* stream);
+int gpode_elbo_iw_bwd_ll(const float* g_loss, const float* g_nll, const float* g_kl, const float* g_klu, const float* g_ess,
+                         const float* lpart, int rows, int nsplit, const float* lw, int L, int K, int N, int M, int Do, const float* Um,
+                         const float* Us, float nobs, float* grow, float* glw, float* dUm, float* dUs, const float* X, const float* z,
+                         float* ga, size_t n_logits, size_t nX, void* stream);
 int gpode_reparam_bwd(const float* gz, const float* logvar, int ld, const float* eps, float* gmu, float* glogvar, int ldg, int N, int q,
                       void* stream);
 int gpode_normal_kl_fwd(const float* mu, const float* logvar, int ld, float* klrow, int N, int q, void* stream);

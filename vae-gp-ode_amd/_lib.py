@@ -153,6 +153,11 @@ SIGNATURES = {
     'gpode_gather_frames_bwd': (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'gpode_sigmoid_loglik_fwd_pk': (_i, [_vp] * 4 + [_sz, _vp, _i, _sz, _sz, _i, _vp]),
     'gpode_sigmoid_loglik_bwd_pk': (_i, [_vp] * 4 + [_sz, _vp, _i, _i, _sz, _sz, _vp]),
+    # training on the importance-weighted bound: the adjoint of the K draws and the loss stage over (l,k,n) rows
+    'gpode_reparam_draws_bwd': (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'gpode_elbo_iw_fwd': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp]),
+    'gpode_elbo_iw_bwd': (_i, [_vp] * 5 + [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f] + [_vp] * 4 + [_vp]),
+    'gpode_elbo_iw_bwd_ll': (_i, [_vp] * 5 + [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f] + [_vp] * 7 + [_sz, _sz, _vp]),
     'gpode_dec10_predict_len': (_i, [_vp] * 5 + [_i] * 5 + [_vp] * 3 + [_vp, _vp]),
     'gpode_dec10_predict_ll_len': (_i, [_vp] * 5 + [_i] * 5 + [_vp] * 4 + [_i, _vp, _vp]),
 }

@@ -683,6 +683,32 @@ int gpode_reparam_draws_fwd(const float* mu, const float* logvar, int ld, const 
   if (!mu || !logvar || !eps || !z || !lw) return gp::set_error("gpode_reparam_draws_fwd: null pointer");
   return gp::reparam_draws_fwd(mu, logvar, ld, eps, z, ldz, lw, accumulate, L, N, q, GP_ST);
 }
+int gpode_reparam_draws_bwd(const float* gz, int ldgz, const float* glw, const float* mu, const float* logvar, int ld, const float* eps,
+                            float* gmu, float* glogvar, int ldg, int K, int N, int q, void* stream) {
+  if (K < 1 || K > 64 || N < 1 || q < 1 || ld < q || ldg < q || (gz && ldgz < q) || (long long)K * N > 0x7fffffffLL / 64)
+    return gp::set_error("gpode_reparam_draws_bwd: bad argument (K=%d N=%d q=%d ld=%d ldg=%d ldgz=%d; 1 <= K <= 64)", K, N, q, ld, ldg, ldgz);
+  if (!mu || !logvar || !eps || !gmu || !glogvar) return gp::set_error("gpode_reparam_draws_bwd: null pointer");
+  return gp::reparam_draws_bwd(gz, ldgz, glw, mu, logvar, ld, eps, gmu, glogvar, ldg, K, N, q, GP_ST);
+}
+int gpode_elbo_iw_fwd(const float* lpart, int rows, int nsplit, const float* lw, int L, int K, int N, int M, int Do, const float* Um,
+                      const float* Us, float nobs, float* out, void* stream) {
+  if (!lpart || !lw || !Um || !Us || !out) return gp::set_error("gpode_elbo_iw_fwd: null pointer");
+  return gp::elbo_iw_fwd(lpart, rows, nsplit, lw, L, K, N, M, Do, Um, Us, nobs, out, GP_ST);
+}
+int gpode_elbo_iw_bwd(const float* g_loss, const float* g_nll, const float* g_kl, const float* g_klu, const float* g_ess, const float* lpart,
+                      int rows, int nsplit, const float* lw, int L, int K, int N, int M, int Do, const float* Um, const float* Us, float nobs,
+                      float* grow, float* glw, float* dUm, float* dUs, void* stream) {
+  if (!lpart || !lw || !Um || !Us || !grow || !glw || !dUm || !dUs) return gp::set_error("gpode_elbo_iw_bwd: null pointer");
+  return gp::elbo_iw_bwd(g_loss, g_nll, g_kl, g_klu, g_ess, lpart, rows, nsplit, lw, L, K, N, M, Do, Um, Us, nobs, grow, glw, dUm, dUs, GP_ST);
+}
+int gpode_elbo_iw_bwd_ll(const float* g_loss, const float* g_nll, const float* g_kl, const float* g_klu, const float* g_ess,
+                         const float* lpart, int rows, int nsplit, const float* lw, int L, int K, int N, int M, int Do, const float* Um,
+                         const float* Us, float nobs, float* grow, float* glw, float* dUm, float* dUs, const float* X, const float* z,
+                         float* ga, size_t n_logits, size_t nX, void* stream) {
+  if (!lpart || !lw || !Um || !Us || !grow || !glw || !dUm || !dUs || !X || !z || !ga) return gp::set_error("gpode_elbo_iw_bwd_ll: null pointer");
+  return gp::elbo_iw_bwd_ll(g_loss, g_nll, g_kl, g_klu, g_ess, lpart, rows, nsplit, lw, L, K, N, M, Do, Um, Us, nobs, grow, glw, dUm, dUs, X, z,
+                            ga, n_logits, nX, GP_ST);
+}
 int gpode_reparam_bwd(const float* gz, const float* logvar, int ld, const float* eps, float* gmu, float* glogvar, int ldg, int N, int q,
                       void* stream) {
   if (N == 0) return 0;

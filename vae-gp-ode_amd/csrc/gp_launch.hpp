@@ -241,6 +241,17 @@ int elbo_all_bwd_ll_kl(const float* g0, const float* g1, const float* g2, const 
 int reparam_fwd(const float* mu, const float* logvar, int ld, const float* eps, float* z, int N, int q, hipStream_t st);
 int reparam_draws_fwd(const float* mu, const float* logvar, int ld, const float* eps, float* z, int ldz, float* lw, int accumulate, int L, int N,
                       int q, hipStream_t st);
+int reparam_draws_bwd(const float* gz, int ldgz, const float* glw, const float* mu, const float* logvar, int ld, const float* eps, float* gmu,
+                      float* glogvar, int ldg, int K, int N, int q, hipStream_t st);
+// the importance-weighted bound over K initial-state draws per sequence (vae_conv.hip)
+int elbo_iw_fwd(const float* lpart, int rows, int nsplit, const float* lw, int L, int K, int N, int M, int Do, const float* Um,
+                const float* Us, float nobs, float* out, hipStream_t st);
+int elbo_iw_bwd(const float* g0, const float* g1, const float* g2, const float* g3, const float* g4, const float* lpart, int rows, int nsplit,
+                const float* lw, int L, int K, int N, int M, int Do, const float* Um, const float* Us, float nobs, float* grow, float* glw,
+                float* dUm, float* dUs, hipStream_t st);
+int elbo_iw_bwd_ll(const float* g0, const float* g1, const float* g2, const float* g3, const float* g4, const float* lpart, int rows, int nsplit,
+                   const float* lw, int L, int K, int N, int M, int Do, const float* Um, const float* Us, float nobs, float* grow, float* glw,
+                   float* dUm, float* dUs, const float* X, const float* z, float* ga, size_t n, size_t nX, hipStream_t st);
 int reparam_bwd(const float* gz, const float* logvar, int ld, const float* eps, float* gmu, float* glogvar, int ldg, int N, int q, hipStream_t st);
 int normal_kl_fwd(const float* mu, const float* logvar, int ld, float* klrow, int N, int q, hipStream_t st);
 int normal_kl_bwd(const float* grow, const float* mu, const float* logvar, int ld, float* gmu, float* glogvar, int ldg, int N, int q, hipStream_t st);

@@ -619,6 +619,30 @@ __global__ __launch_bounds__(256) void k_reparam_draws_fwd(const float* __restri
   }
   lw[r] = accumulate ? lw[r] + acc : acc;
 }
+// The adjoint of k_reparam_draws_fwd (training on the importance-weighted bound): gz (K,N,.) with row stride ldgz, glw (K,N), either
+// may be NULL (zero).  With sigma = exp(logvar / 2), z = mu + sigma eps:  d z / d mu = 1, d z / d logvar = sigma eps / 2,
+// d lw / d mu = -z, d lw / d logvar = 1/2 - z sigma eps / 2.  One lane per (n, i) sums the draws k = 0 .. K-1 in that order: a fixed
+// order, no atomics.
+__global__ __launch_bounds__(256) void k_reparam_draws_bwd(const float* __restrict__ gz, int ldgz, const float* __restrict__ glw,
+                                                            const float* __restrict__ mu, const float* __restrict__ logvar, int ld,
+                                                            const float* __restrict__ eps, float* __restrict__ gmu,
+                                                            float* __restrict__ glogvar, int ldg, int K, int N, int q) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= N * q) return;
+  const int n = e / q, d = e % q;
+  const float m = mu[(size_t)n * ld + d], sg = expf(0.5f * logvar[(size_t)n * ld + d]);
+  float am = 0.f, al = 0.f;
+  for (int k = 0; k < K; ++k) {
+    const size_t r = (size_t)k * N + n;
+    const float g = gz ? gz[r * ldgz + d] : 0.f, gl = glw ? glw[r] : 0.f;
+    const float se = sg * eps[r * q + d];
+    const float zd = m + se;
+    am += g - gl * zd;
+    al += g * (0.5f * se) + gl * (0.5f - zd * (0.5f * se));
+  }
+  gmu[(size_t)n * ldg + d] = am;
+  glogvar[(size_t)n * ldg + d] = al;
+}
 __global__ void k_reparam_bwd(const float* __restrict__ gz, const float* __restrict__ logvar, int ld, const float* __restrict__ eps,
                               float* __restrict__ gmu, float* __restrict__ glogvar, int ldg, int N, int q) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -996,6 +1020,154 @@ __global__ void k_elbo_loglik_bwd(const float* __restrict__ g0p, const float* __
   }
 }
 
+// ---- the importance-weighted bound: K initial-state draws per sequence, shared by the L function draws ---------------------------------
+// Rows of the likelihood are ordered (l, k, n) -- X is broadcast by row % N -- and lw (K,N) = log p(z0) - log q(z0 | x) comes from
+// k_reparam_draws_fwd.  a[l,k,n] = sum_s lpart[row][s] + lw[k,n];  iw[l,n] = logsumexp_k a - log K;  the weighting is over z0 only, the
+// mean over the function draws stays outside the log.  One wavefront owns a group (l, n), lane k its draw (K <= 64): the maximum over
+// the draws is subtracted before any exp (a group's a spans thousands of nats), so the largest weight is exactly 1 and a weight that
+// underflows is exactly 0.  Fixed summation orders, no atomics.
+__device__ __forceinline__ float wave_max64(float x) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
+  return x;
+}
+// lane k of the calling wavefront -> w = exp(a - max_k a) (0 on lanes >= K), wave-uniform top = max_k a, s1 = sum_k w, s2 = sum_k w^2.
+// Every caller goes through this one function, so the weights of the forward, of both backward forms and of the logit blocks agree bit
+// for bit.
+__device__ __forceinline__ void iw_group(const float* __restrict__ lpart, int nsplit, const float* __restrict__ lw, int K, int N, int l,
+                                         int n, float& a, float& top, float& w, float& s1, float& s2) {
+  const int lane = threadIdx.x & 63;
+  a = -INFINITY;
+  if (lane < K) {
+    const float* p = lpart + ((size_t)((size_t)l * K + lane) * N + n) * nsplit;
+    float acc = 0.f;
+    for (int s = 0; s < nsplit; ++s) acc = __fadd_rn(acc, p[s]);
+    a = __fadd_rn(acc, lw[(size_t)lane * N + n]);
+  }
+  top = wave_max64(a);
+  w = lane < K ? expf(__fsub_rn(a, top)) : 0.f;
+  const float in2[2] = {w, __fmul_rn(w, w)};
+  float out2[2];
+  wave_sum_multi<2>(in2, out2);
+  s1 = out2[0];
+  s2 = out2[1];
+}
+// the gradient every likelihood row's softmax weight is scaled by: d loss / d iw[l,n] = (-g0 nobs - g1) / (L N)
+__device__ __forceinline__ float iw_row_scale(const float* g0p, const float* g1p, float nobs, int L, int N) {
+  const float g0 = g0p ? *g0p : 0.f, g1 = g1p ? *g1p : 0.f;
+  return __fdiv_rn(__fmaf_rn(-g0, nobs, -g1), (float)((size_t)L * N));
+}
+// out[0..4] = {loss = -(nobs mean iw - kl_u), -mean iw, -mean lw (the Monte-Carlo KL(q(z0) || p), for the log line), kl_u, mean ess},
+// ess[l,n] = (sum_k w)^2 / sum_k w^2.  ONE workgroup of 16 wavefronts: wavefront v takes the groups v, v + 16, ... in that order, lane 0
+// of every wavefront leaves its sums, thread 0 adds the 16 in order.  KL(q(u) || p(u)) as in k_elbo_all_fwd.
+__global__ __launch_bounds__(1024) void k_elbo_iw_fwd(const float* __restrict__ lpart, int nsplit, const float* __restrict__ lw, int L, int K,
+                                                       int N, int M, int Do, const float* __restrict__ Um, const float* __restrict__ Us,
+                                                       float nobs, float* __restrict__ out, const float* __restrict__ usq_part) {
+  __shared__ float red[16][4];
+  const size_t P = (size_t)M * (M + 1) / 2;
+  const int wv = threadIdx.x >> 6;
+  float u = 0.f, b = 0.f;
+  if (usq_part) {
+    for (int e = threadIdx.x; e < kElboParts; e += blockDim.x) u += usq_part[e];
+  } else {
+    for (size_t e = threadIdx.x; e < P * Do; e += blockDim.x) u = fmaf(Us[e], Us[e], u);
+  }
+  for (int e = threadIdx.x; e < M * Do; e += blockDim.x) {
+    const int m = e / Do, d = e % Do;
+    const float l = Us[(size_t)d * P + (size_t)m * (m + 1) / 2 + m];
+    const float v = Um[e];
+    u += v * v - logf(l * l);
+  }
+  for (int e = threadIdx.x; e < K * N; e += blockDim.x) b += lw[e];
+  const float in2[2] = {u, b};
+  float out2[2];
+  wave_sum_multi<2>(in2, out2);
+  float siw = 0.f, sess = 0.f;
+  const float logK = logf((float)K);
+  for (int g = wv; g < L * N; g += 16) {
+    float a, top, w, s1, s2;
+    iw_group(lpart, nsplit, lw, K, N, g / N, g % N, a, top, w, s1, s2);
+    siw += top + logf(s1) - logK;
+    sess += s1 * s1 / s2;
+  }
+  if ((threadIdx.x & 63) == 0) { red[wv][0] = out2[0]; red[wv][1] = out2[1]; red[wv][2] = siw; red[wv][3] = sess; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int v = 0; v < 16; ++v) { t[0] += red[v][0]; t[1] += red[v][1]; t[2] += red[v][2]; t[3] += red[v][3]; }
+    const float ku = 0.5f * (t[0] - (float)M * (float)Do);
+    const float groups = (float)((size_t)L * N), iw = t[2] / groups;
+    out[0] = -(iw * nobs - ku);
+    out[1] = -iw;
+    out[2] = -(t[1] / (float)((size_t)K * N));
+    out[3] = ku;
+    out[4] = t[3] / groups;
+  }
+}
+// g0..g4: gradients w.r.t. the five outputs (device scalars, NULL = 0; the ess output is a diagnostic and carries NO gradient: g4 is
+// accepted and not read) -> grow[row] = softmax_k(a)[l,k,n] (-g0 nobs - g1) / (L N), glw[k,n] = sum_l grow[(l,k,n)] - g2 / (K N),
+// dUm, dUs as in k_elbo_all_bwd.  Blocks [0, nb_small): wavefront n' takes sequence n' and walks l = 0 .. L-1 in order (lane k sums its
+// glw in a register); the same threads do the elementwise (M,Do)- and packed-Us-sized outputs.
+// LL (gpode_elbo_iw_bwd_ll): the blocks behind them do the logits, block (row, c) the elements [c kIwSpan, (c+1) kIwSpan) of its row.
+// Rows do NOT share one gradient here, so every wavefront of a logit block recomputes its row's weight from the K nsplit partial sums of
+// its group through iw_group -- K nsplit loads (out of the L2) against up to kIwSpan / 4 elements of work per wavefront, no row-gradient
+// tensor staged between blocks and so no ordering between blocks of one launch -- and ga is k_sigmoid_loglik_bwd's expression.
+constexpr int kIwSpan = 2048;
+template <bool LL>
+__global__ __launch_bounds__(256) void k_elbo_iw_bwd(const float* __restrict__ g0p, const float* __restrict__ g1p, const float* __restrict__ g2p,
+                                                      const float* __restrict__ g3p, const float* __restrict__ lpart, int nsplit,
+                                                      const float* __restrict__ lw, int L, int K, int N, int M, int Do,
+                                                      const float* __restrict__ Um, const float* __restrict__ Us, float nobs,
+                                                      float* __restrict__ grow, float* __restrict__ glw, float* __restrict__ dUm,
+                                                      float* __restrict__ dUs, int nb_small, const float* __restrict__ X,
+                                                      const float* __restrict__ z, float* __restrict__ ga, size_t inner, size_t nX, int cpr) {
+  const float c = iw_row_scale(g0p, g1p, nobs, L, N);
+  const int lane = threadIdx.x & 63;
+  if (!LL || (int)blockIdx.x < nb_small) {
+    const float g0 = g0p ? *g0p : 0.f, g2 = g2p ? *g2p : 0.f, g3 = g3p ? *g3p : 0.f;
+    const size_t P = (size_t)M * (M + 1) / 2;
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t n = e >> 6;                         // this wavefront's sequence (wave-uniform)
+    if (n < (size_t)N) {
+      float acc = 0.f;
+      for (int l = 0; l < L; ++l) {
+        float a, top, w, s1, s2;
+        iw_group(lpart, nsplit, lw, K, N, l, (int)n, a, top, w, s1, s2);
+        const float gr = __fmul_rn(__fdiv_rn(w, s1), c);
+        if (lane < K) grow[((size_t)l * K + lane) * N + n] = gr;
+        acc = __fadd_rn(acc, gr);
+      }
+      if (lane < K) glw[(size_t)lane * N + n] = __fsub_rn(acc, __fdiv_rn(g2, (float)((size_t)K * N)));
+    }
+    const float g = g0 + g3;
+    if (e < (size_t)M * Do) dUm[e] = g * Um[e];
+    if (e < P * Do) {
+      const size_t k = e % P;
+      int r = (int)((sqrtf(8.f * (float)k + 1.f) - 1.f) * 0.5f);
+      while ((size_t)(r + 1) * (r + 2) / 2 <= k) ++r;
+      while ((size_t)r * (r + 1) / 2 > k) --r;
+      const bool diag = (k - (size_t)r * (r + 1) / 2) == (size_t)r;
+      const float v = Us[e];
+      dUs[e] = g * (diag ? v - 1.f / v : v);
+    }
+    return;
+  }
+  if constexpr (LL) {
+    const size_t bl = (size_t)blockIdx.x - nb_small, row = bl / cpr, p0 = (bl % cpr) * (size_t)kIwSpan;
+    const size_t p1 = p0 + kIwSpan < inner ? p0 + kIwSpan : inner;
+    const int n = (int)(row % N), k = (int)((row / N) % K), l = (int)(row / ((size_t)N * K));
+    float a, top, w, s1, s2;
+    iw_group(lpart, nsplit, lw, K, N, l, n, a, top, w, s1, s2);
+    const float gl = __shfl(__fmul_rn(__fdiv_rn(w, s1), c), k, 64);
+    for (size_t p = p0 + threadIdx.x; p < p1; p += 256) {
+      const size_t e = row * inner + p;
+      const float xv = X[e % nX], zv = z[e];
+      const float gz = gl * (xv / zv - (1.f - xv) / (1.f - zv));
+      ga[e] = gz * zv * (1.f - zv);
+    }
+  }
+}
+
 int sigmoid_loglik_splits(size_t rows, size_t inner) {
   if (rows == 0 || inner == 0) return 1;             // nothing to split (and no division by rows)
   size_t ns = (1024 + rows - 1) / rows, cap = (inner + 1023) / 1024;
@@ -1300,6 +1472,62 @@ int reparam_draws_fwd(const float* mu, const float* logvar, int ld, const float*
   const int rows = L * N;
   hipLaunchKernelGGL(k_reparam_draws_fwd, (rows + 255) / 256, 256, 0, st, mu, logvar, ld, eps, z, ldz, lw, accumulate, rows, N, q);
   return check_launch("reparam_draws_fwd");
+}
+int reparam_draws_bwd(const float* gz, int ldgz, const float* glw, const float* mu, const float* logvar, int ld, const float* eps, float* gmu,
+                      float* glogvar, int ldg, int K, int N, int q, hipStream_t st) {
+  hipLaunchKernelGGL(k_reparam_draws_bwd, (N * q + 255) / 256, 256, 0, st, gz, ldgz, glw, mu, logvar, ld, eps, gmu, glogvar, ldg, K, N, q);
+  return check_launch("reparam_draws_bwd");
+}
+// what the four importance-weighted entry points refuse alike (nullptr: fine)
+static const char* iw_refusal(int rows, int nsplit, int L, int K, int N, int M, int Do) {
+  if (K < 1 || K > 64) return "1 <= K <= 64 (one lane of a wavefront per draw)";
+  if (L < 1 || N < 1 || M < 1 || Do < 1) return "L, N, M, Do >= 1";
+  if (nsplit < 1) return "nsplit >= 1";
+  if (rows > 65535) return "rows <= 65535 (the grid of gpode_sigmoid_loglik_fwd)";
+  if ((long long)rows != (long long)L * K * N) return "rows = L * K * N";
+  return nullptr;
+}
+int elbo_iw_fwd(const float* lpart, int rows, int nsplit, const float* lw, int L, int K, int N, int M, int Do, const float* Um,
+                const float* Us, float nobs, float* out, hipStream_t st) {
+  if (const char* why = iw_refusal(rows, nsplit, L, K, N, M, Do)) return set_error("gpode_elbo_iw_fwd: %s", why);
+  // out: 5 results + kElboParts floats of scratch
+  const size_t nus = (size_t)M * (M + 1) / 2 * Do;
+  const float* usq = nullptr;
+  if (nus > ((size_t)1 << 16)) {
+    hipLaunchKernelGGL(k_sumsq_parts, kElboParts, 256, 0, st, Us, nus, out + 5);
+    usq = out + 5;
+  }
+  hipLaunchKernelGGL(k_elbo_iw_fwd, 1, 1024, 0, st, lpart, nsplit, lw, L, K, N, M, Do, Um, Us, nobs, out, usq);
+  return check_launch(usq ? "elbo_iw_fwd (Us in parts)" : "elbo_iw_fwd");
+}
+static int iw_small_blocks(int N, int M, int Do) {
+  size_t ns = (size_t)M * (M + 1) / 2 * Do;
+  if ((size_t)N * 64 > ns) ns = (size_t)N * 64;      // one wavefront per sequence
+  if ((size_t)M * Do > ns) ns = (size_t)M * Do;
+  return (int)((ns + 255) / 256);
+}
+int elbo_iw_bwd(const float* g0, const float* g1, const float* g2, const float* g3, const float* g4, const float* lpart, int rows, int nsplit,
+                const float* lw, int L, int K, int N, int M, int Do, const float* Um, const float* Us, float nobs, float* grow, float* glw,
+                float* dUm, float* dUs, hipStream_t st) {
+  (void)g4;                                          // the ess output carries no gradient
+  if (const char* why = iw_refusal(rows, nsplit, L, K, N, M, Do)) return set_error("gpode_elbo_iw_bwd: %s", why);
+  const int nb_small = iw_small_blocks(N, M, Do);
+  hipLaunchKernelGGL(k_elbo_iw_bwd<false>, (unsigned)nb_small, 256, 0, st, g0, g1, g2, g3, lpart, nsplit, lw, L, K, N, M, Do, Um, Us, nobs, grow,
+                     glw, dUm, dUs, nb_small, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (size_t)0, (size_t)0, 0);
+  return check_launch("elbo_iw_bwd");
+}
+int elbo_iw_bwd_ll(const float* g0, const float* g1, const float* g2, const float* g3, const float* g4, const float* lpart, int rows, int nsplit,
+                   const float* lw, int L, int K, int N, int M, int Do, const float* Um, const float* Us, float nobs, float* grow, float* glw,
+                   float* dUm, float* dUs, const float* X, const float* z, float* ga, size_t n, size_t nX, hipStream_t st) {
+  (void)g4;
+  if (const char* why = iw_refusal(rows, nsplit, L, K, N, M, Do)) return set_error("gpode_elbo_iw_bwd_ll: %s", why);
+  if (n == 0 || nX == 0 || n % (size_t)rows != 0 || n % nX != 0) return set_error("gpode_elbo_iw_bwd_ll: the logits must be whole rows and X must tile them");
+  const size_t inner = n / (size_t)rows, cpr = (inner + kIwSpan - 1) / kIwSpan;
+  if (cpr * (size_t)rows > 0x7fffffffu - 65536u) return set_error("gpode_elbo_iw_bwd_ll: too many logits for one launch");
+  const int nb_small = iw_small_blocks(N, M, Do);
+  hipLaunchKernelGGL(k_elbo_iw_bwd<true>, (unsigned)(nb_small + cpr * rows), 256, 0, st, g0, g1, g2, g3, lpart, nsplit, lw, L, K, N, M, Do, Um, Us,
+                     nobs, grow, glw, dUm, dUs, nb_small, X, z, ga, inner, nX, (int)cpr);
+  return check_launch("elbo_iw_loglik_bwd");
 }
 int reparam_bwd(const float* gz, const float* logvar, int ld, const float* eps, float* gmu, float* glogvar, int ldg, int N, int q,
                 hipStream_t st) {

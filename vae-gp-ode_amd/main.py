@@ -76,6 +76,9 @@ EXT_FLAGS = [
     ('ragged_compact', eval, False, 'with --ragged_frames: take the padded frames out in front of the decoder -- they are integrated but not '
                                     'decoded, and enter neither the BatchNorm statistics nor the loss; the frame counts are read back once '
                                     'per step and the launch sizes follow them, so not with --hip_graph and not on several ranks'),
+    ('iw_draws', int, 0, 'K in 1..64: train on the importance-weighted bound -- K initial states per sequence, shared by the function '
+                         'draws; the likelihood rows and the decoder batch grow K-fold, the log line shows the Monte-Carlo KL(q(z0)||p) '
+                         'as kl_reg; not with --ragged_compact and not on several ranks; 0: off, the standard ELBO'),
     ('sync_bn', eval, True, 'data parallel: BatchNorm normalises with the statistics of the GLOBAL minibatch (all ranks), as the '
                             'single-process reference does (vae.py:55,58,113,116,119)'),
 ]
@@ -175,6 +178,21 @@ def check_ragged_compact(args):
                          'built' % os.environ['WORLD_SIZE'])
 
 
+def check_iw_draws(args):
+    """--iw_draws K: 0 (off) or 1..64, without --ragged_compact and on one rank; refused with a message otherwise, ahead of any device work"""
+    K = args.iw_draws
+    if not K:
+        return
+    if not 1 <= K <= 64:
+        raise SystemExit('--iw_draws %d: must be 0 (off) or 1..64 -- one lane of a wavefront reduces each draw of a sequence' % K)
+    if args.ragged_compact:
+        raise SystemExit('--iw_draws %d: not with --ragged_compact True -- the compact ragged route has no importance-weighted loss stage; '
+                         '--ragged_frames alone works' % K)
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        raise SystemExit('--iw_draws %d: not on several ranks (WORLD_SIZE %s) -- sharding is per sequence and would probably work, but it '
+                         'is untested' % (K, os.environ['WORLD_SIZE']))
+
+
 def subsample_generator(args):
     """The generator of the frame subsets: its own, on the device, seeded from --seed alone -- identical on every rank, so the ranks
     draw the same subsets for the global minibatch before they take their shards."""
@@ -255,6 +273,7 @@ def main(argv=None):
     check_subsample(args)
     check_ragged(args)
     check_ragged_compact(args)
+    check_iw_draws(args)
     check_dense_scale(args)
     from .model.core.initialization import initialize_and_fix_kernel_parameters
     from .model.create_model import build_model, compute_loss, compute_test_error, backward
@@ -318,6 +337,7 @@ def main(argv=None):
         torch.manual_seed(args.seed + 7919 * (rank + 1))     # encoder reparameterisation noise: independent per shard
         torch.cuda.manual_seed(args.seed + 7919 * (rank + 1))
     kern = model.flow.odefunc.diffeq.kern
+    iw = args.iw_draws or None                       # --iw_draws K: every step trains on the importance-weighted bound
     graphs = {}     # --hip_graph: one captured step per (L, batch shape), replayed on a static input buffer
     if args.hip_graph:
         from . import ops
@@ -347,7 +367,9 @@ def main(argv=None):
 
             def step():
                 optimizer.zero_grad()
-                if nbuf is not None:
+                if iw is not None:
+                    out = compute_loss(model, buf, L, ts=tbuf, n_obs=nbuf, iw_draws=iw)
+                elif nbuf is not None:
                     out = compute_loss(model, buf, L, ts=tbuf, n_obs=nbuf)
                 else:
                     out = compute_loss(model, buf, L) if tbuf is None else compute_loss(model, buf, L, ts=tbuf)
@@ -391,6 +413,9 @@ def main(argv=None):
                             'only (frame counts read back once per step)')
         else:
             logger.info('Every sequence keeps {} of its frames, drawn per minibatch; time grids per sequence'.format(args.subsample_frames))
+    if iw is not None:
+        logger.info('Importance-weighted bound: {} initial states per sequence, shared by the function draws; nlhood is -mean iw, kl_reg '
+                    'the Monte-Carlo KL(q(z0)||p)'.format(iw))
     logger.info('********** Started Training **********')
     begin = time.time()
     for ep in range(args.Nepoch):
@@ -421,6 +446,8 @@ def main(argv=None):
                     bn_sync.set_shares(None)
             if args.hip_graph and capture_ok:
                 loss, nlhood, kl_reg, kl_u = graphed_step(minibatch, L, ts, n_obs) if n_obs is not None else graphed_step(minibatch, L, ts)
+            elif iw is not None:                     # the importance-weighted bound: nlhood is -mean iw, kl_reg the Monte-Carlo KL
+                loss, nlhood, kl_reg, kl_u = compute_loss(model, minibatch, L, ts=ts, n_obs=n_obs, iw_draws=iw)
             elif n_obs is not None and args.ragged_compact:
                 loss, nlhood, kl_reg, kl_u = compute_loss(model, minibatch, L, ts=ts, n_obs=n_obs, compact=True)
             elif n_obs is not None:

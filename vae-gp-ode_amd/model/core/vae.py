@@ -80,7 +80,16 @@ class Encoder(nn.Module):
     def sample_draws(self, mu, logvar, L, out=None, col=0, lw=None):
         """L reparameterised draws and their importance log-weights log p(z) - log q(z | x), one launch (V.reparam_draws):
         -> (z (L,N,q), lw (L,N)).  ``next_eps`` (L,N,q), if set, replaces the N(0,1) draw once.  ``out`` (L,N,W) / ``col``: z goes
-        into columns col .. col+q-1 of it; ``lw``: this encoder's sum is added to it.  Forward only."""
+        into columns col .. col+q-1 of it; ``lw``: this encoder's sum is added to it -- the in-place form, forward only (evaluation).
+        Without ``out`` and ``lw``, with gradients enabled and (mu, logvar) requiring one, z and lw are fresh tensors and DIFFERENTIABLE
+        (V.reparam_draws_train): training on the importance-weighted bound."""
+        eps = self.draws_eps(mu, L)
+        if out is None and lw is None and torch.is_grad_enabled() and (mu.requires_grad or logvar.requires_grad):
+            return V.reparam_draws_train(mu, logvar, eps.to(mu))
+        return V.reparam_draws(mu, logvar, eps.to(mu), out=out, col=col, lw=lw)
+
+    def draws_eps(self, mu, L):
+        """the N(0,1) noise of L draws, (L,) + mu.shape: ``next_eps`` once if set, else the device source or torch's generator"""
         shape = (int(L),) + tuple(mu.shape)
         eps = getattr(self, 'next_eps', None)
         if eps is None:
@@ -89,7 +98,7 @@ class Encoder(nn.Module):
         elif tuple(eps.shape) != shape:
             raise ValueError('sample_draws: next_eps must be %s, got %s' % (shape, tuple(eps.shape)))
         self.next_eps = None
-        return V.reparam_draws(mu, logvar, eps.to(mu), out=out, col=col, lw=lw)
+        return eps
 
     def kl_rows(self, mu_s, logvar_s, mu_v=None, logvar_v=None):
         """kl_divergence(q_dist(...), N(0, I)).sum(-1) (create_model.py:47-49) without building the distributions: (N,)."""

@@ -52,7 +52,37 @@ def _compact_index(model, data, n_obs, counts):
     return V.frame_index(n_obs, data.shape[1], counts=counts)
 
 
-def compute_loss(model, data, L, ts=None, n_obs=None, compact=False, counts=None):
+IW_MAX_DRAWS, IW_MAX_ROWS = 64, 65535
+
+
+def _iw_loss(model, data, L, K, grid, n_obs, compact):
+    """compute_loss(iw_draws=K): its refusals, then the importance-weighted bound (vae_ops.elbo_iw)"""
+    from .. import vae_ops as V
+    if compact:
+        raise ValueError('compute_loss: iw_draws is not built for compact=True (the compact ragged route); use n_obs alone')
+    if not _FUSED_LOSS:
+        raise ValueError('compute_loss: iw_draws has one loss route, from the logits; it is not available under GPODE_UNFUSED_LOSS=1')
+    if isinstance(K, bool) or int(K) != K or not 1 <= K <= IW_MAX_DRAWS:
+        raise ValueError('compute_loss: iw_draws must be an integer in 1..%d (one lane of a wavefront per draw), got %r' % (IW_MAX_DRAWS, K))
+    K, N = int(K), data.shape[0]
+    if L * K * N > IW_MAX_ROWS:
+        raise ValueError('compute_loss: L * iw_draws * N = %d x %d x %d = %d likelihood rows, more than the %d the loss stage takes'
+                         % (L, K, N, L * K * N, IW_MAX_ROWS))
+    field = model.flow.odefunc.diffeq
+    if not hasattr(field, 'us_packed') or model.vae.decoder.distribution != 'bernoulli':
+        raise ValueError('compute_loss: iw_draws needs the Bernoulli decoder and the fused loss stage (a %s decoder is not covered)'
+                         % model.vae.decoder.distribution)
+    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        raise ValueError('compute_loss: iw_draws on several ranks is out of scope: the sharding is per sequence and would probably work, '
+                         'but it is untested')
+    logits, _, _, lw = model(data, L, logits=True, z0_draws=K, **grid)
+    lpart, _ = V.sigmoid_loglik_parts(data, logits, L * K * N, n_obs)
+    loss, iw_nll, kl_mc, kl_u, ess = V.elbo_iw(lpart, lw, field.Um.optvar, field.us_packed(), L, K, N, field.M, model.num_observations)
+    model.last_ess = ess.detach()                    # the mean effective sample size of the step: a device scalar, not read back
+    return loss, iw_nll, kl_mc, kl_u
+
+
+def compute_loss(model, data, L, ts=None, n_obs=None, compact=False, counts=None, iw_draws=None):
     """-> (loss, nll, kl_reg, kl_u) (create_model.py:61-73).  Same terms as elbo() above; the per-row pieces go through
     three fused launches (KL rows, likelihood row sums, loss algebra) instead of ~25 elementwise ones.
     ``ts`` (N,T): the observation time of every frame of every sequence (ODEGPVAE.forward); None = the uniform grid, the call as
@@ -68,9 +98,19 @@ def compute_loss(model, data, L, ts=None, n_obs=None, compact=False, counts=None
     (gpode_sigmoid_loglik_fwd_pk, gpode_elbo_all_fwd; backward: gpode_elbo_all_bwd and gpode_sigmoid_loglik_bwd_pk).  What the padded
     columns of ``ts`` and the padded target frames hold then reaches no result.  The index needs the counts on the host: ``counts`` (a
     host sequence) if the caller has them, else ``n_obs`` is read back once per call (one synchronisation).  One loss route, from the
-    logits: refused under GPODE_UNFUSED_LOSS=1, for a non-Bernoulli decoder, and with several ranks."""
+    logits: refused under GPODE_UNFUSED_LOSS=1, for a non-Bernoulli decoder, and with several ranks.
+    ``iw_draws`` = K in 1..64: train on the importance-weighted bound -- K initial states z0_{k,n} ~ q(z0 | x_n) per sequence, shared by
+    the L function draws; with lw[k,n] = log p(z0) - log q(z0 | x), ll[l,k,n] the log-likelihood of sequence n under (z0_{k,n}, f_l)
+    and iw[l,n] = logsumexp_k (ll + lw) - log K:  loss = -(nobs mean_{l,n} iw - kl_u) -> (loss, iw_nll = -mean iw, kl_mc = -mean lw,
+    kl_u).  The weighting is over z0 only, the mean over the function draws stays outside the log; the analytic
+    KL(q(z0) || p) does not appear, lw stands for it.  K = 1 is legal: a = ll + lw.  The mean effective sample size of the step is
+    left in ``model.last_ess`` (a device scalar, not read back).  Works with ``ts`` and ``n_obs``; L K N <= 65535.  Refused:
+    compact=True, GPODE_UNFUSED_LOSS=1, a non-Bernoulli decoder, several ranks (sharding is per sequence and would probably work, but
+    it is untested).  None: the call as it always was."""
     from .. import vae_ops as V
     grid = {} if ts is None else {'ts': ts}
+    if iw_draws is not None:
+        return _iw_loss(model, data, L, iw_draws, grid, n_obs, compact)
     index = None
     if compact:                                      # the index stands for the counts from here on
         index, n_obs = _compact_index(model, data, n_obs, counts), None

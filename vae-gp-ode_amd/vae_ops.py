@@ -869,12 +869,13 @@ class _ElboAll(torch.autograd.Function):
         return glr, ghs, ghv, dUm, dUs, None, None, None, None
 
 
-def _elbo_all_bwd(ctx, seeds, name, ll, Um, Us, rows, lshape, args):
+def _elbo_all_bwd(ctx, seeds, name, ll, Um, Us, rows, lshape, args, kl_inputs=(3, 4)):
     """What the backward of both ELBO forms does: gradient seeds -> ONE launch -> in overlap mode the gradients of (Um, Us) go to the
     flow's deferred backward -> the row gradient as a broadcast view.  ``name``: the entry point, without the route's suffix;
     ``args(glrow, dUm, dUs)``: its arguments between the seeds and the logit block.  ``ll`` = (X, z, route) of sigmoid_loglik_parts: the
     logits' gradient comes out of the same launch (every likelihood row receives the same gradient) and rides on the row gradient,
-    where _SigmoidLogLikParts.backward finds it and launches nothing.  -> (row gradient, dUm, dUs)"""
+    where _SigmoidLogLikParts.backward finds it and launches nothing.  ``kl_inputs``: where (Um, Us) stand among the Function's inputs.
+    -> (row gradient, dUm, dUs)"""
     gs = [None if g is None else g.contiguous().float() for g in seeds]
     glrow, dUm, dUs = _new((rows,), Um), torch.empty_like(Um), torch.empty_like(Us)
     ga, logit_block = None, ()
@@ -883,7 +884,7 @@ def _elbo_all_bwd(ctx, seeds, name, ll, Um, Us, rows, lshape, args):
         ga = torch.empty_like(z)
         name, logit_block = name + route.suffix, (_ptr(X), _ptr(z), _ptr(ga), z.numel(), X.numel(), *route.tail)
     _lib.call(name, *[_ptr(g) for g in gs], *args(glrow, dUm, dUs), *logit_block, _stream())
-    if (ctx.needs_input_grad[3] and ctx.needs_input_grad[4] and Um.is_leaf and Us.is_leaf and
+    if (ctx.needs_input_grad[kl_inputs[0]] and ctx.needs_input_grad[kl_inputs[1]] and Um.is_leaf and Us.is_leaf and
             ops.defer_kl_grads((Um, Us), (dUm, dUs))):
         dUm = dUs = None                             # overlap mode: the flow's deferred backward adds its share to them in place
     # every slice of a likelihood row carries the row's gradient (a broadcast view: nothing is copied)
@@ -1069,7 +1070,7 @@ def reparam_draws(mu, logvar, eps, out=None, col=0, lw=None):
     eps (L,N,q) -> z[l] = mu + exp(logvar / 2) eps[l] -- the bits reparam() gives draw by draw -- and
     lw[l,n] = sum_i log N(z; 0, 1) - log N(z; mu, sigma^2) (L,N).  ``out`` (L,N,W) with ``col``: z is written into columns
     col .. col+q-1 of it (one half of an order-2 state) and that view is returned; ``lw``: the sum is ADDED to it (the other half's).
-    Forward only: evaluation, not training."""
+    Forward only, in place: the evaluation's form.  reparam_draws_train() is the differentiable one."""
     h = _chk(_pack(mu, logvar).detach(), 'h')
     N, q = h.shape[0], h.shape[1] // 2
     if eps.dim() != 3:
@@ -1089,6 +1090,103 @@ def reparam_draws(mu, logvar, eps, out=None, col=0, lw=None):
     _lib.call('gpode_reparam_draws_fwd', _ptr(h), ctypes.c_void_p(h.data_ptr() + 4 * q), 2 * q, _ptr(eps),
               ctypes.c_void_p(out.data_ptr() + 4 * col), W, _ptr(lw), acc, L, N, q, _stream())
     return out[..., col:col + q], lw
+
+
+class _ReparamDraws(torch.autograd.Function):
+    """K reparameterised draws of the encoders' distributions and their importance log-weights, with a backward (training on the
+    importance-weighted bound): hs = [mu | logvar] (N, 2q) of the position encoder, hv the velocity encoder's of a second-order model
+    or None -> z (K,N,order*q), the two halves side by side, and lw (K,N), the sum of the two.  One gpode_reparam_draws_fwd per encoder,
+    the second adding to lw; the backward is one gpode_reparam_draws_bwd per encoder, reading its half of the state gradient in place."""
+
+    @staticmethod
+    def forward(ctx, hs, hv, eps_s, eps_v):
+        hs = _chk(hs, 'hs')
+        N, q = hs.shape[0], hs.shape[1] // 2
+        if eps_s.dim() != 3:
+            raise _lib.GpodeError('reparam_draws_train: eps must be (K,N,q), got %s' % (tuple(eps_s.shape),))
+        K = eps_s.shape[0]
+        eps_s = _chk(eps_s, 'eps', (K, N, q))
+        W = q if hv is None else 2 * q
+        z, lw = _new((K, N, W), hs), _new((K, N), hs)
+        _lib.call('gpode_reparam_draws_fwd', _ptr(hs), ctypes.c_void_p(hs.data_ptr() + 4 * q), 2 * q, _ptr(eps_s), _ptr(z), W, _ptr(lw), 0,
+                  K, N, q, _stream())
+        if hv is not None:
+            hv, eps_v = _chk(hv, 'hv', (N, 2 * q)), _chk(eps_v, 'eps (v)', (K, N, q))
+            _lib.call('gpode_reparam_draws_fwd', _ptr(hv), ctypes.c_void_p(hv.data_ptr() + 4 * q), 2 * q, _ptr(eps_v),
+                      ctypes.c_void_p(z.data_ptr() + 4 * q), W, _ptr(lw), 1, K, N, q, _stream())
+        ctx.save_for_backward(hs, hv, eps_s, eps_v)
+        ctx.set_materialize_grads(False)
+        return z, lw
+
+    @staticmethod
+    def backward(ctx, gz, glw):
+        hs, hv, eps_s, eps_v = ctx.saved_tensors
+        N, q = hs.shape[0], hs.shape[1] // 2
+        K, W = eps_s.shape[0], (q if hv is None else 2 * q)
+        gz = gz.contiguous() if gz is not None else None
+        glw = glw.contiguous() if glw is not None else None
+        out = []
+        for col, h, eps in ((0, hs, eps_s), (q, hv, eps_v)):
+            if h is None:
+                out.append(None)
+                continue
+            g = _new(h.shape, h)
+            _lib.call('gpode_reparam_draws_bwd', ctypes.c_void_p(gz.data_ptr() + 4 * col) if gz is not None else None, W, _ptr(glw), _ptr(h),
+                      ctypes.c_void_p(h.data_ptr() + 4 * q), 2 * q, _ptr(eps), _ptr(g), ctypes.c_void_p(g.data_ptr() + 4 * q), 2 * q, K, N, q,
+                      _stream())
+            out.append(g)
+        return out[0], out[1], None, None
+
+
+def reparam_draws_train(mu_s, logvar_s, eps_s, mu_v=None, logvar_v=None, eps_v=None):
+    """The differentiable form of reparam_draws(): K draws per sequence of q(z0 | x) -> fresh z (K,N,order*q) and
+    lw (K,N) = log p(z) - log q(z | x), the gradients of both flowing back to (mu, logvar) of either encoder (_ReparamDraws)."""
+    hv = _pack(mu_v, logvar_v) if mu_v is not None else None
+    return _ReparamDraws.apply(_pack(mu_s, logvar_s), hv, eps_s, eps_v)
+
+
+class _ElboIW(torch.autograd.Function):
+    """(loss, -mean iw, -mean lw, KL(u), mean ess) of the importance-weighted bound from the likelihood partial sums of L K N rows
+    ordered (l,k,n) and the log-weights lw (K,N): gpode_elbo_iw_fwd, and ONE backward launch -- gpode_elbo_iw_bwd_ll, which also
+    produces the logits' gradient (ll = (X, z, route) of sigmoid_loglik_parts), or gpode_elbo_iw_bwd where the route has no fused
+    form, _SigmoidLogLikParts.backward then launching from column 0 of the row gradient.  The ess output carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, lpart, lw, Um, Us, L, K, N, M, nobs, ll):
+        lpart, lw, Um, Us = _chk(lpart, 'lpart'), _chk(lw, 'lw', (K, N)), _chk(Um, 'Um'), _chk(Us, 'Us_sqrt.optvar')
+        rows = L * K * N
+        if lpart.dim() != 2 or lpart.shape[0] != rows:
+            raise _lib.GpodeError('elbo_iw: lpart must be (L K N, nsplit) = (%d, nsplit), got %s' % (rows, tuple(lpart.shape)))
+        out = _new((5 + 256,), lpart)                # five results + the library's scratch
+        _lib.call('gpode_elbo_iw_fwd', _ptr(lpart), rows, lpart.shape[1], _ptr(lw), L, K, N, M, Um.shape[1], _ptr(Um), _ptr(Us),
+                  ctypes.c_float(nobs), _ptr(out), _stream())
+        ctx.save_for_backward(lpart, lw, Um, Us)
+        ctx.dims = (rows, L, K, N, M, float(nobs), tuple(lpart.shape))
+        ctx.ll = ll
+        ctx.set_materialize_grads(False)
+        return out[0], out[1], out[2], out[3], out[4]
+
+    @staticmethod
+    def backward(ctx, g0, g1, g2, g3, _g4):
+        lpart, lw, Um, Us = ctx.saved_tensors
+        rows, L, K, N, M, nobs, lshape = ctx.dims
+        glw = torch.empty_like(lw)
+        ll = ctx.ll if ctx.needs_input_grad[0] else None
+        glr, dUm, dUs = _elbo_all_bwd(
+            ctx, (g0, g1, g2, g3, None), 'gpode_elbo_iw_bwd' if ll is None else 'gpode_elbo_iw_bwd_ll', ll, Um, Us, rows, lshape,
+            lambda grow, dUm, dUs: (_ptr(lpart), rows, lshape[1], _ptr(lw), L, K, N, M, Um.shape[1], _ptr(Um), _ptr(Us), ctypes.c_float(nobs),
+                                    _ptr(grow), _ptr(glw), _ptr(dUm), _ptr(dUs)), kl_inputs=(2, 3))
+        return glr, glw, dUm, dUs, None, None, None, None, None, None
+
+
+def elbo_iw(lpart, lw, Um, Us_packed, L, K, N, M, nobs, fused=True):
+    """-> (loss, iw_nll, kl_mc, kl_u, ess): the importance-weighted bound over K initial-state draws per sequence, shared by the L
+    function draws (_ElboIW).  ``lpart``: sigmoid_loglik_parts over the L K N rows ordered (l,k,n); ``lw`` (K,N): reparam_draws_train.
+    ``fused=False`` (A/B), and every route without the fused form (ragged minibatches): the logits' gradient is a launch of its own."""
+    ll = getattr(lpart, '_gpode_ll', None) if fused else None
+    if ll is not None and not (ll[2].fused and ll[2].suffix == '' and ll[1].numel() % ll[0].numel() == 0):
+        ll = None
+    return _ElboIW.apply(lpart, lw, Um, Us_packed, int(L), int(K), int(N), int(M), float(nobs), ll)
 
 
 def normal_kl_rows(mu, logvar):
