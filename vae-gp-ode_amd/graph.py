@@ -30,10 +30,21 @@ def capturing_step():
     return _capture['active']
 
 
-def after_capture(fn):
+def after_capture(fn, undo=None):
     """Run ``fn()`` once, eagerly, right after the running GraphedStep capture ends (before its first replay): for constants
-    of the captured graph that are only known during the capture (e.g. a table of the gradient tensors' addresses)."""
-    _capture['after'].append(fn)
+    of the captured graph that are only known during the capture (e.g. a table of the gradient tensors' addresses).
+    ``undo``: run in its place when the capture raises -- whatever the caller booked for a graph that now never exists (a table
+    entry without content, a buffer taken from a pool) is given back there."""
+    _capture['after'].append((fn, undo))
+
+
+def abandon_capture():
+    """The capture that was running has failed: run the undos of its registrations, latest first, and none of the uploads."""
+    _capture['active'] = False
+    after, _capture['after'] = _capture['after'], []
+    for _, undo in reversed(after):
+        if undo is not None:
+            undo()
 
 
 class GraphedStep:
@@ -64,11 +75,13 @@ class GraphedStep:
         try:
             with torch.cuda.graph(self.graph, capture_error_mode='thread_local'):
                 self.out = _detached(step_fn())
-        finally:
-            _capture['active'] = False
-        for fn in _capture['after']:
+        except BaseException:
+            abandon_capture()
+            raise
+        _capture['active'] = False
+        after, _capture['after'] = _capture['after'], []
+        for fn, _ in after:
             fn()
-        _capture['after'] = []
         torch.cuda.synchronize()
         self.grads = [p.grad for p in self.grad_params] if self.grad_params is not None else None
         self.eager_steps = warmup

@@ -153,12 +153,14 @@ class SVGP_Layer(torch.nn.Module):
         Cholesky chain runs next to the encoder; Flow.forward picks it up with take_prebuilt_cache()."""
         if not ops.overlap_enabled():
             return
+        self.drop_prebuilt_cache()                   # of a forward pass that raised before its flow
         # every tensor the side-stream kernels read is produced on the current stream BEFORE the fork (the side stream then
         # waits for it) and stays referenced by the cache until the step's join
         nz, params = self._cache_inputs(draws=draws)
         side = ops.fork_side_stream()
         with ops.launch_on(side):
             self._prebuilt = cache = self._launch_cache_build(nz, params)
+        self._prebuilt_for = self._prebuilt_stamp()
         # the flow waits for THIS point of the side stream only; the gradient-independent half of the cache backward (L^-1 from the
         # factor) then follows on the same stream, behind the build it depends on -- one fork of the step's graph instead of two
         # (every fork / join of the captured step costs tens of microseconds at replay)
@@ -169,9 +171,27 @@ class SVGP_Layer(torch.nn.Module):
             with ops.launch_on(side):
                 cache.prepared = ops.cache_bwd_prepare(cache)
 
+    def _prebuilt_stamp(self):
+        """What a prebuilt cache is good for: this step (ops.step_token: an optimiser writes the parameters through raw pointers, which
+        no version counter sees) and these parameter values (their storage and version counters: load_state_dict, an in-place edit)."""
+        return (ops.step_token(), tuple((p.data_ptr(), p._version) for p in self.parameters()))
+
+    def drop_prebuilt_cache(self):
+        """Forget a prebuilt cache nobody took.  Its side-stream kernels may still be running and its buffers go back to the allocator
+        of the current stream, which therefore waits for the side stream first."""
+        if getattr(self, '_prebuilt', None) is None:
+            return
+        torch.cuda.current_stream().wait_stream(ops.side_stream())
+        self._prebuilt = None
+
     def take_prebuilt_cache(self):
         cache = getattr(self, '_prebuilt', None)
         if cache is None:
+            return None
+        if self._prebuilt_for != self._prebuilt_stamp():
+            # left behind by a forward pass that raised between prebuild_cache() and its flow: older parameters, older noise.  The
+            # flow builds its own.
+            self.drop_prebuilt_cache()
             return None
         self._prebuilt = None
         torch.cuda.current_stream().wait_event(self._prebuilt_ready)

@@ -60,7 +60,7 @@ def _chk(t, name, shape=None):
 # (profiles/r02b_notes.txt: a torch.zeros there made the GP parameter gradients wobble from run to run).
 # ---------------------------------------------------------------------------------------------
 _launch_override = []          # stack of torch streams that _stream() returns instead of the current stream
-_overlap = {'on': False, 'side': None, 'pending': [], 'forked': False, 'kl': None}
+_overlap = {'on': False, 'side': None, 'pending': [], 'forked': False, 'kl': None, 'step': 0}
 
 
 def _stream():
@@ -132,8 +132,28 @@ def defer_kl_grads(params, grads):
     return True
 
 
+def drop_pending_grads():
+    """The start of a new step (HipAdam.zero_grad): whatever a backward pass left for join_side_stream() belongs to a step that never
+    reached its optimiser -- the pass raised behind the flow's backward -- and must not be added to this step's gradients.  The
+    current stream first waits for the side stream: the buffers go back to the allocator here, and a side-stream kernel of the
+    aborted pass may still be writing them.  A step that ran to its end left nothing, and then this launches nothing."""
+    _overlap['step'] += 1
+    if not _overlap['pending'] and _overlap['kl'] is None:
+        return
+    torch.cuda.current_stream().wait_stream(side_stream())
+    _overlap['forked'] = False
+    _overlap['pending'], _overlap['kl'] = [], None
+
+
+def step_token():
+    """Advances whenever a step begins (drop_pending_grads) or its gradients are joined for the optimiser (join_side_stream): what was
+    prepared under one value belongs to that step alone (SVGP_Layer.prebuild_cache)."""
+    return _overlap['step']
+
+
 def join_side_stream():
     """Current stream waits for the side stream; deferred parameter gradients are accumulated."""
+    _overlap['step'] += 1
     if not _overlap['forked'] and not _overlap['pending'] and _overlap['kl'] is None:
         return
     torch.cuda.current_stream().wait_stream(side_stream())

@@ -55,7 +55,9 @@ class HipAdam:
         # the set is seen) and kept.  Graph replays hand over the same tensors every time and the eager allocator cycles through
         # a few sets, so the steady state uploads nothing.  (A single table refreshed through one pinned staging buffer is a race:
         # the host may overwrite the staging buffer for step i+1 before the device has run step i's asynchronous copy.)
+        # an entry is (table, its host source or None, whether a captured graph reads the table)
         self._tables = {}
+        self._graph_tabs = []                        # the tables captured graphs read: the optimiser's for its lifetime
         self._g = None
         # pinned sources for tables uploaded INSIDE a graph capture (allocating pinned memory is not a capturable call): one per
         # captured graph that holds the update
@@ -67,6 +69,7 @@ class HipAdam:
             self._gflat = torch.tensor([base + 4 * o for o in offs], dtype=torch.int64, device=dev)
 
     def zero_grad(self):
+        ops.drop_pending_grads()                     # side-stream gradients of a pass that never reached step(): not this step's
         if not self.bucketed:
             for p in self.params:
                 p.grad = None
@@ -92,7 +95,8 @@ class HipAdam:
         tab = self._tables.get(key)
         if tab is None:
             if len(self._tables) >= 256:             # an allocator that never repeats itself: do not grow without bound
-                self._tables.clear()
+                # ... but a captured graph reads its table's address at every replay: those entries stay
+                self._tables = {k: v for k, v in self._tables.items() if v[2]}
             if torch.cuda.is_current_stream_capturing():
                 # inside a capture the upload must be a node of the graph: pinned source kept alive with the table
                 if not self._pinned or not self._static_tabs:
@@ -103,21 +107,32 @@ class HipAdam:
                     # capture ends and before the first replay, instead of by a copy node that every replay would repeat.  The
                     # table must then live OUTSIDE the graph's memory pool: a block allocated during the capture may have had an
                     # earlier life inside the same step, and the kernel that wrote it then overwrites the table at every replay.
+                    # A capture that raises never uploads: its entry would map these addresses to a table of zeros, so the undo
+                    # removes it and hands the table back.
                     tab = self._static_tabs.pop()
                     vals = torch.tensor(cur, dtype=torch.int64)
-                    graph.after_capture(lambda t=tab, v=vals: t.copy_(v))
-                    self._tables[key] = (tab, vals)
+                    self._graph_tabs.append(tab)
+                    graph.after_capture(lambda t=tab, v=vals: t.copy_(v), undo=lambda t=tab, k=key: self._release_static_tab(k, t))
+                    self._tables[key] = (tab, vals, True)
                 else:
                     tab = torch.empty(len(cur), dtype=torch.int64, device=self._p.device)
                     host = self._pinned.pop()
                     host.copy_(torch.tensor(cur, dtype=torch.int64))
                     tab.copy_(host, non_blocking=True)
-                    self._tables[key] = (tab, host)
+                    self._graph_tabs.append(tab)
+                    self._tables[key] = (tab, host, True)
             else:
                 tab = torch.tensor(cur, dtype=torch.int64, device=self._p.device)   # synchronous upload, once per set
-                self._tables[key] = (tab, None)
+                self._tables[key] = (tab, None, False)
             tab = self._tables[key]
         self._g = tab[0]
+
+    def _release_static_tab(self, key, tab):
+        """the capture that took ``tab`` for the gradient addresses ``key`` has failed (graph.after_capture's undo)"""
+        if self._tables.get(key, (None,))[0] is tab:
+            del self._tables[key]
+        self._graph_tabs[:] = [t for t in self._graph_tabs if t is not tab]
+        self._static_tabs.append(tab)
 
     def gather_grads(self):
         """bucketed='gather': fill the flat bucket from the gradients autograd produced (one launch)."""

@@ -66,7 +66,10 @@ def _bn_scratch(B, C, like):
 # gradients in zero_grad and takes over the tensors autograd hands it (optim.HipAdam(bucketed=False | 'gather'):
 # ``allows_deferred_reductions``): creating a HipAdam sets the switch for its kind (the optimiser in charge of the step decides);
 # the default, and the setting for any other consumer of ``.grad``, is off.  configs[0]: 14 reduction launches -> 1.
-_deferred = {'on': False, 'keep': [], 'queued': False}
+# The bookkeeping of a pass is keyed on autograd's graph task: a pass that raises never runs its end-of-backward callback (autograd drops
+# the callbacks it had queued), so ``queued`` alone would stay set for good and no later pass would flush.  A reducing call under another
+# task than the stored one therefore starts a new pass, whatever the last one left behind.
+_deferred = {'on': False, 'keep': [], 'queued': False, 'task': -1}
 _DEFER_ALLOWED = os.environ.get('GPODE_EAGER_REDUCTIONS', '0') != '1'
 
 
@@ -74,8 +77,10 @@ def set_deferred_reductions(on):
     _deferred['on'] = bool(on) and _DEFER_ALLOWED
 
 
-def _flush_deferred():
-    _deferred['queued'] = False
+def _flush_deferred(task):
+    if task != _deferred['task']:                    # the callback of a pass that is no longer the current one: nothing of it is recorded
+        return
+    _deferred['queued'], _deferred['task'] = False, -1
     try:
         _lib.call('gpode_flush_reductions', _stream())
     finally:
@@ -84,13 +89,15 @@ def _flush_deferred():
 
 def _bwd_call(name, *args, keep=()):
     """A backward-pass entry point whose last step is a reduction of workgroup partials (``keep``: its scratch buffers)."""
-    if not (_deferred['on'] and torch._C._current_graph_task_id() >= 0):
+    task = torch._C._current_graph_task_id() if _deferred['on'] else -1
+    if task < 0:
         return _lib.call(name, *args)
     lib = _lib.load()
-    if not _deferred['queued']:
+    if not _deferred['queued'] or task != _deferred['task']:
         lib.gpode_defer_reductions(2)                # drop leftovers of an aborted pass, then record
-        torch.autograd.Variable._execution_engine.queue_callback(_flush_deferred)
-        _deferred['queued'] = True
+        _deferred['keep'].clear()                    # ... and its scratch buffers: the jobs that read them are gone
+        torch.autograd.Variable._execution_engine.queue_callback(lambda t=task: _flush_deferred(t))
+        _deferred['queued'], _deferred['task'] = True, task
     else:
         lib.gpode_defer_reductions(1)
     try:
@@ -98,6 +105,22 @@ def _bwd_call(name, *args, keep=()):
     finally:
         lib.gpode_defer_reductions(0)
     _deferred['keep'].extend(keep)
+
+
+def reset_step_state():
+    """Put everything a training step carries over to the next one back to its start: the deferred reductions (recorded jobs, their
+    scratch buffers, the library's recording mode), the side-stream gradients a pass left for the optimiser (ops.drop_pending_grads) and
+    the registrations of a GraphedStep capture.  A step that ran to its end leaves all of these empty, and a step that did not is
+    recovered from by the next one on its own (the graph task above, HipAdam.zero_grad, GraphedStep); this is the explicit form, for a
+    caller that gives up on a step and wants nothing of it kept alive."""
+    from . import graph
+    lib = _lib.load()
+    lib.gpode_defer_reductions(2)
+    lib.gpode_defer_reductions(0)
+    _deferred['keep'].clear()
+    _deferred['queued'], _deferred['task'] = False, -1
+    ops.drop_pending_grads()
+    graph.abandon_capture()
 
 
 _bn_sync = None        # parallel.BatchNormSync while data-parallel training normalises with global-minibatch statistics
