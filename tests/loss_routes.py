@@ -1,5 +1,5 @@
 """Every route of the tail of the training step -- the dense layers, the elementwise kernels, the fused loss stage, the ELBO glue
-(csrc/vae_conv.hip), k_svgp_kl (csrc/gp_misc.hip), Adam and the gradient gather -- shared by test_gpu_loss_routes.py and
+(csrc/vae_dense.hip, csrc/vae_loss.hip), k_svgp_kl (csrc/gp_misc.hip), Adam and the gradient gather (csrc/vae_optim.hip) -- shared by test_gpu_loss_routes.py and
 test_loss_routes_host.py.
 
 A case is a named tuple of one of the families below; case_id(c) names it.

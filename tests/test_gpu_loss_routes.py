@@ -1,4 +1,4 @@
-"""Every route of the tail of the training step -- everything in csrc/vae_conv.hip that is not a convolution, plus k_svgp_kl
+"""Every route of the tail of the training step -- csrc/vae_dense.hip, csrc/vae_loss.hip and csrc/vae_optim.hip, plus k_svgp_kl
 (csrc/gp_misc.hip) -- driven through the C ABI at the smallest shapes that sit on each edge (loss_routes.py): gpode_linear_fwd / _bwd,
 gpode_linear_relu_fwd / _bwd, gpode_act_*, gpode_loglik_*, gpode_loglik_rowsum_*, gpode_sigmoid_loglik_fwd / _bwd, gpode_reparam_*,
 gpode_reparam_kl_*, gpode_normal_kl_*, gpode_elbo_fwd / _bwd, gpode_svgp_kl_fwd / _bwd, the five gpode_elbo_all_* entry points,

@@ -4,9 +4,10 @@
   python tools/kernel_bodies.py compare <old dir> <new dir>   hash each kernel body and report
 
 A kernel body is the text from the kernel's label to s_endpgm with comments stripped and the .LBB<n>_ labels renumbered, so a
-kernel whose mangled name changed (a template parameter dropped) still matches by body.  compare prints, per translation unit,
-the kernel counts, the kernels that disappeared, and every kernel of the new tree whose body does not occur in the old tree
-(there should be none when only dispatch code changed); exit status 1 if there is one."""
+kernel whose mangled name changed (a template parameter dropped) still matches by body.  Matching is pooled over the .s files of a
+tree, so a kernel that moved to another translation unit matches too.  compare prints, per translation unit, the kernel counts, the
+kernels whose body is in no file of the new tree, and every kernel of the new tree whose body is in no file of the old one (there should
+be none when only dispatch code changed or kernels moved); exit status 1 if there is one."""
 import hashlib
 import os
 import re
@@ -60,27 +61,32 @@ def demangle(names):
 
 
 def compare(old, new):
-    bad = 0
-    tot = [0, 0]
-    for f in sorted(set(os.listdir(old)) | set(os.listdir(new))):
-        if not f.endswith('.s'):
-            continue
-        a = bodies(os.path.join(old, f)) if os.path.exists(os.path.join(old, f)) else {}
-        b = bodies(os.path.join(new, f)) if os.path.exists(os.path.join(new, f)) else {}
-        tot[0] += len(a)
-        tot[1] += len(b)
-        old_hashes = set(a.values())
+    """Matching is pooled: a body of the new tree counts as unchanged when it occurs in ANY .s file of the old tree (and a kernel of the
+    old tree as gone when its body occurs in none of the new ones), so a kernel that moved to another translation unit still matches.
+    The per-file lines say where the kernels are; the verdict is the pooled total."""
+    def tree(d):
+        return {f: bodies(os.path.join(d, f)) for f in sorted(os.listdir(d)) if f.endswith('.s')}
+    a_all, b_all = tree(old), tree(new)
+    old_hashes = {h for a in a_all.values() for h in a.values()}
+    new_hashes = {h for b in b_all.values() for h in b.values()}
+    bad = lost = 0
+    for f in sorted(set(a_all) | set(b_all)):
+        a, b = a_all.get(f, {}), b_all.get(f, {})
         changed = [k for k, h in b.items() if h not in old_hashes]
-        new_hashes = set(b.values())
         gone = [k for k, h in a.items() if h not in new_hashes]
-        print('%-22s %3d -> %3d kernels, %d gone, %d with a body not in the old build' % (f, len(a), len(b), len(gone), len(changed)))
+        moved_out = sum(1 for h in a.values() if h in new_hashes and h not in set(b.values()))
+        moved_in = sum(1 for h in b.values() if h in old_hashes and h not in set(a.values()))
+        print('%-22s %3d -> %3d kernels, %d gone, %d with a body not in the old build%s' % (
+            f, len(a), len(b), len(gone), len(changed), ' (%d moved out, %d moved in)' % (moved_out, moved_in) if moved_out or moved_in else ''))
         for d in demangle(gone):
             print('    gone     ' + d)
         for d in demangle(changed):
             print('    CHANGED  ' + d)
         bad += len(changed)
-    print('total %d -> %d kernels; %s' % (tot[0], tot[1], 'every surviving body occurs in the old build' if not bad else
-                                          '%d bodies differ' % bad))
+        lost += len(gone)
+    tot = [sum(map(len, a_all.values())), sum(map(len, b_all.values()))]
+    print('total %d -> %d kernels, %d gone; %s' % (tot[0], tot[1], lost, 'every surviving body occurs in the old build' if not bad else
+                                                   '%d bodies differ' % bad))
     return 1 if bad else 0
 
 

@@ -422,32 +422,34 @@ int gpode_cache_bwd_prepare(int kernel, int Di, int Do, int M, int S, const floa
 
 // ---- conv VAE blocks -----------------------------------------------------------------------
 #define GP_ST ((hipStream_t)stream)
+// the geometry arguments every convolution export names alike
+#define GP_GEOM gp::ConvGeom{.B = B, .Ci = Ci, .H = H, .W = W, .Co = Co, .K = K, .S = S, .P = P, .Ho = Ho, .Wo = Wo}
 int gpode_conv2d_fwd(const float* x, const float* w, const float* bias, float* y, int B, int Ci, int H, int W, int Co,
                      int K, int S, int P, int Ho, int Wo, void* stream) {
   if (!x || !w || !y) return gp::set_error("gpode_conv2d_fwd: null pointer");
-  return gp::conv2d_fwd(x, w, bias, y, B, Ci, H, W, Co, K, S, P, Ho, Wo, GP_ST);
+  return gp::conv2d_fwd(x, w, bias, y, GP_GEOM, GP_ST);
 }
 int gpode_conv2d_bwd_data(const float* gy, const float* w, const float* bias, float* gx, int B, int Ci, int H, int W, int Co,
                           int K, int S, int P, int Ho, int Wo, void* stream) {
   if (!gy || !w || !gx) return gp::set_error("gpode_conv2d_bwd_data: null pointer");
-  return gp::conv2d_bwd_data(gy, w, bias, gx, B, Ci, H, W, Co, K, S, P, Ho, Wo, nullptr, GP_ST);
+  return gp::conv2d_bwd_data(gy, w, bias, gx, GP_GEOM, nullptr, GP_ST);
 }
 int gpode_conv2d_bwd_data_bn(const float* gy, const float* gy_bn, const float* w, const float* bias, float* gx, int B, int Ci, int H,
                              int W, int Co, int K, int S, int P, int Ho, int Wo, void* stream) {
   if (!gy || !gy_bn || !w || !gx) return gp::set_error("gpode_conv2d_bwd_data_bn: null pointer");
-  return gp::conv2d_bwd_data(gy, w, bias, gx, B, Ci, H, W, Co, K, S, P, Ho, Wo, gy_bn, GP_ST);
+  return gp::conv2d_bwd_data(gy, w, bias, gx, GP_GEOM, gy_bn, GP_ST);
 }
 int gpode_conv2d_fwd_bs(const float* x, size_t x_batch_stride, const float* w, const float* bias, float* y, int B, int Ci, int H, int W, int Co,
                         int K, int S, int P, int Ho, int Wo, void* stream) {
   if (!x || !w || !y) return gp::set_error("gpode_conv2d_fwd_bs: null pointer");
   if (x_batch_stride < (size_t)Ci * H * W) return gp::set_error("gpode_conv2d_fwd_bs: images overlap");
-  return gp::conv2d_fwd(x, w, bias, y, B, Ci, H, W, Co, K, S, P, Ho, Wo, GP_ST, x_batch_stride);
+  return gp::conv2d_fwd(x, w, bias, y, GP_GEOM, GP_ST, x_batch_stride);
 }
 int gpode_conv2d_bwd_weight_bs(const float* x, size_t x_batch_stride, const float* gy, float* gw, float* gbias, float* scratch, int B, int Ci,
                                int H, int W, int Co, int K, int S, int P, int Ho, int Wo, void* stream) {
   if (!x || !gy || !gw || !scratch) return gp::set_error("gpode_conv2d_bwd_weight_bs: null pointer");
   if (x_batch_stride < (size_t)Ci * H * W) return gp::set_error("gpode_conv2d_bwd_weight_bs: images overlap");
-  return gp::conv2d_bwd_weight(x, gy, gw, gbias, scratch, B, Ci, H, W, Co, K, S, P, Ho, Wo, nullptr, GP_ST, x_batch_stride);
+  return gp::conv2d_bwd_weight(x, gy, gw, gbias, scratch, GP_GEOM, nullptr, GP_ST, x_batch_stride);
 }
 size_t gpode_convT_fwd_stats_scratch(int Cout) { return gp::convT_fwd_stats_scratch(Cout); }
 int gpode_convT_fwd_stats(const float* x, const float* x_bn, const float* w, const float* bias, float* y, int B, int Ci, int H, int W, int Co,
@@ -457,20 +459,21 @@ int gpode_convT_fwd_stats(const float* x, const float* x_bn, const float* w, con
   if (!x || !w || !y || !gamma || !beta || !save_mean || !save_invstd || !table || !scratch)
     return gp::set_error("gpode_convT_fwd_stats: null pointer");
   if ((running_mean == nullptr) != (running_var == nullptr)) return gp::set_error("gpode_convT_fwd_stats: running_mean and running_var go together");
-  return gp::convT_fwd_stats(x, x_bn, w, bias, y, B, Ci, H, W, Co, K, S, P, Ho, Wo, gamma, beta, save_mean, save_invstd, running_mean,
-                             running_var, num_batches_tracked, momentum, eps, table, scratch, slot, GP_ST);
+  return gp::convT_fwd_stats(x, x_bn, w, bias, y, GP_GEOM, gamma, beta, save_mean, save_invstd, running_mean, running_var, num_batches_tracked,
+                             momentum, eps, table, scratch, slot, GP_ST);
 }
 size_t gpode_conv_wgrad_scratch(int B, int Ci, int Co, int K) { return gp::conv_wgrad_scratch(B, Ci, Co, K); }
 int gpode_conv2d_bwd_weight(const float* x, const float* gy, float* gw, float* gbias, float* scratch, int B, int Ci, int H, int W,
                             int Co, int K, int S, int P, int Ho, int Wo, void* stream) {
   if (!x || !gy || !gw || !scratch) return gp::set_error("gpode_conv2d_bwd_weight: null pointer");
-  return gp::conv2d_bwd_weight(x, gy, gw, gbias, scratch, B, Ci, H, W, Co, K, S, P, Ho, Wo, nullptr, GP_ST);
+  return gp::conv2d_bwd_weight(x, gy, gw, gbias, scratch, GP_GEOM, nullptr, GP_ST);
 }
 int gpode_conv2d_bwd_weight_bn(const float* x, const float* gy, const float* gy_bn, float* gw, float* gbias, float* scratch, int B, int Ci,
                                int H, int W, int Co, int K, int S, int P, int Ho, int Wo, void* stream) {
   if (!x || !gy || !gy_bn || !gw || !scratch) return gp::set_error("gpode_conv2d_bwd_weight_bn: null pointer");
-  return gp::conv2d_bwd_weight(x, gy, gw, gbias, scratch, B, Ci, H, W, Co, K, S, P, Ho, Wo, gy_bn, GP_ST);
+  return gp::conv2d_bwd_weight(x, gy, gw, gbias, scratch, GP_GEOM, gy_bn, GP_ST);
 }
+#undef GP_GEOM
 size_t gpode_bn_scratch(int B, int C) { return gp::bn_scratch(B, C); }
 int gpode_bn_fwd(const float* x, const float* gamma, const float* beta, float* y, float* save_mean, float* save_invstd,
                  float* running_mean, float* running_var, long long* num_batches_tracked, float momentum, float eps, int B, int C,
@@ -559,26 +562,35 @@ int gpode_bn_eval_table(const float* gamma, const float* beta, const float* runn
   if (!gamma || !beta || !running_mean || !running_var || !table) return gp::set_error("gpode_bn_eval_table: null pointer");
   return gp::bn_eval_table(gamma, beta, running_mean, running_var, eps, table, C, GP_ST);
 }
+// The checked operation under the four gpode_dec10_predict* exports, which name themselves and the operands their prototype lacks
+static int predict_any(const char* who, bool ll, bool ragged, const float* c, const float* table, const float* w, const float* bias,
+                       const float* X, int Lc, int F, int Th, int T_obs, int done, float* pred_mean, float* pred_m2, float* se_state,
+                       float* ell, int L_total, const int* n_obs, void* stream) {
+  if (!c || !table || !w || !X || !se_state) return gp::set_error("%s: null pointer", who);
+  const gp::PredictArgs a{.c = c, .table = table, .w = w, .bias = bias, .X = X, .Lc = Lc, .F = F, .Th = Th, .T_obs = T_obs, .done = done,
+                          .pred_mean = pred_mean, .pred_m2 = pred_m2, .se_state = se_state, .ell = ell, .L_total = L_total, .n_obs = n_obs};
+  return gp::dec10_predict(who, ll, ragged, a, GP_ST);
+}
 int gpode_dec10_predict(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th,
                         int T_obs, int done, float* pred_mean, float* pred_m2, float* se_state, void* stream) {
-  if (!c || !table || !w || !X || !se_state) return gp::set_error("gpode_dec10_predict: null pointer");
-  return gp::dec10_predict(c, table, w, bias, X, Lc, F, Th, T_obs, done, pred_mean, pred_m2, se_state, GP_ST);
+  return predict_any("gpode_dec10_predict", false, false, c, table, w, bias, X, Lc, F, Th, T_obs, done, pred_mean, pred_m2, se_state, nullptr, 0,
+                     nullptr, stream);
 }
 int gpode_dec10_predict_ll(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th,
                            int T_obs, int done, float* pred_mean, float* pred_m2, float* se_state, float* ell, int L_total, void* stream) {
-  if (!c || !table || !w || !X || !se_state) return gp::set_error("gpode_dec10_predict_ll: null pointer");
-  return gp::dec10_predict_ll(c, table, w, bias, X, Lc, F, Th, T_obs, done, pred_mean, pred_m2, se_state, ell, L_total, GP_ST);
+  return predict_any("gpode_dec10_predict_ll", true, false, c, table, w, bias, X, Lc, F, Th, T_obs, done, pred_mean, pred_m2, se_state, ell,
+                     L_total, nullptr, stream);
 }
 int gpode_dec10_predict_len(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th,
                             int T_obs, int done, float* pred_mean, float* pred_m2, float* se_state, const int* n_obs, void* stream) {
-  if (!c || !table || !w || !X || !se_state) return gp::set_error("gpode_dec10_predict_len: null pointer");
-  return gp::dec10_predict_len(c, table, w, bias, X, Lc, F, Th, T_obs, done, pred_mean, pred_m2, se_state, n_obs, GP_ST);
+  return predict_any("gpode_dec10_predict_len", false, true, c, table, w, bias, X, Lc, F, Th, T_obs, done, pred_mean, pred_m2, se_state, nullptr,
+                     0, n_obs, stream);
 }
 int gpode_dec10_predict_ll_len(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th,
                                int T_obs, int done, float* pred_mean, float* pred_m2, float* se_state, float* ell, int L_total,
                                const int* n_obs, void* stream) {
-  if (!c || !table || !w || !X || !se_state) return gp::set_error("gpode_dec10_predict_ll_len: null pointer");
-  return gp::dec10_predict_ll_len(c, table, w, bias, X, Lc, F, Th, T_obs, done, pred_mean, pred_m2, se_state, ell, L_total, n_obs, GP_ST);
+  return predict_any("gpode_dec10_predict_ll_len", true, true, c, table, w, bias, X, Lc, F, Th, T_obs, done, pred_mean, pred_m2, se_state, ell,
+                     L_total, n_obs, stream);
 }
 int gpode_chan_sum(const float* v, float* out, int B, int C, int HW, float* scratch, void* stream) {
   if (!v || !out || !scratch) return gp::set_error("gpode_chan_sum: null pointer");
@@ -609,24 +621,32 @@ int gpode_loglik_fwd(const float* X, const float* z, float* ll, size_t n, size_t
 int gpode_loglik_bwd(const float* X, const float* z, const float* g, float* gz, size_t n, size_t nX, void* stream) {
   return gp::loglik_bwd(X, z, g, gz, n, nX, GP_ST);
 }
+// The likelihood's row operations.  The twins without frame counts pass an empty mask; `ragged` says that the export takes counts, so a
+// null n_obs is refused there and means "every frame" here.  The legacy rowsum pair checks nothing (its callers do).
+static int rowsum_any(const char* who, bool ragged, bool bwd, const float* X, const float* z, const float* grow, float* out, size_t rows,
+                      size_t inner, size_t nX, const int* n_obs, int T, size_t frame, void* stream) {
+  if (ragged) {
+    if (!X || !z || !out || (bwd && !grow)) return gp::set_error("%s: null pointer", who);
+    if (!rows || !inner || !nX) return gp::set_error("%s: empty input", who);
+  }
+  const gp::LogLikRows r{.X = X, .z = z, .rows = rows, .inner = inner, .nX = nX};
+  const gp::FrameMask m{.n_obs = n_obs, .T = T, .frame = frame};
+  return bwd ? gp::loglik_rowsum_bwd(who, ragged, r, m, grow, out, GP_ST) : gp::loglik_rowsum_fwd(who, ragged, r, m, out, GP_ST);
+}
 int gpode_loglik_rowsum_fwd(const float* X, const float* z, float* out, size_t rows, size_t inner, size_t nX, void* stream) {
-  return gp::loglik_rowsum_fwd(X, z, out, rows, inner, nX, GP_ST);
+  return rowsum_any("gpode_loglik_rowsum_fwd", false, false, X, z, nullptr, out, rows, inner, nX, nullptr, 0, 0, stream);
 }
 int gpode_loglik_rowsum_bwd(const float* X, const float* z, const float* grow, float* gz, size_t rows, size_t inner, size_t nX,
                             void* stream) {
-  return gp::loglik_rowsum_bwd(X, z, grow, gz, rows, inner, nX, GP_ST);
+  return rowsum_any("gpode_loglik_rowsum_bwd", false, true, X, z, grow, gz, rows, inner, nX, nullptr, 0, 0, stream);
 }
 int gpode_loglik_rowsum_fwd_len(const float* X, const float* z, float* out, size_t rows, size_t inner, size_t nX, const int* n_obs, int T,
                                 size_t frame, void* stream) {
-  if (!X || !z || !out) return gp::set_error("gpode_loglik_rowsum_fwd_len: null pointer");
-  if (!rows || !inner || !nX) return gp::set_error("gpode_loglik_rowsum_fwd_len: empty input");
-  return gp::loglik_rowsum_fwd_len(X, z, out, rows, inner, nX, n_obs, T, frame, GP_ST);
+  return rowsum_any("gpode_loglik_rowsum_fwd_len", true, false, X, z, nullptr, out, rows, inner, nX, n_obs, T, frame, stream);
 }
 int gpode_loglik_rowsum_bwd_len(const float* X, const float* z, const float* grow, float* gz, size_t rows, size_t inner, size_t nX,
                                 const int* n_obs, int T, size_t frame, void* stream) {
-  if (!X || !z || !grow || !gz) return gp::set_error("gpode_loglik_rowsum_bwd_len: null pointer");
-  if (!rows || !inner || !nX) return gp::set_error("gpode_loglik_rowsum_bwd_len: empty input");
-  return gp::loglik_rowsum_bwd_len(X, z, grow, gz, rows, inner, nX, n_obs, T, frame, GP_ST);
+  return rowsum_any("gpode_loglik_rowsum_bwd_len", true, true, X, z, grow, gz, rows, inner, nX, n_obs, T, frame, stream);
 }
 int gpode_noise_fill(float* out, long long n_normal, long long n_uniform, unsigned long long seed, unsigned long long* state, void* stream) {
   if (n_normal < 0 || n_uniform < 0) return gp::set_error("gpode_noise_fill: negative count");
@@ -644,31 +664,6 @@ int gpode_reparam_kl_bwd(const float* gz, const float* gklpart, const float* mu,
   if (N == 0) return 0;
   if (!mu || !logvar || !eps || !gmu || !glogvar || q < 1 || ld < q || ldg < q) return gp::set_error("gpode_reparam_kl_bwd: bad argument");
   return gp::reparam_kl_bwd(gz, gklpart, mu, logvar, ld, eps, gmu, glogvar, ldg, N, q, GP_ST);
-}
-int gpode_elbo_all_fwd_kl(const float* lpart, int nl_rows, int nl_values, const float* kls, int nks, const float* klv, int nkv, int N, int M,
-                          int Do, const float* Um, const float* Us, float nobs, float* out, void* stream) {
-  if (!lpart || !kls || !Um || !Us || !out || (nkv > 0 && !klv)) return gp::set_error("gpode_elbo_all_fwd_kl: null pointer");
-  if (nl_rows < 1 || nl_values < nl_rows || N < 1 || M < 1 || Do < 1 || nks < 1 || nkv < 0) return gp::set_error("gpode_elbo_all_fwd_kl: bad sizes");
-  return gp::elbo_all_fwd_kl(lpart, nl_rows, nl_values, kls, nks, klv, nkv, N, M, Do, Um, Us, nobs, out, GP_ST);
-}
-int gpode_elbo_all_bwd_ll_kl(const float* g_loss, const float* g_nll, const float* g_kl, const float* g_klu, int nl_rows, int N, int M, int Do,
-                             const float* Um, const float* Us, float nobs, float* glrow, float* gkls, int nks, float* gklv, int nkv,
-                             float* dUm, float* dUs, const float* X, const float* z, float* ga, size_t n_logits, size_t nX, void* stream) {
-  if (!Um || !Us || !glrow || !gkls || !dUm || !dUs || (nkv > 0 && !gklv) || !X || !z || !ga) return gp::set_error("gpode_elbo_all_bwd_ll_kl: null pointer");
-  if (nl_rows < 1 || N < 1 || M < 1 || Do < 1 || nks < 1 || nkv < 0 || n_logits < 1 || nX < 1 || n_logits % nX != 0)
-    return gp::set_error("gpode_elbo_all_bwd_ll_kl: bad sizes");
-  return gp::elbo_all_bwd_ll_kl(g_loss, g_nll, g_kl, g_klu, nl_rows, N, M, Do, Um, Us, nobs, glrow, gkls, nks, gklv, nkv, dUm, dUs, X, z, ga,
-                                n_logits, nX, GP_ST);
-}
-int gpode_elbo_all_bwd_ll_kl_len(const float* g_loss, const float* g_nll, const float* g_kl, const float* g_klu, int nl_rows, int N, int M,
-                                 int Do, const float* Um, const float* Us, float nobs, float* glrow, float* gkls, int nks, float* gklv, int nkv,
-                                 float* dUm, float* dUs, const float* X, const float* z, float* ga, size_t n_logits, size_t nX,
-                                 const int* n_obs, int T, size_t frame, void* stream) {
-  if (!Um || !Us || !glrow || !gkls || !dUm || !dUs || (nkv > 0 && !gklv) || !X || !z || !ga) return gp::set_error("gpode_elbo_all_bwd_ll_kl_len: null pointer");
-  if (nl_rows < 1 || N < 1 || M < 1 || Do < 1 || nks < 1 || nkv < 0 || n_logits < 1 || nX < 1 || n_logits % nX != 0)
-    return gp::set_error("gpode_elbo_all_bwd_ll_kl_len: bad sizes");
-  return gp::elbo_all_bwd_ll_kl_len(g_loss, g_nll, g_kl, g_klu, nl_rows, N, M, Do, Um, Us, nobs, glrow, gkls, nks, gklv, nkv, dUm, dUs, X, z, ga,
-                                    n_logits, nX, n_obs, T, frame, GP_ST);
 }
 int gpode_reparam_fwd(const float* mu, const float* logvar, int ld, const float* eps, float* z, int N, int q, void* stream) {
   if (N == 0) return 0;
@@ -693,21 +688,29 @@ int gpode_reparam_draws_bwd(const float* gz, int ldgz, const float* glw, const f
 int gpode_elbo_iw_fwd(const float* lpart, int rows, int nsplit, const float* lw, int L, int K, int N, int M, int Do, const float* Um,
                       const float* Us, float nobs, float* out, void* stream) {
   if (!lpart || !lw || !Um || !Us || !out) return gp::set_error("gpode_elbo_iw_fwd: null pointer");
-  return gp::elbo_iw_fwd(lpart, rows, nsplit, lw, L, K, N, M, Do, Um, Us, nobs, out, GP_ST);
+  return gp::elbo_iw_fwd({.lpart = lpart, .rows = rows, .nsplit = nsplit, .lw = lw, .L = L, .K = K},
+                         {.N = N, .M = M, .Do = Do, .Um = Um, .Us = Us, .nobs = nobs}, out, GP_ST);
 }
+// g_ess is taken and not read: the ess output carries no gradient
 int gpode_elbo_iw_bwd(const float* g_loss, const float* g_nll, const float* g_kl, const float* g_klu, const float* g_ess, const float* lpart,
                       int rows, int nsplit, const float* lw, int L, int K, int N, int M, int Do, const float* Um, const float* Us, float nobs,
                       float* grow, float* glw, float* dUm, float* dUs, void* stream) {
+  (void)g_ess;
   if (!lpart || !lw || !Um || !Us || !grow || !glw || !dUm || !dUs) return gp::set_error("gpode_elbo_iw_bwd: null pointer");
-  return gp::elbo_iw_bwd(g_loss, g_nll, g_kl, g_klu, g_ess, lpart, rows, nsplit, lw, L, K, N, M, Do, Um, Us, nobs, grow, glw, dUm, dUs, GP_ST);
+  return gp::elbo_iw_bwd("gpode_elbo_iw_bwd", false, {.g0 = g_loss, .g1 = g_nll, .g2 = g_kl, .g3 = g_klu},
+                         {.lpart = lpart, .rows = rows, .nsplit = nsplit, .lw = lw, .L = L, .K = K},
+                         {.N = N, .M = M, .Do = Do, .Um = Um, .Us = Us, .nobs = nobs}, {.glrow = grow, .dUm = dUm, .dUs = dUs}, glw, {}, GP_ST);
 }
 int gpode_elbo_iw_bwd_ll(const float* g_loss, const float* g_nll, const float* g_kl, const float* g_klu, const float* g_ess,
                          const float* lpart, int rows, int nsplit, const float* lw, int L, int K, int N, int M, int Do, const float* Um,
                          const float* Us, float nobs, float* grow, float* glw, float* dUm, float* dUs, const float* X, const float* z,
                          float* ga, size_t n_logits, size_t nX, void* stream) {
+  (void)g_ess;
   if (!lpart || !lw || !Um || !Us || !grow || !glw || !dUm || !dUs || !X || !z || !ga) return gp::set_error("gpode_elbo_iw_bwd_ll: null pointer");
-  return gp::elbo_iw_bwd_ll(g_loss, g_nll, g_kl, g_klu, g_ess, lpart, rows, nsplit, lw, L, K, N, M, Do, Um, Us, nobs, grow, glw, dUm, dUs, X, z,
-                            ga, n_logits, nX, GP_ST);
+  return gp::elbo_iw_bwd("gpode_elbo_iw_bwd_ll", true, {.g0 = g_loss, .g1 = g_nll, .g2 = g_kl, .g3 = g_klu},
+                         {.lpart = lpart, .rows = rows, .nsplit = nsplit, .lw = lw, .L = L, .K = K},
+                         {.N = N, .M = M, .Do = Do, .Um = Um, .Us = Us, .nobs = nobs}, {.glrow = grow, .dUm = dUm, .dUs = dUs}, glw,
+                         {.X = X, .z = z, .ga = ga, .n = n_logits, .nX = nX}, GP_ST);
 }
 int gpode_reparam_bwd(const float* gz, const float* logvar, int ld, const float* eps, float* gmu, float* glogvar, int ldg, int N, int q,
                       void* stream) {
@@ -727,29 +730,35 @@ int gpode_normal_kl_bwd(const float* grow, const float* mu, const float* logvar,
   return gp::normal_kl_bwd(grow, mu, logvar, ld, gmu, glogvar, ldg, N, q, GP_ST);
 }
 int gpode_sigmoid_loglik_splits(size_t rows, size_t inner) { return gp::sigmoid_loglik_splits(rows, inner); }
+static int sigmoid_fwd_any(const char* who, bool ragged, const float* X, const float* a, float* z, float* part, size_t rows, size_t inner,
+                           size_t nX, int nsplit, const int* n_obs, int T, size_t frame, void* stream) {
+  if (!X || !a || !z || !part) return gp::set_error("%s: null pointer", who);
+  if (!rows || !inner || !nX) return gp::set_error("%s: empty input", who);
+  return gp::sigmoid_loglik_fwd(who, ragged, {.X = X, .z = nullptr, .rows = rows, .inner = inner, .nX = nX},
+                                {.n_obs = n_obs, .T = T, .frame = frame}, a, z, part, nsplit, GP_ST);
+}
+static int sigmoid_bwd_any(const char* who, bool ragged, const float* X, const float* z, const float* grow, float* ga, size_t rows,
+                           size_t inner, size_t nX, const int* n_obs, int T, size_t frame, void* stream) {
+  if (!X || !z || !grow || !ga) return gp::set_error("%s: null pointer", who);
+  if (!rows || !inner || !nX) return gp::set_error("%s: empty input", who);
+  return gp::sigmoid_loglik_bwd(who, ragged, {.X = X, .z = z, .rows = rows, .inner = inner, .nX = nX}, {.n_obs = n_obs, .T = T, .frame = frame},
+                                grow, ga, GP_ST);
+}
 int gpode_sigmoid_loglik_fwd(const float* X, const float* a, float* z, float* part, size_t rows, size_t inner, size_t nX, int nsplit,
                              void* stream) {
-  if (!X || !a || !z || !part) return gp::set_error("gpode_sigmoid_loglik_fwd: null pointer");
-  if (!rows || !inner || !nX) return gp::set_error("gpode_sigmoid_loglik_fwd: empty input");
-  return gp::sigmoid_loglik_fwd(X, a, z, part, rows, inner, nX, nsplit, GP_ST);
+  return sigmoid_fwd_any("gpode_sigmoid_loglik_fwd", false, X, a, z, part, rows, inner, nX, nsplit, nullptr, 0, 0, stream);
 }
 int gpode_sigmoid_loglik_bwd(const float* X, const float* z, const float* grow, float* ga, size_t rows, size_t inner, size_t nX,
                              void* stream) {
-  if (!X || !z || !grow || !ga) return gp::set_error("gpode_sigmoid_loglik_bwd: null pointer");
-  if (!rows || !inner || !nX) return gp::set_error("gpode_sigmoid_loglik_bwd: empty input");
-  return gp::sigmoid_loglik_bwd(X, z, grow, ga, rows, inner, nX, GP_ST);
+  return sigmoid_bwd_any("gpode_sigmoid_loglik_bwd", false, X, z, grow, ga, rows, inner, nX, nullptr, 0, 0, stream);
 }
 int gpode_sigmoid_loglik_fwd_len(const float* X, const float* a, float* z, float* part, size_t rows, size_t inner, size_t nX, int nsplit,
                                  const int* n_obs, int T, size_t frame, void* stream) {
-  if (!X || !a || !z || !part) return gp::set_error("gpode_sigmoid_loglik_fwd_len: null pointer");
-  if (!rows || !inner || !nX) return gp::set_error("gpode_sigmoid_loglik_fwd_len: empty input");
-  return gp::sigmoid_loglik_fwd_len(X, a, z, part, rows, inner, nX, nsplit, n_obs, T, frame, GP_ST);
+  return sigmoid_fwd_any("gpode_sigmoid_loglik_fwd_len", true, X, a, z, part, rows, inner, nX, nsplit, n_obs, T, frame, stream);
 }
 int gpode_sigmoid_loglik_bwd_len(const float* X, const float* z, const float* grow, float* ga, size_t rows, size_t inner, size_t nX,
                                  const int* n_obs, int T, size_t frame, void* stream) {
-  if (!X || !z || !grow || !ga) return gp::set_error("gpode_sigmoid_loglik_bwd_len: null pointer");
-  if (!rows || !inner || !nX) return gp::set_error("gpode_sigmoid_loglik_bwd_len: empty input");
-  return gp::sigmoid_loglik_bwd_len(X, z, grow, ga, rows, inner, nX, n_obs, T, frame, GP_ST);
+  return sigmoid_bwd_any("gpode_sigmoid_loglik_bwd_len", true, X, z, grow, ga, rows, inner, nX, n_obs, T, frame, stream);
 }
 int gpode_gather_frames_fwd(const float* zt, int ld, int q, const int* src, int L, int N, int T, int P, float* out, void* stream) {
   if (!zt || !out) return gp::set_error("gpode_gather_frames_fwd: null pointer");
@@ -770,44 +779,87 @@ int gpode_sigmoid_loglik_fwd_pk(const float* X, const float* a, float* z, float*
                                 size_t nX, int nsplit, void* stream) {
   if (!X || !a || !z || !part) return gp::set_error("gpode_sigmoid_loglik_fwd_pk: null pointer");
   if (!rows || !nX) return gp::set_error("gpode_sigmoid_loglik_fwd_pk: empty input");
-  return gp::sigmoid_loglik_fwd_pk(X, a, z, part, rows, off, T, frame, nX, nsplit, GP_ST);
+  return gp::sigmoid_loglik_fwd_pk({.X = X, .z = nullptr, .rows = rows, .inner = 0, .nX = nX}, {.index = off, .P = 0, .T = T, .frame = frame}, a, z,
+                                   part, nsplit, GP_ST);
 }
 int gpode_sigmoid_loglik_bwd_pk(const float* X, const float* z, const float* grow, float* ga, size_t rows, const int* src, int P, int T,
                                 size_t frame, size_t nX, void* stream) {
   if (!X || !z || !grow || !ga) return gp::set_error("gpode_sigmoid_loglik_bwd_pk: null pointer");
   if (!rows || !nX) return gp::set_error("gpode_sigmoid_loglik_bwd_pk: empty input");
-  return gp::sigmoid_loglik_bwd_pk(X, z, grow, ga, rows, src, P, T, frame, nX, GP_ST);
+  return gp::sigmoid_loglik_bwd_pk({.X = X, .z = z, .rows = rows, .inner = 0, .nX = nX}, {.index = src, .P = P, .T = T, .frame = frame}, grow, ga,
+                                   GP_ST);
+}
+// The ELBO in one launch.  The latent KL term arrives as the encoder's heads (hs, hv: gpode_elbo_all_fwd, _bwd, _bwd_ll[_len]) or as values
+// computed upstream (kls, klv: the *_kl exports); gp::ElboKl holds either (`heads` says which the export requires).
+static int elbo_fwd_any(const char* who, bool heads, const float* lpart, int nl_rows, int nl_values, const gp::ElboShape& s, const gp::ElboKl& kl,
+                        float* out, void* stream) {
+  if (!lpart || !(heads ? kl.hs : kl.kls) || !s.Um || !s.Us || !out || (kl.nkv > 0 && !kl.klv)) return gp::set_error("%s: null pointer", who);
+  if (nl_rows < 1 || nl_values < nl_rows || s.N < 1 || s.q < 1 || s.M < 1 || s.Do < 1 || (!heads && kl.nks < 1) || kl.nkv < 0)
+    return gp::set_error("%s: bad sizes", who);
+  return gp::elbo_all_fwd(lpart, nl_rows, nl_values, s, kl, out, GP_ST);
 }
 int gpode_elbo_all_fwd(const float* lpart, int nl_rows, int nl_values, const float* hs, const float* hv, int N, int q, int M, int Do,
                        const float* Um, const float* Us, float nobs, float* out, void* stream) {
-  if (!lpart || !hs || !Um || !Us || !out) return gp::set_error("gpode_elbo_all_fwd: null pointer");
-  if (nl_rows < 1 || nl_values < nl_rows || N < 1 || q < 1 || M < 1 || Do < 1) return gp::set_error("gpode_elbo_all_fwd: bad sizes");
-  return gp::elbo_all_fwd(lpart, nl_rows, nl_values, hs, hv, N, q, M, Do, Um, Us, nobs, out, GP_ST);
+  return elbo_fwd_any("gpode_elbo_all_fwd", true, lpart, nl_rows, nl_values, {.N = N, .q = q, .M = M, .Do = Do, .Um = Um, .Us = Us, .nobs = nobs},
+                      {.hs = hs, .hv = hv}, out, stream);
+}
+int gpode_elbo_all_fwd_kl(const float* lpart, int nl_rows, int nl_values, const float* kls, int nks, const float* klv, int nkv, int N, int M,
+                          int Do, const float* Um, const float* Us, float nobs, float* out, void* stream) {
+  return elbo_fwd_any("gpode_elbo_all_fwd_kl", false, lpart, nl_rows, nl_values, {.N = N, .q = 1, .M = M, .Do = Do, .Um = Um, .Us = Us, .nobs = nobs},
+                      {.kls = kls, .klv = klv, .nks = nks, .nkv = nkv}, out, stream);
 }
 int gpode_elbo_all_bwd(const float* g_loss, const float* g_nll, const float* g_kl, const float* g_klu, int nl_rows, const float* hs,
                        const float* hv, int N, int q, int M, int Do, const float* Um, const float* Us, float nobs, float* glrow, float* ghs,
                        float* ghv, float* dUm, float* dUs, void* stream) {
   if (!hs || !Um || !Us || !glrow || !ghs || !dUm || !dUs || (hv && !ghv)) return gp::set_error("gpode_elbo_all_bwd: null pointer");
   if (nl_rows < 1 || N < 1 || q < 1 || M < 1 || Do < 1) return gp::set_error("gpode_elbo_all_bwd: bad sizes");
-  return gp::elbo_all_bwd(g_loss, g_nll, g_kl, g_klu, nl_rows, hs, hv, N, q, M, Do, Um, Us, nobs, glrow, ghs, ghv, dUm, dUs, GP_ST);
+  return gp::elbo_all_bwd({.g0 = g_loss, .g1 = g_nll, .g2 = g_kl, .g3 = g_klu}, nl_rows,
+                          {.N = N, .q = q, .M = M, .Do = Do, .Um = Um, .Us = Us, .nobs = nobs}, {.hs = hs, .hv = hv, .ghs = ghs, .ghv = ghv},
+                          {.glrow = glrow, .dUm = dUm, .dUs = dUs}, GP_ST);
+}
+// the fused backward, heads (`heads`: hs and ghs required, q >= 1) or values (gkls required, nks >= 1), with or without frame counts
+static int elbo_bwd_ll_any(const char* who, bool heads, bool ragged, const gp::ElboSeeds& g, int nl_rows, const gp::ElboShape& s,
+                           const gp::ElboKl& kl, const gp::ElboGrads& o, const gp::ElboLogits& lg, const gp::FrameMask& m, void* stream) {
+  if (!s.Um || !s.Us || !o.glrow || !o.dUm || !o.dUs || !lg.X || !lg.z || !lg.ga ||
+      (heads ? (!kl.hs || !kl.ghs || (kl.hv && !kl.ghv)) : (!kl.gkls || (kl.nkv > 0 && !kl.gklv))))
+    return gp::set_error("%s: null pointer", who);
+  if (nl_rows < 1 || s.N < 1 || s.q < 1 || s.M < 1 || s.Do < 1 || (!heads && (kl.nks < 1 || kl.nkv < 0)) || lg.n < 1 || lg.nX < 1 ||
+      lg.n % lg.nX != 0)
+    return gp::set_error("%s: bad sizes", who);
+  return gp::elbo_loglik_bwd(who, ragged, g, nl_rows, s, kl, o, lg, m, GP_ST);
 }
 int gpode_elbo_all_bwd_ll(const float* g_loss, const float* g_nll, const float* g_kl, const float* g_klu, int nl_rows, const float* hs,
                           const float* hv, int N, int q, int M, int Do, const float* Um, const float* Us, float nobs, float* glrow, float* ghs,
                           float* ghv, float* dUm, float* dUs, const float* X, const float* z, float* ga, size_t n_logits, size_t nX,
                           void* stream) {
-  if (!hs || !Um || !Us || !glrow || !ghs || !dUm || !dUs || (hv && !ghv) || !X || !z || !ga) return gp::set_error("gpode_elbo_all_bwd_ll: null pointer");
-  if (nl_rows < 1 || N < 1 || q < 1 || M < 1 || Do < 1 || n_logits < 1 || nX < 1 || n_logits % nX != 0) return gp::set_error("gpode_elbo_all_bwd_ll: bad sizes");
-  return gp::elbo_all_bwd_ll(g_loss, g_nll, g_kl, g_klu, nl_rows, hs, hv, N, q, M, Do, Um, Us, nobs, glrow, ghs, ghv, dUm, dUs, X, z, ga, n_logits,
-                             nX, GP_ST);
+  return elbo_bwd_ll_any("gpode_elbo_all_bwd_ll", true, false, {.g0 = g_loss, .g1 = g_nll, .g2 = g_kl, .g3 = g_klu}, nl_rows,
+                         {.N = N, .q = q, .M = M, .Do = Do, .Um = Um, .Us = Us, .nobs = nobs}, {.hs = hs, .hv = hv, .ghs = ghs, .ghv = ghv},
+                         {.glrow = glrow, .dUm = dUm, .dUs = dUs}, {.X = X, .z = z, .ga = ga, .n = n_logits, .nX = nX}, {}, stream);
 }
 int gpode_elbo_all_bwd_ll_len(const float* g_loss, const float* g_nll, const float* g_kl, const float* g_klu, int nl_rows, const float* hs,
                               const float* hv, int N, int q, int M, int Do, const float* Um, const float* Us, float nobs, float* glrow, float* ghs,
                               float* ghv, float* dUm, float* dUs, const float* X, const float* z, float* ga, size_t n_logits, size_t nX,
                               const int* n_obs, int T, size_t frame, void* stream) {
-  if (!hs || !Um || !Us || !glrow || !ghs || !dUm || !dUs || (hv && !ghv) || !X || !z || !ga) return gp::set_error("gpode_elbo_all_bwd_ll_len: null pointer");
-  if (nl_rows < 1 || N < 1 || q < 1 || M < 1 || Do < 1 || n_logits < 1 || nX < 1 || n_logits % nX != 0) return gp::set_error("gpode_elbo_all_bwd_ll_len: bad sizes");
-  return gp::elbo_all_bwd_ll_len(g_loss, g_nll, g_kl, g_klu, nl_rows, hs, hv, N, q, M, Do, Um, Us, nobs, glrow, ghs, ghv, dUm, dUs, X, z, ga,
-                                 n_logits, nX, n_obs, T, frame, GP_ST);
+  return elbo_bwd_ll_any("gpode_elbo_all_bwd_ll_len", true, true, {.g0 = g_loss, .g1 = g_nll, .g2 = g_kl, .g3 = g_klu}, nl_rows,
+                         {.N = N, .q = q, .M = M, .Do = Do, .Um = Um, .Us = Us, .nobs = nobs}, {.hs = hs, .hv = hv, .ghs = ghs, .ghv = ghv},
+                         {.glrow = glrow, .dUm = dUm, .dUs = dUs}, {.X = X, .z = z, .ga = ga, .n = n_logits, .nX = nX},
+                         {.n_obs = n_obs, .T = T, .frame = frame}, stream);
+}
+int gpode_elbo_all_bwd_ll_kl(const float* g_loss, const float* g_nll, const float* g_kl, const float* g_klu, int nl_rows, int N, int M, int Do,
+                             const float* Um, const float* Us, float nobs, float* glrow, float* gkls, int nks, float* gklv, int nkv,
+                             float* dUm, float* dUs, const float* X, const float* z, float* ga, size_t n_logits, size_t nX, void* stream) {
+  return elbo_bwd_ll_any("gpode_elbo_all_bwd_ll_kl", false, false, {.g0 = g_loss, .g1 = g_nll, .g2 = g_kl, .g3 = g_klu}, nl_rows,
+                         {.N = N, .q = 1, .M = M, .Do = Do, .Um = Um, .Us = Us, .nobs = nobs}, {.gkls = gkls, .gklv = gklv, .nks = nks, .nkv = nkv},
+                         {.glrow = glrow, .dUm = dUm, .dUs = dUs}, {.X = X, .z = z, .ga = ga, .n = n_logits, .nX = nX}, {}, stream);
+}
+int gpode_elbo_all_bwd_ll_kl_len(const float* g_loss, const float* g_nll, const float* g_kl, const float* g_klu, int nl_rows, int N, int M,
+                                 int Do, const float* Um, const float* Us, float nobs, float* glrow, float* gkls, int nks, float* gklv, int nkv,
+                                 float* dUm, float* dUs, const float* X, const float* z, float* ga, size_t n_logits, size_t nX,
+                                 const int* n_obs, int T, size_t frame, void* stream) {
+  return elbo_bwd_ll_any("gpode_elbo_all_bwd_ll_kl_len", false, true, {.g0 = g_loss, .g1 = g_nll, .g2 = g_kl, .g3 = g_klu}, nl_rows,
+                         {.N = N, .q = 1, .M = M, .Do = Do, .Um = Um, .Us = Us, .nobs = nobs}, {.gkls = gkls, .gklv = gklv, .nks = nks, .nkv = nkv},
+                         {.glrow = glrow, .dUm = dUm, .dUs = dUs}, {.X = X, .z = z, .ga = ga, .n = n_logits, .nX = nX},
+                         {.n_obs = n_obs, .T = T, .frame = frame}, stream);
 }
 int gpode_elbo_fwd(const float* lhood, int nl, const float* klrow, int nk, const float* kl_u, float nobs, float* out, void* stream) {
   if (!lhood || !klrow || !kl_u || !out || nl < 1 || nk < 1) return gp::set_error("gpode_elbo_fwd: bad argument");

@@ -55,6 +55,9 @@ inline int set_max_lds(const void* kern, size_t bytes) {
   return 0;
 }
 
+// grid of an elementwise kernel with a grid-stride loop: one 256-thread block per 256 elements, at most 8192 of them
+inline int ew_grid(size_t n) { size_t g = (n + 255) / 256; return (int)(g < 8192 ? (g ? g : 1) : 8192); }
+
 // Compute units of the current device: the persistent kernels launch one (or two) workgroup(s) per CU.  Queried once (the first
 // eager run of a step, never inside a capture); clamped to 256 because the split-sum scratch buffers are sized for that.
 inline int num_cus() {
@@ -159,19 +162,20 @@ int cache_build_bwd(int kernel, int Di, int Do, int M, int S, int nd, const floa
                     float* g_raw_ell, float* g_raw_var, float* g_Z, float* g_Um, float* g_Us, int prepared, hipStream_t st);
 int cache_bwd_prepare(int kernel, int Di, int Do, int M, int S, int nd, const float* ws, float* bws, hipStream_t st);
 
-// conv VAE blocks (vae_conv.hip)
-int conv2d_fwd(const float* x, const float* w, const float* bias, float* y, int B, int Ci, int H, int W, int Co, int K, int S,
-               int P, int Ho, int Wo, hipStream_t st, size_t xbs = 0);
+// conv VAE blocks, the loss stage and the evaluation epilogue: one argument struct per operation, as the rollouts above.
+// capi.hip checks the pointers and the sizes and fills the structs by member name; grids, chunks and LDS sizes are computed beside the
+// kernel that is launched.  `who`: the export the error texts start with; `ragged`: the export takes a frame count per sequence.
+// The convolution as the exports describe it, x (B,Ci,H,W) -> y (B,Co,Ho,Wo); the direct kernels' ConvDims is made from it (vae_conv.hip)
+struct ConvGeom { int B, Ci, H, W, Co, K, S, P, Ho, Wo; };
+int conv2d_fwd(const float* x, const float* w, const float* bias, float* y, const ConvGeom& g, hipStream_t st, size_t xbs = 0);
 size_t convT_fwd_stats_scratch(int Co_out);
-int convT_fwd_stats(const float* x, const float* x_bn, const float* w, const float* bias, float* y, int B, int Ci, int H, int W, int Co, int K,
-                    int S, int P, int Ho, int Wo, const float* gamma, const float* beta, float* save_mean, float* save_invstd,
-                    float* running_mean, float* running_var, long long* nbt, float momentum, float eps, float* table, float* scratch,
-                    int slot, hipStream_t st);
-int conv2d_bwd_data(const float* gy, const float* w, const float* bias, float* gx, int B, int Ci, int H, int W, int Co, int K, int S,
-                    int P, int Ho, int Wo, const float* gy_bn, hipStream_t st);
+int convT_fwd_stats(const float* x, const float* x_bn, const float* w, const float* bias, float* y, const ConvGeom& g, const float* gamma,
+                    const float* beta, float* save_mean, float* save_invstd, float* running_mean, float* running_var, long long* nbt,
+                    float momentum, float eps, float* table, float* scratch, int slot, hipStream_t st);
+int conv2d_bwd_data(const float* gy, const float* w, const float* bias, float* gx, const ConvGeom& g, const float* gy_bn, hipStream_t st);
 size_t conv_wgrad_scratch(int B, int Ci, int Co, int K);
-int conv2d_bwd_weight(const float* x, const float* gy, float* gw, float* gbias, float* scratch, int B, int Ci, int H, int W, int Co,
-                      int K, int S, int P, int Ho, int Wo, const float* gy_bn, hipStream_t st, size_t xbs = 0);
+int conv2d_bwd_weight(const float* x, const float* gy, float* gw, float* gbias, float* scratch, const ConvGeom& g, const float* gy_bn,
+                      hipStream_t st, size_t xbs = 0);
 size_t bn_scratch(int B, int C);
 int bn_fwd(const float* x, const float* gamma, const float* beta, float* y, float* save_mean, float* save_invstd,
            float* running_mean, float* running_var, long long* num_batches_tracked, float momentum, float eps, int B, int C, int HW,
@@ -210,11 +214,13 @@ int bn_eval(const float* x, const float* gy, const float* gamma, const float* be
             float eps, float* out, int B, int C, int HW, int relu, hipStream_t st);
 int bn_eval_table(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps, float* table, int C,
                   hipStream_t st);
-// decnn.10 of a frozen decoder fused with the predictive statistics over the draws (vae_conv_tiled.hip)
-int dec10_predict(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th, int T_obs,
-                  int done, float* pred_mean, float* pred_m2, float* se_state, hipStream_t st);
-int dec10_predict_ll(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th, int T_obs,
-                     int done, float* pred_mean, float* pred_m2, float* se_state, float* ell, int L_total, hipStream_t st);
+// decnn.10 of a frozen decoder fused with the predictive statistics over the draws (vae_conv_tiled.hip): c (Lc,F,16,32,32), X (F/Th,T_obs,
+// 28,28); ell (L_total,F) with ll, n_obs (F/Th) when ragged -- k_fwd_predict<ll, ragged>
+struct PredictArgs {
+  const float* c; const float* table; const float* w; const float* bias; const float* X; int Lc, F, Th, T_obs, done;
+  float* pred_mean; float* pred_m2; float* se_state; float* ell; int L_total; const int* n_obs;
+};
+int dec10_predict(const char* who, bool ll, bool ragged, const PredictArgs& a, hipStream_t st);
 int chan_sum(const float* v, float* out, int B, int C, int HW, float* scratch, hipStream_t st);
 int act_fwd(const float* x, float* y, size_t n, int mode, hipStream_t st);
 int act_bwd(const float* y, const float* gy, float* gx, size_t n, int mode, hipStream_t st);
@@ -225,74 +231,61 @@ int linear_relu_fwd(const float* x, const float* w, const float* bias, float* y,
 int linear_relu_bwd(const float* x, const float* w, const float* gy, float* gx, float* gw, float* gb, int B, int In, int Out, hipStream_t st);
 int loglik_fwd(const float* X, const float* z, float* ll, size_t n, size_t nX, hipStream_t st);
 int loglik_bwd(const float* X, const float* z, const float* g, float* gz, size_t n, size_t nX, hipStream_t st);
-int loglik_rowsum_fwd(const float* X, const float* z, float* out, size_t rows, size_t inner, size_t nX, hipStream_t st);
-int loglik_rowsum_bwd(const float* X, const float* z, const float* grow, float* gz, size_t rows, size_t inner, size_t nX, hipStream_t st);
-int elbo_all_bwd_ll(const float* g0, const float* g1, const float* g2, const float* g3, int nl_rows, const float* hs, const float* hv, int N,
-                    int q, int M, int Do, const float* Um, const float* Us, float nobs, float* glrow, float* ghs, float* ghv, float* dUm,
-                    float* dUs, const float* X, const float* z, float* ga, size_t n, size_t nX, hipStream_t st);
+// Ragged minibatches: sequence n owns the frames t < n_obs[n] of its T padded ones, `frame` elements each.  A null n_obs means every
+// frame: what the kernels' <false> instantiations get.  An export that takes counts (`ragged`) refuses a null one.
+struct FrameMask { const int* n_obs = nullptr; int T = 0; size_t frame = 0; };
+// `rows` rows (draw, sequence) of `inner` elements; the targets X (nX elements) repeat over the draws.  z: the probabilities an operation
+// reads (the sigmoid forward writes them and takes them with its outputs)
+struct LogLikRows { const float* X; const float* z; size_t rows, inner, nX; };
+int loglik_rowsum_fwd(const char* who, bool ragged, const LogLikRows& r, const FrameMask& m, float* out, hipStream_t st);
+int loglik_rowsum_bwd(const char* who, bool ragged, const LogLikRows& r, const FrameMask& m, const float* grow, float* gz, hipStream_t st);
+int sigmoid_loglik_splits(size_t rows, size_t inner);
+int sigmoid_loglik_fwd(const char* who, bool ragged, const LogLikRows& r, const FrameMask& m, const float* a, float* z, float* part,
+                       int nsplit, hipStream_t st);
+int sigmoid_loglik_bwd(const char* who, bool ragged, const LogLikRows& r, const FrameMask& m, const float* grow, float* ga, hipStream_t st);
+// ragged minibatches with the padding taken out in front of the decoder: the frame gather and the likelihood over compact logits.
+// index: off (exclusive prefix sum of the clamped counts, N + 1 entries, P = off[N]) for the forward, src (src[j] = n T + t of compact
+// image j, P entries) for the backward, which alone reads P; r.inner is not read (a row has off[n + 1] - off[n] frames)
+struct PackedFrames { const int* index; int P, T; size_t frame; };
+int gather_frames_fwd(const float* zt, int ld, int q, const int* src, int L, int N, int T, int P, float* out, hipStream_t st);
+int gather_frames_bwd(const float* gout, int ld, int q, const int* off, int L, int N, int T, int P, float* gzt, hipStream_t st);
+int sigmoid_loglik_fwd_pk(const LogLikRows& r, const PackedFrames& pk, const float* a, float* z, float* part, int nsplit, hipStream_t st);
+int sigmoid_loglik_bwd_pk(const LogLikRows& r, const PackedFrames& pk, const float* grow, float* ga, hipStream_t st);
 int reparam_kl_fwd(const float* mu, const float* logvar, int ld, const float* eps, float* z, float* klpart, int N, int q, hipStream_t st);
 int reparam_kl_bwd(const float* gz, const float* gklpart, const float* mu, const float* logvar, int ld, const float* eps, float* gmu,
                    float* glogvar, int ldg, int N, int q, hipStream_t st);
-int elbo_all_fwd_kl(const float* lpart, int nl_rows, int nl_values, const float* kls, int nks, const float* klv, int nkv, int N, int M, int Do,
-                    const float* Um, const float* Us, float nobs, float* out, hipStream_t st);
-int elbo_all_bwd_ll_kl(const float* g0, const float* g1, const float* g2, const float* g3, int nl_rows, int N, int M, int Do, const float* Um,
-                       const float* Us, float nobs, float* glrow, float* gkls, int nks, float* gklv, int nkv, float* dUm, float* dUs,
-                       const float* X, const float* z, float* ga, size_t n, size_t nX, hipStream_t st);
 int reparam_fwd(const float* mu, const float* logvar, int ld, const float* eps, float* z, int N, int q, hipStream_t st);
 int reparam_draws_fwd(const float* mu, const float* logvar, int ld, const float* eps, float* z, int ldz, float* lw, int accumulate, int L, int N,
                       int q, hipStream_t st);
 int reparam_draws_bwd(const float* gz, int ldgz, const float* glw, const float* mu, const float* logvar, int ld, const float* eps, float* gmu,
                       float* glogvar, int ldg, int K, int N, int q, hipStream_t st);
-// the importance-weighted bound over K initial-state draws per sequence (vae_conv.hip)
-int elbo_iw_fwd(const float* lpart, int rows, int nsplit, const float* lw, int L, int K, int N, int M, int Do, const float* Um,
-                const float* Us, float nobs, float* out, hipStream_t st);
-int elbo_iw_bwd(const float* g0, const float* g1, const float* g2, const float* g3, const float* g4, const float* lpart, int rows, int nsplit,
-                const float* lw, int L, int K, int N, int M, int Do, const float* Um, const float* Us, float nobs, float* grow, float* glw,
-                float* dUm, float* dUs, hipStream_t st);
-int elbo_iw_bwd_ll(const float* g0, const float* g1, const float* g2, const float* g3, const float* g4, const float* lpart, int rows, int nsplit,
-                   const float* lw, int L, int K, int N, int M, int Do, const float* Um, const float* Us, float nobs, float* grow, float* glw,
-                   float* dUm, float* dUs, const float* X, const float* z, float* ga, size_t n, size_t nX, hipStream_t st);
+// The ELBO assembled in one launch and its backward (vae_loss.hip).  N sequences, q latent dimensions, the inducing posterior Um (M,Do) /
+// Us (packed factors), nobs = the data-set size the likelihood is scaled to
+struct ElboShape { int N, q, M, Do; const float* Um; const float* Us; float nobs; };
+// the upstream gradients of the four outputs (loss, nll, kl, kl_u); a null one counts as zero
+struct ElboSeeds { const float* g0; const float* g1; const float* g2; const float* g3; };
+// The latent KL term comes in one of two forms.  heads: the encoder's mean / log-variance hs, hv (N,q) and their gradients (hs set).
+// values: KL partials computed upstream, kls (nks) and klv (nkv), and their gradients (hs null; q is not read).
+struct ElboKl {
+  const float* hs = nullptr; const float* hv = nullptr; float* ghs = nullptr; float* ghv = nullptr;
+  const float* kls = nullptr; const float* klv = nullptr; float* gkls = nullptr; float* gklv = nullptr; int nks = 0, nkv = 0;
+};
+struct ElboGrads { float* glrow; float* dUm; float* dUs; };   // the likelihood's row gradients (nl_rows) and the inducing posterior's
+// the decoder's logits for the fused backward: ga (n) = d loss / d logits from the probabilities z and the targets X (nX, repeating)
+struct ElboLogits { const float* X; const float* z; float* ga; size_t n, nX; };
+int elbo_all_fwd(const float* lpart, int nl_rows, int nl_values, const ElboShape& s, const ElboKl& kl, float* out, hipStream_t st);
+int elbo_all_bwd(const ElboSeeds& g, int nl_rows, const ElboShape& s, const ElboKl& kl, const ElboGrads& o, hipStream_t st);
+int elbo_loglik_bwd(const char* who, bool ragged, const ElboSeeds& g, int nl_rows, const ElboShape& s, const ElboKl& kl, const ElboGrads& o,
+                    const ElboLogits& lg, const FrameMask& m, hipStream_t st);
+// the importance-weighted bound over K initial-state draws per sequence: lpart (rows, nsplit) likelihood partials, lw (L,K,N) log-weights
+struct IwDraws { const float* lpart; int rows, nsplit; const float* lw; int L, K; };
+int elbo_iw_fwd(const IwDraws& iw, const ElboShape& s, float* out, hipStream_t st);
+// o.glrow: the rows' gradients; ll: the likelihood's backward over the logits in the same launch (lg is not read without it)
+int elbo_iw_bwd(const char* who, bool ll, const ElboSeeds& g, const IwDraws& iw, const ElboShape& s, const ElboGrads& o, float* glw,
+                const ElboLogits& lg, hipStream_t st);
 int reparam_bwd(const float* gz, const float* logvar, int ld, const float* eps, float* gmu, float* glogvar, int ldg, int N, int q, hipStream_t st);
 int normal_kl_fwd(const float* mu, const float* logvar, int ld, float* klrow, int N, int q, hipStream_t st);
 int normal_kl_bwd(const float* grow, const float* mu, const float* logvar, int ld, float* gmu, float* glogvar, int ldg, int N, int q, hipStream_t st);
-int sigmoid_loglik_splits(size_t rows, size_t inner);
-int sigmoid_loglik_fwd(const float* X, const float* a, float* z, float* part, size_t rows, size_t inner, size_t nX, int nsplit, hipStream_t st);
-int sigmoid_loglik_bwd(const float* X, const float* z, const float* grow, float* ga, size_t rows, size_t inner, size_t nX, hipStream_t st);
-int elbo_all_fwd(const float* lpart, int nl_rows, int nl_values, const float* hs, const float* hv, int N, int q, int M, int Do,
-                 const float* Um, const float* Us, float nobs, float* out, hipStream_t st);
-int elbo_all_bwd(const float* g0, const float* g1, const float* g2, const float* g3, int nl_rows, const float* hs, const float* hv, int N,
-                 int q, int M, int Do, const float* Um, const float* Us, float nobs, float* glrow, float* ghs, float* ghv, float* dUm,
-                 float* dUs, hipStream_t st);
-// ragged minibatches: the twins above with a frame count per sequence (n_obs[n], frame t observed iff t < n_obs[n]); vae_conv.hip
-int sigmoid_loglik_fwd_len(const float* X, const float* a, float* z, float* part, size_t rows, size_t inner, size_t nX, int nsplit,
-                           const int* n_obs, int T, size_t frame, hipStream_t st);
-int sigmoid_loglik_bwd_len(const float* X, const float* z, const float* grow, float* ga, size_t rows, size_t inner, size_t nX,
-                           const int* n_obs, int T, size_t frame, hipStream_t st);
-int loglik_rowsum_fwd_len(const float* X, const float* z, float* out, size_t rows, size_t inner, size_t nX, const int* n_obs, int T,
-                          size_t frame, hipStream_t st);
-int loglik_rowsum_bwd_len(const float* X, const float* z, const float* grow, float* gz, size_t rows, size_t inner, size_t nX,
-                          const int* n_obs, int T, size_t frame, hipStream_t st);
-int elbo_all_bwd_ll_len(const float* g0, const float* g1, const float* g2, const float* g3, int nl_rows, const float* hs, const float* hv, int N,
-                        int q, int M, int Do, const float* Um, const float* Us, float nobs, float* glrow, float* ghs, float* ghv, float* dUm,
-                        float* dUs, const float* X, const float* z, float* ga, size_t n, size_t nX, const int* n_obs, int T, size_t frame,
-                        hipStream_t st);
-int elbo_all_bwd_ll_kl_len(const float* g0, const float* g1, const float* g2, const float* g3, int nl_rows, int N, int M, int Do, const float* Um,
-                           const float* Us, float nobs, float* glrow, float* gkls, int nks, float* gklv, int nkv, float* dUm, float* dUs,
-                           const float* X, const float* z, float* ga, size_t n, size_t nX, const int* n_obs, int T, size_t frame,
-                           hipStream_t st);
-// ragged minibatches with the padding taken out in front of the decoder: the frame gather and the loss stage over compact logits
-// (off: exclusive prefix sum of the clamped counts, N + 1 entries; src[j] = n T + t of compact image j; P = off[N]); vae_conv.hip
-int gather_frames_fwd(const float* zt, int ld, int q, const int* src, int L, int N, int T, int P, float* out, hipStream_t st);
-int gather_frames_bwd(const float* gout, int ld, int q, const int* off, int L, int N, int T, int P, float* gzt, hipStream_t st);
-int sigmoid_loglik_fwd_pk(const float* X, const float* a, float* z, float* part, size_t rows, const int* off, int T, size_t frame, size_t nX,
-                          int nsplit, hipStream_t st);
-int sigmoid_loglik_bwd_pk(const float* X, const float* z, const float* grow, float* ga, size_t rows, const int* src, int P, int T, size_t frame,
-                          size_t nX, hipStream_t st);
-int dec10_predict_len(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th, int T_obs,
-                      int done, float* pred_mean, float* pred_m2, float* se_state, const int* n_obs, hipStream_t st);
-int dec10_predict_ll_len(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th, int T_obs,
-                         int done, float* pred_mean, float* pred_m2, float* se_state, float* ell, int L_total, const int* n_obs,
-                         hipStream_t st);
 int elbo_fwd(const float* lhood, int nl, const float* klrow, int nk, const float* kl_u, float nobs, float* out, hipStream_t st);
 int elbo_bwd(const float* gout, int nl, int nk, float nobs, float* glhood, float* gklrow, float* gklu, hipStream_t st);
 int gather_multi(const float* const* grads, const long long* offs, int ntensors, long long total, float* flat, hipStream_t st);

@@ -363,9 +363,9 @@ __global__ void k_sum_splits_t(const float* __restrict__ part, int nsplit, size_
 // A request the VALU kernels cannot serve (a fused BatchNorm input, output statistics) is refused with an error, never served
 // without the table.
 // ---------------------------------------------------------------------------------------------
-template <class L> static bool matches(int Ci_conv, int Co_conv, int H, int Ho, int K, int S, int P) {
-  // conv geometry of the adjoint: "input" (B, Ci_conv = L::CO, H = L::HO), "output" (B, Co_conv = L::CI, Ho = L::HI)
-  return Ci_conv == L::CO && Co_conv == L::CI && H == L::HO && Ho == L::HI && K == L::K && S == L::S && P == L::P;
+template <class L> static bool matches(const ConvGeom& g) {
+  // conv geometry of the adjoint: "input" (B, g.Ci = L::CO, g.H = L::HO), "output" (B, g.Co = L::CI, g.Ho = L::HI)
+  return g.Ci == L::CO && g.Co == L::CI && g.H == L::HO && g.Ho == L::HI && g.K == L::K && g.S == L::S && g.P == L::P;
 }
 
 static bool use_mfma() {
@@ -478,21 +478,22 @@ static bool conv_v1() {
 }
 
 // ConvTranspose2d forward (called with the conv geometry of its adjoint, as conv2d_bwd_data is)
-int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx, int B, int Ci, int H, int W, int Co, int K, int S,
-                   int P, int Ho, int Wo, const float* in_bn, hipStream_t st, const BnSink* sink) {
-  if (H != W || Ho != Wo) return -1;
+int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx, const ConvGeom& g, const float* in_bn, hipStream_t st,
+                   const BnSink* sink) {
+  if (g.H != g.W || g.Ho != g.Wo) return -1;
+  const int B = g.B;
   // (whether the matrix-core path is open is each arm's test below: its refusal names that reason)
-  if (sink && !(matches<Dec7>(Ci, Co, H, Ho, K, S, P) || matches<Dec4>(Ci, Co, H, Ho, K, S, P) ||
-                (matches<Dec1>(Ci, Co, H, Ho, K, S, P) && !in_bn)))
+  if (sink && !(matches<Dec7>(g) || matches<Dec4>(g) ||
+                (matches<Dec1>(g) && !in_bn)))
     return set_error("gpode_convT_fwd_stats: no specialisation for this geometry");
   const bool mfma = use_mfma() && aligned16(gy, w, gx, in_bn);
-  if (matches<Dec7>(Ci, Co, H, Ho, K, S, P)) {
+  if (matches<Dec7>(g)) {
     // second engine at every batch size: with in_bn + sink 46.0 vs 48.4 us on the first engine at 512 images (configs[0], two images per
     // CU), 42.5 vs 46.3 us at 256, 242 vs 254 us at 4096; with in_bn alone 36.5 vs 43.7, 22.0 vs 40.9, 199 vs 241 us -- no batch threshold
     if (mfma && !conv_v1()) return conv_v2_dec7_fwd(gy, w, bias, gx, B, in_bn, sink, st);
     return launch_T1<Dec7, 3, 2, 16>(gy, w, bias, gx, B, st, in_bn, sink);
   }
-  if (matches<Dec4>(Ci, Co, H, Ho, K, S, P)) {
+  if (matches<Dec4>(g)) {
     // taps-as-columns form (conv_dec4_mfma.hpp): 48.5 vs 59.7 us for the stage at 512 images (no weight slabs to stage before the first
     // image), 276 vs 267 us at 4096 -- so it takes the small batches (configs[0]: 512 images); GPODE_DEC4_TAPCOLS=0 / 1 forces one
     static const int tapcols = [] { const char* e = getenv("GPODE_DEC4_TAPCOLS"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
@@ -510,7 +511,7 @@ int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx
     }
     return launch_T1<Dec4, 3, 2, 16>(gy, w, bias, gx, B, st, in_bn, sink);
   }
-  if (matches<Dec1>(Ci, Co, H, Ho, K, S, P)) {
+  if (matches<Dec1>(g)) {
     if (!in_bn && mfma) {    // conv_dec1_mfma.hpp: taps folded into the GEMM's columns, weights resident in registers
       const size_t lds = sizeof(float) * 2 * dec1::NPI * dec1::TLD;
       if (set_max_lds((const void*)dec1::k_fwd<false>, lds) || set_max_lds((const void*)dec1::k_fwd<true>, lds)) return 1;
@@ -522,7 +523,7 @@ int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx
     if (sink) return set_error("convT forward with output statistics needs the matrix-core path (16-byte aligned operands, GPODE_CONV_VALU unset)");
     return launch_T1<Dec1, 8, 8, 64>(gy, w, bias, gx, B, st, in_bn);   // dec1::k_fwd takes no in_bn: the first engine does
   }
-  if (matches<Enc3>(Ci, Co, H, Ho, K, S, P) && !in_bn && B >= 96) {
+  if (matches<Enc3>(g) && !in_bn && B >= 96) {
     // d/d input of the encoder's cnn.3 (16 -> 8 channels: no matrix-core tile shape) from 96 images on: the LDS-tiled vector kernel, two
     // images per workgroup -- the direct kernel re-reads every gradient value from L2 for each of its taps (256 images: 38 us direct,
     // 24.5 us tiled with four images per workgroup; 32 images: 21 us direct, 27 us tiled -- 8 workgroups)
@@ -534,13 +535,13 @@ int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx
     hipLaunchKernelGGL(kern, (B + IPB - 1) / IPB, 256, lds, st, gy, w, bias, gx, B);
     return check_launch("enc_conv3_bwd_data_tiled");
   }
-  if (matches<Enc6>(Ci, Co, H, Ho, K, S, P) && mfma) {   // d/d input of the encoder's cnn.6
+  if (matches<Enc6>(g) && mfma) {   // d/d input of the encoder's cnn.6
     // 8 images per group fill the chip from 2048 images on; a minibatch of 256 made 32 workgroups (73 us on an eighth of the CUs):
     // 2 images per group below half a wave of groups
     if (B < 4 * num_cus()) return launch_igemm<FwdPolicy<Enc6, 16>, 2, 4, 1>(gy, w, bias, gx, B, st, "enc_conv6_bwd_data_mfma", in_bn);
     return launch_igemm<FwdPolicy<Enc6, 16>, 8, 4, 1>(gy, w, bias, gx, B, st, "enc_conv6_bwd_data_mfma", in_bn);
   }
-  if (matches<Dec10>(Ci, Co, H, Ho, K, S, P)) {
+  if (matches<Dec10>(g)) {
     if (mfma) {
       const size_t ldsm = sizeof(float) * dec10::KK * dec10::PST;
       if (set_max_lds((const void*)dec10::k_fwd<true>, ldsm) || set_max_lds((const void*)dec10::k_fwd<false>, ldsm)) return 1;
@@ -561,29 +562,29 @@ int tiled_bwd_data(const float* gy, const float* w, const float* bias, float* gx
 }
 
 // ConvTranspose2d d/d input (conv geometry: x := grad_output (B,Ci,H,W) -> y (B,Co,Ho,Wo)), no bias
-int tiled_fwd(const float* x, const float* w, const float* bias, float* y, int B, int Ci, int H, int W, int Co, int K, int S, int P,
-              int Ho, int Wo, hipStream_t st) {
-  if (H != W || Ho != Wo) return -1;
+int tiled_fwd(const float* x, const float* w, const float* bias, float* y, const ConvGeom& g, hipStream_t st) {
+  if (g.H != g.W || g.Ho != g.Wo) return -1;
+  const int B = g.B;
   const bool mfma = use_mfma() && aligned16(x, w, y);
   if (mfma) {   // encoder Conv2d layers (with their bias)
-    if (matches<Enc3>(Ci, Co, H, Ho, K, S, P)) return launch_igemm<BwdDataPolicy<Enc3, 16>, 4, 4, 1>(x, w, bias, y, B, st, "enc_conv3_fwd_mfma");
-    if (matches<Enc6>(Ci, Co, H, Ho, K, S, P)) return launch_igemm<BwdDataPolicy<Enc6, 32>, 8, 1, 2>(x, w, bias, y, B, st, "enc_conv6_fwd_mfma");
+    if (matches<Enc3>(g)) return launch_igemm<BwdDataPolicy<Enc3, 16>, 4, 4, 1>(x, w, bias, y, B, st, "enc_conv3_fwd_mfma");
+    if (matches<Enc6>(g)) return launch_igemm<BwdDataPolicy<Enc6, 32>, 8, 1, 2>(x, w, bias, y, B, st, "enc_conv6_fwd_mfma");
   }
   if (bias) return -1;
-  if (matches<Dec7>(Ci, Co, H, Ho, K, S, P)) {
+  if (matches<Dec7>(g)) {
     if (mfma && !conv_v1()) return conv_v2_dec7_bwd_data(x, w, y, B, st);
     // first engine: one image and 16 input channels per pass, two pixel tiles per job, two 256-thread workgroups per CU
     if (mfma) return launch_igemm<BwdDataPolicy<Dec7, 16>, 1, 2, 1, false, 256>(x, w, nullptr, y, B, st, "convT_bwd_data_mfma");
     return launch_T2<Dec7, 2, 8>(x, w, y, B, st);
   }
-  if (matches<Dec4>(Ci, Co, H, Ho, K, S, P)) {
+  if (matches<Dec4>(g)) {
     if (mfma && !conv_v1()) return conv_v2_dec4_bwd_data(x, w, y, B, st);
     // first engine: 36 output pixels per image; two images and two 16-channel halves per pass make 10 equal jobs for 8 wavefronts
     // (tools/convt_probe.hip: 28 % of wavefront 0's cycles in the group barrier)
     if (mfma) return launch_igemm<BwdDataPolicy<Dec4, 32>, 2, 1, 1>(x, w, nullptr, y, B, st, "convT_bwd_data_mfma");
     return launch_T2<Dec4, 3, 8>(x, w, y, B, st);
   }
-  if (matches<Dec1>(Ci, Co, H, Ho, K, S, P)) {
+  if (matches<Dec1>(g)) {
     if (mfma) {
       const size_t lds = sizeof(float) * (2 * dec1::GYF + 4 * dec1::NPI * 33);
       const int cap = 2 * num_cus();
@@ -592,7 +593,7 @@ int tiled_fwd(const float* x, const float* w, const float* bias, float* y, int B
     }
     return launch_T2<Dec1, 8, 32>(x, w, y, B, st);
   }
-  if (matches<Dec10>(Ci, Co, H, Ho, K, S, P)) {
+  if (matches<Dec10>(g)) {
     if (mfma) {
       constexpr int IPB = 8;
       const size_t ldsm = sizeof(float) * IPB * dec10::PLANE;
@@ -607,71 +608,31 @@ int tiled_fwd(const float* x, const float* w, const float* bias, float* y, int B
 
 // decnn.10 on a frozen decoder fused with the predictive statistics over the draws (conv_dec10_mfma.hpp, k_fwd_predict): one workgroup
 // per frame, at most one per CU; the frame's draws are folded in order, so the grid size does not enter the result.
-int dec10_predict(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th, int T_obs,
-                  int done, float* pred_mean, float* pred_m2, float* se_state, hipStream_t st) {
-  if (!use_mfma()) return set_error("gpode_dec10_predict: matrix-core kernel only (GPODE_CONV_VALU is set)");
-  if (Lc < 1 || F < 1 || Th < 1 || T_obs < 1 || T_obs > Th || F % Th != 0 || done < 0)
-    return set_error("gpode_dec10_predict: need Lc, F >= 1, 1 <= T_obs <= Th, F a multiple of Th, done >= 0");
-  if ((pred_mean == nullptr) != (pred_m2 == nullptr)) return set_error("gpode_dec10_predict: pred_mean and pred_m2 go together");
-  if (!aligned16(table)) return set_error("gpode_dec10_predict: the table must be 16-byte aligned");
-  const size_t lds = sizeof(float) * (dec10::KK * dec10::PST + 16);
-  if (set_max_lds((const void*)dec10::k_fwd_predict<false>, lds)) return 1;
-  hipLaunchKernelGGL(dec10::k_fwd_predict<false>, F < num_cus() ? F : num_cus(), 512, lds, st, c, w, bias, table, X, Lc, F, Th, T_obs, done,
-                     pred_mean, pred_m2, se_state, (float*)nullptr);
-  return check_launch("dec10_predict");
+// ll: it also leaves the log-likelihood of every (draw, frame) image in ell[L_total][F] (k_fwd_predict<true>): rows done .. done + Lc - 1
+// are written, every entry once.  ragged: a frame count per sequence, n_obs[F / Th] (k_fwd_predict<ll, true>).  Nothing is launched and
+// nothing written when an argument is refused.
+template <bool LL, bool RAGGED>
+static int launch_predict(const char* tag, const PredictArgs& a, hipStream_t st) {
+  const size_t lds = sizeof(float) * (dec10::KK * dec10::PST + (LL ? 24 : 16));
+  if (set_max_lds((const void*)dec10::k_fwd_predict<LL, RAGGED>, lds)) return 1;
+  const int nwg = a.F < num_cus() ? a.F : num_cus();
+  hipLaunchKernelGGL((dec10::k_fwd_predict<LL, RAGGED>), nwg, 512, lds, st, a.c, a.w, a.bias, a.table, a.X, a.Lc, a.F, a.Th, a.T_obs, a.done,
+                     a.pred_mean, a.pred_m2, a.se_state, LL ? a.ell : nullptr, RAGGED ? a.n_obs : nullptr);
+  return check_launch(tag);
 }
-
-// the same stage, which also leaves the log-likelihood of every (draw, frame) image in ell[L_total][F] (k_fwd_predict<true>): rows
-// done .. done + Lc - 1 are written, every entry once.  Nothing is launched and nothing written when an argument is refused.
-int dec10_predict_ll(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th, int T_obs,
-                     int done, float* pred_mean, float* pred_m2, float* se_state, float* ell, int L_total, hipStream_t st) {
-  if (!use_mfma()) return set_error("gpode_dec10_predict_ll: matrix-core kernel only (GPODE_CONV_VALU is set)");
-  if (Lc < 1 || F < 1 || Th < 1 || T_obs < 1 || T_obs > Th || F % Th != 0 || done < 0)
-    return set_error("gpode_dec10_predict_ll: need Lc, F >= 1, 1 <= T_obs <= Th, F a multiple of Th, done >= 0");
-  if ((pred_mean == nullptr) != (pred_m2 == nullptr)) return set_error("gpode_dec10_predict_ll: pred_mean and pred_m2 go together");
-  if (!aligned16(table)) return set_error("gpode_dec10_predict_ll: the table must be 16-byte aligned");
-  if (ell == nullptr) return set_error("gpode_dec10_predict_ll: ell is NULL");
-  if (L_total < 1 || Lc > L_total || done > L_total - Lc)
-    return set_error("gpode_dec10_predict_ll: ell has L_total rows, need done + Lc <= L_total");
-  const size_t lds = sizeof(float) * (dec10::KK * dec10::PST + 24);
-  if (set_max_lds((const void*)dec10::k_fwd_predict<true>, lds)) return 1;
-  hipLaunchKernelGGL(dec10::k_fwd_predict<true>, F < num_cus() ? F : num_cus(), 512, lds, st, c, w, bias, table, X, Lc, F, Th, T_obs, done,
-                     pred_mean, pred_m2, se_state, ell);
-  return check_launch("dec10_predict_ll");
-}
-
-// ragged sequences: the two launchers above with a frame count per sequence, n_obs[N] (k_fwd_predict<LL, true>); same refusals
-int dec10_predict_len(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th, int T_obs,
-                      int done, float* pred_mean, float* pred_m2, float* se_state, const int* n_obs, hipStream_t st) {
-  if (!use_mfma()) return set_error("gpode_dec10_predict_len: matrix-core kernel only (GPODE_CONV_VALU is set)");
-  if (Lc < 1 || F < 1 || Th < 1 || T_obs < 1 || T_obs > Th || F % Th != 0 || done < 0)
-    return set_error("gpode_dec10_predict_len: need Lc, F >= 1, 1 <= T_obs <= Th, F a multiple of Th, done >= 0");
-  if ((pred_mean == nullptr) != (pred_m2 == nullptr)) return set_error("gpode_dec10_predict_len: pred_mean and pred_m2 go together");
-  if (!aligned16(table)) return set_error("gpode_dec10_predict_len: the table must be 16-byte aligned");
-  if (n_obs == nullptr) return set_error("gpode_dec10_predict_len: n_obs is NULL");
-  const size_t lds = sizeof(float) * (dec10::KK * dec10::PST + 16);
-  if (set_max_lds((const void*)dec10::k_fwd_predict<false, true>, lds)) return 1;
-  hipLaunchKernelGGL((dec10::k_fwd_predict<false, true>), F < num_cus() ? F : num_cus(), 512, lds, st, c, w, bias, table, X, Lc, F, Th, T_obs, done,
-                     pred_mean, pred_m2, se_state, (float*)nullptr, n_obs);
-  return check_launch("dec10_predict_len");
-}
-int dec10_predict_ll_len(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th, int T_obs,
-                         int done, float* pred_mean, float* pred_m2, float* se_state, float* ell, int L_total, const int* n_obs,
-                         hipStream_t st) {
-  if (!use_mfma()) return set_error("gpode_dec10_predict_ll_len: matrix-core kernel only (GPODE_CONV_VALU is set)");
-  if (Lc < 1 || F < 1 || Th < 1 || T_obs < 1 || T_obs > Th || F % Th != 0 || done < 0)
-    return set_error("gpode_dec10_predict_ll_len: need Lc, F >= 1, 1 <= T_obs <= Th, F a multiple of Th, done >= 0");
-  if ((pred_mean == nullptr) != (pred_m2 == nullptr)) return set_error("gpode_dec10_predict_ll_len: pred_mean and pred_m2 go together");
-  if (!aligned16(table)) return set_error("gpode_dec10_predict_ll_len: the table must be 16-byte aligned");
-  if (ell == nullptr) return set_error("gpode_dec10_predict_ll_len: ell is NULL");
-  if (L_total < 1 || Lc > L_total || done > L_total - Lc)
-    return set_error("gpode_dec10_predict_ll_len: ell has L_total rows, need done + Lc <= L_total");
-  if (n_obs == nullptr) return set_error("gpode_dec10_predict_ll_len: n_obs is NULL");
-  const size_t lds = sizeof(float) * (dec10::KK * dec10::PST + 24);
-  if (set_max_lds((const void*)dec10::k_fwd_predict<true, true>, lds)) return 1;
-  hipLaunchKernelGGL((dec10::k_fwd_predict<true, true>), F < num_cus() ? F : num_cus(), 512, lds, st, c, w, bias, table, X, Lc, F, Th, T_obs, done,
-                     pred_mean, pred_m2, se_state, ell, n_obs);
-  return check_launch("dec10_predict_ll_len");
+int dec10_predict(const char* who, bool ll, bool ragged, const PredictArgs& a, hipStream_t st) {
+  if (!use_mfma()) return set_error("%s: matrix-core kernel only (GPODE_CONV_VALU is set)", who);
+  if (a.Lc < 1 || a.F < 1 || a.Th < 1 || a.T_obs < 1 || a.T_obs > a.Th || a.F % a.Th != 0 || a.done < 0)
+    return set_error("%s: need Lc, F >= 1, 1 <= T_obs <= Th, F a multiple of Th, done >= 0", who);
+  if ((a.pred_mean == nullptr) != (a.pred_m2 == nullptr)) return set_error("%s: pred_mean and pred_m2 go together", who);
+  if (!aligned16(a.table)) return set_error("%s: the table must be 16-byte aligned", who);
+  if (ll) {
+    if (a.ell == nullptr) return set_error("%s: ell is NULL", who);
+    if (a.L_total < 1 || a.Lc > a.L_total || a.done > a.L_total - a.Lc) return set_error("%s: ell has L_total rows, need done + Lc <= L_total", who);
+  }
+  if (ragged && a.n_obs == nullptr) return set_error("%s: n_obs is NULL", who);
+  if (ll) return ragged ? launch_predict<true, true>("dec10_predict_ll_len", a, st) : launch_predict<true, false>("dec10_predict_ll", a, st);
+  return ragged ? launch_predict<false, true>("dec10_predict_len", a, st) : launch_predict<false, false>("dec10_predict", a, st);
 }
 
 // decnn.10's input gradient fused with the backward of the BatchNorm + ReLU in front of it (conv_dec10_mfma.hpp, k_bwd_data_bn).
@@ -754,19 +715,19 @@ int wgrad_v2_dec7(const float* x, const float* gy, float* gw, float* scratch, in
 int wgrad_v2_dec4(const float* x, const float* gy, float* gw, float* scratch, int B, hipStream_t st, const float* in_bn);
 
 // ConvTranspose2d d/d weight (conv geometry: x := grad_output, gy := the layer's input)
-int tiled_bwd_weight(const float* x, const float* gy, float* gw, float* scratch, int B, int Ci, int H, int W, int Co, int K, int S,
-                     int P, int Ho, int Wo, const float* in_bn, hipStream_t st) {
-  if (H != W || Ho != Wo) return -1;
+int tiled_bwd_weight(const float* x, const float* gy, float* gw, float* scratch, const ConvGeom& g, const float* in_bn, hipStream_t st) {
+  if (g.H != g.W || g.Ho != g.Wo) return -1;
+  const int B = g.B;
   const bool mfma = use_mfma() && aligned16(x, gy, in_bn);
-  if (matches<Dec7>(Ci, Co, H, Ho, K, S, P)) {
+  if (matches<Dec7>(g)) {
     if (mfma) return wgrad_v2_dec7(gy, x, gw, scratch, B, st, in_bn);
     return launch_T3<Dec7, 16>(gy, x, gw, scratch, B, st, in_bn);
   }
-  if (matches<Dec4>(Ci, Co, H, Ho, K, S, P)) {
+  if (matches<Dec4>(g)) {
     if (mfma) return wgrad_v2_dec4(gy, x, gw, scratch, B, st, in_bn);
     return launch_T3<Dec4, 16>(gy, x, gw, scratch, B, st, in_bn);
   }
-  if (matches<Dec1>(Ci, Co, H, Ho, K, S, P)) {
+  if (matches<Dec1>(g)) {
     if (!in_bn && mfma) {   // conv_dec1_mfma.hpp
       const size_t lds = sizeof(float) * 2 * dec1::GYF;
       // partial slabs: 256 costs 33.8 + 7.8 us (kernel + reduction of the partials) at 4096 images; 512: 33.1 + 10.8; 128: 56 + 6
@@ -779,9 +740,9 @@ int tiled_bwd_weight(const float* x, const float* gy, float* gw, float* scratch,
     if (mfma) return launch_wgrad_mfma<Dec1, 2, 4, 1>(gy, x, gw, scratch, B, st, in_bn);   // dec1::k_wgrad takes no in_bn: the first engine does
     return launch_T3<Dec1, 32>(gy, x, gw, scratch, B, st, in_bn);
   }
-  if (matches<Enc6>(Ci, Co, H, Ho, K, S, P) && mfma)
+  if (matches<Enc6>(g) && mfma)
     return launch_wgrad_mfma<Enc6, 2, 1, 4>(gy, x, gw, scratch, B, st, in_bn);   // d/d weight of the encoder's cnn.6
-  if (matches<Dec10>(Ci, Co, H, Ho, K, S, P) && mfma) {
+  if (matches<Dec10>(g) && mfma) {
     constexpr int IPB = 1;
     const size_t fl = (size_t)IPB * dec10::PLANE > 8 * 16 * 32 ? (size_t)IPB * dec10::PLANE : 8 * 16 * 32;
     const int ngroups = (B + IPB - 1) / IPB;
@@ -790,7 +751,7 @@ int tiled_bwd_weight(const float* x, const float* gy, float* gw, float* scratch,
     if (reduce_job(RedJob{scratch, gw, nwg, 400, 0, 0, 0, 0}, st)) return 1;
     return check_launch("dec10_wgrad_mfma");
   }
-  if (matches<Dec10>(Ci, Co, H, Ho, K, S, P)) {
+  if (matches<Dec10>(g)) {
     if (in_bn) return set_error("convT weight gradient with a fused BatchNorm input needs the matrix-core path (16-byte aligned operands, GPODE_CONV_VALU unset)");
     int nsplit = B < 256 ? B : 256;
     const int bps = (B + nsplit - 1) / nsplit;
