@@ -254,6 +254,27 @@ int gpode_rollout_bwd_pgrad_ns(int kernel, int order, int method, int Di, int Do
                                const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
                                float* gz0, float* astage, float* slab, int nchunk, float* gpack, int ts_per_traj, int substeps,
                                void* stream);
+/* Forward mode (tangent-linear): J_f(x) v of the sampled field, and the state-transition matrix Phi_t = d z_t / d z0 of the fixed-grid
+ * rollout applied to K directions -- the exact derivative of the discrete step map gpode_rollout_fwd computes (the transpose of what
+ * gpode_rollout_bwd applies).  One wavefront per (row, direction); records streamed from L2 (tags rhs_jvp_{rbf,df}_stream,
+ * rollout_jvp_{rbf,df}_stream).  Shapes, L = ndraws:
+ *   x  (R,Di), or (L,R,Di) with x_per_draw = 1        v  (R,K,Di) / (L,R,K,Di), the leading layout of x
+ *   f  (L,R,Do), may be NULL                           jv (L,R,K,Do),   jv[l,r,k,:] = J_f(x[r]) v[r,k,:]
+ *   z0 (N,Di), or (L,N,Di) with z0_per_draw = 1       v0 (N,K,Di) / (L,N,K,Di), the leading layout of z0
+ *   zt (L,N,T,Di), may be NULL                         vt (L,N,T,K,Di), vt[l,n,t,k,:] = Phi_t v0[n,k,:], vt[.,.,0] = v0
+ *   ts (T,), or (N,T) with ts_per_traj = 1;  substeps 1 ... 64 equal steps per output interval
+ * v / v0 NULL: the identity directions; needs K == Di, and then Phi_t[i,k] = vt[...,t,k,i].  mode as gpode_rhs_fwd (0 full, 1 prior,
+ * 2 update).  Refused before anything is launched, with nothing written and the reason in gpode_last_error(): a NULL pack, x, z0,
+ * jv, vt or ts; K outside 1 ... 64, or K != Di with NULL directions; N, R or T < 1; substeps outside 1 ... 64; Di != order * Do; a
+ * width that is not compiled; mode outside 0 ... 2; a method other than euler, midpoint or rk4 -- dopri5's steps depend on the
+ * state through the controller, and the tangent of the accepted-step sequence is not built. */
+int gpode_rhs_jvp(int kernel, int Di, int Do, int M, int S, int ndraws, const float* pack,
+                  const float* x, int x_per_draw, const float* v, int R, int K,
+                  float* f, float* jv, int mode, void* stream);
+int gpode_rollout_jvp(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws, const float* pack,
+                      const float* z0, int z0_per_draw, const float* v0, int K,
+                      const float* ts, int ts_per_traj, int substeps, int N, int T,
+                      float* zt, float* vt, void* stream);
 /* gpode_rollout_bwd_n and gpode_param_grad_n in ONE pass: the reverse sweep visits every (stage input, adjoint) row anyway, so the
  * rows' parameter-gradient terms are accumulated on the way and come out as gpack (ndraws, pack_floats) -- what the two calls
  * produce together, with one launch and one pass over the rows less.  slab: ndraws * nchunk * pack_floats floats of scratch with

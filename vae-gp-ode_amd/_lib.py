@@ -42,6 +42,9 @@ SIGNATURES = {
     'gpode_rollout_fwd': (_i, [_i] * 7 + [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     'gpode_rollout_bwd': (_i, [_i] * 7 + [_vp] * 4 + [_i, _i, _vp, _vp, _vp]),
     'gpode_rhs_vjp': (_i, [_i] * 5 + [_vp, _vp, _vp, _i, _vp, _vp]),
+    # forward mode: J_f(x) v and the state-transition matrix of the fixed-grid rollout applied to K directions
+    'gpode_rhs_jvp': (_i, [_i] * 6 + [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),
+    'gpode_rollout_jvp': (_i, [_i] * 8 + [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'gpode_param_grad': (_i, [_i] * 5 + [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp]),
     # Monte-Carlo draws batched into one call (a leading draw axis on every per-draw operand; `ndraws` follows S)
     'gpode_cache_sizes_n': (_i, [_i] * 6 + [_sz_p, _sz_p]),

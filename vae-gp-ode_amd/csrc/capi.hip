@@ -203,6 +203,55 @@ int gpode_rollout_fwd(int kernel, int order, int method, int Di, int Do, int M, 
   return gpode_rollout_fwd_n(kernel, order, method, Di, Do, M, S, 1, pack, z0, ts, N, T, zt, xstage, stream);
 }
 
+// Forward mode (gp_tangent.hip).  What the two share: the number of directions, and the widths -- checked here, so that every
+// refusal comes before the first HIP call.
+static int tangents_refused(const char* who, int kernel, int Di, int Do, int K, bool identity, long long rows) {
+  if (identity && K != Di) return gp::set_error("%s: NULL directions are the identity and need K == Di (K=%d Di=%d)", who, K, Di);
+  if (!gp::dims_supported(kernel, Di, Do)) return gp::set_error("%s: no specialisation for kernel=%d Di=%d Do=%d", who, kernel, Di, Do);
+  if (rows * K > 0x7fffffffLL) return gp::set_error("%s: %lld rows x %d directions do not fit one launch", who, rows, K);
+  return 0;
+}
+static int tangent_count_refused(const char* who, int K) {
+  if (K >= 1 && K <= gp::kMaxTangents) return 0;
+  return gp::set_error("%s: K=%d (1 ... %d tangent directions per row)", who, K, gp::kMaxTangents);
+}
+
+int gpode_rhs_jvp(int kernel, int Di, int Do, int M, int S, int ndraws, const float* pack,
+                  const float* x, int x_per_draw, const float* v, int R, int K,
+                  float* f, float* jv, int mode, void* stream) {
+  static const char* const who = "gpode_rhs_jvp";
+  if (mode < 0 || mode > 2) return gp::set_error("%s: mode=%d (0 full, 1 prior, 2 update)", who, mode);
+  if (x_per_draw != 0 && x_per_draw != 1) return gp::set_error("%s: x_per_draw=%d (0 shared, 1 one (R,Di) slab per draw)", who, x_per_draw);
+  if (R < 1 || !draws_ok(ndraws)) return gp::set_error("%s: R=%d draws=%d", who, R, ndraws);
+  if (tangent_count_refused(who, K)) return 1;
+  if (!pack || !x || !jv) return gp::set_error("%s: null pointer", who);
+  if (tangents_refused(who, kernel, Di, Do, K, v == nullptr, R)) return 1;
+  const gp::RhsJvpArgs a{.M = M, .S = S, .pack = pack, .x = x, .v = v, .R = R, .K = K, .f = f, .jv = jv, .mode = mode,
+                         .x_per_draw = x_per_draw != 0};
+  return gp::rhs_jvp(kernel, Di, Do, a, ndraws, (hipStream_t)stream);
+}
+
+int gpode_rollout_jvp(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws, const float* pack,
+                      const float* z0, int z0_per_draw, const float* v0, int K,
+                      const float* ts, int ts_per_traj, int substeps, int N, int T,
+                      float* zt, float* vt, void* stream) {
+  static const char* const who = "gpode_rollout_jvp";
+  if (method == GPODE_METHOD_DOPRI5)
+    return gp::set_error("%s: method 3 (dopri5): its steps depend on the state through the controller, and the tangent of the "
+                         "accepted-step sequence is not built (0 euler, 1 rk4, 2 midpoint)", who);
+  if (method < 0 || method > 2) return gp::set_error("%s: method %d (0 euler, 1 rk4, 2 midpoint)", who, method);
+  if (z0_flag_refused(who, z0_per_draw) || ts_flag_refused(who, ts_per_traj) || substeps_refused(who, substeps)) return 1;
+  if (N < 1 || T < 1 || !draws_ok(ndraws)) return gp::set_error("%s: N=%d T=%d draws=%d", who, N, T, ndraws);
+  if (tangent_count_refused(who, K)) return 1;
+  if (!pack || !z0 || !ts || !vt) return gp::set_error("%s: null pointer", who);
+  if (tangents_refused(who, kernel, Di, Do, K, v0 == nullptr, N)) return 1;
+  if (Di != order * Do || (order != 1 && order != 2))
+    return gp::set_error("%s: order=%d needs Di == order*Do (Di=%d Do=%d)", who, order, Di, Do);
+  const gp::RolloutJvpArgs a{.M = M, .S = S, .pack = pack, .z0 = z0, .v0 = v0, .K = K, .ts = ts, .N = N, .T = T, .zt = zt, .vt = vt,
+                             .z0_per_draw = z0_per_draw != 0, .ts_per_traj = ts_per_traj != 0, .substeps = substeps};
+  return gp::rollout_jvp(kernel, order, method, Di, Do, a, ndraws, (hipStream_t)stream);
+}
+
 int gpode_rollout_bwd_nt(int kernel, int order, int method, int Di, int Do, int M, int S, int ndraws,
                          const float* pack, const float* xstage, const float* gzt, const float* ts, int N, int T,
                          float* gz0, float* astage, int ts_per_traj, void* stream) {

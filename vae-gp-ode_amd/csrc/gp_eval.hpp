@@ -382,4 +382,126 @@ __device__ __forceinline__ void df_ind_half_bwd(const float4 (&r)[DfLayout<D>::R
   }
 }
 
+// ==============================================================================================
+// Forward-mode (tangent-linear) building blocks: the transposes of the blocks above.  `v` is the (wave-uniform) tangent of x; acc
+// accumulates the record's contribution to f exactly as the forward blocks do, jacc its contribution to J_f(x) v.  The two share t,
+// sin, cos, E and the exponent.
+// ==============================================================================================
+template <int DI, int DO>
+__device__ __forceinline__ void rbf_rff_jvp(const float4 (&r)[RbfLayout<DI, DO>::RQ], const float (&x)[DI], const float (&v)[DI],
+                                            float& acc, float& jacc) {
+  float f[4 * RbfLayout<DI, DO>::RQ];
+  unpack(r, f);
+  float t = f[DI], tv = 0.f;
+#pragma unroll
+  for (int i = 0; i < DI; ++i) { t = fmaf(x[i], f[i], t); tv = fmaf(v[i], f[i], tv); }
+  t = __builtin_amdgcn_fractf(t);
+  const float c = __builtin_amdgcn_cosf(t), sn = __builtin_amdgcn_sinf(t);
+  acc = fmaf(f[DI + 1], c, acc);
+  jacc = fmaf(f[DI + 1] * (-GP_2PI) * sn, tv, jacc);   // d/dt cos(2 pi t) = -2 pi sin(2 pi t), dt = om . v
+}
+
+template <int DI, int DO>
+__device__ __forceinline__ void rbf_ind_jvp(const float4 (&r)[RbfLayout<DI, DO>::RQ2], const float (&x)[DI], const float (&v)[DI],
+                                            const float* __restrict__ wl, float (&acc)[DO], float (&jacc)[DO]) {
+  float f[4 * RbfLayout<DI, DO>::RQ2];
+  unpack(r, f);
+  float t2[DI], dt2[DI];
+#pragma unroll
+  for (int i = 0; i < DI; ++i) { const float d = x[i] - f[i]; t2[i] = d * d; dt2[i] = 2.f * d * v[i]; }
+#pragma unroll
+  for (int d = 0; d < DO; ++d) {
+    float e = 0.f, de = 0.f;
+#pragma unroll
+    for (int i = 0; i < DI; ++i) { e = fmaf(wl[d * DI + i], t2[i], e); de = fmaf(wl[d * DI + i], dt2[i], de); }
+    const float E = exp2_fast(e);
+    acc[d] = fmaf(f[DI + d], E, acc[d]);
+    jacc[d] = fmaf(f[DI + d] * E, GP_LN2 * de, jacc[d]);   // d 2^e = 2^e ln 2 de
+  }
+}
+
+template <int D>
+__device__ __forceinline__ void df_rff_jvp(const float4 (&r)[DfLayout<D>::RQ], const float (&x)[D], const float (&v)[D],
+                                           float (&acc)[D], float (&jacc)[D]) {
+  float f[4 * DfLayout<D>::RQ];
+  unpack(r, f);
+  float t = f[D], tv = 0.f;
+#pragma unroll
+  for (int k = 0; k < D; ++k) { t = fmaf(x[k], f[k], t); tv = fmaf(v[k], f[k], tv); }
+  t = __builtin_amdgcn_fractf(t);
+  const float c = __builtin_amdgcn_cosf(t), sn = __builtin_amdgcn_sinf(t);
+  const float rr = fmaf(f[D + 2], sn, f[D + 1] * c);
+  const float drr = GP_2PI * fmaf(f[D + 2], c, -f[D + 1] * sn) * tv;   // d rr / d t (df_rff_bwd's rt) times dt = om . v
+#pragma unroll
+  for (int j = 0; j < D; ++j) { acc[j] = fmaf(rr, f[D + 3 + j], acc[j]); jacc[j] = fmaf(drr, f[D + 3 + j], jacc[j]); }
+}
+
+// DF inducing record: T_ab = var_b nu_a E_ab il_ab term_ab with term = dl_a dl_b il + delta_ab((D-1) - r2 il), E = 2^(r2 wab).
+// With d(dl_a) = v_a and d r2 = 2 dl . v:  dterm = (v_a dl_b + dl_a v_b) il - delta_ab dr2 il,  dE = E ln2 wab dr2 -- the forward
+// reading of df_ind_half_bwd (its gd / gdb are the first part, its gr2 the rest).
+template <int D>
+__device__ __forceinline__ void df_ind_jvp(const float4 (&r)[DfLayout<D>::RQ2], const float (&x)[D], const float (&v)[D],
+                                           const float* __restrict__ uni, float (&acc)[D], float (&jacc)[D]) {
+  float f[4 * DfLayout<D>::RQ2];
+  unpack(r, f);
+  const float* wab = uni;
+  const float* il2 = uni + D * D;
+  const float* var = uni + 2 * D * D;
+  float dl[D];
+  float r2 = 0.f, dr2 = 0.f;
+#pragma unroll
+  for (int a = 0; a < D; ++a) { dl[a] = x[a] - f[a]; r2 = fmaf(dl[a], dl[a], r2); dr2 = fmaf(dl[a], v[a], dr2); }
+  dr2 *= 2.f;
+  if constexpr (D > 8) {
+    // wide fields: the output columns in two sequential halves (a loop that is not unrolled), so that the scheduler interleaves the
+    // D * D / 2 exponential chains of one half only; `half` is wave-uniform and every register index a compile-time constant
+    // (selects, as in df_ind_record_half)
+    constexpr int DH = (D + 1) / 2;
+#pragma unroll 1
+    for (int half = 0; half < 2; ++half) {
+#pragma unroll
+      for (int bb = 0; bb < DH; ++bb) {
+        const bool valid = DH + bb < D;
+        const int bidx = half * DH + bb < D ? half * DH + bb : D - 1;
+        const float dlb = half ? (valid ? dl[valid ? DH + bb : 0] : 0.f) : dl[bb];
+        const float vb = half ? (valid ? v[valid ? DH + bb : 0] : 0.f) : v[bb];
+        float sb = 0.f, dsb = 0.f;
+#pragma unroll
+        for (int a = 0; a < D; ++a) {
+          const float il = il2[a * D + bidx], wv = wab[a * D + bidx];
+          const float E = exp2_fast(r2 * wv);
+          const bool diag = (a == bidx);
+          const float term = dl[a] * dlb * il + (diag ? ((float)(D - 1) - r2 * il) : 0.f);
+          const float dterm = fmaf(v[a], dlb, dl[a] * vb) * il - (diag ? dr2 * il : 0.f);
+          const float cf = f[D + a] * (E * il);
+          sb = fmaf(cf, term, sb);
+          dsb = fmaf(cf, fmaf(term, GP_LN2 * wv * dr2, dterm), dsb);
+        }
+        const float r_ = (half && !valid) ? 0.f : var[bidx] * sb, dr_ = (half && !valid) ? 0.f : var[bidx] * dsb;
+        acc[bb] += half ? 0.f : r_;
+        jacc[bb] += half ? 0.f : dr_;
+        if (valid) { acc[valid ? DH + bb : 0] += half ? r_ : 0.f; jacc[valid ? DH + bb : 0] += half ? dr_ : 0.f; }
+      }
+    }
+    return;
+  }
+#pragma unroll
+  for (int b = 0; b < D; ++b) {
+    float sb = 0.f, dsb = 0.f;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+      const float il = il2[a * D + b], wv = wab[a * D + b];
+      const float E = exp2_fast(r2 * wv);
+      float term = dl[a] * dl[b] * il;
+      float dterm = fmaf(v[a], dl[b], dl[a] * v[b]) * il;
+      if (a == b) { term += (float)(D - 1) - r2 * il; dterm -= dr2 * il; }
+      const float cf = f[D + a] * (E * il);
+      sb = fmaf(cf, term, sb);
+      dsb = fmaf(cf, fmaf(term, GP_LN2 * wv * dr2, dterm), dsb);
+    }
+    acc[b] = fmaf(var[b], sb, acc[b]);
+    jacc[b] = fmaf(var[b], dsb, jacc[b]);
+  }
+}
+
 }  // namespace gp

@@ -110,7 +110,22 @@ struct AdaptBwdArgs {
   int N, T, K; float* gz0; float* astage;
 };
 
+// The tangent-linear (forward-mode) operations (gp_tangent.hip): K tangent columns per row, one wavefront per (row, column).
+// x ([L,] R,Di) (x_per_draw), v ([L,] R,K,Di) with the leading layout of x, null: the identity directions (K == Di);
+// f (L,R,Do), may be null; jv (L,R,K,Do)
+static const int kMaxTangents = 64;
+struct RhsJvpArgs {
+  int M, S; const float* pack; const float* x; const float* v; int R, K; float* f; float* jv; int mode; bool x_per_draw;
+};
+// z0 ([L,] N,Di), v0 ([L,] N,K,Di) with the leading layout of z0, null: the identity; zt (L,N,T,Di), may be null; vt (L,N,T,K,Di)
+struct RolloutJvpArgs {
+  int M, S; const float* pack; const float* z0; const float* v0; int K; const float* ts; int N, T;
+  float* zt; float* vt; bool z0_per_draw, ts_per_traj; int substeps;
+};
+
 // entry points implemented across the .hip files
+int rhs_jvp(int kernel, int Di, int Do, const RhsJvpArgs& a, int nd, hipStream_t st);
+int rollout_jvp(int kernel, int order, int method, int Di, int Do, const RolloutJvpArgs& a, int nd, hipStream_t st);
 int dims_supported(int kernel, int Di, int Do);
 // the row operations take their Draws as it is:
 //   rhs_fwd: in = x, out = f      rhs_vjp: in = x, in2 = a, out = gx      param_grad: in = xr, in2 = ar, out = gpack

@@ -1,6 +1,7 @@
 // gp_rollout.hpp -- what the persistent rollout kernels share: the wave-mapped evaluators (policy objects), the ODE right-hand side on
 // the state, the state store, and the host-side launch policy (grid shapes, the team / wave threshold, the compiled widths).
-// Used by gp_forward.hip (fixed-grid solvers), gp_adaptive.hip (Dormand-Prince) and gp_backward.hip (reverse sweep).
+// Used by gp_forward.hip (fixed-grid solvers), gp_adaptive.hip (Dormand-Prince), gp_backward.hip (reverse sweep) and gp_tangent.hip
+// (forward mode: the jvp members of the streamed evaluators).
 #pragma once
 #include "gp_eval.hpp"
 #include "gp_team.hpp"
@@ -85,6 +86,32 @@ template <int DI, int DO> struct RbfStreamEval {
     }
     wave_sum_all<DO>(acc, f);
   }
+  // f(x) and J_f(x) v in every lane: the records are read once for both, and one reduction carries the 2 DO partials (gp_tangent.hip)
+  template <int MODE> __device__ __forceinline__ void jvp(const float (&x)[DI], const float (&v)[DI], float (&f)[DO], float (&jv)[DO]) const {
+    float acc[DO], jacc[DO];
+#pragma unroll
+    for (int d = 0; d < DO; ++d) acc[d] = jacc[d] = 0.f;
+    if (MODE != 2) {
+      for (int j = 0; j < SJ; ++j) {
+#pragma unroll
+        for (int d = 0; d < DO; ++d) {
+          float4 r[L::RQ];
+#pragma unroll
+          for (int q = 0; q < L::RQ; ++q) r[q] = rff4[((j * DO + d) * L::RQ + q) * 64 + lane];
+          rbf_rff_jvp<DI, DO>(r, x, v, acc[d], jacc[d]);
+        }
+      }
+    }
+    if (MODE != 1) {
+      for (int j = 0; j < MJ; ++j) {
+        float4 r[L::RQ2];
+#pragma unroll
+        for (int q = 0; q < L::RQ2; ++q) r[q] = ind4[(j * L::RQ2 + q) * 64 + lane];
+        rbf_ind_jvp<DI, DO>(r, x, v, wl, acc, jacc);
+      }
+    }
+    wave_sum_pair<DO>(acc, jacc, f, jv);
+  }
 };
 
 extern __shared__ __attribute__((aligned(16))) float4 gp_smem4[];
@@ -129,6 +156,32 @@ template <int D, bool USE_LDS> struct DfEval {
       }
     }
     wave_sum_all<D>(acc, f);
+  }
+  // f(x) and J_f(x) v in every lane, as RbfStreamEval::jvp
+  template <int MODE> __device__ __forceinline__ void jvp(const float (&x)[D], const float (&v)[D], float (&f)[D], float (&jv)[D]) const {
+    float acc[D], jacc[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) acc[d] = jacc[d] = 0.f;
+    if (MODE != 2) {
+      for (int j = 0; j < SJ; ++j) {
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+          float4 r[L::RQ];
+#pragma unroll
+          for (int q = 0; q < L::RQ; ++q) r[q] = ld(((j * D + i) * L::RQ + q) * 64 + lane);
+          df_rff_jvp<D>(r, x, v, acc, jacc);
+        }
+      }
+    }
+    if (MODE != 1) {
+      for (int j = 0; j < MJ; ++j) {
+        float4 r[L::RQ2];
+#pragma unroll
+        for (int q = 0; q < L::RQ2; ++q) r[q] = ld(ind_off + (j * L::RQ2 + q) * 64 + lane);
+        df_ind_jvp<D>(r, x, v, uni, acc, jacc);
+      }
+    }
+    wave_sum_pair<D>(acc, jacc, f, jv);
   }
 };
 

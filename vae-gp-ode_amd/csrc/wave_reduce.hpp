@@ -89,4 +89,14 @@ template <int NV> __device__ __forceinline__ void wave_sum_all(const float (&v)[
   }
 }
 
+// two sets of NV values in ONE reduction over the 2 NV partials (the tangent evaluators: f and J v)
+template <int NV> __device__ __forceinline__ void wave_sum_pair(const float (&a)[NV], const float (&b)[NV], float (&oa)[NV], float (&ob)[NV]) {
+  float w[2 * NV], o[2 * NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) { w[i] = a[i]; w[NV + i] = b[i]; }
+  wave_sum_all<2 * NV>(w, o);
+#pragma unroll
+  for (int i = 0; i < NV; ++i) { oa[i] = o[i]; ob[i] = o[NV + i]; }
+}
+
 }  // namespace gp

@@ -35,8 +35,13 @@ sequence keeps K of its frames (drawn per sequence, reproducibly from ``--seed``
 with a z0 sample per draw and reports ``iw_nll``, ``nlpd_marginal``, ``ess_mean``, ``ess_min``; every other figure is unchanged.
 ``--eval_field True`` then evaluates the posterior of the vector field itself (``field_posterior``: mean and marginal variances of
 q(f(z)), either kernel) at the encoder means of the initial states of the test split, writes ``field_z.npy``, ``field_mean.npy``,
-``field_var.npy`` and adds ``field_points``, ``field_var_mean``, ``field_var_max``; without it nothing changes.  Single process: data-parallel
-evaluation is not built.  No plots.
+``field_var.npy`` and adds ``field_points``, ``field_var_mean``, ``field_var_max``; without it nothing changes.
+``--eval_flow True`` (fixed-grid solvers) then linearises the learnt flow about the same initial states (``flow_diagnostics``: the
+state-transition matrices Phi_t = d z_t / d z0 in forward mode, their log-determinants, the finite-time Lyapunov exponent, the
+divergence of the field along the trajectories), for ``--eval_sample_size`` function draws and for the posterior-mean field: writes
+``flow_phi.npy``, ``flow_logdet.npy``, ``flow_div.npy`` and the same three with the suffix ``_mean``, and adds ``flow_logdet_mean``
+(of log |det Phi| at the last time), ``flow_logdet_absmax`` (over all times), ``flow_ftle_mean``, ``flow_ftle_max``, ``flow_div_absmean``, ``flow_div_absmean_meanfield``; without it nothing
+changes.  Single process: data-parallel evaluation is not built.  No plots.
 """
 import argparse
 import json
@@ -389,6 +394,74 @@ def field_posterior(model, z, cov='diag'):
     return model.flow.odefunc.diffeq.posterior(z, cov=cov)
 
 
+def initial_state_moments(model, X):
+    """(mean, variance) of the encoder's q(z0 | X) for the sequences X (N,T,1,28,28), each (N, order*q) in the layout of the state the
+    flow integrates.  No sample is drawn.  Eval mode, no autograd."""
+    with torch.no_grad(), _EvalMode(model):
+        X = X.contiguous().float()
+        mu_s, lv_s = model.vae.encoder(X[:, 0])
+        if model.order == 1:
+            return mu_s, lv_s.exp()
+        mu_v, lv_v = model.vae.encoder_v(X[:, 0:model.v_steps].squeeze(2))
+        return torch.cat([mu_s, mu_v], dim=1), torch.cat([lv_s, lv_v], dim=1).exp()
+
+
+def flow_logdet(Phi):
+    """log |det Phi_t| of state-transition matrices Phi (..., T, D, D): (..., T) float64 on the CPU.  The volume change of the flow
+    about the trajectory; 0 for a volume-preserving one."""
+    return torch.linalg.slogdet(Phi.detach().double().cpu())[1]
+
+
+def flow_ftle(Phi, ts):
+    """The finite-time Lyapunov exponent log sigma_max(Phi_{T-1}) / (t_{T-1} - t_0) of Phi (..., N, T, D, D) over the grid ts (T,) or
+    (N,T): (..., N) float64 on the CPU."""
+    ts = ts.detach().double().cpu()
+    smax = torch.linalg.matrix_norm(Phi[..., -1, :, :].detach().double().cpu(), ord=2)
+    return smax.log() / (ts[..., -1] - ts[..., 0])
+
+
+def flow_var_lin(Phi, var0):
+    """diag(Phi_t diag(var0) Phi_t^T): the first-order propagation of a diagonal initial covariance var0 (N,D) along Phi
+    (..., N, T, D, D) -> (..., N, T, D) float64 on the CPU."""
+    P = Phi.detach().double().cpu()
+    return (P * P * var0.detach().double().cpu()[:, None, None, :]).sum(-1)
+
+
+def flow_diagnostics(model, X, L=1, ts=None, mean_field=False):
+    """The learnt flow linearised about the trajectories that start at the encoder means of the initial states of X (N,T,1,28,28), as
+    ``field_posterior`` starts there: L function draws from the model's noise stream, or -- ``mean_field`` -- the single draw
+    ``mean_noise()`` under which the field is its posterior mean (the leading axis is then 1).  ``ts``: (T,) or (N,T) output times,
+    None = the uniform grid dt * arange(T).  Fixed-grid solvers only (``Flow.sensitivity``).  Returns a dict of
+      zt (L,N,T,D), Phi (L,N,T,D,D)       the trajectories and d z_t / d z0 (float32, on the device)
+      logdet (L,N,T)                      flow_logdet(Phi)
+      ftle (L,N)                          flow_ftle(Phi, ts)
+      div (L,N,T)                         the divergence of the field at zt (the phase-space divergence for order 2)
+      z_var_lin (L,N,T,D)                 flow_var_lin(Phi, the encoder's variance)
+    the reductions in float64 on the host."""
+    flow = model.flow
+    gp = flow.odefunc.diffeq
+    z0, var0 = initial_state_moments(model, X)
+    if ts is None:
+        ts = model.dt * torch.arange(X.shape[1], dtype=torch.float32, device=z0.device)
+    ts = ts.to(device=z0.device, dtype=torch.float32).contiguous()
+    N, D = z0.shape
+
+    def one(cache):
+        zt, Phi = flow.sensitivity(z0, ts, cache=cache)
+        x = zt.reshape((cache.nd, -1, D) if cache.stacked else (-1, D)).contiguous()
+        div = gp.divergence(x).reshape(zt.shape[:-1])
+        return (zt, Phi, div) if cache.stacked else (zt.unsqueeze(0), Phi.unsqueeze(0), div.unsqueeze(0))
+    with torch.no_grad(), _EvalMode(model):
+        if mean_field:
+            parts = [one(gp.build_cache(noise=gp.mean_noise()))]
+        elif int(L) > 1 and gp.batched_draws_supported():
+            parts = [one(gp.build_cache(draws=int(L)))]
+        else:
+            parts = [one(gp.build_cache()) for _ in range(int(L))]
+    zt, Phi, div = (torch.cat([p[i] for p in parts]) for i in range(3))
+    return dict(zt=zt, Phi=Phi, logdet=flow_logdet(Phi), ftle=flow_ftle(Phi, ts), div=div.double().cpu(), z_var_lin=flow_var_lin(Phi, var0))
+
+
 def build_from_checkpoint(args):
     """(model, test loader, checkpoint file) for a parsed command line, the way ``vae_gp_ode_amd.main`` sets a run up: seed, data,
     model, kernel initialisation, then the checkpoint ``--model_path`` (the .pth file, or the results directory that holds
@@ -427,7 +500,17 @@ def make_parser():
                    help='also evaluate the posterior of the vector field at the encoder means of the initial states of the test split: '
                         'field_z.npy, field_mean.npy, field_var.npy (marginal variances) and field_points, field_var_mean, field_var_max '
                         '(default: False)')
+    p.add_argument('--eval_flow', type=eval, default=argparse.SUPPRESS,
+                   help='also linearise the learnt flow about the encoder means of the initial states of the test split (euler, midpoint, '
+                        'rk4): flow_phi.npy, flow_logdet.npy, flow_div.npy for the sampled draws and for the posterior-mean field (_mean), and '
+                        'flow_logdet_mean, flow_logdet_absmax, flow_ftle_mean, flow_ftle_max, flow_div_absmean, flow_div_absmean_meanfield '
+                        '(default: False)')
     return p
+
+
+def eval_flow(args):
+    """--eval_flow of a parsed command line; False when the switch was not given"""
+    return bool(getattr(args, 'eval_flow', False))
 
 
 def eval_field(args):
@@ -461,6 +544,9 @@ def _subsampled(args, loader):
 def main(argv=None):
     from .main import check_dense_scale, check_ragged, check_subsample
     args = make_parser().parse_args(argv)
+    if eval_flow(args) and args.solver == 'dopri5':  # before any device work: the tangent-linear rollout has fixed grids only
+        from .ops import DOPRI5_TANGENT
+        raise SystemExit('--eval_flow True with --solver dopri5: ' + DOPRI5_TANGENT)
     check_subsample(args)
     check_ragged(args)
     check_dense_scale(args)
@@ -515,6 +601,10 @@ def main(argv=None):
         fz = torch.cat([initial_state_means(model, Xb) for _, Xb, _, _ in _subsampled(args, testset)])
         fm, fv = field_posterior(model, fz)
         field = (fz.cpu().numpy(), fm.cpu().numpy(), fv.cpu().numpy())
+    flowd = None
+    if eval_flow(args):                              # behind everything else: every figure above sees the draws it sees without it
+        Xf = torch.cat([full for full, _, _, _ in _subsampled(args, testset)])     # all frames: the uniform grid dt * arange(T)
+        flowd = (flow_diagnostics(model, Xf, L), flow_diagnostics(model, Xf, mean_field=True))
     torch.cuda.synchronize()
     ms = (time.time() - t0) * 1e3
 
@@ -532,6 +622,15 @@ def main(argv=None):
         out.update(field_points=int(field[0].shape[0]), field_var_mean=float(field[2].mean()), field_var_max=float(field[2].max()))
         for name, arr in zip(('field_z.npy', 'field_mean.npy', 'field_var.npy'), field):
             np.save(os.path.join(args.save, name), arr)
+    if flowd is not None:
+        fs, fm = flowd
+        out.update(flow_logdet_mean=float(fs['logdet'][..., -1].mean()), flow_logdet_absmax=float(fs['logdet'].abs().max()),
+                   flow_ftle_mean=float(fs['ftle'].mean()), flow_ftle_max=float(fs['ftle'].max()),
+                   flow_div_absmean=float(fs['div'].abs().mean()), flow_div_absmean_meanfield=float(fm['div'].abs().mean()))
+        for d, suffix in ((fs, ''), (fm, '_mean')):
+            np.save(os.path.join(args.save, 'flow_phi%s.npy' % suffix), d['Phi'].cpu().numpy())
+            np.save(os.path.join(args.save, 'flow_logdet%s.npy' % suffix), d['logdet'].numpy())
+            np.save(os.path.join(args.save, 'flow_div%s.npy' % suffix), d['div'].numpy())
     np.save(os.path.join(args.save, 'rollout_mean.npy'), roll.mean.cpu().numpy())
     np.save(os.path.join(args.save, 'rollout_var.npy'), roll.var.cpu().numpy())
     with open(os.path.join(args.save, 'eval.json'), 'w') as f:

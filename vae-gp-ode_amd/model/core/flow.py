@@ -143,6 +143,30 @@ class Flow(nn.Module):
         self.odefunc._set_evals(EVALS_PER_STEP[self.solver] * (ts.shape[-1] - 1) * self.substeps)
         return zt
 
+    def sensitivity(self, z0, ts, v0=None, draws=None, cache=None):
+        """(zt, Phi): the trajectories of ``forward`` and their first-order sensitivity to the initial state, in forward mode
+        (ops.rollout_jvp: the exact derivative of the discrete solver, ``substeps`` included; no autograd).  v0 None: Phi
+        ([L,] N,T,D,D) is the state-transition matrix d z_t / d z0, Phi[..., 0, :, :] = I.  v0 ([L,] N,K,D): Phi = vt ([L,] N,T,K,D),
+        row k the image Phi_t v0[k].  A fresh function draw is fixed as ``forward`` fixes it (``draws`` = L: L of them), unless
+        ``cache`` hands one over (``diffeq.cache`` after a build).  'dopri5' is refused: its steps depend on the state."""
+        if self.solver == 'dopri5':
+            raise ValueError(ops.DOPRI5_TANGENT)
+        try:
+            ops.check_solver(self.solver)
+        except ops._lib.GpodeError as e:
+            raise ValueError(str(e)) from None
+        gp = self.odefunc.diffeq
+        pad = getattr(gp, 'width_pad', None)
+        with torch.no_grad():
+            if cache is None and draws is not None and pad is not None:     # a zero-padded width builds its draws one by one
+                per = [self.sensitivity(z0[l] if z0.dim() == 3 else z0, ts, None if v0 is None else (v0[l] if z0.dim() == 3 else v0))
+                       for l in range(draws)]
+                return torch.stack([p[0] for p in per]), torch.stack([p[1] for p in per])
+            if cache is None:
+                cache = gp.build_cache() if draws is None else gp.build_cache(draws=draws)
+            zt, vt = ops.rollout_jvp(cache, z0, ts, self.odefunc.order, self.solver, v0=v0, substeps=self.substeps, pad=pad)
+        return zt, (vt.transpose(-1, -2).contiguous() if v0 is None else vt)
+
     def _take_counts(self, counts):
         self._last_counts = counts
         self.odefunc._set_counts(counts)

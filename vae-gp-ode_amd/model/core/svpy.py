@@ -210,6 +210,27 @@ class SVGP_Layer(torch.nn.Module):
             return ops.rhs(self.cache, pad.state(x).contiguous(), mode=0)[:, :self.D_out]
         return ops.rhs(self.cache, x, mode=0)
 
+    def jacobian(self, x, part='full'):
+        """J_f(x) (N, D_out, D_in) of the cached draw, as ``forward`` evaluates it (forward mode, ops.rhs_jacobian; no autograd).
+        ``part``: 'full', or the 'prior' (random-feature) or 'update' (K(x,Z) nu) term alone."""
+        if self.cache is None:
+            raise RuntimeError('call build_cache() first')
+        if part not in ops.RHS_MODES:
+            raise ValueError("part must be 'full', 'prior' or 'update', got %r" % (part,))
+        with torch.no_grad():
+            x = x.detach().to(self.inducing_loc.optvar.device, torch.float32)
+            return ops.rhs_jacobian(self.cache, x, ops.RHS_MODES[part], pad=self.width_pad)
+
+    def divergence(self, x, part='full'):
+        """tr J_f(x) (N,) for D_in == D_out; for a second-order layer (D_in == 2 D_out, state [s, v], ds/dt = v, dv/dt = f(s, v)) the
+        phase-space divergence sum_i J[i, D_out + i] -- the block ds'/ds contributes no trace."""
+        J = self.jacobian(x, part)
+        if self.D_in == self.D_out:
+            return J.diagonal(dim1=-2, dim2=-1).sum(-1)
+        if self.D_in == 2 * self.D_out:
+            return J[..., self.D_out:].diagonal(dim1=-2, dim2=-1).sum(-1)
+        raise ValueError('divergence needs D_in == D_out or D_in == 2 D_out, got (%d, %d)' % (self.D_in, self.D_out))
+
     def build_conditional(self, x, full_cov=False):
         """q(f(x)) = N(m(x), Sigma(x)) with m = A^T Um, Sigma = K(x,x) + A^T (Us Us^T - I) A, A = L^-1 K(Z,x)
         (svpy.py:176-210): returns (mean (N,D_out), var (N,D_out)) or, with ``full_cov``, var (N,N,D_out).  RBF kernel (the

@@ -598,6 +598,96 @@ def rhs_vjp(cache, x, a):
     return gx
 
 
+# ---------------------------------------------------------------------------------------------
+# Forward mode (csrc/gp_tangent.hip): J_f(x) v, the Jacobian, and the state-transition matrix of the fixed-grid rollout.  Forward
+# only: none of the three records anything for autograd.  ``pad``: the WidthPad of a layer whose cache was built zero-padded
+# (SVGP_Layer.width_pad) -- states and tangents are scattered into the padded width (padded state columns get zero tangents, so
+# they stay zero), and the padded rows and columns of the results are cut off.
+# ---------------------------------------------------------------------------------------------
+MAX_TANGENTS = 64
+RHS_MODES = {'full': 0, 'prior': 1, 'update': 2}
+DOPRI5_TANGENT = ("dopri5 has no tangent-linear rollout: its steps depend on the state through the controller, and the tangent of the "
+                  "accepted-step sequence is not built (use euler, midpoint or rk4, with substeps for accuracy)")
+
+
+def _tangent_dirs(v, lead_shape, D, pad, what):
+    """directions ([L,] R,K,D) -> contiguous, padded; None -> (None, K = D of the compiled width, identity over the real columns)"""
+    if v is None:
+        return None, (pad.Dip if pad is not None else D)
+    v = _chk(v, what)
+    if v.dim() != len(lead_shape) + 2 or tuple(v.shape[:len(lead_shape)]) != tuple(lead_shape) or v.shape[-1] != D:
+        raise _lib.GpodeError('%s: expected %s + (K,%d), got %s' % (what, tuple(lead_shape), D, tuple(v.shape)))
+    K = v.shape[-2]
+    if not 1 <= K <= MAX_TANGENTS:
+        raise _lib.GpodeError('%s: K=%d tangent directions per row (1 ... %d)' % (what, K, MAX_TANGENTS))
+    return (pad.state(v).contiguous() if pad is not None else v), K
+
+
+def rhs_jvp(cache, x, v=None, mode=0, pad=None):
+    """(f, jv): f(x) and J_f(x) v of the cached draw(s).  x (R,Di), or (L,R,Di) with L = the draws of the cache; v ([L,] R,K,Di) with
+    the leading layout of x, None: the identity directions (K = Di, jv[..., k, :] = column k of the Jacobian).  f (R,Do), jv (R,K,Do);
+    a cache of L draws gives (L,R,Do) and (L,R,K,Do).  mode as rhs(): 0 full, 1 prior, 2 update."""
+    x = _chk(x, 'x')
+    D = cache.Di if pad is None else pad.Di
+    xpd = _z0_per_draw(cache, x)
+    if x.shape[-1] != D:
+        raise _lib.GpodeError('x must be ([L,] R,%d), got %s' % (D, tuple(x.shape)))
+    if mode not in (0, 1, 2):
+        raise _lib.GpodeError('mode must be 0 (full), 1 (prior) or 2 (update), got %r' % (mode,))
+    v, K = _tangent_dirs(v, x.shape[:-1], D, pad, 'v')
+    if pad is not None:
+        x = pad.state(x).contiguous()
+    R = x.shape[-2]
+    lead = cache.lead
+    f = torch.empty(lead + (R, cache.Do), dtype=torch.float32, device=x.device)
+    jv = torch.empty(lead + (R, K, cache.Do), dtype=torch.float32, device=x.device)
+    _lib.call('gpode_rhs_jvp', KERNEL_ID[cache.kernel], cache.Di, cache.Do, cache.M, cache.S, cache.nd, _ptr(cache.pack), _ptr(x), xpd,
+              _ptr(v), R, K, _ptr(f), _ptr(jv), mode, _stream())
+    if pad is not None:
+        f, jv = f[..., :pad.Do], jv[..., :pad.Do]
+        if v is None:
+            jv = jv.index_select(jv.dim() - 2, pad.index(jv.device))
+        f, jv = f.contiguous(), jv.contiguous()
+    return f, jv
+
+
+def rhs_jacobian(cache, x, mode=0, pad=None):
+    """J_f(x) ([L,] R,Do,Di) of the cached draw(s): rhs_jvp along the identity directions, transposed."""
+    return rhs_jvp(cache, x, None, mode, pad)[1].transpose(-1, -2).contiguous()
+
+
+def rollout_jvp(cache, z0, ts, order, method, v0=None, substeps=1, pad=None):
+    """(zt, vt): the fixed-grid rollout and its tangent.  z0 (N,D) or (L,N,D), ts (T,) or (N,T), substeps as rollout(); v0
+    ([L,] N,K,D) with the leading layout of z0, None: the identity (K = D).  zt ([L,] N,T,D) as rollout() gives it;
+    vt ([L,] N,T,K,D) with vt[..., t, k, :] = Phi_t v0[..., k, :], Phi_t = d z_t / d z0 of the discrete solver (vt[..., 0, :, :] = v0).
+    euler, midpoint and rk4; dopri5 is refused."""
+    check_solver(method)
+    if method == 'dopri5':
+        raise _lib.GpodeError(DOPRI5_TANGENT)
+    sub = _substeps(substeps, method)
+    if pad is not None:
+        D = pad.Di
+        if _chk(z0, 'z0').shape[-1] != D:
+            raise _lib.GpodeError('state dim %d must equal D_in=%d' % (z0.shape[-1], D))
+        v0, K = _tangent_dirs(v0, z0.shape[:-1], D, pad, 'v0')
+        z0 = pad.state(z0)
+    z0, ts, zpd, tpt, N, Dc = _rollout_args(cache, z0, ts, order)
+    if pad is None:
+        v0, K = _tangent_dirs(v0, z0.shape[:-1], Dc, None, 'v0')
+    T = ts.shape[-1]
+    lead = cache.lead
+    zt = torch.empty(lead + (N, T, Dc), dtype=torch.float32, device=z0.device)
+    vt = torch.empty(lead + (N, T, K, Dc), dtype=torch.float32, device=z0.device)
+    _lib.call('gpode_rollout_jvp', *_head(cache, order, method), _ptr(z0), zpd, _ptr(v0), K, _ptr(ts), tpt, sub, N, T, _ptr(zt), _ptr(vt),
+              _stream())
+    if pad is not None:
+        zt, vt = pad.unstate(zt), pad.unstate(vt)
+        if v0 is None:
+            vt = vt.index_select(vt.dim() - 2, pad.index(vt.device))
+        zt, vt = zt.contiguous(), vt.contiguous()
+    return zt, vt
+
+
 _PGRAD_CHUNKS = int(os.environ.get('GPODE_PGRAD_CHUNKS', '0'))     # 0: by the number of rows (below)
 
 
