@@ -533,6 +533,26 @@ int gpode_dec10_predict_len(const float* c, const float* table, const float* w, 
 int gpode_dec10_predict_ll_len(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th,
                                int T_obs, int done, float* pred_mean, float* pred_m2, float* se_state, float* ell, int L_total,
                                const int* n_obs, void* stream);
+/* gpode_dec10_predict with a log-weight per (draw, sequence): the self-normalised importance-weighted predictive moments behind a
+ * forecast conditioned on an observed prefix (evaluate.predict_conditional).  c, table, w, bias, X, Lc, F, Th, T_obs, done as
+ * in gpode_dec10_predict; neither logits nor reconstructions are written.
+ *   logw [L_total][N]            log-weight of draw l for sequence n (F = N * Th); rows done .. done + Lc - 1 are read.  -inf: weight 0.
+ *                                A NaN is the caller's to refuse (the kernel does not look for one).
+ *   wstate [F][2]                {ref, W}: the largest log-weight folded so far and W = sum_l exp(logw_l - ref)
+ *   pred_mean, pred_m2 [F][784]  weighted mean and weighted M2 of sigmoid(logit) over the draws under the weights exp(logw_l - ref)
+ *                                (West's update: W += u; d = x - mean; mean += (u / W) d; M2 += u d (x - mean)); the variance of the
+ *                                weighted mixture is M2 / W
+ *   wse [F]                      sum_l exp(logw_l - ref) mean_p (sigmoid(a_lp) - X_p)^2 for a frame with a target (wse / W is its
+ *                                weighted per-image MSE), 0 for a frame without one, whose padded target is never loaded
+ *   n_obs [N] or NULL            NULL: every frame t < T_obs has a target; otherwise as gpode_dec10_predict_len
+ * A draw whose log-weight exceeds ref multiplies W, M2 and wse by exp(ref - logw) and moves ref (the mean is left alone); this happens
+ * per draw, so any split of the draws over launches gives the bits of one launch.  A draw whose weight exp(logw - ref) underflows to 0
+ * leaves the state bit for bit as it was.  done == 0: the state is initialised, not read.  All weights 0: W = 0, mean = M2 = 0.
+ * gpode_last_launch(): the twin's tag + "_w".  Refused, with nothing written: logw == NULL, wstate == NULL, another null operand,
+ * N < 1 or F != N * Th, done + Lc > L_total, every argument gpode_dec10_predict refuses, GPODE_CONV_VALU. */
+int gpode_dec10_predict_w(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th,
+                          int T_obs, int done, const float* logw, int L_total, int N, float* wstate, float* pred_mean, float* pred_m2,
+                          float* wse, const int* n_obs, void* stream);
 /* out[c] = sum_{b,hw} v[b,c,hw] (bias gradients); scratch: gpode_bn_scratch(B,C) floats. */
 int gpode_chan_sum(const float* v, float* out, int B, int C, int HW, float* scratch, void* stream);
 /* mode 0: ReLU, 1: sigmoid (vae.py:60,121).  Backward takes the forward OUTPUT y. */

@@ -163,6 +163,8 @@ SIGNATURES = {
     'gpode_elbo_iw_bwd_ll': (_i, [_vp] * 5 + [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f] + [_vp] * 7 + [_sz, _sz, _vp]),
     'gpode_dec10_predict_len': (_i, [_vp] * 5 + [_i] * 5 + [_vp] * 3 + [_vp, _vp]),
     'gpode_dec10_predict_ll_len': (_i, [_vp] * 5 + [_i] * 5 + [_vp] * 4 + [_i, _vp, _vp]),
+    # the importance-weighted twin: logw, L_total, N, wstate, pred_mean, pred_m2, wse, n_obs (may be null)
+    'gpode_dec10_predict_w': (_i, [_vp] * 5 + [_i] * 5 + [_vp, _i, _i] + [_vp] * 5 + [_vp]),
 }
 
 _lib = None

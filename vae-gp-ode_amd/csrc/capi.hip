@@ -641,6 +641,18 @@ int gpode_dec10_predict_ll_len(const float* c, const float* table, const float* 
   return predict_any("gpode_dec10_predict_ll_len", true, true, c, table, w, bias, X, Lc, F, Th, T_obs, done, pred_mean, pred_m2, se_state, ell,
                      L_total, n_obs, stream);
 }
+int gpode_dec10_predict_w(const float* c, const float* table, const float* w, const float* bias, const float* X, int Lc, int F, int Th,
+                          int T_obs, int done, const float* logw, int L_total, int N, float* wstate, float* pred_mean, float* pred_m2,
+                          float* wse, const int* n_obs, void* stream) {
+  const char* who = "gpode_dec10_predict_w";
+  if (!c || !table || !w || !X || !pred_mean || !pred_m2 || !wse) return gp::set_error("%s: null pointer", who);
+  if (!logw) return gp::set_error("%s: logw is NULL", who);
+  if (!wstate) return gp::set_error("%s: wstate is NULL", who);
+  const gp::PredictWArgs a{.c = c, .table = table, .w = w, .bias = bias, .X = X, .Lc = Lc, .F = F, .Th = Th, .T_obs = T_obs, .done = done,
+                           .logw = logw, .L_total = L_total, .N = N, .wstate = wstate, .pred_mean = pred_mean, .pred_m2 = pred_m2,
+                           .wse = wse, .n_obs = n_obs};
+  return gp::dec10_predict_w(who, a, GP_ST);
+}
 int gpode_chan_sum(const float* v, float* out, int B, int C, int HW, float* scratch, void* stream) {
   if (!v || !out || !scratch) return gp::set_error("gpode_chan_sum: null pointer");
   return gp::chan_sum(v, out, B, C, HW, scratch, GP_ST);

@@ -304,6 +304,169 @@ __global__ __launch_bounds__(512) void k_fwd_predict(const float* __restrict__ x
 }
 
 // ---------------------------------------------------------------------------------------------
+// importance-weighted twin of k_fwd_predict (gpode_dec10_predict_w: the forecast conditioned on an observed prefix).
+// Same operands, same tile loop, same ownership (a workgroup owns a frame and folds its draws in order, a thread owns one or two
+// pixels), nothing but statistics leaves the kernel.  Draw l of sequence n = f / Th carries the log-weight logw[(done + l) N + n]; the
+// moments over the draws are the self-normalised weighted ones, folded by West's incremental update about a running reference:
+//   per frame   ref = the largest log-weight folded so far, W = sum_l exp(logw_l - ref)                     (wstate [F][2])
+//               wse = sum_l exp(logw_l - ref) mean_p (z_lp - X_p)^2 for a frame with a target, else 0       (wse [F])
+//   per pixel   mean, M2 of z = sigmoid(logit) under the weights exp(logw_l - ref)                          (pred_mean / pred_m2)
+//   a draw      lw > ref:  s = exp(ref - lw);  W, M2, wse *= s;  ref = lw;  u = 1       (mean is a ratio: a rescale leaves it alone)
+//               else       u = exp(lw - ref)                                            (lw = -inf: u = 0, also while ref = -inf)
+//               u > 0:     W += u;  d = z - mean;  mean += (u / W) d;  M2 += u d (z - mean);  wse += u mean_p (z - X)^2
+//               u == 0:    nothing is touched -- the state keeps its bits and no 0 / 0 is formed
+// The rescale happens per draw and every quantity is carried in fp32 registers exactly as it is stored between launches, so any split
+// of the draws over launches gives the bits of one launch.  lw, s, u and W are the same in every lane: they live in scalar registers
+// (the one logw value per draw is the only memory traffic the weighting adds).  The image's mean squared error takes one wavefront
+// reduction and the 8 wavefronts' sums are added in wavefront order behind the second barrier (the slots of s_r).  n_obs == NULL:
+// every frame t < T_obs has a target; otherwise as k_fwd_predict<LL, true> -- the padded targets are never loaded.  A NaN log-weight is
+// the caller's to refuse (vae_ops.dec10_predict_w does).  grid <= min(F, CUs), block 512, LDS = 25 * PST + 8 floats.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float uniform_f(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+
+__global__ __launch_bounds__(512) void k_fwd_predict_w(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                       const float* __restrict__ in_bn, const float* __restrict__ X, int Lc, int F, int Th,
+                                                       int T_obs, int done, const float* __restrict__ logw, int N,
+                                                       float* __restrict__ wstate, float* __restrict__ pred_mean, float* __restrict__ pred_m2,
+                                                       float* __restrict__ wse, const int* __restrict__ n_obs) {
+  float* s_T = igemm_smem;                           // [25][PST], zero borders
+  float* s_r = s_T + KK * PST;                       // [8] the wavefronts' sums of the current image's squared error
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lr = lane & 15, lk = lane >> 4;
+  constexpr int MAXT = (NTILE + 7) / 8;
+  for (int e = tid; e < KK * PST; e += 512) s_T[e] = 0.f;
+  float wa[4][2];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int tap = 16 * c + lr;
+      wa[ks][c] = tap < KK ? w[(size_t)(4 * ks + lk) * KK + tap] : 0.f;
+    }
+  const float bv = bias ? bias[0] : 0.f;
+  float4 tf[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) tf[ks] = reinterpret_cast<const float4*>(in_bn)[4 * ks + lk];
+  float xb[MAXT][4];
+  auto prefetch = [&](int f, int l) {                // image (draw l, frame f)
+    const float* xp = x + ((size_t)l * F + f) * (CI * NP) + lr;
+#pragma unroll
+    for (int j = 0; j < MAXT; ++j) {
+      const int t = wave + 8 * j;
+      if (t < NTILE) {
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) xb[j][ks] = xp[(size_t)(4 * ks + lk) * NP + 16 * t];
+      }
+    }
+  };
+  if ((int)blockIdx.x < F) prefetch(blockIdx.x, 0);
+  __syncthreads();
+  const int o1 = tid + 512;                          // this thread's pixels: tid and (tid < 272) tid + 512
+  const bool two = o1 < NP;
+  for (int f = blockIdx.x; f < F; f += gridDim.x) {
+    const int n = f / Th, t = f % Th;
+    bool has_t = t < T_obs;                          // workgroup-uniform
+    if (n_obs) has_t = has_t && t < n_obs[n];
+    float xt[2] = {0.f, 0.f}, pm[2] = {0.f, 0.f}, pq[2] = {0.f, 0.f};
+    if (has_t) {
+      const float* Xp = X + ((size_t)n * T_obs + t) * NP;
+      xt[0] = Xp[tid];
+      if (two) xt[1] = Xp[o1];
+    }
+    float ref = -INFINITY, W = 0.f, ws = 0.f;        // the frame's weight state, identical in every thread
+    if (done > 0) {
+      pm[0] = pred_mean[(size_t)f * NP + tid]; pq[0] = pred_m2[(size_t)f * NP + tid];
+      if (two) { pm[1] = pred_mean[(size_t)f * NP + o1]; pq[1] = pred_m2[(size_t)f * NP + o1]; }
+      ref = uniform_f(wstate[(size_t)f * 2]); W = uniform_f(wstate[(size_t)f * 2 + 1]);
+      if (has_t) ws = uniform_f(wse[f]);
+    }
+    for (int l = 0; l < Lc; ++l) {
+      const float lw = uniform_f(logw[(size_t)(done + l) * N + n]);  // one scalar load per draw
+#pragma unroll
+      for (int j = 0; j < MAXT; ++j) {
+        const int tl = wave + 8 * j;
+        if (tl < NTILE) {                            // wave-uniform
+          f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+          for (int ks = 0; ks < 4; ++ks) {
+            const float xv = bn_relu(xb[j][ks], tf[ks]);
+#pragma unroll
+            for (int c = 0; c < 2; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[ks][c], xv, acc[c], 0, 0, 0);
+          }
+          const int p = 16 * tl + lr, pa = (p / H + 2) * WP + p % H + 2;
+#pragma unroll
+          for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int tap = 16 * c + 4 * lk + r;
+              if (tap < KK) s_T[tap * PST + pa] = acc[c][r];
+            }
+        }
+      }
+      if (l + 1 < Lc) prefetch(f, l + 1);
+      else if (f + (int)gridDim.x < F) prefetch(f + gridDim.x, 0);
+      // the draw's weight about the running reference (workgroup-uniform, scalar)
+      float u;
+      if (lw > ref) {
+        const float s = uniform_f(expf(ref - lw));   // ref = -inf (nothing folded yet): 0, and W, M2, wse are 0
+        W *= s; ws *= s;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) pq[q] *= s;
+        ref = lw;
+        u = 1.f;
+      } else {
+        u = lw == -INFINITY ? 0.f : uniform_f(expf(lw - ref));
+      }
+      const bool fold = u > 0.f;
+      float r = 0.f;
+      if (fold) { W += u; r = uniform_f(u / W); }
+      __syncthreads();
+      float ev[2] = {0.f, 0.f};
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int o = tid + 512 * q;
+        if (o < NP) {
+          const int oy = o / H, ox = o % H;
+          const float* tp = s_T + (oy + 4) * WP + ox + 4;
+          float s0 = bv, s1 = 0.f;
+#pragma unroll
+          for (int ky = 0; ky < 5; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 5; ++kx) {
+              const float v = tp[(ky * 5 + kx) * PST - ky * WP - kx];
+              if ((ky * 5 + kx) & 1) s1 += v; else s0 += v;
+            }
+          const float z = 1.f / (1.f + expf(-(s0 + s1)));            // k_act's sigmoid
+          if (fold) {
+            const float d = z - pm[q];
+            pm[q] = __fmaf_rn(d, r, pm[q]);
+            pq[q] = __fmaf_rn(u * d, z - pm[q], pq[q]);
+          }
+          const float df = z - xt[q];
+          ev[q] = df * df;
+        }
+      }
+      if (has_t && fold) {
+        const float in1[1] = {ev[0] + ev[1]};
+        float out1[1];
+        wave_sum_multi<1>(in1, out1);
+        if (lane == 0) s_r[wave] = out1[0];
+      }
+      __syncthreads();                               // s_T is free again; the wavefronts' sums are visible
+      if (has_t && fold) {
+        float e = 0.f;
+#pragma unroll
+        for (int wv = 0; wv < 8; ++wv) e += s_r[wv];
+        ws = __fmaf_rn(u, e * (1.f / (float)NP), ws);
+      }
+    }
+    pred_mean[(size_t)f * NP + tid] = pm[0]; pred_m2[(size_t)f * NP + tid] = pq[0];
+    if (two) { pred_mean[(size_t)f * NP + o1] = pm[1]; pred_m2[(size_t)f * NP + o1] = pq[1]; }
+    if (tid == 0) { wstate[(size_t)f * 2] = ref; wstate[(size_t)f * 2 + 1] = W; wse[f] = ws; }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // d/d input.  grid <= 256, block 512, LDS = IPB planes.
 // ---------------------------------------------------------------------------------------------
 template <int IPB>

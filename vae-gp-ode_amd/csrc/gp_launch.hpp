@@ -236,6 +236,13 @@ struct PredictArgs {
   float* pred_mean; float* pred_m2; float* se_state; float* ell; int L_total; const int* n_obs;
 };
 int dec10_predict(const char* who, bool ll, bool ragged, const PredictArgs& a, hipStream_t st);
+// ... with a log-weight per (draw, sequence): logw (L_total,N), F = N Th; wstate (F,2) = {ref, W}, wse (F); n_obs (N) or null --
+// k_fwd_predict_w
+struct PredictWArgs {
+  const float* c; const float* table; const float* w; const float* bias; const float* X; int Lc, F, Th, T_obs, done;
+  const float* logw; int L_total, N; float* wstate; float* pred_mean; float* pred_m2; float* wse; const int* n_obs;
+};
+int dec10_predict_w(const char* who, const PredictWArgs& a, hipStream_t st);
 int chan_sum(const float* v, float* out, int B, int C, int HW, float* scratch, hipStream_t st);
 int act_fwd(const float* x, float* y, size_t n, int mode, hipStream_t st);
 int act_bwd(const float* y, const float* gy, float* gx, size_t n, int mode, hipStream_t st);

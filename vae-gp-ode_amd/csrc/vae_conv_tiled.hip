@@ -635,6 +635,24 @@ int dec10_predict(const char* who, bool ll, bool ragged, const PredictArgs& a, h
   return ragged ? launch_predict<false, true>("dec10_predict_len", a, st) : launch_predict<false, false>("dec10_predict", a, st);
 }
 
+// gpode_dec10_predict_w: the importance-weighted twin (conv_dec10_mfma.hpp, k_fwd_predict_w) -- the same grid, the same order of the
+// draws.  a.n_obs may be NULL (every frame t < T_obs has a target).  Nothing is launched and nothing written when an argument is refused.
+int dec10_predict_w(const char* who, const PredictWArgs& a, hipStream_t st) {
+  if (!use_mfma()) return set_error("%s: matrix-core kernel only (GPODE_CONV_VALU is set)", who);
+  if (a.Lc < 1 || a.F < 1 || a.Th < 1 || a.T_obs < 1 || a.T_obs > a.Th || a.F % a.Th != 0 || a.done < 0)
+    return set_error("%s: need Lc, F >= 1, 1 <= T_obs <= Th, F a multiple of Th, done >= 0", who);
+  if (a.N < 1 || a.F % a.N != 0 || a.F / a.N != a.Th) return set_error("%s: need N >= 1 and F = N * Th", who);
+  if (!aligned16(a.table)) return set_error("%s: the table must be 16-byte aligned", who);
+  if (a.L_total < 1 || a.Lc > a.L_total || a.done > a.L_total - a.Lc)
+    return set_error("%s: logw has L_total rows, need done + Lc <= L_total", who);
+  const size_t lds = sizeof(float) * (dec10::KK * dec10::PST + 8);
+  if (set_max_lds((const void*)dec10::k_fwd_predict_w, lds)) return 1;
+  const int nwg = a.F < num_cus() ? a.F : num_cus();
+  hipLaunchKernelGGL(dec10::k_fwd_predict_w, nwg, 512, lds, st, a.c, a.w, a.bias, a.table, a.X, a.Lc, a.F, a.Th, a.T_obs, a.done, a.logw, a.N,
+                     a.wstate, a.pred_mean, a.pred_m2, a.wse, a.n_obs);
+  return check_launch(a.n_obs ? "dec10_predict_len_w" : "dec10_predict_w");
+}
+
 // decnn.10's input gradient fused with the backward of the BatchNorm + ReLU in front of it (conv_dec10_mfma.hpp, k_bwd_data_bn).
 // scratch: part[nwg][16][2] | part_gx[nwg][16][2], nwg <= kDec10BnMaxWg.  The grid is a function of B alone, so the two
 // passes (and the partials they exchange through scratch) agree.

@@ -41,7 +41,12 @@ state-transition matrices Phi_t = d z_t / d z0 in forward mode, their log-determ
 divergence of the field along the trajectories), for ``--eval_sample_size`` function draws and for the posterior-mean field: writes
 ``flow_phi.npy``, ``flow_logdet.npy``, ``flow_div.npy`` and the same three with the suffix ``_mean``, and adds ``flow_logdet_mean``
 (of log |det Phi| at the last time), ``flow_logdet_absmax`` (over all times), ``flow_ftle_mean``, ``flow_ftle_max``, ``flow_div_absmean``, ``flow_div_absmean_meanfield``; without it nothing
-changes.  Single process: data-parallel evaluation is not built.  No plots.
+changes.  ``--eval_condition_frames K`` then forecasts every test sequence CONDITIONED on its first K frames
+(``predict_conditional``: the joint draws of ``--eval_z0_draws`` weighted by how well each explains those frames, the weighted moments
+folded inside the decoder's last kernel, ``gpode_dec10_predict_w``): adds ``cond_frames``, ``fc_mse``, ``fc_mse_uncond`` (the same draws
+equally weighted), ``fc_nlpd``, ``fc_mse_t``, ``fc_nlpd_t``, ``cond_ess_mean``, ``cond_ess_min`` and writes ``forecast_mean.npy``,
+``forecast_var.npy`` (the three rolled-out sequences, ``--Troll`` * T frames); 0, the default: nothing changes.
+Single process: data-parallel evaluation is not built.  No plots.
 """
 import argparse
 import json
@@ -83,6 +88,69 @@ def iw_stats(ll, lw):
     s1, s2 = w.sum(dim=0), (w * w).sum(dim=0)
     iw_ll = top + torch.log(s1) - math.log(a.shape[0])
     return iw_ll, -iw_ll.mean().item(), s1 * s1 / s2
+
+
+CondStats = namedtuple('CondStats', 'logw wn ess evidence fc_ll fc_nlpd fc_nlpd_t prefix forecast')
+CondStats.__doc__ = """cond_stats' result: logw (L,N), wn (L,N) the normalised weights, ess (N,), evidence (N,), fc_ll (N,), fc_nlpd,
+fc_nlpd_t (T,), prefix (N,) the frames every sequence is conditioned on, forecast (N,T) bool: the observed frames behind the prefix."""
+
+
+def _prefix(n_cond, N, T, n_obs=None):
+    """frames t < min(n_cond[n], T, n_obs[n]) of sequence n are conditioned on: (N,) int64 on the CPU"""
+    k = torch.as_tensor(n_cond).detach().cpu().to(torch.int64)
+    k = k.expand(N) if k.dim() == 0 else k.reshape(N)
+    k = k.clamp(min=0, max=T)
+    if n_obs is not None:
+        k = torch.minimum(k, torch.as_tensor(n_obs).detach().cpu().to(torch.int64).reshape(N).clamp(min=0))
+    return k
+
+
+def _split_frames(n_cond, N, T, n_obs=None):
+    """(prefix (N,), conditioned-on frames (N,T) bool, forecast frames that have a target (N,T) bool), on the CPU"""
+    k, o = _prefix(n_cond, N, T, n_obs), _prefix(T, N, T, n_obs)
+    tt = torch.arange(T)[None, :]
+    return k, tt < k[:, None], (tt >= k[:, None]) & (tt < o[:, None])
+
+
+def cond_stats(ell, lw, n_cond, T, n_obs=None):
+    """The weights of a forecast conditioned on an observed prefix, and what is read off them, from the frame log-likelihoods ell
+    (L,N,Th) of L joint draws (z0_l ~ q(z0 | x), f_l ~ q(f)) and their log-weights lw (L,N) = log p(z0_l) - log q(z0_l | x_n).  With
+    k[n] = min(n_cond[n], T, n_obs[n]) (``n_cond`` an int or (N,); T the observed length; ``n_obs`` (N,) the frame counts of ragged
+    sequences or None) and o[n] = min(T, n_obs[n]):
+      logw[l,n]    = lw[l,n] + sum_{t < k[n]} ell[l,n,t]
+      wn[l,n]      = softmax_l logw[., n]                                (self-normalised weights)
+      ess[n]       = (sum_l w)^2 / sum_l w^2                             (in [1, L])
+      evidence[n]  = log (1/L) sum_l exp logw[l,n]                       (the estimate of log p(x_{<k}))
+      fc_ll[n]     = log sum_l wn[l,n] exp sum_{k[n] <= t < o[n]} ell[l,n,t]   (= the estimate of log p(x) minus evidence)
+      fc_nlpd      = -mean of fc_ll over the sequences that have a frame behind their prefix (nan when none has)
+      fc_nlpd_t[t] = -mean_n log sum_l wn[l,n] exp ell[l,n,t] over the sequences with k[n] <= t < o[n]; nan where there is none.
+    A column of logw that is -inf throughout (no draw has any weight) gives evidence = -inf and ess, wn, fc_ll = nan.  Double precision
+    on the CPU, every maximum subtracted before its exp, a fixed order of operations: the same input gives the same bits.  -> CondStats."""
+    ell = torch.as_tensor(ell, dtype=torch.float64).cpu()
+    lw = torch.as_tensor(lw, dtype=torch.float64).cpu()
+    L, N = lw.shape
+    T = int(T)
+    ell = ell[:, :, :T]
+    k, pre, fut = _split_frames(n_cond, N, T, n_obs)
+    zero = torch.zeros((), dtype=torch.float64)
+    logw = lw + torch.where(pre[None], ell, zero).sum(dim=2)
+    top = logw.max(dim=0).values
+    top0 = torch.where(torch.isfinite(top), top, zero)
+    w = torch.exp(logw - top0)
+    s1, s2 = w.sum(dim=0), (w * w).sum(dim=0)
+    evidence = top0 + torch.log(s1) - math.log(L)
+    wn = w / s1
+    a = logw + torch.where(fut[None], ell, zero).sum(dim=2)
+    atop = a.max(dim=0).values
+    atop0 = torch.where(torch.isfinite(atop), atop, zero)
+    fc_ll = atop0 + torch.log(torch.exp(a - atop0).sum(dim=0)) - (top0 + torch.log(s1))
+    has = fut.any(dim=1)
+    fc_nlpd = -(torch.where(has, fc_ll, zero).sum() / has.sum().to(torch.float64)).item()
+    b = logw[:, :, None] + ell                                                         # (L,N,T)
+    btop = b.max(dim=0).values
+    btop0 = torch.where(torch.isfinite(btop), btop, zero)
+    lt = btop0 + torch.log(torch.exp(b - btop0).sum(dim=0)) - (top0 + torch.log(s1))[:, None]
+    return CondStats(logw, wn, s1 * s1 / s2, evidence, fc_ll, fc_nlpd, -frame_means(lt, fut), k, fut)
 
 
 def log_mean_exp(ll):
@@ -345,6 +413,132 @@ def compute_iw_nll(model, loader, L, images_per_pass=8192):
     return iw / nseq, nlpd / nseq, ess / nseq
 
 
+ConditionalPrediction = namedtuple('ConditionalPrediction',
+                                   'mean var logw ess evidence fc_ll fc_nlpd fc_nlpd_t fc_mse fc_mse_t fc_mse_uncond_t passes')
+ConditionalPrediction.__doc__ = """mean, var (N,Th,1,28,28): the self-normalised importance-weighted predictive mean and variance of the
+decoded images given the observed prefix; var = M2 / W is the variance of the weighted mixture of the draws -- NO Bessel correction (a
+weighted sample has no agreed one, and with the weight on one draw it is 0, not nan);  logw (L,N) float64 on the CPU: the log-weights
+lw + sum_{t < prefix} ell;  ess (N,): their effective sample size, in [1, L] -- read it first: at ess ~ 1 every other field rests on one
+draw;  evidence (N,): log (1/L) sum_l exp logw, the estimate of log p(x_{<prefix});  fc_ll (N,): log sum_l wn_l exp(sum of ell over the
+observed frames behind the prefix), the predictive log-density of those frames given the prefix;  fc_nlpd: -mean_n fc_ll;  fc_nlpd_t
+(T,): the same per frame, nan where no sequence has frame t behind its prefix;  fc_mse: the weighted mean squared error over the
+forecast frames that have a target;  fc_mse_t (T,): per frame;  fc_mse_uncond_t (T,): the same frames with the draws equally weighted
+-- the baseline the weighting is meant to beat;  passes: draws per decoder pass."""
+
+
+def _cond_frames(model, n_cond, T, who):
+    """``n_cond`` of predict_conditional against what the encoder reads and the observed length; before any device work"""
+    need = 1 if model.order == 1 else int(model.v_steps)
+    k = torch.as_tensor(n_cond).detach().cpu()
+    if k.is_floating_point() or k.dtype == torch.bool or k.dim() > 1:
+        raise ValueError('%s: n_cond must be an int or an (N,) integer tensor' % who)
+    lo, hi = int(k.min()), int(k.max())
+    if lo < need:
+        raise ValueError('%s: n_cond = %d, but the encoder reads the first %d frame(s) (order %d): the proposal q(z0 | x) would have '
+                         'seen frames the target has not' % (who, lo, need, model.order))
+    if hi > T:
+        raise ValueError('%s: n_cond = %d exceeds the observed length T = %d' % (who, hi, T))
+    return k.to(torch.int64)
+
+
+def predict_conditional(model, X, L, n_cond, T_custom=None, images_per_pass=8192, ts=None, n_obs=None):
+    """The forecast of the sequences X (N,T,1,28,28) CONDITIONED on their first frames: sequence n on the frames
+    t < min(n_cond[n], T, n_obs[n]) (``n_cond`` an int or an (N,) integer tensor).  L joint draws (z0_l ~ q(z0 | x), f_l ~ q(f)) are
+    rolled out over ``T_custom or T`` frames exactly as predict_marginal draws them, and draw l gets the self-normalised weight
+    wn[l,n] = softmax_l (lw[l,n] + sum_{t < prefix} ell[l,n,t]) -- how well it explains what was in fact observed.  Per decoder pass, on
+    the same raw decoder output: dec10_predict leaves ell and the unweighted error, the log-weights of the pass are formed on the device
+    (float64, no host sync) and handed over relative to the log-weight of draw 0 of each sequence (so that float32 resolves them, and so
+    that the split into passes does not enter), and dec10_predict_w folds the weighted moments.  -> ConditionalPrediction.
+    ValueError: n_cond below what the encoder reads (1 frame; ``model.v_steps`` for order 2) or above T.  ``ts`` (N,Th), ``n_obs`` (N,)
+    int32 as in predict.  Runs without autograd and in eval mode; leaves every module buffer and ``training`` flag as it found them."""
+    from . import vae_ops as V
+    if X.dim() != 5 or tuple(X.shape[2:]) != (1, 28, 28):
+        raise ValueError('predict_conditional: X must be (N,T,1,28,28)')
+    N, T = X.shape[0], X.shape[1]
+    kc = _cond_frames(model, n_cond, T, 'predict_conditional')
+    if kc.dim() == 1 and kc.shape[0] != N:
+        raise ValueError('predict_conditional: n_cond must be an int or (N,) = (%d,); got %s' % (N, tuple(kc.shape)))
+    Th = int(T_custom) if T_custom else T
+    if Th < T:
+        raise ValueError('predict_conditional: T_custom (%d) must be at least the observed length (%d)' % (Th, T))
+    n_obs = _counts(n_obs, X, 'predict_conditional')
+    ts = _grid(ts, N, Th, T, 'predict_conditional')
+    L = int(L)
+    F = N * Th
+    passes = plan_passes(L, F, int(images_per_pass))
+    dec = model.vae.decoder
+    k_host = _prefix(kc, N, T, n_obs)
+    with torch.no_grad(), _EvalMode(model):
+        X = X.contiguous().float()
+        z0, lw, _, _ = model.encode_initial_state(X, draws=L)          # (L,N,order*q), (L,N)
+        ztL = model.sample_trajectories(z0, Th, L) if ts is None else model.sample_trajectories(z0, Th, L, ts=ts.to(X.device))
+        lat = ztL if model.order == 1 else ztL[..., :ztL.shape[-1] // 2]
+        tables = dec._frozen_tables()
+        state = V.PredictState(F, X.device, False, loglik=L)
+        cond = V.CondState(F, N, X.device)
+        kmax = int(k_host.max())
+        pre = torch.arange(kmax)[None, :] < k_host[:, None]            # (N,kmax): frame t of sequence n is conditioned on
+        pre = pre.to(X.device)
+        zero = torch.zeros((), dtype=torch.float64, device=X.device)
+        lw64 = lw.double()
+        rel = torch.empty(L, N, dtype=torch.float32, device=X.device)
+        ref = None
+        for l0, l1 in passes:
+            c, t8 = dec.decode_frozen_raw(lat[l0:l1], tables)
+            if n_obs is None:
+                V.dec10_predict(c, t8, dec.decnn[10].weight, dec.decnn[10].bias, X, Th, state)
+            else:
+                V.dec10_predict(c, t8, dec.decnn[10].weight, dec.decnn[10].bias, X, Th, state, n_obs=n_obs)
+            e = state.ell[l0:l1].view(l1 - l0, N, Th).double()
+            lg = lw64[l0:l1]
+            for t in range(kmax):                                      # element-wise, frame by frame: the same bits for any pass size
+                lg = lg + torch.where(pre[:, t], e[:, :, t], zero)
+            if ref is None:                                            # draw 0 of every sequence: the same whatever the passes are
+                ref = torch.where(torch.isfinite(lg[0]), lg[0], torch.zeros_like(lg[0]))
+            rel[l0:l1] = (lg - ref).float()
+            V.dec10_predict_w(c, t8, dec.decnn[10].weight, dec.decnn[10].bias, X, Th, cond, rel, n_obs=n_obs)
+            del c
+        cond.check()
+        se = state.se.double().cpu().view(N, Th, 3)[:, :T]
+        ell = state.ell.cpu().double().view(L, N, Th)
+        W = cond.wstate[:, 1]
+        mean = cond.mean.view(N, Th, 1, 28, 28)
+        var = (cond.m2 / W[:, None]).view(N, Th, 1, 28, 28)
+        wmse = (cond.wse.double() / W.double()).cpu().view(N, Th)[:, :T]
+        lw = lw.cpu().double()
+    st = cond_stats(ell, lw, kc, T, n_obs)
+    nf = st.forecast.sum().to(torch.float64)
+    fc_mse = (torch.where(st.forecast, wmse, torch.zeros((), dtype=torch.float64)).sum() / nf).item()
+    return ConditionalPrediction(mean, var, st.logw, st.ess, st.evidence, st.fc_ll, st.fc_nlpd, st.fc_nlpd_t, fc_mse,
+                                 frame_means(wmse, st.forecast), frame_means(se[:, :, 1], st.forecast), [b - a for a, b in passes])
+
+
+def compute_forecast(model, loader, L, n_cond, images_per_pass=8192):
+    """(fc_mse, fc_nlpd, mean ess) of the forecast conditioned on the first ``n_cond`` frames over a whole loader with L joint draws per
+    batch (predict_conditional): fc_mse is the mean over all forecast frames that have a target, fc_nlpd the mean over the sequences
+    that have such a frame, ess the mean over all sequences.  A loader that yields (X, ts) pairs is evaluated on its time grids, one
+    that yields (X, ts, n_obs) triples on its ragged sequences."""
+    dev = next(model.parameters()).device
+    nseq = nfc = nfr = 0
+    mse = nlpd = ess = 0.0
+    for batch in loader:
+        X, ts, n_obs = _frames_ts(batch)
+        X = X.to(dev)
+        p = predict_conditional(model, X, L, n_cond, images_per_pass=images_per_pass, **_grid_kw(ts, n_obs))
+        fut = _split_frames(n_cond, X.shape[0], X.shape[1], n_obs)[2]
+        frames, seqs = int(fut.sum()), int(fut.any(dim=1).sum())
+        nseq += X.shape[0]
+        ess += p.ess.sum().item()
+        if frames:
+            mse += p.fc_mse * frames
+            nlpd += p.fc_nlpd * seqs
+            nfr += frames
+            nfc += seqs
+    if nseq == 0:
+        return float('nan'), float('nan'), float('nan')
+    return (mse / nfr if nfr else float('nan')), (nlpd / nfc if nfc else float('nan')), ess / nseq
+
+
 def compute_mse_std(model, loader, L=1, images_per_pass=8192):
     """(mse, std) of the squared reconstruction error over a whole loader with L draws per batch -- ``compute_mse_std`` of the
     evaluation notebook: the batches' (n, mean, M2) triples are merged, so the result is the mean / std over all elements.
@@ -518,6 +712,25 @@ def eval_field(args):
     return bool(getattr(args, 'eval_field', False))
 
 
+def _nullable(v):
+    """a (T,) tensor as a list for eval.json, None (null) where it is nan: a frame that no sequence forecasts"""
+    return [None if math.isnan(x) else x for x in v.tolist()]
+
+
+def check_condition_frames(args):
+    """--eval_condition_frames K: 0 (off), or at least what the encoder reads (1 frame; --frames for --ode 2) and at most the frames a
+    test sequence has (--subsample_frames if set, else --T); refused with a message otherwise, ahead of any device work"""
+    K = args.eval_condition_frames
+    if not K:
+        return
+    need, T = (1 if args.ode == 1 else args.frames), (args.subsample_frames or args.T)
+    if K < need:
+        raise SystemExit('--eval_condition_frames %d: the encoder reads the first %d frame(s) (--ode %d), so the forecast must be '
+                         'conditioned on at least as many' % (K, need, args.ode))
+    if K > T:
+        raise SystemExit('--eval_condition_frames %d: a test sequence has %d frames' % (K, T))
+
+
 def _subsampled(args, loader):
     """The loader's items as (all frames, X, ts, n_obs): with --subsample_frames K every sequence keeps K frames, drawn per batch from
     a generator of its own seeded from --seed (so a second pass sees the same subsets), ts = dt * (kept indices); with
@@ -550,6 +763,7 @@ def main(argv=None):
     check_subsample(args)
     check_ragged(args)
     check_dense_scale(args)
+    check_condition_frames(args)
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
         raise SystemExit('vae_gp_ode_amd.evaluate is a single-process tool: data-parallel evaluation is not built '
                          '(start it without torchrun, or with one rank)')
@@ -605,6 +819,32 @@ def main(argv=None):
     if eval_flow(args):                              # behind everything else: every figure above sees the draws it sees without it
         Xf = torch.cat([full for full, _, _, _ in _subsampled(args, testset)])     # all frames: the uniform grid dt * arange(T)
         flowd = (flow_diagnostics(model, Xf, L), flow_diagnostics(model, Xf, mean_field=True))
+    forecast = None
+    if args.eval_condition_frames:                   # behind everything else: every figure above sees the draws it sees without it
+        K = args.eval_condition_frames
+        fr = sq = 0
+        fmse = fnl = ess_sum = 0.0
+        ess_min = float('inf')
+        wt_t = mse_t = unc_t = nl_t = None
+        for _, Xb, tsb, nb in _subsampled(args, testset):
+            pc = predict_conditional(model, Xb, L, K, **_grid_kw(tsb, nb))
+            fut = _split_frames(K, Xb.shape[0], Xb.shape[1], nb)[2]
+            wt = fut.sum(0).to(torch.float64)
+            seqs = int(fut.any(dim=1).sum())
+            if seqs:
+                fmse += pc.fc_mse * float(wt.sum())
+                fnl += pc.fc_nlpd * seqs
+            fr += float(wt.sum())
+            sq += seqs
+            ess_sum += pc.ess.sum().item()
+            ess_min = min(ess_min, pc.ess.min().item())
+            parts = [torch.nan_to_num(v) * wt for v in (pc.fc_mse_t, pc.fc_mse_uncond_t, pc.fc_nlpd_t)]
+            mse_t, unc_t, nl_t = parts if wt_t is None else (mse_t + parts[0], unc_t + parts[1], nl_t + parts[2])
+            wt_t = wt if wt_t is None else wt_t + wt
+        froll = predict_conditional(model, first[:3].contiguous(), L, K, T_custom=args.Troll * first.shape[1])
+        forecast = (dict(cond_frames=K, fc_mse=fmse / fr if fr else float('nan'), fc_mse_uncond=float(unc_t.sum() / wt_t.sum()),
+                         fc_nlpd=fnl / sq if sq else float('nan'), fc_mse_t=_nullable(mse_t / wt_t), fc_nlpd_t=_nullable(nl_t / wt_t),
+                         cond_ess_mean=ess_sum / nseq, cond_ess_min=ess_min), froll.mean.cpu().numpy(), froll.var.cpu().numpy())
     torch.cuda.synchronize()
     ms = (time.time() - t0) * 1e3
 
@@ -631,6 +871,10 @@ def main(argv=None):
             np.save(os.path.join(args.save, 'flow_phi%s.npy' % suffix), d['Phi'].cpu().numpy())
             np.save(os.path.join(args.save, 'flow_logdet%s.npy' % suffix), d['logdet'].numpy())
             np.save(os.path.join(args.save, 'flow_div%s.npy' % suffix), d['div'].numpy())
+    if forecast is not None:
+        out.update(forecast[0])
+        np.save(os.path.join(args.save, 'forecast_mean.npy'), forecast[1])
+        np.save(os.path.join(args.save, 'forecast_var.npy'), forecast[2])
     np.save(os.path.join(args.save, 'rollout_mean.npy'), roll.mean.cpu().numpy())
     np.save(os.path.join(args.save, 'rollout_var.npy'), roll.var.cpu().numpy())
     with open(os.path.join(args.save, 'eval.json'), 'w') as f:

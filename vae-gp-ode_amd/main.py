@@ -79,6 +79,10 @@ EXT_FLAGS = [
     ('iw_draws', int, 0, 'K in 1..64: train on the importance-weighted bound -- K initial states per sequence, shared by the function '
                          'draws; the likelihood rows and the decoder batch grow K-fold, the log line shows the Monte-Carlo KL(q(z0)||p) '
                          'as kl_reg; not with --ragged_compact and not on several ranks; 0: off, the standard ELBO'),
+    ('eval_condition_frames', int, 0, 'read by vae_gp_ode_amd.evaluate only (training ignores it, so one command line serves both): K > 0 '
+                                      'adds the forecast conditioned on the first K frames of every test sequence -- the draws weighted by '
+                                      'how well they explain those frames (fc_mse, fc_nlpd, cond_ess_mean, forecast_mean.npy, '
+                                      'forecast_var.npy); K at least 1 (--ode 2: --frames) and at most T; 0: off'),
     ('sync_bn', eval, True, 'data parallel: BatchNorm normalises with the statistics of the GLOBAL minibatch (all ranks), as the '
                             'single-process reference does (vae.py:55,58,113,116,119)'),
 ]

@@ -1364,3 +1364,56 @@ def dec10_predict(c, table, w, b, X, Th, state, n_obs=None):
               Lc, F, int(Th), T_obs, state.done, _ptr(state.mean), _ptr(state.m2), _ptr(state.se), *extra, _stream())
     state.done += Lc
     return state
+
+
+class CondState:
+    """State of gpode_dec10_predict_w for F = N * Th frames of N sequences: ``wstate`` (F,2) = {ref, W} -- the largest log-weight folded
+    so far and W = sum_l exp(logw_l - ref) --, the weighted ``mean`` / ``m2`` (F,784) of the decoded images over the draws, ``wse`` (F,)
+    the weighted sum of the per-image squared error, and ``done``, the number of draws folded in.  ``bad`` is a device flag that
+    dec10_predict_w raises (without a host sync) when a log-weight is NaN or +inf; ``check()`` reads it -- one sync, where the results
+    are read anyway -- and refuses such a state."""
+
+    def __init__(self, F, N, device):
+        self.F, self.N, self.done = int(F), int(N), 0
+        if self.N < 1 or self.F < 1 or self.F % self.N != 0:
+            raise _lib.GpodeError('CondState: F = N * Th frames of N >= 1 sequences; got F = %d, N = %d' % (self.F, self.N))
+        self.wstate = torch.zeros(self.F, 2, dtype=torch.float32, device=device)
+        self.mean = torch.zeros(self.F, 784, dtype=torch.float32, device=device)
+        self.m2 = torch.zeros(self.F, 784, dtype=torch.float32, device=device)
+        self.wse = torch.zeros(self.F, dtype=torch.float32, device=device)
+        self.bad = torch.zeros((), dtype=torch.bool, device=device)
+
+    def check(self):
+        if bool(self.bad.item()):
+            raise _lib.GpodeError('dec10_predict_w: a log-weight was NaN or +inf (-inf means weight 0; anything else must be finite)')
+        return self
+
+
+def dec10_predict_w(c, table, w, b, X, Th, state, logw, n_obs=None):
+    """The importance-weighted twin of dec10_predict (gpode_dec10_predict_w): fold the draws held in ``c`` -- (Lc * F, 16, 28, 28), laid
+    out (draw, frame) -- into the CondState ``state`` under the log-weights ``logw`` (L_total, N) float32, whose rows
+    state.done .. state.done + Lc - 1 belong to these draws.  -inf is weight 0; a NaN or +inf is refused: the flag ``state.bad`` is
+    raised on the device and ``state.check()`` throws, so that a pass costs no host sync (the kernel itself treats such a draw as
+    weight 0).  ``n_obs`` (N,) int32 as in dec10_predict; None: every frame t < T_obs has a target."""
+    c, w, table, X = _chk(c.detach(), 'c'), _chk(w.detach(), 'weight'), _chk(table, 'table'), _chk(X, 'X')
+    if not isinstance(state, CondState):
+        raise _lib.GpodeError('dec10_predict_w: state must be a vae_ops.CondState')
+    if n_obs is not None:
+        n_obs = _chk_n_obs(n_obs, X, 'dec10_predict_w')[0]
+    F, N, T_obs = state.F, X.shape[0], X.shape[1]
+    if tuple(c.shape[1:]) != (16, 28, 28) or tuple(w.shape) != (16, 1, 5, 5) or tuple(table.shape) != (16, 4):
+        raise _lib.GpodeError('dec10_predict_w: c (B,16,28,28), weight (16,1,5,5), table (16,4)')
+    if tuple(X.shape[2:]) != (1, 28, 28) or N != state.N or F != N * Th or c.shape[0] % F != 0 or c.shape[0] == 0:
+        raise _lib.GpodeError('dec10_predict_w: X (N,T_obs,1,28,28), F = N * Th frames, c a whole number of draws of F frames')
+    Lc = c.shape[0] // F
+    if not (torch.is_tensor(logw) and logw.is_cuda and logw.dtype == torch.float32 and logw.dim() == 2 and logw.shape[1] == N
+            and logw.is_contiguous()):
+        raise _lib.GpodeError('gpode_dec10_predict_w: logw must be a contiguous float32 (L_total, N) tensor on the device')
+    if state.done + Lc > logw.shape[0]:
+        raise _lib.GpodeError('gpode_dec10_predict_w: logw has %d rows, need done + Lc = %d' % (logw.shape[0], state.done + Lc))
+    state.bad |= ~(logw[state.done:state.done + Lc] < float('inf')).all()      # NaN or +inf; stays on the device
+    _lib.call('gpode_dec10_predict_w', _ptr(c), _ptr(table), _ptr(w), _ptr(None if b is None else _chk(b.detach(), 'bias')), _ptr(X),
+              Lc, F, int(Th), T_obs, state.done, _ptr(logw), logw.shape[0], N, _ptr(state.wstate), _ptr(state.mean), _ptr(state.m2),
+              _ptr(state.wse), _ptr(n_obs), _stream())
+    state.done += Lc
+    return state
