@@ -29,7 +29,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GUARD = 4096
 S, N, T, METHOD = 32, 4, 3, 'euler'
-Case = collections.namedtuple('Case', 'kernel Di Do M nd')
+Case = collections.namedtuple('Case', 'kernel Di Do M nd regime', defaults=('base',))     # regime: gp_regimes.TABLE, 'base' = synthetic_gp as it is
 C = Case
 
 FWD_TAGS = ('cache build: lds', 'cache build: chain32+deep', 'cache build: chain32+back<1>', 'cache build: chain32+back<2>',
@@ -135,7 +135,8 @@ COND_N = (892, 893, 1100)                     # M + N = 992: the last 32-tile si
 
 
 def case_id(c):
-    return '%s-%d-%d-M%d-L%d' % c
+    import gp_regimes
+    return '%s-%d-%d-M%d-L%d' % c[:5] + gp_regimes.suffix(c.regime)
 
 
 # ---- inputs, reference -------------------------------------------------------------------------------------------------------------
@@ -143,7 +144,9 @@ def inputs(c):
     """parameters of test_gpu_backward.synthetic_gp (widths >= 6: K_uu well conditioned), the noise of nd draws with a leading draw
     axis, initial states, output times and dL/dzt of a loss that is summed over the draws"""
     from test_gpu_backward import synthetic_gp
+    import gp_regimes
     p, _, z0, ts, _ = synthetic_gp(c.kernel, c.Di, c.Do, c.M, S, N, T, seed=7000 + c.M + c.Di + 31 * c.Do)
+    p, z0, ts = gp_regimes.apply(c.regime, p, z0, c.kernel) + (gp_regimes.times(c.regime, ts),)
     g = torch.Generator().manual_seed(9000 + c.M + 17 * c.nd + c.Di)
     nz = dict(eps_u=torch.randn(c.nd, c.M, c.Do, generator=g), rff_w=torch.randn(c.nd, S if c.kernel == 'RBF' else 2 * S, c.Do, generator=g),
               rff_eps=torch.randn(c.nd, c.Di, S, c.Do, generator=g), rff_u=torch.rand(c.nd, 1, S, c.Do, generator=g))

@@ -31,7 +31,7 @@ import torch
 
 GUARD = 4096
 CHUNK = 256                                          # rows per oracle pass: the DF oracle holds (rows, 2 S, D, D) per evaluation
-Case = collections.namedtuple('Case', 'kernel Di Do order M S N T method nd kind')
+Case = collections.namedtuple('Case', 'kernel Di Do order M S N T method nd kind regime', defaults=('base',))     # regime: gp_regimes.TABLE
 NSTAGE = {'euler': 1, 'rk4': 4, 'midpoint': 2}
 TS = {3: (0.0, 0.05, 0.2), 2: (0.0, 0.2)}            # non-uniform: a sweep that read another step's dt would be seen
 
@@ -186,7 +186,8 @@ REQUIRED_TAGS = tuple('%s_%s' % (e, f) for e in ('rhs', 'rollout') for f in _F) 
 
 
 def case_id(c):
-    return '%s-%d-%d-o%d-M%d-S%d-N%d-T%d-%s-L%d-%s' % c
+    import gp_regimes
+    return '%s-%d-%d-o%d-M%d-S%d-N%d-T%d-%s-L%d-%s' % c[:11] + gp_regimes.suffix(c.regime)
 
 
 # ---- inputs ------------------------------------------------------------------------------------------------------------------------
@@ -194,9 +195,11 @@ def case_id(c):
 def inputs(c):
     """parameters and noise of test_gpu_backward.synthetic_gp (nd draws of noise, stacked on a leading axis when nd > 1), initial
     states, the non-uniform output times and dL/dzt (nd, N, T, Di) of a loss that is summed over the draws"""
+    import gp_regimes
     from test_gpu_backward import synthetic_gp
     seed = 4000 + c.M + 3 * c.S + 7 * c.Di + 11 * c.Do
     p, nz, z0, _, _ = synthetic_gp(c.kernel, c.Di, c.Do, max(c.M, 1), c.S, c.N, c.T, seed=seed)
+    p, z0 = gp_regimes.apply(c.regime, p, z0, c.kernel)
     if c.nd > 1:
         more = [synthetic_gp(c.kernel, c.Di, c.Do, max(c.M, 1), c.S, 1, c.T, seed=seed + 100 * l)[1] for l in range(1, c.nd)]
         nz = {k: torch.stack([nz[k]] + [m[k] for m in more]) for k in nz}
@@ -206,7 +209,7 @@ def inputs(c):
         p = dict(p, Z=3.0 * p['Z'])                  # of large terms (fp32 oracle 1e-4 from fp64); three times as far apart |nu| stays under 5
     g = torch.Generator().manual_seed(seed + 1)
     gw = torch.randn(c.nd, c.N, c.T, c.Di, generator=g)
-    return p, nz, z0, torch.tensor(TS[c.T]), gw
+    return p, nz, z0, gp_regimes.times(c.regime, torch.tensor(TS[c.T])), gw
 
 
 def draw(nz, c, l):
@@ -488,7 +491,8 @@ def compare(c, got, r64, r32, keys, what=''):
 
 
 def check_case(c, got, seen=None):
-    """got (run_case) against the dispatch table and the fp64 oracle on the cache the GPU built; prints every figure before it asserts"""
+    """got (run_case) against the dispatch table and the fp64 oracle on the cache the GPU built; prints every figure before it asserts.
+    Returns {(what, key): (relerr(hip, fp64), relerr(fp32 oracle, fp64))} of every comparison it made."""
     want = expected(c)
     tags = {kk[4:]: v for kk, v in got.items() if kk.startswith('tag_')}
     print('%s %s' % (case_id(c), tags))
@@ -497,20 +501,25 @@ def check_case(c, got, seen=None):
     assert tags == want, (case_id(c), tags, want)
     assert not got['guards_changed'], (case_id(c), 'wrote past its buffer', got['guards_changed'])
     r64, r32 = reference(c, got['cache'], torch.float64), reference(c, got['cache'], torch.float32)
+    errs = {}
+
+    def held(what, *args):
+        errs.update({(what, k): v for k, v in compare(c, *args, what).items()})
     if c.kind == 'prior':
-        compare(c, got, r64, r32, ('f1',))
+        held('', got, r64, r32, ('f1',))
         assert not got['second_run_differs'], (case_id(c), got['second_run_differs'])
-        return
-    compare(c, got, r64, r32, OUT_F + OUT_ROLL[:4])
+        return errs
+    held('', got, r64, r32, OUT_F + OUT_ROLL[:4])
     v64, v32 = (reference_rows(c, got['cache'], dt, got['vjp_x'], got['vjp_a'])[0] for dt in (torch.float64, torch.float32))
-    compare(c, got, dict(gx=v64), dict(gx=v32), ('gx',))
+    held('', got, dict(gx=v64), dict(gx=v32), ('gx',))
     leaf = [k for k in OUT_LEAF if k in r64]
-    compare(c, unpack(c, got['gpack'], got['cache']), r64, r32, leaf, 'param_grad: ')
+    held('param_grad: ', unpack(c, got['gpack'], got['cache']), r64, r32, leaf)
     if c.kind == 'fused':
         fused = dict(unpack(c, got['fused_gpack'].view(c.nd, -1), got['cache']), gz0=got['fused_gz0'].view(c.nd, c.N, c.Di),
                      astage=got['fused_astage'].view_as(got['astage']))
-        compare(c, fused, r64, r32, ['gz0', 'astage'] + leaf, 'fused: ')
+        held('fused: ', fused, r64, r32, ['gz0', 'astage'] + leaf)
     assert not got['second_run_differs'], (case_id(c), got['second_run_differs'])
+    return errs
 
 
 def check_accumulate(c, got, seen=None):

@@ -38,7 +38,10 @@ SHAPES = [('rbf_lds', 'RBF', 6, 6, 100, 256, 8, 6, 5),      # six 128-row system
 
 def _params(kernel, Di, Do, M, seed):
     g = torch.Generator().manual_seed(seed)
-    # DF: one lengthscale and one variance for all entries -- its matrix-valued kernel is only symmetric positive definite then
+    # DF: one lengthscale and one variance for all entries.  Neither the reference nor the library needs K_uu symmetric (the
+    # factor reads the lower triangle; gp_routes.py and gp_regimes.py run DF with different ell and var in every entry).  What the shapes
+    # of THIS file need is a matrix that factorises with Z = randn: with RBF's spread (ell 2 .. 2.3, var 1 .. 1.2) the matrix the lower
+    # triangle defines has a negative eigenvalue at df_tiny, df_chain and df_big (-5e-3, -2e-2, -5e-2 in fp64), with one value it has none
     return dict(raw_ell=O.invsoftplus(torch.full((Do, Di), 2.0) + (0.3 if kernel == 'RBF' else 0.0) * torch.rand(Do, Di, generator=g)),
                 raw_var=O.invsoftplus(torch.ones(Do) + (0.2 if kernel == 'RBF' else 0.0) * torch.rand(Do, generator=g)),
                 Z=torch.randn(M, Di, generator=g), Um=0.1 * torch.randn(M, Do, generator=g),
