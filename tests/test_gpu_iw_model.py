@@ -74,7 +74,7 @@ def build(kind):
     return m, src
 
 
-def batch(m, K, seed=5):
+def batch(m, K, seed=5, N=N):
     g = torch.Generator().manual_seed(seed)
     X = torch.rand(N, T, 1, 28, 28, generator=g).cuda()
     q = m.vae.encoder.fc.out_features // 2
@@ -102,7 +102,7 @@ def run_hip(m, src, X, L, K, eps, **kw):
     return [t.detach().clone() for t in out] + [m.last_ess.detach().clone()], grads(m)
 
 
-def torch_side(m, src, X, L, K, eps, dt, ts=None, n_obs=None):
+def torch_side(m, src, X, L, K, eps, dt, ts=None, n_obs=None, N=N):
     """the composition: the model's own encoder, flow and decoder; the draws and the loss stage in plain torch (the stage in ``dt``)
     -> (five figures, their scales, gradients)"""
     from vae_gp_ode_amd import vae_ops as V
@@ -149,12 +149,12 @@ def torch_side(m, src, X, L, K, eps, dt, ts=None, n_obs=None):
     return [t.detach().double() for t in out], scale, grads(m), (ll.detach(), lw.detach())
 
 
-def one_case(m, src, init, K, L, **kw):
+def one_case(m, src, init, K, L, N=N, **kw):
     """-> the kernel's and the float32 composition's distances from the float64 composition: {figure: (error, floor)}, {parameter: ...}"""
-    X, eps = batch(m, K)
+    X, eps = batch(m, K, N=N)
     res, steps = {}, {}
-    for tag, fn in (('hip', lambda: run_hip(m, src, X, L, K, eps, **kw)), ('f64', lambda: torch_side(m, src, X, L, K, eps, torch.float64, **kw)),
-                    ('f32', lambda: torch_side(m, src, X, L, K, eps, torch.float32, **kw))):
+    for tag, fn in (('hip', lambda: run_hip(m, src, X, L, K, eps, **kw)), ('f64', lambda: torch_side(m, src, X, L, K, eps, torch.float64, N=N, **kw)),
+                    ('f32', lambda: torch_side(m, src, X, L, K, eps, torch.float32, N=N, **kw))):
         m.load_state_dict(init)
         res[tag] = fn()
         steps[tag] = m.flow.last_counts.clone() if m.flow.solver == 'dopri5' else None

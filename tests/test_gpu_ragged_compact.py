@@ -296,7 +296,7 @@ def bn_buffers(m):
     return [t.detach().clone() for i in (2, 5, 8) for t in (d[i].running_mean, d[i].running_var, d[i].num_batches_tracked)]
 
 
-def torch_side_compact(m, src, X, ts, n_obs, monkeypatch):
+def torch_side_compact(m, src, X, ts, n_obs, monkeypatch, N=N):
     """the compact ELBO composed in torch: the model's rollout, index_select on the flattened states, the model's decoder on the compact
     states, the loss in float64 over compact rows -> (four terms, their scales, gradients)"""
     from vae_gp_ode_amd import vae_ops as V

@@ -53,7 +53,7 @@ _orders = pytest.mark.parametrize('order', list(ORDERS))
 _routes = pytest.mark.parametrize('fused', [True, False], ids=['fused', 'unfused'])
 
 
-def ragged_batch(m, seed=5, full_T=8):
+def ragged_batch(m, seed=5, full_T=8, N=N):
     """(Xpad (N,T,...), ts (N,T), n_obs (N,) int32) with at least one padded frame"""
     from vae_gp_ode_amd.data.utils import ragged_frames
     lead = 1 if m.order == 1 else m.v_steps

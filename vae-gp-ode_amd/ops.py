@@ -6,6 +6,7 @@ libgpode_hip.so and returns torch tensors.  Nothing here computes on the CPU.
 import ctypes
 import os
 import typing
+import weakref
 
 import torch
 
@@ -329,19 +330,24 @@ NSTAGE = {'euler': 1, 'rk4': 4, 'midpoint': 2, 'dopri5': 6}   # recorded stage i
 NSTAGE_DENSE = 7     # dopri5 with dense output: the end state of the step, where the seventh slope is evaluated, is recorded too
 
 
-_ts_checked = [None]
+_ts_checked = [None]      # (weak reference to the grid checked last, its key)
 
 
 def _check_increasing(ts):
     """Refuse output times that are not strictly increasing -- row by row for a grid per trajectory (N,T).  Reads the device, so it
     is skipped while the stream is being captured into a graph and remembered per tensor (the kernel itself gives such a trajectory
-    status 3 and NaN)."""
+    status 3 and NaN).  The tensor is remembered by weak reference next to (address, version, shape): once it is freed its block goes
+    back to the caching allocator, and the next grid of that shape lands on the same address at version 0 -- the key alone would
+    take the new grid for the checked one."""
+    if ts.shape[-1] < 2 or torch.cuda.is_current_stream_capturing():
+        return
     key = (ts.data_ptr(), ts._version, tuple(ts.shape))
-    if ts.shape[-1] < 2 or _ts_checked[0] == key or torch.cuda.is_current_stream_capturing():
+    seen = _ts_checked[0]
+    if seen is not None and seen[0]() is not None and seen[1] == key:
         return
     if not bool((ts[..., 1:] > ts[..., :-1]).all()):
         raise _lib.GpodeError('dopri5: ts must be strictly increasing' + (' in every row' if ts.dim() == 2 else ''))
-    _ts_checked[0] = key
+    _ts_checked[0] = (weakref.ref(ts), key)
 
 
 def _ts_per_traj(ts, N, T=None, rows='z0'):
