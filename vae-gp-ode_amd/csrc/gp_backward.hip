@@ -224,6 +224,48 @@ __device__ __forceinline__ void store_grads_rbf(const typename RbfTeamEval<DI, D
   }
 }
 
+// The rows [r0, r1) of a chunk for the register-resident DF parameter-sum kernels, one row ahead: the (wave-uniform, scalar) loads of
+// row r + 1 are issued before the arithmetic of row r, so their latency hides behind a row's worth of work instead of standing at
+// the top of every row.  The index is clamped, not branched around: the last row asks for itself again and the copy is dropped, so
+// nothing past r1 - 1 is read and no row of the next chunk can reach these sums.
+template <int DI, int DO, class ROW>
+__device__ __forceinline__ void chunk_rows_ahead(const float* __restrict__ xr, const float* __restrict__ ar, int r0, int r1, ROW&& row) {
+  if (r0 >= r1) return;
+  // The first row goes through readfirstlane (it is uniform already): were it a plain load, the compiler would merge it with the
+  // load at the bottom of the loop into ONE load of a loop-carried address at the top of every row -- the loop this replaces.
+  float xn[DI], an[DO];
+#pragma unroll
+  for (int i = 0; i < DI; ++i) xn[i] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(xr[(size_t)r0 * DI + i])));
+#pragma unroll
+  for (int i = 0; i < DO; ++i) an[i] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ar[(size_t)r0 * DO + i])));
+  // Every load issued so far (the pack's records, the uniform tail) lands here: a scalar load still pending at the loop's entry makes
+  // its first use inside the loop a wait for ALL scalar loads -- they return out of order -- in every row, the row just requested
+  // included.
+  __builtin_amdgcn_s_waitcnt(0x0070);                // vmcnt(0) lgkmcnt(0)
+  for (int r = r0; r < r1; ++r) {
+    float x[DI], a[DO];
+#pragma unroll
+    for (int i = 0; i < DI; ++i) x[i] = xn[i];
+#pragma unroll
+    for (int i = 0; i < DO; ++i) a[i] = an[i];
+    const int rn = min(r + 1, r1 - 1);
+#pragma unroll
+    for (int i = 0; i < DI; ++i) xn[i] = xr[(size_t)rn * DI + i];
+#pragma unroll
+    for (int i = 0; i < DO; ++i) an[i] = ar[(size_t)rn * DO + i];
+    __builtin_amdgcn_sched_barrier(0);               // nothing in the block uses them: left alone, the scheduler puts them last
+    row(x, a);
+  }
+}
+// ... with the loop unswitched on prior_only by hand (row(x, a, std::bool_constant)): a row has to stay ONE basic block -- with the
+// branch inside the loop the compiler sinks the next row's loads past it, to the end of the iteration, and they wait as before.
+template <int DI, int DO, class ROW>
+__device__ __forceinline__ void chunk_rows_ahead(const float* __restrict__ xr, const float* __restrict__ ar, int r0, int r1, int prior_only,
+                                                 ROW&& row) {
+  if (prior_only) chunk_rows_ahead<DI, DO>(xr, ar, r0, r1, [&](const float (&x)[DI], const float (&a)[DO]) { row(x, a, std::true_type()); });
+  else chunk_rows_ahead<DI, DO>(xr, ar, r0, r1, [&](const float (&x)[DI], const float (&a)[DO]) { row(x, a, std::false_type()); });
+}
+
 template <int DI, int DO, int NJ>
 __global__ __launch_bounds__(256) void param_grad_rbf_kernel(const float* __restrict__ pack, int M, int S,
                                                               const float* __restrict__ xr, const float* __restrict__ ar,
@@ -338,16 +380,14 @@ __global__ __launch_bounds__(256) void param_grad_df_kernel(const float* __restr
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   EV ev;
   ev.init(pack, M, S, slots, wave, lane);
+  typename EV::Tail tail;
+  ev.load_tail(tail, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1);
   typename EV::Grads G;
   G.zero();
   const int r0 = blockIdx.x * rows_per_chunk;
   const int r1 = min(R, r0 + rows_per_chunk);
-  for (int r = r0; r < r1; ++r) {
-    float x[D], a[D];
-#pragma unroll
-    for (int i = 0; i < D; ++i) { x[i] = xr[(size_t)r * D + i]; a[i] = ar[(size_t)r * D + i]; }
-    ev.grad_row(x, a, G, prior_only != 0);
-  }
+  chunk_rows_ahead<D, D>(xr, ar, r0, r1, prior_only,
+                         [&](const float (&x)[D], const float (&a)[D], auto po) { ev.grad_row(x, a, G, decltype(po)::value, tail); });
   store_grads_df<D, NJ>(G, slab + (size_t)blockIdx.x * pack_floats, M, S, wave, lane, sInd, sUni);
 }
 
@@ -368,14 +408,16 @@ __device__ __forceinline__ void pgrad_df_part(const float* __restrict__ pack, in
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   EV ev;
   ev.init(pack, M, S, slots, wave, lane);
+  typename EV::Tail tail;
+  if constexpr (PART != 1) ev.load_tail(tail, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1);
   typename EV::Grads G;
   G.zero();
-  for (int r = r0; r < r1; ++r) {
-    float x[D], a[D];
-#pragma unroll
-    for (int i = 0; i < D; ++i) { x[i] = xr[(size_t)r * D + i]; a[i] = ar[(size_t)r * D + i]; }
-    ev.template grad_row_part<PART>(x, a, G, prior_only != 0);
-  }
+  if constexpr (PART == 1)                           // the Fourier-feature records do not look at prior_only
+    chunk_rows_ahead<D, D>(xr, ar, r0, r1, [&](const float (&x)[D], const float (&a)[D]) { ev.template grad_row_part<1>(x, a, G, false, tail); });
+  else
+    chunk_rows_ahead<D, D>(xr, ar, r0, r1, prior_only, [&](const float (&x)[D], const float (&a)[D], auto po) {
+      ev.template grad_row_part<PART>(x, a, G, decltype(po)::value, tail);
+    });
   store_grads_df<D, 1, PART>(G, out, M, S, wave, lane, sInd, sUni);
 }
 template <int D>

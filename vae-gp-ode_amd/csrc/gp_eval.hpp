@@ -382,6 +382,88 @@ __device__ __forceinline__ void df_ind_half_bwd(const float4 (&r)[DfLayout<D>::R
   }
 }
 
+// The columns b = half*DH + bb (clamped as df_ind_half_bwd clamps them) of the uniform tail, copied once per kernel and read at
+// compile-time indices: with a provably wave-uniform `half` the copy is made by scalar loads and sits in scalar registers.
+template <int D> struct DfTailHalf {
+  static constexpr int DH = (D + 1) / 2;
+  float wab[D][DH], il2[D][DH], var[DH];
+  __device__ __forceinline__ void load(const float* __restrict__ uni, int half) {
+#pragma unroll
+    for (int bb = 0; bb < DH; ++bb) {
+      const int bidx = half * DH + bb < D ? half * DH + bb : D - 1;   // as df_ind_half_bwd clamps it
+#pragma unroll
+      for (int aa = 0; aa < D; ++aa) { wab[aa][bb] = uni[aa * D + bidx]; il2[aa][bb] = uni[D * D + aa * D + bidx]; }
+      var[bb] = uni[2 * D * D + bidx];
+    }
+  }
+};
+
+// df_ind_half_bwd with the uniform tail read from such a copy.  The arithmetic is df_ind_half_bwd's, expression for expression: the
+// two must stay so (a kernel on this one has to return the bits of a kernel on that one; bench.py --dump-outputs against the parent
+// build and tests/test_gpu_row_pipeline.py against the oracle are what holds them together).  A copy, not one body templated on where
+// the tail is read: with df_ind_half_bwd forwarding to such a template, 38 reverse-sweep and rhs_vjp instances that only ever use the
+// pointer form came out of the compiler with another body (tools/kernel_bodies.py), and those kernels are not to move.
+template <int D, bool WITH_G>
+__device__ __forceinline__ void df_ind_half_bwd_t(const float4 (&r)[DfLayout<D>::RQ2], const float (&x)[D],
+                                                  const DfTailHalf<D>& tl, int half, const float (&a)[D],
+                                                  float (&gx)[D], float (&g)[4 * DfLayout<D>::RQ2],
+                                                  float (&gwab)[D][(D + 1) / 2], float (&gil2)[D][(D + 1) / 2],
+                                                  float (&gvar)[(D + 1) / 2]) {
+  constexpr int DH = (D + 1) / 2;
+  float f[4 * DfLayout<D>::RQ2];
+  unpack(r, f);
+  float dl[D];
+  float r2 = 0.f;
+#pragma unroll
+  for (int q = 0; q < D; ++q) { dl[q] = x[q] - f[q]; r2 = fmaf(dl[q], dl[q], r2); }
+  const int b0 = half * DH;
+  float gd[D];      // d L / d delta_c
+  float gr2 = 0.f;  // d L / d r2 (through E and the diagonal term), applied as 2 delta_c at the end
+#pragma unroll
+  for (int q = 0; q < D; ++q) gd[q] = 0.f;
+#pragma unroll
+  for (int bb = 0; bb < DH; ++bb) {
+    const bool hi_ok = DH + bb < D;
+    const int bidx = b0 + bb < D ? b0 + bb : D - 1;  // wave-uniform
+    const bool live = half ? hi_ok : true;
+    const float dlb = half ? (hi_ok ? dl[hi_ok ? DH + bb : 0] : 0.f) : dl[bb];
+    const float ab = live ? (half ? (hi_ok ? a[hi_ok ? DH + bb : 0] : 0.f) : a[bb]) : 0.f;
+    const float vb = tl.var[bb];
+    float gdb = 0.f;  // d L / d delta_b from the cross term
+    float gv = 0.f;
+#pragma unroll
+    for (int aa = 0; aa < D; ++aa) {
+      const float il = tl.il2[aa][bb], wv = tl.wab[aa][bb];
+      const float E = exp2_fast(r2 * wv);
+      const bool diag = (aa == bidx);
+      const float term = dl[aa] * dlb * il + (diag ? ((float)(D - 1) - r2 * il) : 0.f);
+      const float G = ab * f[D + aa];               // upstream x coefficient nu[(m,aa)]
+      const float GE = G * vb * E * il;             // G * dT/dterm
+      // T = vb * E * il * term
+      gr2 = fmaf(GE, term * (GP_LN2 * wv) - (diag ? il : 0.f), gr2);
+      gd[aa] = fmaf(GE * il, dlb, gd[aa]);
+      gdb = fmaf(GE * il, dl[aa], gdb);
+      if (WITH_G) {
+        g[D + aa] = fmaf(ab, vb * E * il * term, g[D + aa]);                       // d/d nu[(m,aa)]
+        gv = fmaf(G, E * il * term, gv);                                           // d/d var_b
+        gwab[aa][bb] = fmaf(G * vb * il * term, E * GP_LN2 * r2, gwab[aa][bb]);    // d/d wab[aa][b]
+        gil2[aa][bb] = fmaf(G * vb * E, term + il * (dl[aa] * dlb - (diag ? r2 : 0.f)), gil2[aa][bb]);
+      }
+    }
+    if (WITH_G) gvar[bb] += gv;
+    // scatter d/d delta_b to its compile-time slot
+    if (live) {
+      if (half) { if (hi_ok) gd[hi_ok ? DH + bb : 0] += gdb; }
+      else gd[bb] += gdb;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < D; ++q) {
+    const float v = fmaf(2.f * gr2, dl[q], gd[q]);
+    gx[q] += v;
+    if (WITH_G) g[q] -= v;
+  }
+}
 // ==============================================================================================
 // Forward-mode (tangent-linear) building blocks: the transposes of the blocks above.  `v` is the (wave-uniform) tangent of x; acc
 // accumulates the record's contribution to f exactly as the forward blocks do, jacc its contribution to J_f(x) v.  The two share t,

@@ -214,17 +214,16 @@ template <int D, int NJ> struct DfTeamEval {
       for (int b = 0; b < (D + 1) / 2; ++b) gvar[b] = 0.f;
     }
   };
-  __device__ __forceinline__ void grad_row(const float (&x)[D], const float (&a)[D], Grads& G, bool prior_only) const {
-    float gx[D];
-#pragma unroll
-    for (int i = 0; i < D; ++i) gx[i] = 0.f;
-#pragma unroll
-    for (int r = 0; r < NJ * D; ++r) df_rff_bwd<D, true>(rff[r], x, a, gx, G.rff[r]);
-    if (!prior_only) df_ind_half_bwd<D, true>(ind, x, uni, half, a, gx, G.ind, G.gwab, G.gil2, G.gvar);
-  }
-  // PART 1: the Fourier-feature records only; PART 2: the inducing records (and the uniform tail) only -- the two halves of
-  // grad_row for workgroups that split the pack instead of the rows (param_grad_df_split_kernel)
-  template <int PART> __device__ __forceinline__ void grad_row_part(const float (&x)[D], const float (&a)[D], Grads& G, bool prior_only) const {
+  // The per-row parameter gradients, with this wavefront's half of the uniform tail held by the caller: load_tail once per kernel,
+  // with half_uniform = readfirstlane(threadIdx.x >> 6) & 1 -- the same value as `half`, but provably wave-uniform, so the copy is
+  // loaded by scalar loads into scalar registers.  vjp() above and vjp_grad() below re-read its 2 D DH + DH floats from the pack in
+  // every call, through vector loads, because `half` is not provably uniform.  Same arithmetic, same order.
+  using Tail = DfTailHalf<D>;
+  __device__ __forceinline__ void load_tail(Tail& tl, int half_uniform) const { tl.load(uni, half_uniform); }
+  // PART 0: the whole row; PART 1: the Fourier-feature records only; PART 2: the inducing records (and the uniform tail) only -- the
+  // two halves are for workgroups that split the pack instead of the rows (param_grad_df_split_kernel)
+  template <int PART> __device__ __forceinline__ void grad_row_part(const float (&x)[D], const float (&a)[D], Grads& G, bool prior_only,
+                                                                    const Tail& tl) const {
     float gx[D];
 #pragma unroll
     for (int i = 0; i < D; ++i) gx[i] = 0.f;
@@ -233,8 +232,11 @@ template <int D, int NJ> struct DfTeamEval {
       for (int r = 0; r < NJ * D; ++r) df_rff_bwd<D, true>(rff[r], x, a, gx, G.rff[r]);
     }
     if constexpr (PART != 1) {
-      if (!prior_only) df_ind_half_bwd<D, true>(ind, x, uni, half, a, gx, G.ind, G.gwab, G.gil2, G.gvar);
+      if (!prior_only) df_ind_half_bwd_t<D, true>(ind, x, tl, half, a, gx, G.ind, G.gwab, G.gil2, G.gvar);
     }
+  }
+  __device__ __forceinline__ void grad_row(const float (&x)[D], const float (&a)[D], Grads& G, bool prior_only, const Tail& tl) const {
+    grad_row_part<0>(x, a, G, prior_only, tl);
   }
   __device__ __forceinline__ void vjp_grad(const float (&x)[D], const float (&a)[D], float (&gx)[D], Grads& G) {
     float acc[D];
